@@ -10,10 +10,14 @@ resident in HBM.  Workload = BASELINE.json configs[2] (batch 8 per GPU).  Scenes
 so ranks shard them with no data-path collective ("scaling": "weak"); value = scenes processed
 by all ranks / max-over-ranks wall time.
 
-Rank 0 prints ONE JSON line with the metric plus
+Rank 0 prints ONE JSON line with the metric (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  A plain run
+does only what that figure needs: set-up, warm-up, the timed steps, then the line.  ``--full`` adds what else the benchmark
+measures, each after the timed region unless stated otherwise:
   "roofline":     the dominant kernel of this run, timed with HIP events inside the timed region;
   "cpu_baseline": the same forward on the host CPU through the C oracle (oracle/, kind "port"),
-                  on a bounded sample (rank 0, N=1 only).
+                  on a bounded sample (rank 0, N=1 only);
+  the latency, no-look-ahead, real-density, split-products and training side measurements.
+``--dump-outputs DIR`` writes the arrays the last timed step returned to DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -51,7 +55,7 @@ def parse():
                     help="batch-1 forwards timed AFTER the timed region for latency_ms_single_scene (0 = skip, e.g. under "
                          "rocprofv3 so that the trace holds the bench's launches only)")
     ap.add_argument("--time-every", type=int, default=8,
-                    help="bracket every n-th call of each native op (per shape) with HIP events; bracketing all calls costs ~2 %")
+                    help="bracket every n-th call of each native op (per shape) with HIP events; bracketing all calls costs ~2 %%")
     ap.add_argument("--train", action="store_true",
                     help="configs[3]: the reference's training iteration (forward with labels, losses, backward, two Adam "
                          "steps, one flat gradient all-reduce per network over RCCL) instead of the forward pipeline")
@@ -106,6 +110,14 @@ def parse():
     ap.add_argument("--set", action="append", default=[], metavar="module.NAME=0|1",
                     help="A/B measurement only: flip a module-level switch of the package before the run, e.g. "
                          "--set fused.FP_HEAD_INTERP=0 (reported in config.switches)")
+    ap.add_argument("--full", action="store_true",
+                    help="forward bench: also measure everything beside the headline -- per-kernel HIP-event timing and the "
+                         "roofline, cpu_baseline + parity, latency, no-look-ahead, real-density, split-products, exclusive and "
+                         "training side measurements (the *-steps / --cpu-scenes / --latency-runs options size them).  "
+                         "Without it a run only sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="forward bench: write the arrays the LAST timed step returned (rank 0) to DIR/<name>.npy, float32 "
+                         "(integer and boolean outputs as float64), at most 64 MB in all (larger arrays: a fixed, seeded sample)")
     return ap.parse_args()
 
 
@@ -779,8 +791,49 @@ def sa_chain_executed_share(score_net, pcs):
             "executed_share_of_algorithmic_flops": round(1.0 - (0.5 * small + 0.25 * paired) * 49152.0 / 49920.0, 4)}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE_ELEMENTS = 1 << 21     # an output with more elements is written as a sample of this many
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: the arrays of one pipeline result (what ``ForwardPipeline.run`` hands its caller for a batch) ->
+    ``path/<name>.npy``; tuple / list entries as ``<name>_<i>``, non-array entries (events, counts) skipped.  Floating
+    arrays are written as float32 (float64 ones as float64), integer and boolean ones as float64 (exact).  An array of more
+    than DUMP_SAMPLE_ELEMENTS elements is written flat, as the elements at DUMP_SAMPLE_ELEMENTS indices drawn by numpy's
+    Generator seeded with 0 and sorted: the same indices for every run whose output has that shape.  At most
+    DUMP_BUDGET_BYTES in all.  -> {name: shape of the output}."""
+    arrays = []
+
+    def walk(name, v):
+        if torch.is_tensor(v):
+            arrays.append((name, v))
+        elif isinstance(v, (list, tuple)):
+            for i, x in enumerate(v):
+                walk("%s_%d" % (name, i), x)
+
+    for key in sorted(out):
+        walk(key, out[key])
+    os.makedirs(path, exist_ok=True)
+    total, shapes = 0, {}
+    for name, t in arrays:
+        flat = t.detach()
+        if flat.numel() > DUMP_SAMPLE_ELEMENTS:
+            idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), DUMP_SAMPLE_ELEMENTS))
+            flat = flat.reshape(-1)[torch.from_numpy(idx).to(flat.device)]
+        a = flat.cpu()
+        a = (a.float() if a.is_floating_point() and a.dtype != torch.float64 else a.double()).numpy()
+        total += a.nbytes
+        if total > DUMP_BUDGET_BYTES:
+            raise SystemExit("--dump-outputs: the outputs exceed %d MB" % (DUMP_BUDGET_BYTES >> 20))
+        np.save(os.path.join(path, name + ".npy"), a)
+        shapes[name] = list(t.shape)
+    return shapes
+
+
 def main():
     args = parse()
+    if args.dump_outputs and args.train:
+        raise SystemExit("--dump-outputs writes the forward pipeline's outputs; it does not combine with --train")
     guard_stdout()
     from regnet_for_3d_grasping_amd import sharding
     rank, local_rank, world = sharding.env_world()
@@ -846,7 +899,8 @@ def main():
 
     from regnet_for_3d_grasping_amd import pipeline, synthetic
     timer = OpTimer(args.time_every)
-    install_timers(timer)
+    if args.full:
+        install_timers(timer)
 
     score_net, region_net = pipeline.build_models(dev)
     # each rank owns its shard of independent scenes: rank r holds scenes (k*W + r)*B .. +B-1 of global batch k; the steps
@@ -903,8 +957,9 @@ def main():
     fence()
     # (read the handles only now: the HIP runtime binds a stream to a hardware queue when its handle is first used, and a
     # feature stream that is bound first -- before the pipeline's own first use of its streams -- ends up 8 % slower)
-    timer.critical_streams = {m.cuda_stream for m in pipe.s_mlps}
-    timer.enabled = True
+    if args.full:
+        timer.critical_streams = {m.cuda_stream for m in pipe.s_mlps}
+        timer.enabled = True
     pipe.graph_replays = 0
     pipe.host_late_feature_stages = pipe.geometry_pending_at_enqueue = 0
     # CPython's cyclic collector inside the timed region (reported as config.host_gc): a generation-2 pass over a process
@@ -927,11 +982,12 @@ def main():
     timer.enabled = False
     main_summary = timer.summary() if rank == 0 else None
     dt = sharding.max_over_ranks(dt, dev)
+    dumped = dump_outputs(out, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     first_launch_batches = pipe.first_launch_batches
     first_launch_split = getattr(pipe, "first_launch_split", None)
     graph_replays = pipe.graph_replays
     graph_accounting_steps = 0
-    if graph_replays and rank == 0:
+    if graph_replays and rank == 0 and args.full:
         # the timed steps replayed hipGraphs: no per-launch events exist for their kernels.  The per-kernel accounting of the
         # line comes from a short pass of the SAME launches issued one by one (graphs off), outside the timed region.
         timer.records, timer.calls = [], {}
@@ -950,7 +1006,7 @@ def main():
         main_summary = timer.summary()
 
     no_lookahead = None
-    if world == 1 and args.no_lookahead_steps > 0:
+    if args.full and world == 1 and args.no_lookahead_steps > 0:
         # the same steps with ONE sampling launch per batch and a first launch like every other (the pipeline then reads
         # 3-4 batches ahead instead of up to 32): what the grouped sampling + enlarged first launch are worth, same
         # process, same scenes, outside the timed region
@@ -967,7 +1023,7 @@ def main():
         no_lookahead = args.batch * args.no_lookahead_steps / (time.perf_counter() - t1)
 
     split_products = None
-    if world == 1 and args.split_products_steps > 0 and not args.score_only and args.points <= 102400:
+    if args.full and world == 1 and args.split_products_steps > 0 and not args.score_only and args.points <= 102400:
         # The fenced ceiling experiment (DESIGN.md par. 10): the SAME pipeline, scenes and weights with sa_chain_kernel replaced by
         # csrc/sa_split.hip -- every operand as three bf16 pieces, six products on the bf16 matrix pipe, fp32 accumulation.  After
         # the timed region; its own value, its own parity figures (the bench scene's scores against the exact path's), never `value`.
@@ -1005,7 +1061,7 @@ def main():
                           "ceiling_tflops_fp32_equivalent": 310.6}
 
     real_density = None
-    if world == 1 and args.real_density_steps > 0:
+    if args.full and world == 1 and args.real_density_steps > 0:
         # SURVEY 8(d) "real-density variant": the SAME pipeline configuration and weights over scenes whose level-1
         # neighbourhood sizes match the reference's own clouds (mean 49.5 members, 23 % <= 32, 49 % full: the uniform scenes
         # above have 30 % <= 32 and 19 % full) -- sa_chain_kernel skips less on them.  After the timed region.
@@ -1039,7 +1095,7 @@ def main():
         del pcs_r, pipe_r
 
     exclusive = None
-    if args.mlp_streams > 1 and world == 1 and args.exclusive_steps > 0:
+    if args.full and args.mlp_streams > 1 and world == 1 and args.exclusive_steps > 0:
         # per-kernel accounting without feature stages overlapping each other: a short extra pass (outside the timed
         # region) through a pipeline with ONE feature-stage stream, same scenes, same event bracketing
         timer.records, timer.calls = [], {}
@@ -1059,7 +1115,7 @@ def main():
         exclusive = (timer.summary(), dt1)
 
     latency_ms = None
-    if rank == 0 and world == 1 and args.latency_runs > 0:
+    if args.full and rank == 0 and world == 1 and args.latency_runs > 0:
         # latency of ONE scene through the whole forward (batch 1, nothing else in flight), outside the timed region:
         # the furthest-point-sampling chains (level 1: ~880 dependent rounds of ~6 exact picks on one CU) are ~5 of its ~8 ms
         one = pc[:1].contiguous()
@@ -1075,7 +1131,7 @@ def main():
         np.random.set_state(state)
 
     train_line = None
-    if args.train_steps > 0 and not args.score_only:
+    if args.full and args.train_steps > 0 and not args.score_only:
         # configs[3]'s training iteration on the same box, after the timed region (every rank takes part: the gradient
         # all-reduce is a collective)
         try:
@@ -1085,64 +1141,6 @@ def main():
 
     if rank == 0:
         total_scenes = args.batch * args.steps * world
-        agg = main_summary
-        by_time = sorted(agg.items(), key=lambda kv: -kv[1][0])
-        kernels = [{"op": k[0], "shape": k[1], "calls": c, "avg_ms": round(tot / c, 4), "total_ms": round(tot, 3)}
-                   for k, (tot, c) in by_time]
-        fam, roofline = roofline_of(agg, graph_accounting_steps or args.steps, args.batch,
-                                    timer.critical if timer.critical_streams is not None else None)
-        if roofline and graph_accounting_steps:
-            roofline["accounting_note"] = ("the %d timed steps replayed hipGraphs (%d feature stages); launch durations are from %d "
-                                           "extra steps outside the timed region with the same launches issued one by one"
-                                           % (args.steps, graph_replays, graph_accounting_steps))
-        # sa_chain_kernel skips the padded point tiles of small neighbourhoods (exact: a duplicate cannot move a maximum), so
-        # the ALGORITHMIC flops of its launches (all 64 slots, what the reference multiplies) overstate what the matrix pipe
-        # executes; every fraction quoted as a utilisation below is computed from the EXECUTED flops
-        chain_exec = sa_chain_executed_share(score_net, pcs)
-        launched_gflop = sum(f["units"] for f in fam.values() if f["bound"] == "mfma") / 1e9 / max(
-            (graph_accounting_steps or args.steps) * args.batch, 1)
-        chain_alg_gflop = (fam["sa_chain_kernel"]["units"] / 1e9 / max((graph_accounting_steps or args.steps) * args.batch, 1)
-                           if "sa_chain_kernel" in fam else 0.0)
-        share = chain_exec["executed_share_of_algorithmic_flops"] if chain_exec else 1.0
-        executed_gflop = launched_gflop - chain_alg_gflop * (1.0 - share)
-        if roofline and roofline["bound"] == "mfma":
-            k_share = share if roofline["kernel"] == "sa_chain_kernel" else 1.0
-            if roofline["kernel"] == "sa_chain_kernel" and chain_exec:
-                roofline.update(chain_exec)
-            roofline["frac_algorithmic"] = roofline["frac"]
-            roofline["achieved_algorithmic"] = roofline["achieved"]
-            roofline["frac"] = round(roofline["frac_algorithmic"] * k_share, 6)          # executed flops / event duration / peak
-            roofline["achieved"] = round(roofline["achieved_algorithmic"] * k_share, 4)
-            roofline["frac_executed"] = roofline["frac"]
-            roofline["executed_flop_per_launch"] = round(roofline["algorithmic_units_per_launch"] * k_share)
-            rp_ms, rp_src, rp_note = rocprof_launch(roofline["kernel"], args.batch, args.points)
-            roofline["rocprof_avg_launch_ms"] = rp_ms
-            roofline["rocprof_source"] = rp_src
-            roofline["frac_rocprof"] = None
-            if rp_note:
-                roofline["rocprof_note"] = rp_note
-            if rp_ms:
-                # the same fraction from the committed trace's duration instead of this run's events (the trace is of
-                # another run of this command on another box: durations differ by a few per cent)
-                roofline["frac_rocprof"] = round(roofline["executed_flop_per_launch"] / (rp_ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS, 6)
-            # whole step: executed flops of ALL matrix kernels of a batch / ms_per_step / peak
-            roofline["step_frac_executed"] = round(executed_gflop * args.batch / (dt / args.steps * 1e3)   # GFLOP / ms = TFLOP/s
-                                                   / MFMA_F32_PEAK_TFLOPS, 6)
-            roofline["frac_note"] = ("frac / achieved / frac_rocprof count EXECUTED flops (sa_chain_kernel skips padded point tiles: "
-                                     "executed_share_of_algorithmic_flops); frac_algorithmic / achieved_algorithmic count SURVEY "
-                                     "8(d)'s algorithmic flops and may exceed what a matrix pipe can do")
-        if roofline:
-            src = traffic_source()
-            roofline["traffic_source"] = src
-            roofline["traffic_source_stale"] = src["stale"]
-        if roofline and getattr(pipe, "split_chain_tail", False):
-            roofline["overlap_note"] = ("the previous batch's last chain kernel leaves its partial final round of row blocks (64 of "
-                                        "1600 workgroup passes) on a side stream; it runs beside the first ~0.25 ms of this kernel's "
-                                        "launches, whose duration includes that sharing")
-        if roofline and args.mlp_streams > 1:
-            roofline["concurrency"] = ("%d feature-stage streams: launches of this family overlap each other, so the launch "
-                                       "duration above (what rocprofv3 shows too) includes time-sharing; roofline_exclusive "
-                                       "is the same measurement with one feature-stage stream" % args.mlp_streams)
         res = {
             "metric": "scenes/sec (%s-pt ScoreNet+GRN fwd)" % _pts(args.points), "value": round(total_scenes / dt, 3),
             "unit": "scenes/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1172,13 +1170,7 @@ def main():
                            "valid_crops_per_step": (None if any(r[1] is None for r in refine_stats) else
                                                     round(sum(r[1] for r in refine_stats) / len(refine_stats), 1)),
                            "class1_grasps_per_step": round(sum(r[2] for r in refine_stats) / len(refine_stats), 1),
-                           "steps_with_refine": sum(1 for r in refine_stats if r[2] > 0 or (r[1] or 0) >= 2),
-                           # launches of the refine network's own kernels in the timed region (their row count -- the
-                           # valid crops of the step -- varies, so the per-shape list below holds one entry per count)
-                           "kernel_calls": {"gather_max G64 (crop features + MaxPool1d(64))":
-                                            sum(c for (n, m), (_, c) in agg.items() if n == "gather_max" and " G64 " in m),
-                                            "mlp_layer K384 N1024 (conv_formal)":
-                                            sum(c for (n, m), (_, c) in agg.items() if n == "mlp_layer" and " K384 N1024" in m)}},
+                           "steps_with_refine": sum(1 for r in refine_stats if r[2] > 0 or (r[1] or 0) >= 2)},
                        # of the timed steps: feature stages enqueued when the previous batch's had already finished (the launching
                        # thread paced them, not the GPU), and feature stages whose geometry was still running when they were enqueued
                        "host_late_feature_stages": getattr(pipe, "host_late_feature_stages", None),
@@ -1188,59 +1180,130 @@ def main():
                        # itself has no data-path collective -- the probe all-reduce is the training bucket's size
                        "collective": collective,
                        "hip_graphs": bool(graph_replays),
-                       "scorenet_gflop_per_scene": SCORENET_GFLOP_PER_SCENE.get(args.points),
-                       # flops of the launched matrix kernels per scene: "launched" after the algebraic restructuring (layer 1
-                       # of levels 2-3 and of the propagation blocks evaluated per source point), "executed" also without the
-                       # padded point tiles sa_chain_kernel skips
-                       "launched_gflop_per_scene": round(launched_gflop, 2),
-                       "executed_gflop_per_scene": round(executed_gflop, 2),
-                       "level1_balls": chain_exec},
-            "roofline": roofline,
-            "roofline_exclusive": None,
-            "latency_ms_single_scene": latency_ms,
-            # the same pipeline on density-matched scenes (level-1 neighbourhoods like the reference's clouds), after the timed region
-            "value_real_density": None if real_density is None else real_density["value"],
-            # EXPERIMENT, never the headline: the same run with the level-1 block on the bf16 matrix pipe (fp32-faithful split products)
-            "value_split_products": None if split_products is None else split_products["value"],
-            "split_products": split_products,
-            "real_density": real_density,
-            "value_no_lookahead": None if no_lookahead is None else round(no_lookahead, 3),
-            "value_no_lookahead_note": None if no_lookahead is None else (
-                "%d steps after the timed region, --fps-group 1 --first-launch-groups 1 (one sampling launch per batch, "
-                "look-ahead 3-4 batches)" % args.no_lookahead_steps),
+                       "scorenet_gflop_per_scene": SCORENET_GFLOP_PER_SCENE.get(args.points)},
             "mlp_tflops": round(SCORENET_GFLOP_PER_SCENE.get(args.points, 0.0) * total_scenes / world / dt / 1e3, 3),
-            "kernels": kernels[:40],
             "grasps_last_step": int(out["next_grasp"].shape[0]) if "next_grasp" in out else None,
         }
-        if exclusive is not None:
-            _, r1 = roofline_of(exclusive[0], args.exclusive_steps, args.batch, timer.critical if timer.critical_streams is not None else None)
-            if r1:
-                r1["steps"] = args.exclusive_steps
-                r1["scenes_per_s_in_this_mode"] = round(args.batch * args.exclusive_steps / exclusive[1], 1)
-            res["roofline_exclusive"] = r1
-        else:
-            res.pop("roofline_exclusive")
-        if train_line is not None and "error" in train_line:
-            res["train"] = train_line
-        elif train_line is not None:
-            res["train"] = {"scenes_per_s": train_line["value"], "ms_per_step": train_line["ms_per_step"],
-                            "steps": train_line["steps"], "warmup": train_line["warmup"],
-                            "batch_per_gpu": args.train_batch, "roofline": train_line["roofline"],
-                            "allreduce_ms": train_line["allreduce_ms"], "workload": train_line["config"]["workload"],
-                            "ms_per_step_median": train_line["ms_per_step_median"], "iteration_ms": train_line["iteration_ms"],
-                            "host_iteration_ms": train_line["host_iteration_ms"], "trunk_stream": train_line["trunk_stream"],
-                            "graph_replays": train_line["graph_replays"], "readback_wait_ms": train_line["readback_wait_ms"],
-                            "host_ms_per_step": train_line["host_ms_per_step"],
-                            "host_blocked_ms_per_step": train_line["host_blocked_ms_per_step"],
-                            "gpu_idle_ms_per_step": train_line["gpu_idle_ms_per_step"], "gpu_timeline": train_line["gpu_timeline"],
-                            "distinct_batches": train_line["config"]["distinct_batches"],
-                            "bucket_bytes": train_line["config"]["bucket_bytes"],
-                            "parallelism": train_line["config"]["parallelism"],
-                            "note": "measured after the timed region; `python bench.py --train` times it alone"}
-        if world == 1 and args.cpu_scenes > 0:
-            res["cpu_baseline"] = cpu_baseline(args, args.cpu_scenes, (score_net, region_net))
-            res["parity"] = res["cpu_baseline"].pop("parity")
-            res["speedup_vs_cpu_baseline"] = round(res["value"] / res["cpu_baseline"]["value"], 1)
+        if dumped is not None:
+            res["dumped_outputs"] = dumped      # name -> shape of the output the .npy file was written from
+        if args.full:
+            agg = main_summary
+            by_time = sorted(agg.items(), key=lambda kv: -kv[1][0])
+            kernels = [{"op": k[0], "shape": k[1], "calls": c, "avg_ms": round(tot / c, 4), "total_ms": round(tot, 3)}
+                       for k, (tot, c) in by_time]
+            fam, roofline = roofline_of(agg, graph_accounting_steps or args.steps, args.batch,
+                                        timer.critical if timer.critical_streams is not None else None)
+            if roofline and graph_accounting_steps:
+                roofline["accounting_note"] = ("the %d timed steps replayed hipGraphs (%d feature stages); launch durations are from %d "
+                                               "extra steps outside the timed region with the same launches issued one by one"
+                                               % (args.steps, graph_replays, graph_accounting_steps))
+            # sa_chain_kernel skips the padded point tiles of small neighbourhoods (exact: a duplicate cannot move a maximum), so
+            # the ALGORITHMIC flops of its launches (all 64 slots, what the reference multiplies) overstate what the matrix pipe
+            # executes; every fraction quoted as a utilisation below is computed from the EXECUTED flops
+            chain_exec = sa_chain_executed_share(score_net, pcs)
+            launched_gflop = sum(f["units"] for f in fam.values() if f["bound"] == "mfma") / 1e9 / max(
+                (graph_accounting_steps or args.steps) * args.batch, 1)
+            chain_alg_gflop = (fam["sa_chain_kernel"]["units"] / 1e9 / max((graph_accounting_steps or args.steps) * args.batch, 1)
+                               if "sa_chain_kernel" in fam else 0.0)
+            share = chain_exec["executed_share_of_algorithmic_flops"] if chain_exec else 1.0
+            executed_gflop = launched_gflop - chain_alg_gflop * (1.0 - share)
+            if roofline and roofline["bound"] == "mfma":
+                k_share = share if roofline["kernel"] == "sa_chain_kernel" else 1.0
+                if roofline["kernel"] == "sa_chain_kernel" and chain_exec:
+                    roofline.update(chain_exec)
+                roofline["frac_algorithmic"] = roofline["frac"]
+                roofline["achieved_algorithmic"] = roofline["achieved"]
+                roofline["frac"] = round(roofline["frac_algorithmic"] * k_share, 6)          # executed flops / event duration / peak
+                roofline["achieved"] = round(roofline["achieved_algorithmic"] * k_share, 4)
+                roofline["frac_executed"] = roofline["frac"]
+                roofline["executed_flop_per_launch"] = round(roofline["algorithmic_units_per_launch"] * k_share)
+                rp_ms, rp_src, rp_note = rocprof_launch(roofline["kernel"], args.batch, args.points)
+                roofline["rocprof_avg_launch_ms"] = rp_ms
+                roofline["rocprof_source"] = rp_src
+                roofline["frac_rocprof"] = None
+                if rp_note:
+                    roofline["rocprof_note"] = rp_note
+                if rp_ms:
+                    # the same fraction from the committed trace's duration instead of this run's events (the trace is of
+                    # another run of this command on another box: durations differ by a few per cent)
+                    roofline["frac_rocprof"] = round(roofline["executed_flop_per_launch"] / (rp_ms * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS, 6)
+                # whole step: executed flops of ALL matrix kernels of a batch / ms_per_step / peak
+                roofline["step_frac_executed"] = round(executed_gflop * args.batch / (dt / args.steps * 1e3)   # GFLOP / ms = TFLOP/s
+                                                       / MFMA_F32_PEAK_TFLOPS, 6)
+                roofline["frac_note"] = ("frac / achieved / frac_rocprof count EXECUTED flops (sa_chain_kernel skips padded point tiles: "
+                                         "executed_share_of_algorithmic_flops); frac_algorithmic / achieved_algorithmic count SURVEY "
+                                         "8(d)'s algorithmic flops and may exceed what a matrix pipe can do")
+            if roofline:
+                src = traffic_source()
+                roofline["traffic_source"] = src
+                roofline["traffic_source_stale"] = src["stale"]
+            if roofline and getattr(pipe, "split_chain_tail", False):
+                roofline["overlap_note"] = ("the previous batch's last chain kernel leaves its partial final round of row blocks (64 of "
+                                            "1600 workgroup passes) on a side stream; it runs beside the first ~0.25 ms of this kernel's "
+                                            "launches, whose duration includes that sharing")
+            if roofline and args.mlp_streams > 1:
+                roofline["concurrency"] = ("%d feature-stage streams: launches of this family overlap each other, so the launch "
+                                           "duration above (what rocprofv3 shows too) includes time-sharing; roofline_exclusive "
+                                           "is the same measurement with one feature-stage stream" % args.mlp_streams)
+            res["config"].update({
+                # flops of the launched matrix kernels per scene: "launched" after the algebraic restructuring (layer 1
+                # of levels 2-3 and of the propagation blocks evaluated per source point), "executed" also without the
+                # padded point tiles sa_chain_kernel skips
+                "launched_gflop_per_scene": round(launched_gflop, 2),
+                "executed_gflop_per_scene": round(executed_gflop, 2),
+                "level1_balls": chain_exec})
+            if res["config"]["refine_stage"] is not None:
+                # launches of the refine network's own kernels in the timed region (their row count -- the
+                # valid crops of the step -- varies, so the per-shape list below holds one entry per count)
+                res["config"]["refine_stage"]["kernel_calls"] = {
+                    "gather_max G64 (crop features + MaxPool1d(64))":
+                    sum(c for (n, m), (_, c) in agg.items() if n == "gather_max" and " G64 " in m),
+                    "mlp_layer K384 N1024 (conv_formal)":
+                    sum(c for (n, m), (_, c) in agg.items() if n == "mlp_layer" and " K384 N1024" in m)}
+            res.update({
+                "roofline": roofline,
+                "roofline_exclusive": None,
+                "latency_ms_single_scene": latency_ms,
+                # the same pipeline on density-matched scenes (level-1 neighbourhoods like the reference's clouds), after the timed region
+                "value_real_density": None if real_density is None else real_density["value"],
+                # EXPERIMENT, never the headline: the same run with the level-1 block on the bf16 matrix pipe (fp32-faithful split products)
+                "value_split_products": None if split_products is None else split_products["value"],
+                "split_products": split_products,
+                "real_density": real_density,
+                "value_no_lookahead": None if no_lookahead is None else round(no_lookahead, 3),
+                "value_no_lookahead_note": None if no_lookahead is None else (
+                    "%d steps after the timed region, --fps-group 1 --first-launch-groups 1 (one sampling launch per batch, "
+                    "look-ahead 3-4 batches)" % args.no_lookahead_steps),
+                "kernels": kernels[:40]})
+            if exclusive is not None:
+                _, r1 = roofline_of(exclusive[0], args.exclusive_steps, args.batch, timer.critical if timer.critical_streams is not None else None)
+                if r1:
+                    r1["steps"] = args.exclusive_steps
+                    r1["scenes_per_s_in_this_mode"] = round(args.batch * args.exclusive_steps / exclusive[1], 1)
+                res["roofline_exclusive"] = r1
+            else:
+                res.pop("roofline_exclusive")
+            if train_line is not None and "error" in train_line:
+                res["train"] = train_line
+            elif train_line is not None:
+                res["train"] = {"scenes_per_s": train_line["value"], "ms_per_step": train_line["ms_per_step"],
+                                "steps": train_line["steps"], "warmup": train_line["warmup"],
+                                "batch_per_gpu": args.train_batch, "roofline": train_line["roofline"],
+                                "allreduce_ms": train_line["allreduce_ms"], "workload": train_line["config"]["workload"],
+                                "ms_per_step_median": train_line["ms_per_step_median"], "iteration_ms": train_line["iteration_ms"],
+                                "host_iteration_ms": train_line["host_iteration_ms"], "trunk_stream": train_line["trunk_stream"],
+                                "graph_replays": train_line["graph_replays"], "readback_wait_ms": train_line["readback_wait_ms"],
+                                "host_ms_per_step": train_line["host_ms_per_step"],
+                                "host_blocked_ms_per_step": train_line["host_blocked_ms_per_step"],
+                                "gpu_idle_ms_per_step": train_line["gpu_idle_ms_per_step"], "gpu_timeline": train_line["gpu_timeline"],
+                                "distinct_batches": train_line["config"]["distinct_batches"],
+                                "bucket_bytes": train_line["config"]["bucket_bytes"],
+                                "parallelism": train_line["config"]["parallelism"],
+                                "note": "measured after the timed region; `python bench.py --train` times it alone"}
+            if world == 1 and args.cpu_scenes > 0:
+                res["cpu_baseline"] = cpu_baseline(args, args.cpu_scenes, (score_net, region_net))
+                res["parity"] = res["cpu_baseline"].pop("parity")
+                res["speedup_vs_cpu_baseline"] = round(res["value"] / res["cpu_baseline"]["value"], 1)
         emit(res)
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()

@@ -12,7 +12,7 @@ for i in $(seq 1 $R); do
       t8)   E="REGNET_G2_T8=1"; X="--set fused.STREAM_LAYERS=0";;
       strm) E="REGNET_G2_T8=1"; X="--set fused.STREAM_LAYERS=1";;
     esac
-    env $E python bench.py $COMMON $X 2>/dev/null | python -c "
+    env $E python bench.py --full $COMMON $X 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=j['roofline']
 plain=sum(k['total_ms'] for k in j['kernels'] if k['op']=='mlp_layer' and int(k['shape'].split()[0][1:])>=2048)/j['steps']

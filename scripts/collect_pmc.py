@@ -1,9 +1,9 @@
 #!/usr/bin/env python
 """Post-processes rocprofv3 PMC passes of `python bench.py` into profiles/pmc_traffic.json.
 
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_fetch -o p -- python bench.py ...
-    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/pmc_write -o p -- python bench.py ...
-    python scripts/collect_pmc.py gpurun_out/pmc_fetch gpurun_out/pmc_write > profiles/pmc_traffic.json
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d <out>/pmc_fetch -o p -- python bench.py --full ...
+    rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d <out>/pmc_write -o p -- python bench.py --full ...
+    python scripts/collect_pmc.py <out>/pmc_fetch <out>/pmc_write > profiles/pmc_traffic.json
 
 Units / corrections (MI355X_MICROARCH.md §HBM): FETCH_SIZE and WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE
 counts 64 B per 128-B request for wide (16 B/lane) coalesced streams, so it is DOUBLED for the kernels whose

@@ -1,8 +1,8 @@
 """Timeline analysis of a rocprofv3 --kernel-trace CSV of `python bench.py`: how much of the steady-state
 wall time has at least one MFMA kernel (mlp_gemm_kernel / sa_chain_kernel) running, and what runs in the gaps.
 
-    rocprofv3 --kernel-trace --output-format csv -d gpurun_out/kt -o kt -- python bench.py --cpu-scenes 0 --steps 20
-    python scripts/gemm_gaps.py gpurun_out/kt
+    rocprofv3 --kernel-trace --output-format csv -d <out>/kt -o kt -- python bench.py --full --cpu-scenes 0 --steps 20
+    python scripts/gemm_gaps.py <out>/kt
 """
 import collections, csv, glob, sys
 

@@ -27,10 +27,10 @@ line() {   # name N bench-arguments...
   local out=$OUT/${name}_n${n}.json
   PORT=$((PORT + 1))
   if [ "$n" = 1 ]; then
-    timeout 900 python bench.py --gpus 1 --single-rank-group "$@" > $out 2> ${out%.json}.err
+    timeout 900 python bench.py --full --gpus 1 --single-rank-group "$@" > $out 2> ${out%.json}.err
   else
     timeout 1500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $PORT \
-      bench.py --gpus $n "$@" > $out 2> ${out%.json}.err
+      bench.py --full --gpus $n "$@" > $out 2> ${out%.json}.err
   fi
   python - "$out" "$name" "$n" <<'PY' || FAIL=1
 import json, sys

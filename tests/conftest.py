@@ -11,7 +11,7 @@ if REPO not in sys.path:
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
     config.addinivalue_line("markers", "refpy: cross-check against the reference's Python graph "
-                                       "(authoring container only; skipped when /root/reference is absent)")
+                                       "(its stored outputs for a seed no other fixture uses)")
 
 
 def pytest_collection_modifyitems(config, items):

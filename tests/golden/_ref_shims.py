@@ -2,8 +2,7 @@
 
 AUTHORING-CONTAINER ONLY: /root/reference does not exist on the GPU box, so nothing in the
 test-suite imports this module at run time -- it is used by make_golden.py (which generates the
-committed fixtures) and by the optional ``-m refpy`` cross-checks that skip when the reference is
-absent.  Three shims are needed:
+committed fixtures, make_golden_refpy.py's for the ``-m refpy`` cross-check among them).  Three shims are needed:
   1. a module named ``pn2_ext`` / ``dgcnn_ext`` on sys.modules  -> the CPU oracle binding,
   2. a stub ``open3d`` module (dead import, get_regiondataset.py:10),
   3. ``torch.Tensor.cuda`` -> identity (gripper_region_network.py:40-41,66-67 call it unconditionally).

@@ -1,9 +1,12 @@
-"""bench.py's driver contract: one JSON line with the agreed fields, the roofline object of the dominant kernel, the CPU
-baseline and the parity figures; also under torch.distributed.run with one rank (the RCCL init / barrier path)."""
+"""bench.py's driver contract: one JSON line with the agreed fields; with --full also the roofline object of the dominant
+kernel, the CPU baseline and the parity figures; also under torch.distributed.run with one rank (the RCCL init / barrier path);
+a plain run measures the headline only, and --dump-outputs writes the last timed step's arrays."""
 import json
 import os
 import subprocess
 import sys
+
+import numpy as np
 
 import pytest
 
@@ -20,7 +23,7 @@ def _line(cmd, env=None):
 
 
 def test_bench_line_has_the_contract_fields():
-    d = _line([sys.executable, "bench.py", "--steps", "6", "--warmup", "2", "--cpu-scenes", "1"])
+    d = _line([sys.executable, "bench.py", "--full", "--steps", "6", "--warmup", "2", "--cpu-scenes", "1"])
     for key, typ in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
                      ("ms_per_step", float), ("higher_is_better", bool), ("scaling", str), ("dtype", str), ("data", str),
                      ("config", dict), ("roofline", dict), ("cpu_baseline", dict)):
@@ -49,12 +52,12 @@ def test_bench_line_has_the_contract_fields():
 def test_bench_under_torch_distributed_run_single_rank():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     d = _line([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
-               "127.0.0.1", "--master-port", "29533", "bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1", "--cpu-scenes", "1"], env)
+               "127.0.0.1", "--master-port", "29533", "bench.py", "--full", "--gpus", "1", "--steps", "4", "--warmup", "1", "--cpu-scenes", "1"], env)
     assert d["n_gpus"] == 1 and d["steps"] == 4 and d["value"] > 0 and "cpu_baseline" in d
 
 
 def test_bench_line_carries_the_round3_fields():
-    d = _line([sys.executable, "bench.py", "--steps", "6", "--warmup", "2", "--cpu-scenes", "0", "--latency-runs", "0",
+    d = _line([sys.executable, "bench.py", "--full", "--steps", "6", "--warmup", "2", "--cpu-scenes", "0", "--latency-runs", "0",
                "--no-lookahead-steps", "4", "--train-steps", "6"])
     assert d["config"]["sampling_lookahead_batches"] == 6          # all six batches of the run were sampled by the first launch
     assert d["value_no_lookahead"] > 0 and "fps-group 1" in d["value_no_lookahead_note"]
@@ -81,7 +84,7 @@ def test_bench_line_carries_the_round3_fields():
 def test_bench_small_batch_replays_graphs_and_says_so():
     """One scene per batch: the geometry + feature stages are hipGraph replays (pipeline._StageGraphs); the line says so and
     takes its per-kernel accounting from extra launch-by-launch steps outside the timed region."""
-    d = _line([sys.executable, "bench.py", "--batch", "1", "--steps", "12", "--warmup", "3", "--cpu-scenes", "1", "--latency-runs", "0",
+    d = _line([sys.executable, "bench.py", "--full", "--batch", "1", "--steps", "12", "--warmup", "3", "--cpu-scenes", "1", "--latency-runs", "0",
                "--no-lookahead-steps", "0", "--train-steps", "0"])
     assert d["config"]["hip_graphs"] is True and d["config"]["batch_per_gpu"] == 1 and d["value"] > 0
     r = d["roofline"]
@@ -97,7 +100,7 @@ def test_bench_two_ranks_over_gloo_on_one_device():
     this checks that the line comes out and adds up, not its speed."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", REGNET_BENCH_ONE_DEVICE_GLOO="1")
     d = _line([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-               "127.0.0.1", "--master-port", "29544", "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1",
+               "127.0.0.1", "--master-port", "29544", "bench.py", "--full", "--gpus", "2", "--steps", "3", "--warmup", "1",
                "--batch", "2", "--points", "6144", "--train-steps", "2", "--train-batch", "1"], env)
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 4 and d["scaling"] == "weak"
     assert abs(d["value"] - 4 * 3 / (d["ms_per_step"] * 3 / 1e3)) < 1e-2 * d["value"]     # whole-job scenes / max-over-ranks time
@@ -112,3 +115,34 @@ def test_bench_two_ranks_over_gloo_on_one_device():
     assert c["probe_bytes"] == (7066927 + 128) * 4 and c["probe_allreduce_ms"] > 0 and c["bus_GBps"] > 0
     assert c["rccl_version"] is None                                # gloo here; under RCCL the version tuple is reported
     assert 28e6 < t["bucket_bytes"] < 29e6          # both networks' 7 066 927 gradients + one presence flag per parameter, fp32
+
+
+def test_plain_bench_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the line holds the headline (and no side measurement); --steps sets the timed steps; --dump-outputs
+    writes the last timed step's arrays (float32 / float64, at most 64 MB), the same ones for two runs with the same
+    arguments."""
+    dumps = []
+    for run in range(2):
+        out = tmp_path / ("run%d" % run)
+        d = _line([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2",
+                   "--dump-outputs", str(out)])
+        for key, typ in (("metric", str), ("value", float), ("unit", str), ("higher_is_better", bool), ("dtype", str),
+                         ("ms_per_step", float), ("steps", int), ("warmup", int)):
+            assert isinstance(d[key], typ), key
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "scenes/s" and d["dtype"] == "f32"
+        assert d["metric"].startswith("scenes/sec") and d["higher_is_better"] is True
+        assert abs(d["value"] - 2 * 3 / (d["ms_per_step"] * 3 / 1e3)) < 1e-2 * d["value"]
+        for key in ("roofline", "kernels", "cpu_baseline", "parity", "train", "latency_ms_single_scene", "value_no_lookahead",
+                    "real_density", "split_products"):
+            assert key not in d, key
+        files = sorted(p.name for p in out.iterdir())
+        assert files == sorted(name + ".npy" for name in d["dumped_outputs"])
+        assert "score.npy" in files and "all_feature.npy" in files and "next_grasp.npy" in files
+        arrays = {name: np.load(out / name) for name in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["score.npy"].shape == tuple(d["dumped_outputs"]["score"]) and arrays["score.npy"].size == 2 * 25600
+        dumps.append(arrays)
+    assert sorted(dumps[0]) == sorted(dumps[1])
+    np.testing.assert_allclose(dumps[0]["score.npy"], dumps[1]["score.npy"], rtol=0, atol=1e-5)
+    np.testing.assert_allclose(dumps[0]["all_feature.npy"], dumps[1]["all_feature.npy"], rtol=0, atol=1e-4)
