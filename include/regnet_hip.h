@@ -12,7 +12,7 @@
  *   - return value: 0 on success, REGNET_ERR_* (<0) for an argument the reference would have
  *     rejected with TORCH_CHECK / CHECK_EQ / CHECK_GT / CHECK_GE, or a positive hipError_t from
  *     the launch (the reference's THCudaCheck(cudaGetLastError())).  Never throws.
- *   - float data is fp32, indices are int64, xyz tensors are the reference's channel-first
+ *   - float data is fp32 (the _f64 operators: double), indices are int64, xyz tensors are the reference's channel-first
  *     (B,3,N) views addressed through explicit element strides (sb, sc, sn), so the
  *     non-contiguous views ScoreNet passes (score_network.py:46, pointnet2.py:89-90) need no copy.
  *
@@ -132,6 +132,50 @@ int regnet_gather_knn_fwd_f32(const float* input, int64_t sb, int64_t sc, int64_
 int regnet_gather_knn_bwd_f32(const float* grad_out, int64_t sb, int64_t sc, int64_t sn2,
                               int64_t sk, const int64_t* index, int64_t B, int64_t C, int64_t N,
                               int64_t NI, int64_t K, float* grad_in, void* stream);
+
+/* ---- float64 operators (csrc/ops_f64.hip) -------------------------------------------------------------------------------
+ * The reference dispatches every pn2_ext / dgcnn_ext kernel on float32 and float64 (AT_DISPATCH_FLOATING_TYPES).  These
+ * are the float64 instances: same arguments and semantics as the _f32 entry points above, with double data (indices stay
+ * int64), plus caller-provided scratch where noted.  Nothing here is reached by float32 data.
+ *   - distances are ((dx*dx) + (dy*dy)) + (dz*dz) in individually rounded double operations;
+ *   - regnet_fps_f64: the reference's tie order for its block of get_block(N) (min 16) threads, as regnet_fps_f32;
+ *     workspace of regnet_fps_f64_workspace_bytes(B, N, M) bytes (the running distances, initialised by the callee);
+ *   - regnet_ball_query_f64: `radius` is a float as in the reference (ball_query_kernel.cu:90): widened to double and
+ *     squared in double; strict d2 < r2;
+ *   - regnet_three_nn_f64: dist2 in double; the reference's initial {1e40, 0, 0} / {-1, 0, 0} state as it is;
+ *   - interpolate forward: ((+0 + x0*w0) + x1*w1) + x2*w2; weight (B,N,3) double, contiguous;
+ *   - the three backwards are deterministic: grad_in[b,c,n] = the sum of the contributions to n in ascending flattened
+ *     source position (group / gather_knn: m*K + k; interpolate: n*3 + k, adding the rounded product g*w), from +0.0 --
+ *     the bits of numpy's np.add.at.  grad_in is written whole (no zero fill needed).  Workspace of
+ *     regnet_scatter_f64_workspace_bytes(B, num_dest, num_src) bytes, 16-byte aligned (group / gather_knn: num_dest = N1
+ *     or N, num_src = N2*K or NI*K; interpolate: num_dest = M, num_src = N*3).  Source indices outside [0, num_dest)
+ *     contribute nothing; forward gathers read them as 0.                                                                 */
+int64_t regnet_fps_f64_workspace_bytes(int64_t B, int64_t N, int64_t M);
+int regnet_fps_f64(const double* xyz, int64_t sb, int64_t sc, int64_t sn, int64_t B, int64_t N, int64_t M,
+                   int64_t* index, double* workspace, void* stream);
+int regnet_ball_query_f64(const double* xyz, int64_t sb, int64_t sc, int64_t sn, const double* centroids, int64_t cb,
+                          int64_t cc, int64_t cn, int64_t B, int64_t N1, int64_t N2, float radius, int64_t K,
+                          int64_t* index, int64_t* count, void* stream);
+int regnet_three_nn_f64(const double* query, int64_t qb, int64_t qc, int64_t qn, const double* key, int64_t kb,
+                        int64_t kc, int64_t kn, int64_t B, int64_t N1, int64_t N2, int64_t* index, double* dist2,
+                        void* stream);
+int64_t regnet_scatter_f64_workspace_bytes(int64_t B, int64_t num_dest, int64_t num_src);
+int regnet_group_points_fwd_f64(const double* input, int64_t sb, int64_t sc, int64_t sn, const int64_t* index, int64_t B,
+                                int64_t C, int64_t N1, int64_t N2, int64_t K, double* out, void* stream);
+int regnet_group_points_bwd_f64(const double* grad_out, int64_t sb, int64_t sc, int64_t sn2, int64_t sk,
+                                const int64_t* index, int64_t B, int64_t C, int64_t N1, int64_t N2, int64_t K,
+                                double* grad_in, void* workspace, void* stream);
+int regnet_interpolate_fwd_f64(const double* input, int64_t sb, int64_t sc, int64_t sm, const int64_t* index,
+                               const double* weight, int64_t B, int64_t C, int64_t M, int64_t N, double* out,
+                               void* stream);
+int regnet_interpolate_bwd_f64(const double* grad_out, int64_t sb, int64_t sc, int64_t sn, const int64_t* index,
+                               const double* weight, int64_t B, int64_t C, int64_t M, int64_t N, double* grad_in,
+                               void* workspace, void* stream);
+int regnet_gather_knn_fwd_f64(const double* input, int64_t sb, int64_t sc, int64_t sn, const int64_t* index, int64_t B,
+                              int64_t C, int64_t N, int64_t NI, int64_t K, double* out, void* stream);
+int regnet_gather_knn_bwd_f64(const double* grad_out, int64_t sb, int64_t sc, int64_t sn2, int64_t sk,
+                              const int64_t* index, int64_t B, int64_t C, int64_t N, int64_t NI, int64_t K,
+                              double* grad_in, void* workspace, void* stream);
 
 /* ---- region grouping (host Python loops in the reference) -----------------------------------
  * regnet_radius_group_f32: dataset_utils/get_regiondataset.py:279-295,:311-352.

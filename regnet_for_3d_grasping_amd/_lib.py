@@ -36,7 +36,21 @@ SIGNATURES = {
     "regnet_interpolate_bwd_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
     "regnet_gather_knn_fwd_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
     "regnet_gather_knn_bwd_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
-    "regnet_radius_group_f32": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _f32, _i64, _vp, _vp,
+    "regnet_fps_f64_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "regnet_fps_f64": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "regnet_ball_query_f64": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i64,
+                                     _vp, _vp, _vp]),
+    "regnet_three_nn_f64": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "regnet_scatter_f64_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "regnet_group_points_fwd_f64": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "regnet_group_points_bwd_f64": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp,
+                                           _vp, _vp]),
+    "regnet_interpolate_fwd_f64": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "regnet_interpolate_bwd_f64": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "regnet_gather_knn_fwd_f64": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "regnet_gather_knn_bwd_f64": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp,
+                                         _vp]),
+    "regnet_radius_group_f32":(_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _f32, _i64, _vp, _vp,
                                        _vp]),
     "regnet_select_positive_f32": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
     "regnet_box_crop_f32": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _f32, _i64, _i64, _vp, _vp, _vp]),

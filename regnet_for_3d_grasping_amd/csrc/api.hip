@@ -1,7 +1,7 @@
 // api.hip -- library identification + error strings for libregnet_hip.so.
 #include "common.h"
 
-extern "C" int regnet_abi_version(void) { return 1; }
+extern "C" int regnet_abi_version(void) { return 2; }
 
 extern "C" const char* regnet_build_info(void) {
   return "libregnet_hip gfx950 (CDNA4, wave64) built " __DATE__ " " __TIME__;

@@ -26,20 +26,28 @@ _check = _lib.check
 _L = _lib.lib
 
 
+def _f32_weights(module):
+    p = next(module.parameters(), None)
+    return p is None or p.dtype == torch.float32
+
+
 def usable(module, xyz):
-    return ENABLED and xyz.is_cuda and not module.training and not torch.is_grad_enabled()
+    """The fused chains are float32 kernels: float64 tensors or weights take the operator-granular path."""
+    return (ENABLED and xyz.is_cuda and xyz.dtype == torch.float32 and not module.training and not torch.is_grad_enabled()
+            and _f32_weights(module))
 
 
 def supports_sa(module, feature):
     """True when the fused set-abstraction chain covers this module's configuration; otherwise the caller takes the
     operator-granular GPU path (pn2_ext group / torch conv), exactly like the reference."""
     grouper = getattr(module, "grouper", None)
-    return (grouper is not None and grouper.num_neighbours == 64 and len(module.mlp) >= 2
+    return (grouper is not None and grouper.num_neighbours == 64 and len(module.mlp) >= 2 and _f32_weights(module)
             and (feature is None or (module.use_xyz and feature.dtype == torch.float32)))
 
 
 def supports_fp(module, sparse_feature):
-    return sparse_feature.dtype == torch.float32 and getattr(module.interpolator, "num_neighbors", 0) == 3
+    return (sparse_feature.dtype == torch.float32 and _f32_weights(module)
+            and getattr(module.interpolator, "num_neighbors", 0) == 3)
 
 
 def _stream(t):

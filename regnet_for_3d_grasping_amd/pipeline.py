@@ -33,8 +33,18 @@ def build_models(device, score_seed=7, region_seed=11):
     return score_net.to(device).eval(), region_net.to(device).eval()
 
 
+def require_float32(pc, what):
+    """The inference pipeline, the training steps and the region stage are float32 paths (their kernels are fp32 only): a
+    float64 batch is refused here rather than computed on in another precision.  Returns ``pc``."""
+    if pc.dtype != torch.float32:
+        raise RuntimeError("%s is float32 only (got %s); float64 models run their forward / backward on the operator "
+                           "path, without the pipeline" % (what, pc.dtype))
+    return pc
+
+
 def forward_scenes(score_net, region_net, pc, with_region=True):
     """pc (B,N,6) -> dict(all_feature, score, centres, next_grasp, select_grasp_class, ...)."""
+    require_float32(pc, "forward_scenes")
     with torch.no_grad():
         all_feature, score, _ = score_net(pc)
         out = {"all_feature": all_feature, "score": score}
@@ -523,7 +533,7 @@ class ForwardPipeline:
                     want = first_want if first_launch else group
                     while first_want <= 0 or len(pcs) < want:
                         try:
-                            pcs.append(next(it))
+                            pcs.append(require_float32(next(it), "ForwardPipeline.run"))
                         except StopIteration:
                             exhausted = True
                             break

@@ -5,6 +5,11 @@ Same names, argument order, shapes, dtypes and error behaviour as the CUDA exten
 inputs must be GPU tensors (the reference's CHECK_CUDA -- there is no CPU path), may be
 non-contiguous views, are never modified; outputs are freshly allocated; failed checks raise
 RuntimeError.  Kernels are enqueued on torch's current stream of the input's device.
+
+dtypes: float32 or float64, like the reference's AT_DISPATCH_FLOATING_TYPES.  float32 runs the tuned kernels
+(csrc/geometry.hip, grid.hip, gather.hip); float64 runs csrc/ops_f64.hip (same semantics, deterministic
+backwards: see include/regnet_hip.h).  All float inputs of one call share one dtype (mixing raises, as the
+reference's ``data<scalar_t>()`` does); float outputs take it, index / count outputs are int64.
 """
 import torch
 
@@ -36,6 +41,17 @@ def _need_f32(t, name):
         raise RuntimeError("%s must be float32 (REGNet's path is fp32 only)" % name)
 
 
+def _need_float(t, name, like=None):
+    """float32 or float64 GPU tensor (the reference's AT_DISPATCH_FLOATING_TYPES), of the dtype of ``like`` when given.
+    -> True for float64."""
+    _need_gpu(t, name)
+    if t.dtype not in (torch.float32, torch.float64):
+        raise RuntimeError("%s must be float32 or float64" % name)
+    if like is not None and t.dtype != like.dtype:
+        raise RuntimeError("%s is %s but the other float inputs are %s" % (name, t.dtype, like.dtype))
+    return t.dtype == torch.float64
+
+
 def _need_i64(t, name):
     _need_gpu(t, name)
     if t.dtype != torch.int64:
@@ -60,8 +76,8 @@ class FpsChain:
 
 def farthest_point_sample(points, num_centroids, chain=None):
     """points (B,3,N1) -> index (B,N2) int64.  csrc/sampling_kernel.cu:126-170.  ``chain``: see FpsChain (not part of the
-    reference's signature; the result does not depend on it)."""
-    _need_f32(points, "points")
+    reference's signature; the result does not depend on it; float32 only)."""
+    f64 = _need_float(points, "points")
     _eq(points.dim(), 3, "points must be (B, 3, N)")
     _eq(points.size(1), 3, "points.size(1) does not equal to 3")
     B, _, N = points.shape
@@ -70,6 +86,16 @@ def farthest_point_sample(points, num_centroids, chain=None):
         raise RuntimeError("num_centroids is not greater than 0")
     if not N >= M:
         raise RuntimeError("num_points is less than num_centroids")
+    if f64:
+        if chain is not None:
+            raise RuntimeError("FpsChain is a float32 mechanism; float64 points take no chain")
+        with torch.cuda.device(points.device):
+            index = torch.empty((B, M), dtype=torch.int64, device=points.device)
+            ws = torch.empty((max(_L.regnet_fps_f64_workspace_bytes(B, N, M) // 8, 1),), dtype=torch.float64,
+                             device=points.device)
+            _check(_L.regnet_fps_f64(points.data_ptr(), *points.stride(), B, N, M, index.data_ptr(), ws.data_ptr(),
+                                     _stream(points)), "farthest_point_sample")
+        return index
     with torch.cuda.device(points.device):
         index = torch.empty((B, M), dtype=torch.int64, device=points.device)
         ws_bytes = _L.regnet_fps_workspace_bytes(B, N, M)
@@ -160,8 +186,8 @@ def raise_if_fps_failed():
 def ball_query(points, centroids, radius, num_neighbours):
     """points (B,3,N1), centroids (B,3,N2) -> [index (B,N2,K) int64, count (B,N2) int64].
     csrc/ball_query_kernel.cu:87-131."""
-    _need_f32(points, "points")
-    _need_f32(centroids, "centroids")
+    f64 = _need_float(points, "points")
+    _need_float(centroids, "centroids", points)
     _eq(points.size(1), 3, "points.size(1) does not equal to 3")
     _eq(centroids.size(1), 3, "centroids.size(1) does not equal to 3")
     _eq(centroids.size(0), points.size(0), "centroids.size(0) does not equal to batch_size")
@@ -171,7 +197,11 @@ def ball_query(points, centroids, radius, num_neighbours):
     with torch.cuda.device(points.device):
         index = torch.empty((B, N2, K), dtype=torch.int64, device=points.device)
         count = torch.empty((B, N2), dtype=torch.int64, device=points.device)
-        if N1 >= GRID_MIN_POINTS_BALL and K <= 64 and B > 0 and float(radius) > 0:
+        if f64:
+            _check(_L.regnet_ball_query_f64(points.data_ptr(), *points.stride(), centroids.data_ptr(),
+                                            *centroids.stride(), B, N1, N2, float(radius), K, index.data_ptr(),
+                                            count.data_ptr(), _stream(points)), "ball_query")
+        elif N1 >= GRID_MIN_POINTS_BALL and K <= 64 and B > 0 and float(radius) > 0:
             ws = torch.empty((_L.regnet_grid_workspace_bytes(B, N1),), dtype=torch.uint8, device=points.device)
             _check(_L.regnet_ball_query_grid_f32(points.data_ptr(), *points.stride(), centroids.data_ptr(),
                                                  *centroids.stride(), B, N1, N2, float(radius), K,
@@ -186,7 +216,7 @@ def ball_query(points, centroids, radius, num_neighbours):
 
 def group_points_forward(input, index):
     """input (B,C,N1), index (B,N2,K) -> (B,C,N2,K).  csrc/grouping_kernel.cu:29-51."""
-    _need_f32(input, "input")
+    f64 = _need_float(input, "input")
     _need_i64(index, "index")
     _eq(input.dim(), 3, "input.dim() does not equal to 3")
     _eq(index.dim(), 3, "index.dim() does not equal to 3")
@@ -195,6 +225,11 @@ def group_points_forward(input, index):
     _, N2, K = index.shape
     with torch.cuda.device(input.device):
         idx = index.contiguous()
+        if f64:
+            out = torch.empty((B, C, N2, K), dtype=torch.float64, device=input.device)
+            _check(_L.regnet_group_points_fwd_f64(input.data_ptr(), *input.stride(), idx.data_ptr(), B, C, N1, N2, K,
+                                                  out.data_ptr(), _stream(input)), "group_points_forward")
+            return out
         out = torch.empty((B, C, N2, K), dtype=torch.float32, device=input.device)
         _check(_L.regnet_group_points_fwd_f32(input.data_ptr(), *input.stride(), idx.data_ptr(), B, C, N1, N2, K,
                                               out.data_ptr(), _stream(input)), "group_points_forward")
@@ -202,8 +237,9 @@ def group_points_forward(input, index):
 
 
 def group_points_backward(grad_output, index, num_points):
-    """grad_output (B,C,N2,K), index (B,N2,K) -> grad_input (B,C,N1).  csrc/grouping_kernel.cu:103-149."""
-    _need_f32(grad_output, "grad_output")
+    """grad_output (B,C,N2,K), index (B,N2,K) -> grad_input (B,C,N1).  csrc/grouping_kernel.cu:103-149.  float64: summed
+    in ascending (n2, k) order per destination, run to run bit-identical."""
+    f64 = _need_float(grad_output, "grad_output")
     _need_i64(index, "index")
     _eq(grad_output.dim(), 4, "grad_output.dim() does not equal to 4")
     _eq(index.dim(), 3, "index.dim() does not equal to 3")
@@ -214,6 +250,13 @@ def group_points_backward(grad_output, index, num_points):
     N1 = int(num_points)
     with torch.cuda.device(grad_output.device):
         idx = index.contiguous()
+        if f64:
+            grad_in = torch.empty((B, C, N1), dtype=torch.float64, device=grad_output.device)
+            ws = _scatter_workspace(B, N1, N2 * K, grad_output.device)
+            _check(_L.regnet_group_points_bwd_f64(grad_output.data_ptr(), *grad_output.stride(), idx.data_ptr(), B, C,
+                                                  N1, N2, K, grad_in.data_ptr(), ws.data_ptr(), _stream(grad_output)),
+                   "group_points_backward")
+            return grad_in
         grad_in = torch.empty((B, C, N1), dtype=torch.float32, device=grad_output.device)
         _check(_L.regnet_group_points_bwd_f32(grad_output.data_ptr(), *grad_output.stride(), idx.data_ptr(), B, C,
                                               N1, N2, K, grad_in.data_ptr(), _stream(grad_output)),
@@ -221,11 +264,17 @@ def group_points_backward(grad_output, index, num_points):
     return grad_in
 
 
+def _scatter_workspace(B, num_dest, num_src, device):
+    """Scratch of the deterministic float64 backwards (include/regnet_hip.h: regnet_scatter_f64_workspace_bytes)."""
+    n = _L.regnet_scatter_f64_workspace_bytes(B, num_dest, num_src)
+    return torch.empty((max(n, 16),), dtype=torch.uint8, device=device)
+
+
 def point_search(query_xyz, key_xyz, num_neighbours):
     """query (B,3,N1), key (B,3,N2) -> [index (B,N1,3) int64, squared distance (B,N1,3)].
     csrc/interpolate_kernel.cu:88-128."""
-    _need_f32(query_xyz, "query_xyz")
-    _need_f32(key_xyz, "key_xyz")
+    f64 = _need_float(query_xyz, "query_xyz")
+    _need_float(key_xyz, "key_xyz", query_xyz)
     B, _, N1 = query_xyz.shape
     N2 = key_xyz.size(2)
     _eq(key_xyz.size(0), B, "key_xyz.size(0) does not equal to batch_size")
@@ -236,6 +285,12 @@ def point_search(query_xyz, key_xyz, num_neighbours):
         raise RuntimeError("num_key is less than num_neighbours")
     with torch.cuda.device(query_xyz.device):
         index = torch.empty((B, N1, 3), dtype=torch.int64, device=query_xyz.device)
+        if f64:
+            dist = torch.empty((B, N1, 3), dtype=torch.float64, device=query_xyz.device)
+            _check(_L.regnet_three_nn_f64(query_xyz.data_ptr(), *query_xyz.stride(), key_xyz.data_ptr(),
+                                          *key_xyz.stride(), B, N1, N2, index.data_ptr(), dist.data_ptr(),
+                                          _stream(query_xyz)), "point_search")
+            return [index, dist]
         dist = torch.empty((B, N1, 3), dtype=torch.float32, device=query_xyz.device)
         if N2 >= GRID_MIN_POINTS and B > 0:
             ws = torch.empty((_L.regnet_grid_workspace_bytes(B, N2),), dtype=torch.uint8, device=query_xyz.device)
@@ -251,7 +306,7 @@ def point_search(query_xyz, key_xyz, num_neighbours):
 
 def _check_interp(first, index, weight, B, N):
     _need_i64(index, "index")
-    _need_f32(weight, "weight")
+    _need_float(weight, "weight", first)
     _eq(index.size(0), B, "index.size(0) does not equal to batch_size")
     _eq(index.size(2), 3, "index.size(2) does not equal to K")
     _eq(weight.size(0), B, "weight.size(0) does not equal to batch_size")
@@ -261,12 +316,17 @@ def _check_interp(first, index, weight, B, N):
 
 def interpolate_forward(input, index, weight):
     """input (B,C,M), index/weight (B,N,3) -> (B,C,N).  csrc/interpolate_kernel.cu:187-232."""
-    _need_f32(input, "input")
+    f64 = _need_float(input, "input")
     B, C, M = input.shape
     N = index.size(1)
     _check_interp(input, index, weight, B, N)
     with torch.cuda.device(input.device):
         idx, w = index.contiguous(), weight.contiguous()
+        if f64:
+            out = torch.empty((B, C, N), dtype=torch.float64, device=input.device)
+            _check(_L.regnet_interpolate_fwd_f64(input.data_ptr(), *input.stride(), idx.data_ptr(), w.data_ptr(), B, C,
+                                                 M, N, out.data_ptr(), _stream(input)), "interpolate_forward")
+            return out
         out = torch.empty((B, C, N), dtype=torch.float32, device=input.device)
         _check(_L.regnet_interpolate_fwd_f32(input.data_ptr(), *input.stride(), idx.data_ptr(), w.data_ptr(), B, C,
                                              M, N, out.data_ptr(), _stream(input)), "interpolate_forward")
@@ -274,13 +334,21 @@ def interpolate_forward(input, index, weight):
 
 
 def interpolate_backward(grad_output, index, weight, num_inst):
-    """grad_output (B,C,N) -> grad_input (B,C,M).  csrc/interpolate_kernel.cu:292-337."""
-    _need_f32(grad_output, "grad_output")
+    """grad_output (B,C,N) -> grad_input (B,C,M).  csrc/interpolate_kernel.cu:292-337.  float64: summed in ascending
+    (n, k) order per destination, run to run bit-identical."""
+    f64 = _need_float(grad_output, "grad_output")
     B, C, N = grad_output.shape
     _check_interp(grad_output, index, weight, B, N)
     M = int(num_inst)
     with torch.cuda.device(grad_output.device):
         idx, w = index.contiguous(), weight.contiguous()
+        if f64:
+            grad_in = torch.empty((B, C, M), dtype=torch.float64, device=grad_output.device)
+            ws = _scatter_workspace(B, M, N * 3, grad_output.device)
+            _check(_L.regnet_interpolate_bwd_f64(grad_output.data_ptr(), *grad_output.stride(), idx.data_ptr(),
+                                                 w.data_ptr(), B, C, M, N, grad_in.data_ptr(), ws.data_ptr(),
+                                                 _stream(grad_output)), "interpolate_backward")
+            return grad_in
         grad_in = torch.empty((B, C, M), dtype=torch.float32, device=grad_output.device)
         _check(_L.regnet_interpolate_bwd_f32(grad_output.data_ptr(), *grad_output.stride(), idx.data_ptr(),
                                              w.data_ptr(), B, C, M, N, grad_in.data_ptr(), _stream(grad_output)),

@@ -59,6 +59,7 @@ class PointNet2Seg(nn.Module):
         xyz = points[:, :3, :]
         if not (fused.ENABLED and xyz.is_cuda):
             raise RuntimeError("PointNet2Seg.sample_level1 needs GPU tensors")
+        _need_f32_geometry(xyz, "sample_level1")
         with torch.no_grad():
             return fused.sa_sample(self.sa_modules[0], xyz)[0]
 
@@ -70,6 +71,7 @@ class PointNet2Seg(nn.Module):
         xyz = points[:, :3, :]
         if not (fused.ENABLED and xyz.is_cuda):
             raise RuntimeError("PointNet2Seg.sample_levels needs GPU tensors")
+        _need_f32_geometry(xyz, "sample_levels")
         ctrs = []
         first_tie = None         # of the level above: levels 2+ sample that level's picks in pick order (fused.sa_sample)
         with torch.no_grad():
@@ -93,6 +95,7 @@ class PointNet2Seg(nn.Module):
         xyz = points[:, :3, :]
         if not (fused.ENABLED and xyz.is_cuda):
             raise RuntimeError("PointNet2Seg.plan needs GPU tensors")
+        _need_f32_geometry(xyz, "plan")
         with torch.no_grad():
             return self._plan(xyz, level1_ctr, on_level)
 
@@ -183,6 +186,13 @@ class PointNet2Seg(nn.Module):
             x = self.bn_score(x)
         score = self.sigmoid(x.transpose(2, 1).contiguous()).view(B, N)
         return sparse_feature, score
+
+
+def _need_f32_geometry(xyz, what):
+    """Geometry plans feed the fused float32 chains and the fp32 pipeline; a float64 model runs forward() without one."""
+    if xyz.dtype != torch.float32:
+        raise RuntimeError("PointNet2Seg.%s is float32 only (got %s); a float64 model takes the operator path: call "
+                           "forward() without a plan" % (what, xyz.dtype))
 
 
 def _wait_ready(geo):

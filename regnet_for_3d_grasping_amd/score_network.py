@@ -16,8 +16,9 @@ class ScoreNetwork(nn.Module):
         self.criterion_reg = nn.MSELoss(reduction="mean")
 
     def compute_loss(self, pscore, tscore):
-        """MSE between predicted and target per-point score (score_network.py:18-29)."""
-        return self.criterion_reg(pscore, tscore.float())
+        """MSE between predicted and target per-point score (score_network.py:18-29).  The target takes the prediction's
+        dtype: float32 as in the reference (``tscore.float()``), float64 for a ``.double()`` model."""
+        return self.criterion_reg(pscore, tscore.to(pscore.dtype))
 
     def sample_level1(self, pc):
         """Level-1 FPS indices for ``pc``; see PointNet2Seg.sample_level1."""

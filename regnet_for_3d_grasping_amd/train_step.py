@@ -358,6 +358,8 @@ class ScoreTrainer:
             self.bucket = GradientBucket([self.net], self.reduce)
 
     def step(self, pc, pc_score, pc_label=None, plan=None):
+        from .pipeline import require_float32
+        require_float32(pc, "ScoreTrainer.step")
         self.net.train()
         self._ensure_bucket()
         if self.bucket is None:
@@ -797,6 +799,8 @@ class RefineTrainer:
             self._marks[name] = ev
 
     def step(self, pc, pc_score, grasp_records, plan=None):
+        from .pipeline import require_float32
+        require_float32(pc, "RefineTrainer.step")
         self.score_net.train()
         self.region_net.train()
         self._ensure_bucket()
