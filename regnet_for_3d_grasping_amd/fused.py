@@ -100,9 +100,16 @@ def _tickets(device, n=1):
 
 
 class _Layer:
-    """One conv(1x1, bias-free or biased) + eval BatchNorm (+ReLU) packed for the GEMM kernel."""
+    """One conv(1x1, bias-free or biased) + eval BatchNorm (+ReLU) packed for the GEMM kernel.  ``derived``: packs computed
+    from this one (see ``_derived``), which therefore go away with it."""
 
-    __slots__ = ("W", "W8", "scale", "shift", "N", "K", "Kpad", "relu", "premul")
+    __slots__ = ("W", "W8", "scale", "shift", "N", "K", "Kpad", "relu", "derived")
+
+    def __init__(self, **fields):
+        self.W8 = None
+        self.derived = {}
+        for name, value in fields.items():
+            setattr(self, name, value)
 
 
 def _pack(conv, bn, relu, col_order=None):
@@ -111,8 +118,7 @@ def _pack(conv, bn, relu, col_order=None):
     if col_order is not None:
         w = w[:, col_order]
         K = w.shape[1]
-    L = _Layer()
-    L.N, L.K, L.Kpad, L.relu = N, K, _round_up(max(K, 1), 16), 1 if relu else 0
+    L = _Layer(N=N, K=K, Kpad=_round_up(max(K, 1), 16), relu=1 if relu else 0)
     Wp = torch.zeros((_round_up(N, 128), L.Kpad), dtype=torch.float32, device=w.device)
     Wp[:N, :K] = w
     if bn is not None:
@@ -124,8 +130,6 @@ def _pack(conv, bn, relu, col_order=None):
     if conv.bias is not None:
         shift = shift + conv.bias.detach().float() * scale
     L.W, L.scale, L.shift = Wp.contiguous(), scale.contiguous(), shift.contiguous()
-    L.W8 = None
-    L.premul = None
     if K <= 8:  # narrow first layer: also keep the [N][8] form consumed by the layer-1-fused gather kernel
         W8 = torch.zeros((N, 8), dtype=torch.float32, device=w.device)
         W8[:, :K] = w
@@ -153,21 +157,34 @@ def forget(*nets):
                 m.__dict__.pop("_regnet_sig_tensors", None)
 
 
+def _cached(owner, slot, sig, build):
+    """The pack ``slot`` of module ``owner``: ``build()``'s value, rebuilt whenever ``sig`` (a ``_signature`` of the modules
+    whose weights it is made of) differs from the one it was built with.  Every pack of a module lives in one dict,
+    ``owner._regnet_packs``: slot -> (sig, value)."""
+    packs = owner.__dict__.setdefault("_regnet_packs", {})
+    entry = packs.get(slot)
+    if entry is None or entry[0] != sig:
+        entry = packs[slot] = (sig, build())
+    return entry[1]
+
+
+def _derived(layer, key, build):
+    """A pack computed from the packed layer ``layer`` (and from nothing but its stack pack), kept on it: it lives exactly as
+    long as that layer pack."""
+    if key not in layer.derived:
+        layer.derived[key] = build()
+    return layer.derived[key]
+
+
 def _packed_stack(owner, stack, first_col_order=None):
     """Packed layers of a SharedMLP (list of conv/bn/relu blocks), cached on ``owner`` and rebuilt
     whenever a parameter or BN buffer is modified (in-place updates bump ``_version``).
     ``first_col_order``: optional callable returning the column permutation of the first layer (only
     evaluated on a cache miss -- it involves a host->device copy, which would stall the stream)."""
-    sig = _signature(stack)
-    cache = getattr(owner, "_regnet_packed", None)
-    if cache is None or cache[0] != sig:
-        layers = []
+    def build():
         order = first_col_order() if first_col_order is not None else None
-        for i, block in enumerate(stack):
-            layers.append(_pack(block.conv, block.bn, block.relu is not None, order if i == 0 else None))
-        cache = (sig, layers)
-        owner._regnet_packed = cache
-    return cache[1]
+        return [_pack(block.conv, block.bn, block.relu is not None, order if i == 0 else None) for i, block in enumerate(stack)]
+    return _cached(owner, "stack", _signature(stack), build)
 
 
 # ---- thin kernel wrappers (module-level names so bench.py can bracket them with events) ------
@@ -231,16 +248,14 @@ def sa_layer12(feature, xyz, nbr, ctr, first, layer, B, M, group, pool_group=0):
 def _premul_layers(first, Cf):
     """Derived packings of a set-abstraction block's first layer (columns [feature | xyz]) for the
     per-source-point evaluation: ``u`` = scale * W [f | x] (no shift, no ReLU) and ``v`` = scale * Wx x_c - shift."""
-    if first.premul is None:
-        u, v = _Layer(), _Layer()
-        u.W, u.W8, u.premul, u.scale, u.N, u.K, u.Kpad, u.relu = first.W, None, None, first.scale, first.N, first.K, first.Kpad, 0
-        u.shift = torch.zeros_like(first.shift)
+    def build():
+        u = _Layer(W=first.W, scale=first.scale, shift=torch.zeros_like(first.shift), N=first.N, K=first.K, Kpad=first.Kpad,
+                   relu=0)
         Wx = torch.zeros((first.W.shape[0], 16), dtype=torch.float32, device=first.W.device)
         Wx[:, :3] = first.W[:, Cf:Cf + 3]
-        v.W, v.W8, v.premul, v.scale, v.N, v.K, v.Kpad, v.relu = Wx.contiguous(), None, None, first.scale, first.N, 3, 16, 0
-        v.shift = (-first.shift).contiguous()
-        first.premul = (u, v)
-    return first.premul
+        v = _Layer(W=Wx.contiguous(), scale=first.scale, shift=(-first.shift).contiguous(), N=first.N, K=3, Kpad=16, relu=0)
+        return u, v
+    return _derived(first, "premul", build)
 
 
 @_on_tensor_device
@@ -287,24 +302,22 @@ def chain3_order(count):
 # EXPERIMENT, off: the level-1 block with fp32-faithful products on the bf16 matrix pipe (csrc/sa_split.hip).  Never a
 # default path; bench.py reports it under its own name (value_split_products).
 SPLIT_PRODUCTS = False
-_split_planes = {}
 
 
 @_on_tensor_device
 def sa_chain3_split(feature, xyz, nbr, ctr, l1, l2, l3, B, M, group, count=None, order=None):
-    """``sa_chain3`` by ``regnet_sa_chain3_split_f32``; the weights' bf16 pieces are built once per packed-weight tensor pair."""
+    """``sa_chain3`` by ``regnet_sa_chain3_split_f32``; the weights' bf16 pieces are built by the kernel's first launch on
+    a layer pack (both layers are of the same stack pack: the planes are kept on ``l3``)."""
     out = torch.empty((B * M, l3.N), dtype=torch.float32, device=xyz.device)
     if feature is None:
         fptr, fb, fn, fc, Cf = None, 0, 0, 0, 0
     else:
         fptr, (fb, fc, fn), Cf = feature.data_ptr(), feature.stride(), feature.size(1)
-    key = (l2.W.data_ptr(), l2.W._version, l3.W.data_ptr(), l3.W._version)
-    planes = _split_planes.get(key)
+    planes = l3.derived.get("split_planes")
     build = planes is None
     if build:
-        _split_planes.clear()
-        planes = torch.empty((_L.regnet_sa_chain3_split_plane_bytes(l3.N),), dtype=torch.uint8, device=xyz.device)
-        _split_planes[key] = planes
+        planes = l3.derived["split_planes"] = torch.empty((_L.regnet_sa_chain3_split_plane_bytes(l3.N),), dtype=torch.uint8,
+                                                          device=xyz.device)
     _check(_L.regnet_sa_chain3_split_f32(fptr, fb, fn, fc, Cf, xyz.data_ptr(), *xyz.stride(), nbr.data_ptr(), ctr.data_ptr(),
                                          None if count is None else count.data_ptr(), None if order is None else order.data_ptr(), B, M,
                                          group, l1.W8.data_ptr(), l1.scale.data_ptr(), l1.shift.data_ptr(), l2.W.data_ptr(), l2.Kpad,
@@ -357,33 +370,30 @@ def interp_concat(sparse_cl, idx, dist2, eps, dense_feature, B, Nd):
 def _fp_split_layers(first, Cs):
     """Derived packings of a feature-propagation block's first layer (columns [interpolated | skip]):
     ``s`` = W[:, :Cs] and ``d`` = W[:, Cs:], both without affine / ReLU (applied after the interpolation)."""
-    if first.premul is None:
-        def part(cols):
-            L = _Layer()
-            K = cols.shape[1]
-            L.N, L.K, L.Kpad, L.relu, L.W8, L.premul = first.N, K, _round_up(max(K, 1), 16), 0, None, None
-            Wp = torch.zeros((first.W.shape[0], L.Kpad), dtype=torch.float32, device=first.W.device)
-            Wp[:, :K] = cols
-            L.W = Wp.contiguous()
-            L.scale = torch.ones_like(first.scale)
-            L.shift = torch.zeros_like(first.shift)
-            return L
+    def part(cols):
+        K, Kpad = cols.shape[1], _round_up(max(cols.shape[1], 1), 16)
+        Wp = torch.zeros((first.W.shape[0], Kpad), dtype=torch.float32, device=first.W.device)
+        Wp[:, :K] = cols
+        return _Layer(W=Wp.contiguous(), scale=torch.ones_like(first.scale), shift=torch.zeros_like(first.shift), N=first.N,
+                      K=K, Kpad=Kpad, relu=0)
+
+    def build():
         Cd = first.K - Cs
         wd4 = None
         if 0 < Cd <= 4:   # narrow skip input (rgb): multiplied inside the interpolation kernel
             wd4 = torch.zeros((first.N, 4), dtype=torch.float32, device=first.W.device)
             wd4[:, :Cd] = first.W[:first.N, Cs:first.K]
             wd4 = wd4.contiguous()
-        first.premul = (part(first.W[:, :Cs]), part(first.W[:, Cs:first.K]) if Cd > 4 else None, wd4)
-    return first.premul[:3]
+        return part(first.W[:, :Cs]), part(first.W[:, Cs:first.K]) if Cd > 4 else None, wd4
+    return _derived(first, "fp_split", build)
 
 
 def _interp_tables(first, wd4):
     """Wd4 (256 x 4) | scale1 (256) | shift1 (256): the tables of fp_head_chain_interp's prologue, cached on the layer."""
-    if len(first.premul) < 4:
+    def build():
         wd = wd4 if wd4 is not None else torch.zeros((256, 4), dtype=torch.float32, device=first.W.device)
-        first.premul = tuple(first.premul[:3]) + (torch.cat([wd.reshape(-1), first.scale[:256], first.shift[:256]]).contiguous(),)
-    return first.premul[3]
+        return torch.cat([wd.reshape(-1), first.scale[:256], first.shift[:256]]).contiguous()
+    return _derived(first, "interp_tables", build)
 
 
 @_on_tensor_device
@@ -407,17 +417,14 @@ def interp_affine(Ys, idx, dist2, eps, Yd, dense_small, wd4, layer, B, Ns, Nd):
 def _packed_head(seg):
     """conv_score weight + folded bn_score scalars, cached like the layer stacks (reading the
     scalars costs a device sync, so do it once per weight version, not per forward)."""
-    sig = _signature(seg.conv_score) + _signature(seg.bn_score)
-    cache = getattr(seg, "_regnet_head", None)
-    if cache is None or cache[0] != sig:
+    def build():
         conv, bn = seg.conv_score, seg.bn_score
         w = conv.weight.detach().reshape(-1).float().contiguous()
         bn_scale = float(bn.weight.detach()[0] / torch.sqrt(bn.running_var.detach()[0] + bn.eps))
         bn_shift = float(bn.bias.detach()[0] - bn.running_mean.detach()[0] * bn_scale)
         bias = float(conv.bias.detach()[0]) if conv.bias is not None else 0.0
-        cache = (sig, (w, bias, bn_scale, bn_shift))
-        seg._regnet_head = cache
-    return cache[1]
+        return w, bias, bn_scale, bn_shift
+    return _cached(seg, "score_head", _signature(seg.conv_score) + _signature(seg.bn_score), build)
 
 
 @_on_tensor_device
@@ -507,9 +514,9 @@ def sa_group(module, xyz, ctr, first_tie=None):
             geo["mu"] = xyz.mean(dim=2, keepdim=True) if PREMUL_CENTRE else None
             geo["V"] = mlp_layer(pack_rows(None, new_xyz, 4, geo["mu"]), 4, v_layer, B * M)
             # V = W_xyz . centre with the first layer's BatchNorm folded in: a function of the WEIGHTS too, unlike the rest
-            # of the plan.  sa_features recomputes it when the block's weights changed since (a plan reused across an
-            # optimizer step / load_state_dict)
-            geo["V_signature"] = _signature(module.mlp)
+            # of the plan.  The plan keeps the pack it was made with; sa_features recomputes V when the block's pack is
+            # another one by then (the weights changed: a plan reused across an optimizer step / load_state_dict)
+            geo["V_layer"] = v_layer
     return geo
 
 
@@ -560,7 +567,7 @@ def sa_features(module, xyz, feature, geo):
         # U[j] - V[c] = s W [f_j | x_j - x_c] - t only up to fp32 rounding of the two big terms: both sides use the
         # coordinates RELATIVE TO THE SCENE'S MEAN (the difference is unchanged, the magnitudes -- table-top scenes sit
         # ~0.75 m from the origin -- and with them the cancellation error of the subtraction shrink)
-        if "V" in geo and geo.get("V_signature") == _signature(module.mlp):
+        if "V" in geo and geo.get("V_layer") is v_layer:
             mu, V = geo["mu"], geo["V"]                  # already done by the geometry stage (sa_group), same weights
         elif "V" in geo:                                 # stale: the weights moved after the plan was made
             mu = geo["mu"]
@@ -668,18 +675,15 @@ def head_forward(seg, sparse_feature):
 # ---- level-2 set-abstraction block: layers 2 + 3 + pooling as ONE kernel (csrc/rowchain.hip) ---------------------------
 def _packed_sa_chain(module, layers):
     """Weight stream (24 stages [32 rows][256 k], layer 2 then layer 3) + affine table of sa_premul_chain."""
-    sig = _signature(module.mlp)
-    cache = getattr(module, "_regnet_sa_chain", None)
-    if cache is None or cache[0] != sig:
+    def build():
         l2, l3 = layers[1], layers[2]
         stages = [_swizzle_stage(l2.W[32 * s:32 * s + 32, :256]) for s in range(8)]
         stages += [_swizzle_stage(l3.W[32 * s:32 * s + 32, :256]) for s in range(16)]
         stream = torch.cat(stages).contiguous()
         affine = torch.cat([l2.scale[:256], l2.shift[:256], l3.scale[:512], l3.shift[:512]]).contiguous()
         assert stream.numel() == _L.regnet_sa_premul_chain_stream_floats() and affine.numel() == 1536
-        cache = (sig, (stream, affine))
-        module._regnet_sa_chain = cache
-    return cache[1]
+        return stream, affine
+    return _cached(module, "sa_chain", _signature(module.mlp), build)
 
 
 def supports_sa_chain(layers):
@@ -704,18 +708,15 @@ def sa_premul_chain(U, V, nbr, module, layers, B, Nsrc, M):
 def _packed_sa3_chain(module, layers):
     """Weight stream (96 stages [32 rows][256 k]: W2 as (K-half, 16 row blocks), W3 as (32 row blocks, K-half)) + affine
     table of sa3_premul_chain."""
-    sig = _signature(module.mlp)
-    cache = getattr(module, "_regnet_sa3_chain", None)
-    if cache is None or cache[0] != sig:
+    def build():
         l2, l3 = layers[1], layers[2]
         stages = [_swizzle_stage(l2.W[32 * rg:32 * rg + 32, 256 * kh:256 * kh + 256]) for kh in range(2) for rg in range(16)]
         stages += [_swizzle_stage(l3.W[32 * s:32 * s + 32, 256 * kh:256 * kh + 256]) for s in range(32) for kh in range(2)]
         stream = torch.cat(stages).contiguous()
         affine = torch.cat([l2.scale[:512], l2.shift[:512], l3.scale[:1024], l3.shift[:1024]]).contiguous()
         assert stream.numel() == _L.regnet_sa3_premul_chain_stream_floats() and affine.numel() == 3072
-        cache = (sig, (stream, affine))
-        module._regnet_sa3_chain = cache
-    return cache[1]
+        return stream, affine
+    return _cached(module, "sa3_chain", _signature(module.mlp), build)
 
 
 def supports_sa3_chain(layers):
@@ -769,20 +770,17 @@ def _rowchain_pair_stream(la, lb):
 
 def _packed_rowchain(seg, fp_layers):
     """Weight stream + affine table of the FP3-tail + head chain, cached on ``seg`` per weight version."""
-    head = _packed_stack(seg.mlp, seg.mlp)
-    layers = list(fp_layers[1:]) + list(head)
-    sig = _signature(seg.fp_modules[-1]) + _signature(seg.mlp)
-    cache = getattr(seg, "_regnet_rowchain", None)
-    if cache is None or cache[0] != sig:
+    layers = list(fp_layers[1:]) + list(_packed_stack(seg.mlp, seg.mlp))
+
+    def build():
         stages = []
         for a, b in ((layers[0], layers[1]), (layers[2], layers[3]), (layers[4], layers[5])):
             stages += _rowchain_pair_stream(a, b)
         stream = torch.cat(stages).contiguous()
         affine = torch.cat([torch.cat([L.scale[:L.N], L.shift[:L.N]]) for L in layers]).contiguous()
         assert stream.numel() == _L.regnet_fp_head_chain_stream_floats() and affine.numel() == 3328
-        cache = (sig, (stream, affine))
-        seg._regnet_rowchain = cache
-    return cache[1]
+        return stream, affine
+    return _cached(seg, "rowchain", _signature(seg.fp_modules[-1]) + _signature(seg.mlp), build)
 
 
 def supports_rowchain(seg, fp_module):
@@ -928,8 +926,8 @@ def prepack(score_net, region_net=None):
     if supports_rowchain(seg, seg.fp_modules[-1]):
         _packed_rowchain(seg, _packed_stack(seg.fp_modules[-1], seg.fp_modules[-1].mlp))
     if region_net is not None:
-        _packed_named(region_net.extrat_feature_region, _TWOSTAGE)
-        _packed_named(region_net.extrat_feature_refine, _REFINE)
+        _packed_named(region_net.extrat_feature_region, _TWOSTAGE, _TWOSTAGE_TREE)
+        _packed_named(region_net.extrat_feature_refine, _REFINE, _REFINE_TREE)
 
 
 def plan_tensors(plan):
@@ -942,14 +940,20 @@ def plan_tensors(plan):
 
 # ---- grasp-region / refine heads (tiny GEMMs: P = #centres; kept on the same kernel so the whole
 #      forward is deterministic and independent of the torch convolution backend) -----------------
-def _packed_named(net, names):
-    """names: list of (conv_attr, bn_attr, relu).  Cached on ``net`` like the SharedMLP stacks."""
-    sig = _signature(net)
-    cache = getattr(net, "_regnet_heads", None)
-    if cache is None or cache[0] != sig:
-        cache = (sig, {c: _pack(getattr(net, c), getattr(net, b), relu) for c, b, relu in names})
-        net._regnet_heads = cache
-    return cache[1]
+def _packed_named(net, names, tree):
+    """names: list of (conv_attr, bn_attr, relu).  Cached on ``net`` like the SharedMLP stacks.  ``tree``: (trunk, (a, b)) of
+    heads_tree_kernel (see _heads_tree); when the layers' shapes suit that kernel, the pack also holds the two branches'
+    first layers a and b as ONE layer under the key (a, b): weights and folded BatchNorm concatenated row-wise."""
+    def build():
+        L = {c: _pack(getattr(net, c), getattr(net, bn), relu) for c, bn, relu in names}
+        trunk, (a, b) = tree
+        la, lb, lt = L[a], L[b], L[trunk]
+        if (lt.N % 256 == 0 and la.K == lb.K == lt.N and la.relu == lb.relu and la.N % 16 == 0
+                and la.N + lb.N in (256, 512)):
+            L[a, b] = _Layer(W=torch.cat([la.W[:la.N], lb.W[:lb.N]]), scale=torch.cat([la.scale, lb.scale]),
+                             shift=torch.cat([la.shift, lb.shift]), N=la.N + lb.N, K=la.K, Kpad=la.Kpad, relu=la.relu)
+        return L
+    return _cached(net, "heads", _signature(net), build)
 
 
 _TWOSTAGE = [("conv", "bn", True), ("conv_cls2", "bn_cls2", True), ("conv_cls3", "bn_cls3", True),
@@ -958,6 +962,8 @@ _TWOSTAGE = [("conv", "bn", True), ("conv_cls2", "bn_cls2", True), ("conv_cls3",
 _REFINE = [("conv_formal", "bn_formal", True), ("conv_formal_cls2", "bn_formal_cls2", True),
            ("conv_formal_cls3", "bn_formal_cls3", False), ("conv_formal_reg2", "bn_formal_reg2", True),
            ("conv_formal_reg3", "bn_formal_reg3", False)]
+_TWOSTAGE_TREE = ("conv", ("conv_cls2", "conv_reg2"))
+_REFINE_TREE = ("conv_formal", ("conv_formal_cls2", "conv_formal_reg2"))
 
 
 FPS_CHAIN = True     # levels 2+ hand the level above's sampling certificate down (sa_sample): no sampling unless it had a tie
@@ -992,25 +998,15 @@ HEADS_TREE = True    # more rows than HEADS_CHAIN_MAX_ROWS: ONE launch of csrc/h
                      # the trunk activation chunked through LDS) instead of a split-K GEMM + its reduction per layer
 
 
-def _heads_tree(net, x, L, trunk, first, tails, n_a, n_b):
-    """x (n, K) rows -> (out_a (n, n_a), out_b (n, n_b)) by ``regnet_heads_tree_f32``.  ``trunk``: layer name; ``first``: the
-    two branches' first layers (their packed weights / folded BatchNorm concatenated row-wise, cached on ``net`` with the
-    packed layers' signature); ``tails``: [(layer, src, src_off, dst, dst_off)] in execution order."""
+def _heads_tree(x, L, tree, tails, n_a, n_b):
+    """x (n, K) rows -> (out_a (n, n_a), out_b (n, n_b)) by ``regnet_heads_tree_f32``.  ``tree``: (trunk layer name, the two
+    branches' first layer names), whose joined layer ``_packed_named`` put in ``L``; ``tails``: [(layer, src, src_off, dst,
+    dst_off)] in execution order."""
     n = x.shape[0]
     x = x if x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 else x.contiguous().clone()
-    la, lb = L[first[0]], L[first[1]]
-    cache = getattr(net, "_regnet_heads_tree", None)
-    key = (la.W.data_ptr(), lb.W.data_ptr(), la.scale.data_ptr(), lb.scale.data_ptr())
-    if cache is None or cache[0] != key:
-        joined = (torch.cat([la.W[:la.N], lb.W[:lb.N]]).contiguous(), torch.cat([la.scale, lb.scale]).contiguous(),
-                  torch.cat([la.shift, lb.shift]).contiguous())
-        cache = (key, joined)
-        net._regnet_heads_tree = cache
-    W2, s2, t2 = cache[1]
-    lt = L[trunk]
-    descr = [lt.W.data_ptr(), lt.scale.data_ptr(), lt.shift.data_ptr(), lt.K, lt.Kpad, lt.N, lt.relu, 0, 0, 0, 0,
-             W2.data_ptr(), s2.data_ptr(), t2.data_ptr(), lt.N, lt.N, la.N + lb.N, la.relu, 0, 0, 0, 0]
-    for name, src, src_off, dst, dst_off in tails:
+    trunk, first = tree
+    descr = []
+    for name, src, src_off, dst, dst_off in [(trunk, 0, 0, 0, 0), (first, 0, 0, 0, 0)] + tails:
         lay = L[name]
         descr += [lay.W.data_ptr(), lay.scale.data_ptr(), lay.shift.data_ptr(), lay.K, lay.Kpad, lay.N, lay.relu, src, src_off,
                   dst, dst_off]
@@ -1024,10 +1020,8 @@ def _heads_tree(net, x, L, trunk, first, tails, n_a, n_b):
     return out_a, out_b
 
 
-def _tree_ok(L, trunk, first, x):
-    la, lb, lt = L[first[0]], L[first[1]], L[trunk]
-    return (HEADS_TREE and x.shape[1] % 4 == 0 and lt.N % 256 == 0 and la.K == lb.K == lt.N and la.relu == lb.relu
-            and la.N % 16 == 0 and la.N + lb.N in (256, 512))
+def _tree_ok(L, tree, x):
+    return HEADS_TREE and x.shape[1] % 4 == 0 and tree[1] in L
 
 
 _TWOSTAGE_PLAN = [("conv", 0, 1), ("conv_cls2", 1, 2), ("conv_cls3", 2, 3), ("conv_cls4", 3, 4),
@@ -1048,7 +1042,7 @@ def twostage_forward(net, mp_x, raw_reg=False):
     x_cls (n, k_cls), x_reg (n, k_cls, k_reg/k_cls) with sigmoid on channels 7: (``raw_reg``: without it -- the caller's
     decode kernel applies it to the one anchor it keeps, region_ops.stage2_decode)."""
     n = mp_x.shape[0]
-    L = _packed_named(net, _TWOSTAGE)
+    L = _packed_named(net, _TWOSTAGE, _TWOSTAGE_TREE)
     x = mp_x.reshape(n, -1).contiguous()
     if HEADS_CHAIN and n <= HEADS_CHAIN_MAX_ROWS and x.shape[1] % 16 == 0:
         x_cls, x_reg = _heads_chain(x, L, _TWOSTAGE_PLAN, L["conv_cls4"].N, L["conv_reg4"].N)
@@ -1056,9 +1050,9 @@ def twostage_forward(net, mp_x, raw_reg=False):
         if not raw_reg:
             x_reg[:, :, 7:] = torch.sigmoid(x_reg[:, :, 7:])
         return x_cls, x_reg
-    if _tree_ok(L, "conv", ("conv_cls2", "conv_reg2"), x) and L["conv_cls3"].K == L["conv_cls2"].N:
+    if _tree_ok(L, _TWOSTAGE_TREE, x) and L["conv_cls3"].K == L["conv_cls2"].N:
         n2, n3 = L["conv_cls2"].N, L["conv_cls3"].N
-        x_cls, x_reg = _heads_tree(net, x, L, "conv", ("conv_cls2", "conv_reg2"),
+        x_cls, x_reg = _heads_tree(x, L, _TWOSTAGE_TREE,
                                    [("conv_cls3", 0, 0, 1, 0), ("conv_reg3", 0, n2, 1, _round_up(n3, 16)),
                                     ("conv_cls4", 1, 0, 4, 0), ("conv_reg4", 1, _round_up(n3, 16), 5, 0)],
                                    L["conv_cls4"].N, L["conv_reg4"].N)
@@ -1078,13 +1072,13 @@ def refine_forward(net, x):
     """PointNet2Refine.forward after pooling + concat (pointnet2.py:240-253): x (n, 384, 1) ->
     x_cls (n, 2), x_reg (n, k_reg)."""
     n = x.shape[0]
-    L = _packed_named(net, _REFINE)
+    L = _packed_named(net, _REFINE, _REFINE_TREE)
     if HEADS_CHAIN and n <= HEADS_CHAIN_MAX_ROWS and (x.numel() // max(n, 1)) % 16 == 0:
         return _heads_chain(x.reshape(n, -1), L, _REFINE_PLAN, L["conv_formal_cls3"].N, L["conv_formal_reg3"].N)
     rows = x.reshape(n, -1)
-    if _tree_ok(L, "conv_formal", ("conv_formal_cls2", "conv_formal_reg2"), rows):
+    if _tree_ok(L, _REFINE_TREE, rows):
         n2 = L["conv_formal_cls2"].N
-        return _heads_tree(net, rows, L, "conv_formal", ("conv_formal_cls2", "conv_formal_reg2"),
+        return _heads_tree(rows, L, _REFINE_TREE,
                            [("conv_formal_cls3", 0, 0, 4, 0), ("conv_formal_reg3", 0, n2, 5, 0)],
                            L["conv_formal_cls3"].N, L["conv_formal_reg3"].N)
     h = mlp_layer(x.reshape(n, -1).contiguous(), L["conv_formal"].K, L["conv_formal"], n)

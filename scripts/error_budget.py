@@ -17,8 +17,7 @@ def run(tag, **sw):
     old = {k: getattr(fused, k) for k in sw}
     for k, v in sw.items(): setattr(fused, k, v)
     for mod in net.modules():
-        for a in ("_regnet_packed", "_regnet_sa_chain", "_regnet_sa3_chain", "_regnet_rowchain", "_regnet_head"):
-            if hasattr(mod, a): delattr(mod, a)
+        mod.__dict__.pop("_regnet_packs", None)
     try:
         with torch.no_grad():
             _, s, _ = net(pc)

@@ -34,8 +34,7 @@ def run(tag, split, **sw):
     for k, v in sw.items(): setattr(fused, k, v)
     fused.mlp_layer = split_layer if split else orig
     for mod in net.modules():
-        for a in ("_regnet_packed", "_regnet_sa_chain", "_regnet_sa3_chain", "_regnet_rowchain", "_regnet_head"):
-            if hasattr(mod, a): delattr(mod, a)
+        mod.__dict__.pop("_regnet_packs", None)
     try:
         with torch.no_grad():
             _, s, _ = net(pc)

@@ -549,3 +549,53 @@ def test_heads_chain_kernel_matches_the_layerwise_heads(n):
         fused.ENABLED = old
     for got, want in zip(outs[True], (c64, r64, fc64, fr64)):
         assert float((got.double() - want).abs().max()) <= 2e-5
+
+
+def test_heads_tree_follows_in_place_weight_updates(monkeypatch):
+    """heads_tree_kernel's joined first layer (cls2 | reg2 rows, formal_cls2 | formal_reg2 rows) is part of the named-heads
+    pack: tree (512 rows), in-place update, chain (64 rows), in-place update, tree again -- every result equals a freshly
+    built network's with the same state_dict, and the second tree call uses a new joined layer (whatever addresses the
+    allocator hands the packs of the generation in between)."""
+    from regnet_for_3d_grasping_amd import fused, synthetic
+    from regnet_for_3d_grasping_amd.gripper_region_network import GripperRegionNetwork
+
+    def build(state=None):
+        net = GripperRegionNetwork(training=True, group_num=256, gripper_num=64, grasp_score_threshold=0.5, radius=0.06,
+                                   reg_channel=10)
+        net.load_state_dict(synthetic.seeded_state_dict(net, 11) if state is None else state)
+        return net.to(DEV).eval()
+
+    def run(model, n):
+        g = torch.Generator().manual_seed(n)
+        x2 = torch.randn(n, 256, 1, generator=g).to(DEV)
+        x3 = torch.randn(n, 384, 1, generator=g).to(DEV)
+        with torch.no_grad():
+            return fused.twostage_forward(model.extrat_feature_region, x2) + fused.refine_forward(model.extrat_feature_refine, x3)
+
+    joined = []
+    heads_tree = fused._heads_tree
+
+    def spy(x, L, tree, *args):
+        joined.append(L[tree[1]])
+        return heads_tree(x, L, tree, *args)
+
+    monkeypatch.setattr(fused, "_heads_tree", spy)
+    net = build()
+    g = torch.Generator().manual_seed(5)
+    stages = []                                      # (rows, outputs, state_dict copy, joined layers used)
+    for n in (512, 64, 512):
+        if stages:
+            with torch.no_grad():                    # an optimizer step's kind of update: in place, same tensors
+                for p in net.parameters():
+                    p.add_(torch.randn(p.shape, generator=g).to(DEV) * 0.05)
+        before = len(joined)
+        outs = run(net, n)
+        stages.append((n, outs, {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}, joined[before:]))
+    assert [len(s[3]) for s in stages] == [2, 0, 2]  # tree, chain, tree (each: region head + refine head)
+    for a, b in zip(stages[0][3], stages[2][3]):
+        assert a is not b and a.W is not b.W and a.scale is not b.scale and a.shift is not b.shift
+    for n, outs, state, _ in stages:
+        want = run(build(state), n)
+        for a, b in zip(outs, want):
+            assert a.shape == b.shape and torch.equal(a, b)
+    assert not torch.equal(stages[0][1][0], stages[2][1][0])
