@@ -766,6 +766,42 @@ int regnet_dataset_resample_f32(const float* cloud, const float* color, const fl
                                 const int64_t* pick, int64_t N, const double* rand6, float* pc, float* score_out,
                                 float* label_out, int32_t* out_of_range, void* stream);
 
+/* ---- deterministic mode (csrc/det.hip, csrc/ops_f64.hip, csrc/bn_train.hip) ------------------------------------------
+ * The float32 kernels behind torch.use_deterministic_algorithms(True): every sum of the training backward is formed in one
+ * fixed order, so runs agree bit for bit.  The default entry points above are unchanged.
+ *   - regnet_scatter_plan: the per-scene sort plan of a destination table index (B, num_src) int64 contiguous (source
+ *     position p of scene b -> destination index[b, p]; outside [0, num_dest): no destination) into `plan`, of
+ *     regnet_scatter_plan_bytes(B, num_dest, num_src) bytes, 16-byte aligned: the source positions of every destination in
+ *     ascending order.  It depends on the indices alone; build it once per table and hand it to every segment sum of it.
+ *   - regnet_scatter_segsum_f32: grad_in (B, C, num_dest) contiguous, written whole, = per destination the sum of its
+ *     contributions in ascending source position, sequentially from +0.0 (np.add.at on float32 arrays).  Unweighted
+ *     (weight NULL, group_points / gather_knn): p = row * inner + k, the value grad_out[b*sb + c*sc + row*s_hi + k*s_lo].
+ *     Weighted (interpolate, inner must be 3, s_lo unused): weight (B, num_src) contiguous, the value is the float32
+ *     product grad_out[b*sb + c*sc + (p/3)*s_hi] * weight[b, p].  `plan` built from the same index and sizes.
+ *   - regnet_scatter_max_grad_det_f32: regnet_scatter_max_grad_f32 with the additions to every destination in ascending r,
+ *     onto the value already there.  R <= 8192 (else REGNET_ERR_UNSUPPORTED).
+ *   - regnet_bn_*_det_f32: the training BatchNorm entry points with per-workgroup partials added in a fixed order instead
+ *     of float atomics; workspace of regnet_bn_det_workspace_bytes(B, C, L) bytes.                                        */
+int64_t regnet_scatter_plan_bytes(int64_t B, int64_t num_dest, int64_t num_src);
+int regnet_scatter_plan(const int64_t* index, int64_t B, int64_t num_dest, int64_t num_src, void* plan, void* stream);
+int regnet_scatter_segsum_f32(const float* grad_out, int64_t sb, int64_t sc, int64_t s_hi, int64_t s_lo, int64_t inner,
+                              const float* weight, int64_t B, int64_t C, int64_t num_dest, int64_t num_src, const void* plan,
+                              float* grad_in, void* stream);
+int regnet_scatter_max_grad_det_f32(const float* dy, const int64_t* arg, int64_t R, int64_t F, int64_t scene_rows,
+                                    int64_t batch_stride, int64_t row_stride, int64_t ch_stride, float* grad, void* stream);
+int64_t regnet_bn_det_workspace_bytes(int64_t B, int64_t C, int64_t L);
+int regnet_bn_relu_train_fwd_det_f32(const float* x, int64_t B, int64_t C, int64_t L, const float* gamma, const float* beta,
+                                     float eps, float momentum, float* running_mean, float* running_var, int relu,
+                                     int64_t pool_group, float* y, int32_t* pool_index, float* save_mean, float* save_invstd,
+                                     void* workspace, void* stream);
+int regnet_bn_relu_train_bwd_det_f32(const float* x, const float* y, const float* dy, const int32_t* pool_index, int64_t B,
+                                     int64_t C, int64_t L, const float* gamma, const float* beta, const float* save_mean,
+                                     const float* save_invstd, int relu, int64_t pool_group, float* dx, float* dgamma,
+                                     float* dbeta, void* workspace, void* stream);
+int regnet_bn_train_stats_det_f32(const float* x, int64_t B, int64_t C, int64_t L, const float* gamma, const float* beta,
+                                  float eps, float momentum, float* running_mean, float* running_var, float* save_mean,
+                                  float* save_invstd, float* scale, float* shift, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,6 +157,17 @@ SIGNATURES = {
     "regnet_np_choice_rows_dev": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp]),
     "regnet_np_rand_doubles_dev": (_int, [_vp, _vp, _i64, _vp, _vp]),
     "regnet_dataset_resample_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # deterministic mode
+    "regnet_scatter_plan_bytes": (_i64, [_i64, _i64, _i64]),
+    "regnet_scatter_plan": (_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
+    "regnet_scatter_segsum_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "regnet_scatter_max_grad_det_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "regnet_bn_det_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    "regnet_bn_relu_train_fwd_det_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _f32, _f32, _vp, _vp, _int, _i64, _vp, _vp, _vp,
+                                                _vp, _vp, _vp]),
+    "regnet_bn_relu_train_bwd_det_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _int, _i64, _vp, _vp,
+                                                _vp, _vp, _vp]),
+    "regnet_bn_train_stats_det_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

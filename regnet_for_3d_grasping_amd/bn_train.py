@@ -6,10 +6,13 @@ inside every Conv1d / Conv2d block (multi_model/utils/pn2_utils/nn/modules/conv.
 ``torch.max(new_feature, 3)`` that ends a set-abstraction block (modules.py:245).  Same values up to fp32 rounding
 (statistics are accumulated in fp64); running statistics and ``num_batches_tracked`` are updated exactly like torch.
 GPU only -- there is no CPU path; callers keep torch's modules for anything ``supported`` rejects.
+
+Deterministic mode (determinism.py): the ``_det`` entry points, whose per-workgroup partial sums are added in a fixed order
+instead of by float atomics, and never the statistics a convolution left (conv1x1_train does not fuse them then).
 """
 import torch
 
-from . import _lib
+from . import _lib, determinism
 
 ENABLED = True
 _check = _lib.check
@@ -29,6 +32,11 @@ def supported(bn, x, pool_group=0):
     return True
 
 
+def _workspace(B, C, L, dev, det):
+    n = _L.regnet_bn_det_workspace_bytes(B, C, L) if det else _L.regnet_bn_workspace_bytes(C)
+    return torch.empty((n,), dtype=torch.uint8, device=dev)
+
+
 def _aligned(t):
     t = t.contiguous()
     return t if t.data_ptr() % 16 == 0 else t.clone()
@@ -43,7 +51,8 @@ class _BnReluTrain(torch.autograd.Function):
         dev = x.device
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            ws = sums if sums is not None else torch.empty((_L.regnet_bn_workspace_bytes(C),), dtype=torch.uint8, device=dev)
+            det = sums is None and determinism.enabled()
+            ws = sums if sums is not None else _workspace(B, C, L, dev, det)
             mean = torch.empty((C,), dtype=torch.float32, device=dev)
             invstd = torch.empty((C,), dtype=torch.float32, device=dev)
             if pool_group:
@@ -54,6 +63,8 @@ class _BnReluTrain(torch.autograd.Function):
             gamma, beta = gamma.contiguous(), beta.contiguous()
             # sums: the convolution that produced x left the statistics (conv1x1_train FUSE_STATS): no pass over x for them
             fwd = _L.regnet_bn_relu_train_fwd_f32 if sums is None else _L.regnet_bn_relu_train_fwd_from_sums_f32
+            if det:
+                fwd = _L.regnet_bn_relu_train_fwd_det_f32
             _check(fwd(x.data_ptr(), B, C, L, gamma.data_ptr(), beta.data_ptr(), float(eps),
                        float(momentum), running_mean.data_ptr(), running_var.data_ptr(),
                        int(relu), int(pool_group), y.data_ptr(),
@@ -74,15 +85,17 @@ class _BnReluTrain(torch.autograd.Function):
         dy = _aligned(dy)
         with torch.cuda.device(dev):
             stream = torch.cuda.current_stream(dev).cuda_stream
-            ws = torch.empty((_L.regnet_bn_workspace_bytes(C),), dtype=torch.uint8, device=dev)
+            det = determinism.enabled()
+            ws = _workspace(B, C, L, dev, det)
             dx = torch.empty_like(x)
             dgamma = torch.empty((C,), dtype=torch.float32, device=dev)
             dbeta = torch.empty((C,), dtype=torch.float32, device=dev)
-            _check(_L.regnet_bn_relu_train_bwd_f32(x.data_ptr(), y.data_ptr() if y is not None else None, dy.data_ptr(),
-                                                   index.data_ptr() if index is not None else None, B, C, L,
-                                                   gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                                                   ctx.relu, ctx.pool_group, dx.data_ptr(), dgamma.data_ptr(),
-                                                   dbeta.data_ptr(), ws.data_ptr(), stream), "bn_relu_train_bwd")
+            bwd = _L.regnet_bn_relu_train_bwd_det_f32 if det else _L.regnet_bn_relu_train_bwd_f32
+            _check(bwd(x.data_ptr(), y.data_ptr() if y is not None else None, dy.data_ptr(),
+                       index.data_ptr() if index is not None else None, B, C, L,
+                       gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
+                       ctx.relu, ctx.pool_group, dx.data_ptr(), dgamma.data_ptr(),
+                       dbeta.data_ptr(), ws.data_ptr(), stream), "bn_relu_train_bwd")
         return dx, dgamma, dbeta, None, None, None, None, None, None, None
 
 
@@ -97,7 +110,7 @@ def _sums_of(x):
     """Per-channel (sum, sum of squares) of ``x`` (2 C float64) if the convolution that produced this very tensor left them
     (conv1x1_train._with_sums), else None."""
     sums = getattr(x, "_bn_sums", None)
-    if sums is None or sums.numel() != 2 * x.shape[1] or sums.dtype != torch.float64 or sums.device != x.device:
+    if sums is None or determinism.enabled() or sums.numel() != 2 * x.shape[1] or sums.dtype != torch.float64 or sums.device != x.device:
         return None
     return sums
 
@@ -126,11 +139,12 @@ def bn_stats(bn, x, relu=True):
                                                           p.mean.data_ptr(), p.invstd.data_ptr(), p.scale.data_ptr(),
                                                           p.shift.data_ptr(), sums.data_ptr(), stream), "bn_train_stats_from_sums")
         else:
-            ws = torch.empty((_L.regnet_bn_workspace_bytes(C),), dtype=torch.uint8, device=dev)
-            _check(_L.regnet_bn_train_stats_f32(xc.data_ptr(), B, C, L, g.data_ptr(), b.data_ptr(), float(bn.eps),
-                                                float(bn.momentum), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                                                p.mean.data_ptr(), p.invstd.data_ptr(), p.scale.data_ptr(), p.shift.data_ptr(),
-                                                ws.data_ptr(), stream), "bn_train_stats")
+            det = determinism.enabled()
+            ws = _workspace(B, C, L, dev, det)
+            stats = _L.regnet_bn_train_stats_det_f32 if det else _L.regnet_bn_train_stats_f32
+            _check(stats(xc.data_ptr(), B, C, L, g.data_ptr(), b.data_ptr(), float(bn.eps), float(bn.momentum),
+                         bn.running_mean.data_ptr(), bn.running_var.data_ptr(), p.mean.data_ptr(), p.invstd.data_ptr(),
+                         p.scale.data_ptr(), p.shift.data_ptr(), ws.data_ptr(), stream), "bn_train_stats")
     p.x, p.relu = xc, int(relu)
     return p
 
@@ -143,14 +157,15 @@ def bn_backward(x, dz, gamma, beta, mean, invstd, relu):
     dz = _aligned(dz)
     gamma, beta = gamma.detach().contiguous(), beta.detach().contiguous()
     with torch.cuda.device(dev):
-        ws = torch.empty((_L.regnet_bn_workspace_bytes(C),), dtype=torch.uint8, device=dev)
+        det = determinism.enabled()
+        ws = _workspace(B, C, L, dev, det)
         dx = torch.empty_like(x)
         dgamma = torch.empty((C,), dtype=torch.float32, device=dev)
         dbeta = torch.empty((C,), dtype=torch.float32, device=dev)
-        _check(_L.regnet_bn_relu_train_bwd_f32(x.data_ptr(), None, dz.data_ptr(), None, B, C, L, gamma.data_ptr(), beta.data_ptr(),
-                                               mean.data_ptr(), invstd.data_ptr(), int(relu), 0, dx.data_ptr(), dgamma.data_ptr(),
-                                               dbeta.data_ptr(), ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-               "bn_relu_train_bwd")
+        bwd = _L.regnet_bn_relu_train_bwd_det_f32 if det else _L.regnet_bn_relu_train_bwd_f32
+        _check(bwd(x.data_ptr(), None, dz.data_ptr(), None, B, C, L, gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(),
+                   invstd.data_ptr(), int(relu), 0, dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(),
+                   torch.cuda.current_stream(dev).cuda_stream), "bn_relu_train_bwd")
     return dx, dgamma, dbeta
 
 

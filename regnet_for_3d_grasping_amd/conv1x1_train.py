@@ -29,7 +29,9 @@ PAD_CHANNELS = True
 # operand as three bf16 pieces, six products, fp32 accumulation).  Never a default path; bench.py reports it under its own name.
 SPLIT_PRODUCTS = False
 # the statistics pass of the BatchNorm that follows a convolution taken from the convolution's output tiles while they are in
-# registers (csrc/tgemm.hip STATS: per-channel sum / sum of squares in fp64), so that bn_train does not read the output for them
+# registers (csrc/tgemm.hip STATS: per-channel sum / sum of squares in fp64), so that bn_train does not read the output for them.
+# Not under torch.use_deterministic_algorithms (determinism.py): the kernel adds its partials with fp64 atomics, so bn_train's
+# deterministic statistics pass runs instead.
 FUSE_STATS = True
 DEFERRED = {"layers": 0}     # convolutions that consumed a pending BatchNorm since import (tests, bench)
 STATS_FUSED = {"layers": 0}  # convolutions that left the following BatchNorm's statistics since import
@@ -81,10 +83,15 @@ def supported(conv, x):
 
 
 # ---- thin wrappers of the native kernels (module-level names so bench.py --train can bracket them with events) --------
+def _fuse_stats():
+    from . import determinism
+    return FUSE_STATS and not determinism.enabled()
+
+
 def stats_ok(Co, Ci, L, affine=False):
     """The forward of this shape can leave the statistics of the BatchNorm that follows it (``sums`` of native_fwd /
     native_fwd_bnrelu)."""
-    if not (FUSE_STATS and NATIVE and STREAM) or _split_ok(Co, Ci, L, affine):
+    if not (_fuse_stats() and NATIVE and STREAM) or _split_ok(Co, Ci, L, affine):
         return False
     from . import _lib
     return bool(_lib.lib.regnet_conv1x1_fwd_stats_supported(Co, Ci, L, int(affine)))
@@ -474,7 +481,7 @@ def conv1x1(conv, x, stats=False):
     xf = x.contiguous().view(B, Ci, -1)
     L = xf.shape[2]
     sums = None
-    if stats and x.is_cuda and FUSE_STATS:
+    if stats and x.is_cuda and _fuse_stats():
         if _native_ok(B, Co, Ci, L):
             sums = new_sums(Co, x.device) if stats_ok(Co, Ci, L) else None
         elif _padded_channels(B, Co, Ci, L):

@@ -14,6 +14,10 @@
 // Layout: x (B, C, L) contiguous, channel statistics over (B, L); L = M * K for grouped tensors with the K neighbours of
 // a centroid innermost (what conv2d over (B,C,M,K) produces).  Per-channel sums are accumulated in fp64 (thread partials
 // of <= 32 fp32 values, then fp64 wave/workgroup reduction and one fp64 atomic per workgroup).
+//
+// Deterministic mode (the _det entry points, torch.use_deterministic_algorithms): no atomics -- every workgroup writes its
+// (sum, sum of squares) partial to a slot of its own, and bn_partials_reduce_kernel adds a channel's slots in one fixed
+// order before the finalize / apply kernels read the sums.  Workspace: regnet_bn_det_workspace_bytes(B, C, L).
 #include "common.h"
 
 #define BN_T 256
@@ -31,8 +35,9 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
-// adds the workgroup's (a, b) to sums[0], sums[1]
-__device__ __forceinline__ void block_accumulate(double a, double b, double* sums) {
+// adds the workgroup's (a, b) to sums[0], sums[1]; deterministic mode (part != NULL): stores it to the workgroup's slot
+// of the channel's partials instead, part[2 * (blockIdx.z * gridDim.x + blockIdx.x) + 0 / 1]
+__device__ __forceinline__ void block_accumulate(double a, double b, double* sums, double* part = nullptr) {
   __shared__ double red[2][BN_T / 64];
   a = wave_sum(a);
   b = wave_sum(b);
@@ -43,14 +48,35 @@ __device__ __forceinline__ void block_accumulate(double a, double b, double* sum
     double sa = 0, sb = 0;
 #pragma unroll
     for (int i = 0; i < BN_T / 64; ++i) { sa += red[0][i]; sb += red[1][i]; }
-    atomicAdd(sums, sa);
-    atomicAdd(sums + 1, sb);
+    if (part) {
+      const int64_t slot = (int64_t)blockIdx.z * gridDim.x + blockIdx.x;
+      part[2 * slot] = sa;
+      part[2 * slot + 1] = sb;
+    } else {
+      atomicAdd(sums, sa);
+      atomicAdd(sums + 1, sb);
+    }
   }
+}
+
+// deterministic mode: sums[2c + 0 / 1] = the channel's nblk partials added in a fixed order (a wave per channel: lane j
+// adds slots j, j + 64, ... in order, then a fixed butterfly over the lanes)
+__global__ __launch_bounds__(256) void bn_partials_reduce_kernel(const double* __restrict__ part, int64_t nblk, int C,
+                                                                 double* __restrict__ sums) {
+  const int c = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+  if (c >= C) return;   // wave-uniform
+  const int lane = threadIdx.x & 63;
+  const double* p = part + (int64_t)c * nblk * 2;
+  double a = 0.0, b = 0.0;
+  for (int64_t j = lane; j < nblk; j += 64) { a += p[2 * j]; b += p[2 * j + 1]; }
+  a = wave_sum(a);
+  b = wave_sum(b);
+  if (lane == 0) { sums[2 * c] = a; sums[2 * c + 1] = b; }
 }
 
 // ---- forward -------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(BN_T) void bn_stats_kernel(const float* __restrict__ x, int C, int64_t L,
-                                                        double* __restrict__ sums) {
+                                                        double* __restrict__ sums, double* __restrict__ part = nullptr) {
   const int c = blockIdx.y;
   const float* row = x + ((int64_t)blockIdx.z * C + c) * L;
   const int64_t beg = (int64_t)blockIdx.x * BN_STATS_CHUNK, end = min(L, beg + BN_STATS_CHUNK);
@@ -80,7 +106,7 @@ __global__ __launch_bounds__(BN_T) void bn_stats_kernel(const float* __restrict_
     }
     s += (double)s32; q += (double)q32;
   }
-  block_accumulate(s, q, sums + 2 * c);
+  block_accumulate(s, q, sums + 2 * c, part ? part + (int64_t)c * gridDim.x * gridDim.z * 2 : nullptr);
 }
 
 // one thread per channel: batch mean / inverse std (saved for the backward), running statistics (momentum update with
@@ -179,7 +205,7 @@ __global__ __launch_bounds__(BN_T) void bn_bwd_reduce_kernel(const float* __rest
                                                              const float* __restrict__ beta,
                                                              const float* __restrict__ save_mean,
                                                              const float* __restrict__ save_invstd, int relu,
-                                                             double* __restrict__ sums) {
+                                                             double* __restrict__ sums, double* __restrict__ part = nullptr) {
   const int c = blockIdx.y;
   const int64_t off = ((int64_t)blockIdx.z * C + c) * L;
   const float mean = save_mean[c], invstd = save_invstd[c], g = gamma[c], bt = beta[c];
@@ -199,7 +225,7 @@ __global__ __launch_bounds__(BN_T) void bn_bwd_reduce_kernel(const float* __rest
   } else {
     for (int64_t i = beg + threadIdx.x; i < end; i += BN_T) one(x[off + i], dy[off + i]);
   }
-  block_accumulate((double)s, (double)q, sums + 2 * c);
+  block_accumulate((double)s, (double)q, sums + 2 * c, part ? part + (int64_t)c * gridDim.x * gridDim.z * 2 : nullptr);
 }
 
 // pooled variant: the gradient of a (b, c, m) maximum goes to the single element that produced it
@@ -208,7 +234,8 @@ __global__ __launch_bounds__(BN_T) void bn_pool_bwd_reduce_kernel(const float* _
                                                                   const int* __restrict__ index, int C, int64_t M,
                                                                   int group, const float* __restrict__ save_mean,
                                                                   const float* __restrict__ save_invstd, int relu,
-                                                                  double* __restrict__ sums) {
+                                                                  double* __restrict__ sums,
+                                                                  double* __restrict__ part = nullptr) {
   const int c = blockIdx.y;
   const int64_t row = (int64_t)blockIdx.z * C + c;
   const float mean = save_mean[c], invstd = save_invstd[c];
@@ -221,7 +248,7 @@ __global__ __launch_bounds__(BN_T) void bn_pool_bwd_reduce_kernel(const float* _
     s += d;
     q += d * ((xv - mean) * invstd);
   }
-  block_accumulate((double)s, (double)q, sums + 2 * c);
+  block_accumulate((double)s, (double)q, sums + 2 * c, part ? part + (int64_t)c * gridDim.x * gridDim.z * 2 : nullptr);
 }
 
 __global__ void bn_bwd_finalize_kernel(const double* __restrict__ sums, int C, float* __restrict__ dgamma,
@@ -304,10 +331,27 @@ static inline bool bn_dims_ok(int64_t B, int64_t C, int64_t L) {
 
 extern "C" int64_t regnet_bn_workspace_bytes(int64_t C) { return C > 0 ? C * 2 * (int64_t)sizeof(double) : 0; }
 
+// deterministic mode: the sums, then a (sum, sum of squares) slot per channel and workgroup of the widest reduction grid
+static inline int64_t bn_det_blocks(int64_t B, int64_t L) { return B * ((L + BN_CHUNK - 1) / BN_CHUNK); }
+
+extern "C" int64_t regnet_bn_det_workspace_bytes(int64_t B, int64_t C, int64_t L) {
+  if (B <= 0 || C <= 0 || L <= 0) return 0;
+  return regnet_bn_workspace_bytes(C) + C * bn_det_blocks(B, L) * 2 * (int64_t)sizeof(double);
+}
+
+// the workgroups of `grid` wrote their partials to `part`: add them into sums in a fixed order
+static int bn_reduce_partials(const double* part, dim3 grid, int64_t C, double* sums, hipStream_t st) {
+  hipLaunchKernelGGL(bn_partials_reduce_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, st, part,
+                     (int64_t)grid.x * grid.z, (int)C, sums);
+  REGNET_LAUNCH_CHECK();
+  return REGNET_OK;
+}
+
 static int bn_relu_train_fwd(const float* x, int64_t B, int64_t C, int64_t L, const float* gamma,
                              const float* beta, float eps, float momentum, float* running_mean,
                              float* running_var, int relu, int64_t pool_group, float* y, int32_t* pool_index,
-                             float* save_mean, float* save_invstd, void* workspace, void* stream, bool sums_ready) {
+                             float* save_mean, float* save_invstd, void* workspace, void* stream, bool sums_ready,
+                             bool det = false) {
   if (B < 0 || C < 0 || L < 0 || pool_group < 0) return REGNET_ERR_SHAPE;
   if (B == 0 || C == 0 || L == 0) return REGNET_OK;
   if (!x || !gamma || !beta || !y || !save_mean || !save_invstd || !workspace || (pool_group && !pool_index))
@@ -316,7 +360,13 @@ static int bn_relu_train_fwd(const float* x, int64_t B, int64_t C, int64_t L, co
   hipStream_t st = as_stream(stream);
   double* sums = static_cast<double*>(workspace);
   dim3 grid((unsigned)((L + BN_CHUNK - 1) / BN_CHUNK), (unsigned)C, (unsigned)B);
-  if (!sums_ready) {
+  if (det) {
+    double* part = sums + 2 * C;
+    dim3 sgrid((unsigned)((L + BN_STATS_CHUNK - 1) / BN_STATS_CHUNK), (unsigned)C, (unsigned)B);
+    hipLaunchKernelGGL(bn_stats_kernel, sgrid, dim3(BN_T), 0, st, x, (int)C, L, sums, part);
+    const int rc = bn_reduce_partials(part, sgrid, C, sums, st);
+    if (rc != REGNET_OK) return rc;
+  } else if (!sums_ready) {
     hipError_t e = hipMemsetAsync(sums, 0, regnet_bn_workspace_bytes(C), st);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(bn_stats_kernel, dim3((unsigned)((L + BN_STATS_CHUNK - 1) / BN_STATS_CHUNK), (unsigned)C, (unsigned)B), dim3(BN_T), 0, st,
@@ -341,6 +391,16 @@ extern "C" int regnet_bn_relu_train_fwd_f32(const float* x, int64_t B, int64_t C
                            save_mean, save_invstd, workspace, stream, false);
 }
 
+// deterministic mode: workspace of regnet_bn_det_workspace_bytes(B, C, L) bytes
+extern "C" int regnet_bn_relu_train_fwd_det_f32(const float* x, int64_t B, int64_t C, int64_t L, const float* gamma,
+                                                const float* beta, float eps, float momentum, float* running_mean,
+                                                float* running_var, int relu, int64_t pool_group, float* y,
+                                                int32_t* pool_index, float* save_mean, float* save_invstd, void* workspace,
+                                                void* stream) {
+  return bn_relu_train_fwd(x, B, C, L, gamma, beta, eps, momentum, running_mean, running_var, relu, pool_group, y, pool_index,
+                           save_mean, save_invstd, workspace, stream, false, true);
+}
+
 // ... with the statistics pass already done: `workspace` holds the per-channel (sum, sum of squares) of x over all B L elements as
 // regnet_conv1x1_fwd_stats_stream_f32, the convolution that produced x, left them
 extern "C" int regnet_bn_relu_train_fwd_from_sums_f32(const float* x, int64_t B, int64_t C, int64_t L, const float* gamma,
@@ -352,10 +412,10 @@ extern "C" int regnet_bn_relu_train_fwd_from_sums_f32(const float* x, int64_t B,
                            save_mean, save_invstd, workspace, stream, true);
 }
 
-extern "C" int regnet_bn_relu_train_bwd_f32(const float* x, const float* y, const float* dy, const int32_t* pool_index,
-                                            int64_t B, int64_t C, int64_t L, const float* gamma, const float* beta,
-                                            const float* save_mean, const float* save_invstd, int relu, int64_t pool_group,
-                                            float* dx, float* dgamma, float* dbeta, void* workspace, void* stream) {
+static int bn_relu_train_bwd(const float* x, const float* y, const float* dy, const int32_t* pool_index, int64_t B,
+                             int64_t C, int64_t L, const float* gamma, const float* beta, const float* save_mean,
+                             const float* save_invstd, int relu, int64_t pool_group, float* dx, float* dgamma,
+                             float* dbeta, void* workspace, void* stream, bool det) {
   if (B < 0 || C < 0 || L < 0 || pool_group < 0) return REGNET_ERR_SHAPE;
   if (B == 0 || C == 0 || L == 0) return REGNET_OK;
   if (!x || !dy || !gamma || !beta || !save_mean || !save_invstd || !dx || !dgamma || !dbeta || !workspace ||
@@ -364,20 +424,31 @@ extern "C" int regnet_bn_relu_train_bwd_f32(const float* x, const float* y, cons
   if (!bn_dims_ok(B, C, L) || (pool_group && !pool_ok(L, pool_group))) return REGNET_ERR_UNSUPPORTED;
   hipStream_t st = as_stream(stream);
   double* sums = static_cast<double*>(workspace);
-  hipError_t e = hipMemsetAsync(sums, 0, regnet_bn_workspace_bytes(C), st);
-  if (e != hipSuccess) return (int)e;
+  double* part = det ? sums + 2 * C : nullptr;
+  if (!det) {
+    hipError_t e = hipMemsetAsync(sums, 0, regnet_bn_workspace_bytes(C), st);
+    if (e != hipSuccess) return (int)e;
+  }
   const double n = (double)B * (double)L;
   dim3 grid((unsigned)((L + BN_CHUNK - 1) / BN_CHUNK), (unsigned)C, (unsigned)B);
   if (pool_group) {
     const int64_t M = L / pool_group;
     dim3 rgrid((unsigned)((M + BN_CHUNK - 1) / BN_CHUNK), (unsigned)C, (unsigned)B);
     hipLaunchKernelGGL(bn_pool_bwd_reduce_kernel, rgrid, dim3(BN_T), 0, st, x, y, dy, pool_index, (int)C, M, (int)pool_group,
-                       save_mean, save_invstd, relu, sums);
+                       save_mean, save_invstd, relu, sums, part);
+    if (det) {
+      const int rc = bn_reduce_partials(part, rgrid, C, sums, st);
+      if (rc != REGNET_OK) return rc;
+    }
     hipLaunchKernelGGL(bn_pool_bwd_apply_kernel, grid, dim3(BN_T), 0, st, x, y, dy, pool_index, (int)C, L, (int)pool_group,
                        gamma, save_mean, save_invstd, relu, sums, n, dx);
   } else {
     hipLaunchKernelGGL(bn_bwd_reduce_kernel, grid, dim3(BN_T), 0, st, x, dy, (int)C, L, gamma, beta, save_mean, save_invstd,
-                       relu, sums);
+                       relu, sums, part);
+    if (det) {
+      const int rc = bn_reduce_partials(part, grid, C, sums, st);
+      if (rc != REGNET_OK) return rc;
+    }
     hipLaunchKernelGGL(bn_bwd_apply_kernel, grid, dim3(BN_T), 0, st, x, dy, (int)C, L, gamma, beta, save_mean, save_invstd,
                        relu, sums, n, dx);
   }
@@ -386,19 +457,44 @@ extern "C" int regnet_bn_relu_train_bwd_f32(const float* x, const float* y, cons
   return REGNET_OK;
 }
 
+extern "C" int regnet_bn_relu_train_bwd_f32(const float* x, const float* y, const float* dy, const int32_t* pool_index,
+                                            int64_t B, int64_t C, int64_t L, const float* gamma, const float* beta,
+                                            const float* save_mean, const float* save_invstd, int relu, int64_t pool_group,
+                                            float* dx, float* dgamma, float* dbeta, void* workspace, void* stream) {
+  return bn_relu_train_bwd(x, y, dy, pool_index, B, C, L, gamma, beta, save_mean, save_invstd, relu, pool_group, dx, dgamma,
+                           dbeta, workspace, stream, false);
+}
+
+// deterministic mode: workspace of regnet_bn_det_workspace_bytes(B, C, L) bytes
+extern "C" int regnet_bn_relu_train_bwd_det_f32(const float* x, const float* y, const float* dy, const int32_t* pool_index,
+                                                int64_t B, int64_t C, int64_t L, const float* gamma, const float* beta,
+                                                const float* save_mean, const float* save_invstd, int relu,
+                                                int64_t pool_group, float* dx, float* dgamma, float* dbeta, void* workspace,
+                                                void* stream) {
+  return bn_relu_train_bwd(x, y, dy, pool_index, B, C, L, gamma, beta, save_mean, save_invstd, relu, pool_group, dx, dgamma,
+                           dbeta, workspace, stream, true);
+}
+
 // The statistics half of the forward alone: batch mean / inverse std (+ running statistics), and the normalisation as a
 // per-channel affine (scale = gamma * invstd, shift = beta - mean * scale) for a consumer that applies it itself
 // (regnet_conv1x1_fwd_bnrelu_stream_f32 / regnet_conv1x1_wgrad_bnrelu_f32): the normalised activation is never written.
 static int bn_train_stats(const float* x, int64_t B, int64_t C, int64_t L, const float* gamma, const float* beta,
                           float eps, float momentum, float* running_mean, float* running_var, float* save_mean,
-                          float* save_invstd, float* scale, float* shift, void* workspace, void* stream) {
+                          float* save_invstd, float* scale, float* shift, void* workspace, void* stream,
+                          bool det = false) {
   if (B < 0 || C < 0 || L < 0) return REGNET_ERR_SHAPE;
   if (B == 0 || C == 0 || L == 0) return REGNET_OK;
   if (!gamma || !beta || !save_mean || !save_invstd || !scale || !shift || !workspace) return REGNET_ERR_NULL;
   if (!bn_dims_ok(B, C, L)) return REGNET_ERR_UNSUPPORTED;
   hipStream_t st = as_stream(stream);
   double* sums = static_cast<double*>(workspace);
-  if (x) {      // x == NULL: `workspace` already holds the sums
+  if (x && det) {
+    double* part = sums + 2 * C;
+    dim3 sgrid((unsigned)((L + BN_STATS_CHUNK - 1) / BN_STATS_CHUNK), (unsigned)C, (unsigned)B);
+    hipLaunchKernelGGL(bn_stats_kernel, sgrid, dim3(BN_T), 0, st, x, (int)C, L, sums, part);
+    const int rc = bn_reduce_partials(part, sgrid, C, sums, st);
+    if (rc != REGNET_OK) return rc;
+  } else if (x) {      // x == NULL: `workspace` already holds the sums
     hipError_t e = hipMemsetAsync(sums, 0, regnet_bn_workspace_bytes(C), st);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(bn_stats_kernel, dim3((unsigned)((L + BN_STATS_CHUNK - 1) / BN_STATS_CHUNK), (unsigned)C, (unsigned)B), dim3(BN_T), 0, st,
@@ -424,4 +520,14 @@ extern "C" int regnet_bn_train_stats_from_sums_f32(int64_t B, int64_t C, int64_t
                                                    float* save_invstd, float* scale, float* shift, void* workspace, void* stream) {
   return bn_train_stats(nullptr, B, C, L, gamma, beta, eps, momentum, running_mean, running_var, save_mean, save_invstd, scale,
                         shift, workspace, stream);
+}
+
+// deterministic mode: workspace of regnet_bn_det_workspace_bytes(B, C, L) bytes
+extern "C" int regnet_bn_train_stats_det_f32(const float* x, int64_t B, int64_t C, int64_t L, const float* gamma,
+                                             const float* beta, float eps, float momentum, float* running_mean,
+                                             float* running_var, float* save_mean, float* save_invstd, float* scale,
+                                             float* shift, void* workspace, void* stream) {
+  if (!x && B > 0 && C > 0 && L > 0) return REGNET_ERR_NULL;
+  return bn_train_stats(x, B, C, L, gamma, beta, eps, momentum, running_mean, running_var, save_mean, save_invstd, scale,
+                        shift, workspace, stream, true);
 }

@@ -2,8 +2,9 @@
 //
 // The reference dispatches every native operator on float32 AND float64 (AT_DISPATCH_FLOATING_TYPES).  The float32
 // path of this library is the tuned one (geometry.hip, grid.hip, gather.hip); this translation unit is the float64
-// path: the same semantics with double coordinates / features, written for correctness first.  Nothing here is
-// reached by a float32 tensor.
+// path: the same semantics with double coordinates / features, written for correctness first.  No float32 data is
+// read here; the sort plan of the deterministic backwards (count / scan / place below) depends on the indices alone and
+// also serves the float32 deterministic mode (det.hip, through regnet_scatter_plan).
 //
 // Reference behaviour restated (relative to multi_model/utils/pn2_utils/):
 //   FPS         csrc/sampling_kernel.cu:47-117      ball query  csrc/ball_query_kernel.cu:31-74
@@ -22,6 +23,7 @@
 //              advances the destination's cursor: every segment lists its source positions in ascending order,
 //   segsum  -- a thread per destination walks its segment in order, a few channels at a time.
 #include "common.h"
+#include "scatter_plan.h"
 
 __device__ __forceinline__ double sqdist3_f64(double ax, double ay, double az, double bx, double by, double bz) {
   double dx = ax - bx, dy = ay - by, dz = az - bz;
@@ -455,12 +457,45 @@ __global__ __launch_bounds__(SC64_T) void scatter_segsum_kernel(const double* __
     if (c < nc) dst[(int64_t)c * R] = acc[c];
 }
 
-static inline int64_t round16(int64_t x) { return (x + 15) & ~(int64_t)15; }
-
 extern "C" int64_t regnet_scatter_f64_workspace_bytes(int64_t B, int64_t num_dest, int64_t num_src) {
   if (B <= 0 || num_dest <= 0) return 0;
   if (num_src < 0) num_src = 0;
   return round16(B * num_dest * 4) + round16(B * (num_dest + 1) * 4) + round16(B * num_src * 4);
+}
+
+// count -> scan -> place of `index` (B, L) into the plan in `workspace` (scatter_plan.h); the caller checked the limits
+static int build_scatter_plan(const int64_t* index, int64_t B, int64_t R, int64_t L, void* workspace, hipStream_t st) {
+  ScatterPlan pl = scatter_plan_parts(workspace, B, R);
+  hipError_t e = hipMemsetAsync(pl.cursor, 0, sizeof(int) * (size_t)(B * R), st);
+  if (e != hipSuccess) return (int)e;
+  if (L > 0) {
+    hipLaunchKernelGGL(scatter_count_kernel, dim3((unsigned)((L + SC64_T - 1) / SC64_T), (unsigned)B), dim3(SC64_T), 0, st,
+                       index, (int)R, L, pl.cursor);
+    REGNET_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(scatter_scan_kernel, dim3((unsigned)B), dim3(SCAN64_T), 0, st, pl.cursor, (int)R, pl.off);
+  REGNET_LAUNCH_CHECK();
+  if (L > 0) {
+    int nbits = 0;
+    while (((int64_t)1 << nbits) < R) ++nbits;
+    hipLaunchKernelGGL(scatter_place_kernel, dim3((unsigned)B), dim3(64), 0, st, index, (int)R, L, nbits, pl.cursor,
+                       pl.perm);
+    REGNET_LAUNCH_CHECK();
+  }
+  return REGNET_OK;
+}
+
+extern "C" int64_t regnet_scatter_plan_bytes(int64_t B, int64_t num_dest, int64_t num_src) {
+  return regnet_scatter_f64_workspace_bytes(B, num_dest, num_src);
+}
+
+extern "C" int regnet_scatter_plan(const int64_t* index, int64_t B, int64_t num_dest, int64_t num_src, void* plan,
+                                   void* stream) {
+  if (B < 0 || num_dest < 0 || num_src < 0) return REGNET_ERR_SHAPE;
+  if (B == 0 || num_dest == 0) return REGNET_OK;
+  if (!scatter_plan_dims_ok(B, num_dest, num_src)) return REGNET_ERR_UNSUPPORTED;
+  if (!plan || (num_src > 0 && !index)) return REGNET_ERR_NULL;
+  return build_scatter_plan(index, B, num_dest, num_src, plan, as_stream(stream));
 }
 
 template <bool WEIGHTED>
@@ -475,21 +510,11 @@ static int scatter_f64(const double* go, int64_t sb, int64_t sc, int64_t s_hi, i
       (L + SC64_T - 1) / SC64_T >= (int64_t)1 << 31)
     return REGNET_ERR_UNSUPPORTED;
   if (!go || !index || !workspace || (WEIGHTED && !weight)) return REGNET_ERR_NULL;
-  char* ws = (char*)workspace;
-  int* cursor = (int*)ws;
-  int* off = (int*)(ws + round16(B * R * 4));
-  int* perm = (int*)(ws + round16(B * R * 4) + round16(B * (R + 1) * 4));
-  hipError_t e = hipMemsetAsync(cursor, 0, sizeof(int) * (size_t)(B * R), st);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(scatter_count_kernel, dim3((unsigned)((L + SC64_T - 1) / SC64_T), (unsigned)B), dim3(SC64_T), 0, st,
-                     index, (int)R, L, cursor);
-  REGNET_LAUNCH_CHECK();
-  hipLaunchKernelGGL(scatter_scan_kernel, dim3((unsigned)B), dim3(SCAN64_T), 0, st, cursor, (int)R, off);
-  REGNET_LAUNCH_CHECK();
-  int nbits = 0;
-  while (((int64_t)1 << nbits) < R) ++nbits;
-  hipLaunchKernelGGL(scatter_place_kernel, dim3((unsigned)B), dim3(64), 0, st, index, (int)R, L, nbits, cursor, perm);
-  REGNET_LAUNCH_CHECK();
+  const int rc = build_scatter_plan(index, B, R, L, workspace, st);
+  if (rc != REGNET_OK) return rc;
+  const ScatterPlan pl = scatter_plan_parts(workspace, B, R);
+  int* off = pl.off;
+  int* perm = pl.perm;
   dim3 grid((unsigned)((R + SC64_T - 1) / SC64_T), (unsigned)((C + SEG64_CH - 1) / SEG64_CH), (unsigned)B);
   hipLaunchKernelGGL(scatter_segsum_kernel<WEIGHTED>, grid, dim3(SC64_T), 0, st, go, sb, sc, s_hi, s_lo, (int)inner,
                      weight, (int)C, (int)R, L, off, perm, gi);

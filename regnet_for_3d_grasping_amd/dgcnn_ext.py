@@ -5,8 +5,8 @@ completeness on top of the group_points kernels.  float32 or float64 (see pn2_ex
 """
 import torch
 
-from . import _lib
-from .pn2_ext import _eq, _need_float, _need_i64, _scatter_workspace, _stream
+from . import _lib, determinism
+from .pn2_ext import _det_segsum, _eq, _need_float, _need_i64, _scatter_workspace, _stream
 
 _check = _lib.check
 _L = _lib.lib
@@ -35,8 +35,8 @@ def gather_knn_forward(input, index):
 
 
 def gather_knn_backward(grad_output, index):
-    """grad_output (B,C,N,K), index (B,N,K) -> (B,C,N).  gather_knn_kernel.cu:100-153.  float64: summed in ascending
-    (ni, k) order per destination, run to run bit-identical."""
+    """grad_output (B,C,N,K), index (B,N,K) -> (B,C,N).  gather_knn_kernel.cu:100-153.  float64, and float32 in
+    deterministic mode: summed in ascending (ni, k) order per destination, run to run bit-identical."""
     f64 = _need_float(grad_output, "grad_output")
     _need_i64(index, "index")
     _eq(grad_output.dim(), 4, "grad_output.dim() does not equal to 4")
@@ -54,6 +54,11 @@ def gather_knn_backward(grad_output, index):
                                                 NI, K, grad_in.data_ptr(), ws.data_ptr(), _stream(grad_output)),
                    "gather_knn_backward")
             return grad_in
+        if determinism.enabled():
+            grad_in = _det_segsum("gather_knn_backward", grad_output, grad_output.stride(), index, idx, None, B, C, N,
+                                  NI * K, K, None)
+            if grad_in is not None:
+                return grad_in
         grad_in = torch.empty((B, C, N), dtype=torch.float32, device=grad_output.device)
         # grad_output rows follow the index rows (NI); the reference sizes grad_input by N
         _check(_L.regnet_gather_knn_bwd_f32(grad_output.data_ptr(), *grad_output.stride(), idx.data_ptr(), B, C, N,

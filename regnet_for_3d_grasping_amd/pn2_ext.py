@@ -10,10 +10,13 @@ dtypes: float32 or float64, like the reference's AT_DISPATCH_FLOATING_TYPES.  fl
 (csrc/geometry.hip, grid.hip, gather.hip); float64 runs csrc/ops_f64.hip (same semantics, deterministic
 backwards: see include/regnet_hip.h).  All float inputs of one call share one dtype (mixing raises, as the
 reference's ``data<scalar_t>()`` does); float outputs take it, index / count outputs are int64.
+
+Under ``torch.use_deterministic_algorithms(True)`` the float32 backwards follow the float64 ones' contract in float32
+(each destination adds its contributions in ascending source position from +0.0; see determinism.py).
 """
 import torch
 
-from . import _lib
+from . import _lib, determinism
 
 _check = _lib.check
 _L = _lib.lib
@@ -236,9 +239,10 @@ def group_points_forward(input, index):
     return out
 
 
-def group_points_backward(grad_output, index, num_points):
-    """grad_output (B,C,N2,K), index (B,N2,K) -> grad_input (B,C,N1).  csrc/grouping_kernel.cu:103-149.  float64: summed
-    in ascending (n2, k) order per destination, run to run bit-identical."""
+def group_points_backward(grad_output, index, num_points, plan=None):
+    """grad_output (B,C,N2,K), index (B,N2,K) -> grad_input (B,C,N1).  csrc/grouping_kernel.cu:103-149.  float64, and
+    float32 in deterministic mode: summed in ascending (n2, k) order per destination, run to run bit-identical.
+    ``plan``: ``scatter_plan(index, num_points)`` when the caller already has it (deterministic mode; else built here)."""
     f64 = _need_float(grad_output, "grad_output")
     _need_i64(index, "index")
     _eq(grad_output.dim(), 4, "grad_output.dim() does not equal to 4")
@@ -257,6 +261,11 @@ def group_points_backward(grad_output, index, num_points):
                                                   N1, N2, K, grad_in.data_ptr(), ws.data_ptr(), _stream(grad_output)),
                    "group_points_backward")
             return grad_in
+        if determinism.enabled():
+            grad_in = _det_segsum("group_points_backward", grad_output, grad_output.stride(), index, idx, None, B, C, N1,
+                                  N2 * K, K, plan)
+            if grad_in is not None:
+                return grad_in
         grad_in = torch.empty((B, C, N1), dtype=torch.float32, device=grad_output.device)
         _check(_L.regnet_group_points_bwd_f32(grad_output.data_ptr(), *grad_output.stride(), idx.data_ptr(), B, C,
                                               N1, N2, K, grad_in.data_ptr(), _stream(grad_output)),
@@ -268,6 +277,58 @@ def _scatter_workspace(B, num_dest, num_src, device):
     """Scratch of the deterministic float64 backwards (include/regnet_hip.h: regnet_scatter_f64_workspace_bytes)."""
     n = _L.regnet_scatter_f64_workspace_bytes(B, num_dest, num_src)
     return torch.empty((max(n, 16),), dtype=torch.uint8, device=device)
+
+
+PLANS = {"built": 0}     # scatter plans built since import (tests, bench)
+
+
+class ScatterPlan:
+    """The sort plan of one destination table (include/regnet_hip.h: regnet_scatter_plan): per scene, the source positions
+    of every destination in ascending order.  It depends on the indices alone, so one plan serves every deterministic
+    backward of the table (the grouping backward of a pre-multiplied layer's ``dU`` and any other gradient grouped by the
+    same neighbours).  ``buffer`` holds it on the device; ``index`` is the table it was built from."""
+    __slots__ = ("index", "num_dest", "num_src", "buffer")
+
+
+def scatter_plan(index, num_dest):
+    """index (B, ...) int64 GPU tensor of destinations in [0, num_dest) (others are skipped) -> ScatterPlan, built on the
+    current stream.  RuntimeError when the table exceeds the plan kernels' limits."""
+    _need_i64(index, "index")
+    B = index.size(0)
+    idx = index.contiguous()
+    L = idx.numel() // max(B, 1)
+    R = int(num_dest)
+    with torch.cuda.device(index.device):
+        buf = torch.empty((max(_L.regnet_scatter_plan_bytes(B, R, L), 16),), dtype=torch.uint8, device=index.device)
+        _check(_L.regnet_scatter_plan(idx.data_ptr(), B, R, L, buf.data_ptr(), _stream(index)), "scatter_plan")
+    PLANS["built"] += 1
+    p = ScatterPlan()
+    p.index, p.num_dest, p.num_src, p.buffer = idx, R, L, buf
+    return p
+
+
+def _det_segsum(op, go, strides, index, idx, weight, B, C, R, L, inner, plan):
+    """Deterministic float32 scatter-add of ``go`` (strides (sb, sc, s_hi[, s_lo])) by ``index`` -> (B, C, R), or None after
+    determinism.unsupported (warn_only) when this shape has no deterministic kernel."""
+    if plan is not None and (plan.index is not index and plan.index is not idx or plan.num_dest != R or plan.num_src != L):
+        raise RuntimeError("%s: the plan was built for another table" % op)
+    try:
+        if plan is None:
+            plan = scatter_plan(idx, R)
+    except RuntimeError:
+        determinism.unsupported(op, "%d destinations / %d sources per scene" % (R, L))
+        return None
+    sb, sc, s_hi = strides[:3]
+    s_lo = strides[3] if len(strides) > 3 else 0
+    grad_in = torch.empty((B, C, R), dtype=torch.float32, device=go.device)
+    st = _L.regnet_scatter_segsum_f32(go.data_ptr(), sb, sc, s_hi, s_lo, inner,
+                                      weight.data_ptr() if weight is not None else None, B, C, R, L,
+                                      plan.buffer.data_ptr(), grad_in.data_ptr(), _stream(go))
+    if st == determinism.REGNET_ERR_UNSUPPORTED:
+        determinism.unsupported(op, "%d channels" % C)
+        return None
+    _check(st, op)
+    return grad_in
 
 
 def point_search(query_xyz, key_xyz, num_neighbours):
@@ -334,8 +395,9 @@ def interpolate_forward(input, index, weight):
 
 
 def interpolate_backward(grad_output, index, weight, num_inst):
-    """grad_output (B,C,N) -> grad_input (B,C,M).  csrc/interpolate_kernel.cu:292-337.  float64: summed in ascending
-    (n, k) order per destination, run to run bit-identical."""
+    """grad_output (B,C,N) -> grad_input (B,C,M).  csrc/interpolate_kernel.cu:292-337.  float64, and float32 in
+    deterministic mode: summed in ascending (n, k) order per destination (adding the float32 products g * w), run to run
+    bit-identical."""
     f64 = _need_float(grad_output, "grad_output")
     B, C, N = grad_output.shape
     _check_interp(grad_output, index, weight, B, N)
@@ -349,6 +411,11 @@ def interpolate_backward(grad_output, index, weight, num_inst):
                                                  w.data_ptr(), B, C, M, N, grad_in.data_ptr(), ws.data_ptr(),
                                                  _stream(grad_output)), "interpolate_backward")
             return grad_in
+        if determinism.enabled():
+            grad_in = _det_segsum("interpolate_backward", grad_output, grad_output.stride(), index, idx, w, B, C, M, N * 3,
+                                  3, None)
+            if grad_in is not None:
+                return grad_in
         grad_in = torch.empty((B, C, M), dtype=torch.float32, device=grad_output.device)
         _check(_L.regnet_interpolate_bwd_f32(grad_output.data_ptr(), *grad_output.stride(), idx.data_ptr(),
                                              w.data_ptr(), B, C, M, N, grad_in.data_ptr(), _stream(grad_output)),

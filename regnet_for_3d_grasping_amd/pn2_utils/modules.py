@@ -52,10 +52,14 @@ class _GroupMinus(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dY):
-        from .. import pn2_ext, region_ops
+        from .. import determinism, pn2_ext, region_ops
         (index,) = ctx.saved_tensors
         dY = dY.contiguous()
-        dU = pn2_ext.group_points_backward(dY, index, ctx.num_points) if ctx.needs_input_grad[0] else None
+        dU = None
+        if ctx.needs_input_grad[0]:
+            # deterministic mode: the table's sort plan, built once here for every grouping backward of this index
+            plan = pn2_ext.scatter_plan(index, ctx.num_points) if determinism.enabled() else None
+            dU = pn2_ext.group_points_backward(dY, index, ctx.num_points, plan)
         dV = None
         if ctx.needs_input_grad[1]:
             K = dY.shape[-1]

@@ -3,7 +3,7 @@ closing-box candidates and the fused feature gather + max-pool.  GPU tensors onl
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, determinism
 from .pn2_ext import _need_f32, _need_i64, _stream
 
 _check = _lib.check
@@ -104,6 +104,13 @@ def _gather_max_arg(feature_rows, rows):
 def _scatter_max_grad(dy, arg, grad, scene_rows, batch_stride, row_stride, ch_stride):
     dy = dy.contiguous()
     with torch.cuda.device(dy.device):
+        if determinism.enabled():     # ascending r per destination (csrc/det.hip)
+            st = _L.regnet_scatter_max_grad_det_f32(dy.data_ptr(), arg.data_ptr(), arg.shape[0], arg.shape[1], scene_rows,
+                                                    batch_stride, row_stride, ch_stride, grad.data_ptr(), _stream(dy))
+            if st != determinism.REGNET_ERR_UNSUPPORTED:
+                _check(st, "scatter_max_grad")
+                return
+            determinism.unsupported("scatter_max_grad", "%d rows (at most 8192)" % arg.shape[0])
         _check(_L.regnet_scatter_max_grad_f32(dy.data_ptr(), arg.data_ptr(), arg.shape[0], arg.shape[1], scene_rows,
                                               batch_stride, row_stride, ch_stride, grad.data_ptr(), _stream(dy)),
                "scatter_max_grad")

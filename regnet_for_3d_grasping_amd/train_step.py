@@ -551,7 +551,9 @@ class _TrunkGraphs:
         from .pn2_utils import modules
         switches = tuple((m.__name__, k, v) for m in (conv1x1_train, bn_train, modules) for k, v in sorted(vars(m).items())
                          if k.isupper() and isinstance(v, (bool, int, float)))
-        return (tuple(p.data_ptr() for p in self.params), switches, HEAD_BACKWARD_FREE_SLOTS)
+        # the deterministic mode (torch.use_deterministic_algorithms) selects other kernels: a toggle re-captures
+        return (tuple(p.data_ptr() for p in self.params), switches, HEAD_BACKWARD_FREE_SLOTS,
+                torch.are_deterministic_algorithms_enabled())
 
     def matches(self, pc, pc_score):
         return self._key(pc, pc_score) == self.key and self._signature() == self.signature
