@@ -133,7 +133,7 @@ int regnet_gather_knn_bwd_f32(const float* grad_out, int64_t sb, int64_t sc, int
                               int64_t sk, const int64_t* index, int64_t B, int64_t C, int64_t N,
                               int64_t NI, int64_t K, float* grad_in, void* stream);
 
-/* ---- float64 operators (csrc/ops_f64.hip) -------------------------------------------------------------------------------
+/* ---- float64 operators (csrc/ops_f64.hip, backwards in csrc/scatter.hip) ------------------------------------------------
  * The reference dispatches every pn2_ext / dgcnn_ext kernel on float32 and float64 (AT_DISPATCH_FLOATING_TYPES).  These
  * are the float64 instances: same arguments and semantics as the _f32 entry points above, with double data (indices stay
  * int64), plus caller-provided scratch where noted.  Nothing here is reached by float32 data.
@@ -766,7 +766,7 @@ int regnet_dataset_resample_f32(const float* cloud, const float* color, const fl
                                 const int64_t* pick, int64_t N, const double* rand6, float* pc, float* score_out,
                                 float* label_out, int32_t* out_of_range, void* stream);
 
-/* ---- deterministic mode (csrc/det.hip, csrc/ops_f64.hip, csrc/bn_train.hip) ------------------------------------------
+/* ---- deterministic mode (csrc/scatter.hip, csrc/det.hip, csrc/bn_train.hip) ------------------------------------------
  * The float32 kernels behind torch.use_deterministic_algorithms(True): every sum of the training backward is formed in one
  * fixed order, so runs agree bit for bit.  The default entry points above are unchanged.
  *   - regnet_scatter_plan: the per-scene sort plan of a destination table index (B, num_src) int64 contiguous (source

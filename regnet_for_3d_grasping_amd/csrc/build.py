@@ -34,7 +34,8 @@ SOURCES = [
     ("np_random_dev.hip", []),
     ("dataset.hip", ["-ffp-contract=off"]),
     ("ops_f64.hip", ["-ffp-contract=off"]),   # float64 operators: indices depend on individually rounded distances
-    ("det.hip", ["-ffp-contract=off"]),   # deterministic mode: interpolate adds individually rounded products
+    ("scatter.hip", ["-ffp-contract=off"]),   # deterministic scatter-adds: interpolate adds individually rounded products
+    ("det.hip", ["-ffp-contract=off"]),   # deterministic mode: scatter_max_grad
 ]
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc"]
@@ -63,8 +64,8 @@ REPO = os.path.dirname(os.path.dirname(HERE))
 # kernels whose register budget is part of their design: a build in which one of them spills vector registers to scratch is an
 # error, not a slow kernel found later in a profile (object file -> mangled-name fragments)
 NO_VGPR_SPILL = {"mlp.o": ["mlp_gemm_kernelILi0E", "gemm2_kernel"], "sa_chain.o": ["sa_chain_kernel"],
-                 "heads.o": ["heads_chain_kernel", "heads_tree_kernel"], "ops_f64.o": ["_f64_kernel", "scatter_"],
-                 "det.o": ["det_"]}
+                 "heads.o": ["heads_chain_kernel", "heads_tree_kernel"], "ops_f64.o": ["_f64_kernel"],
+                 "scatter.o": ["scatter_", "segsum_"], "det.o": ["det_"]}
 
 
 def check_no_vgpr_spill(obj_path, fragments):

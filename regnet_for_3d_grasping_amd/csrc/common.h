@@ -24,3 +24,8 @@ __device__ __forceinline__ float sqdist3(float ax, float ay, float az, float bx,
 }
 
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
+
+// number of set bits of `mask` below this lane
+__device__ __forceinline__ int mbcnt64(uint64_t mask) {
+  return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}

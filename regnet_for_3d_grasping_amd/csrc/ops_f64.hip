@@ -2,9 +2,9 @@
 //
 // The reference dispatches every native operator on float32 AND float64 (AT_DISPATCH_FLOATING_TYPES).  The float32
 // path of this library is the tuned one (geometry.hip, grid.hip, gather.hip); this translation unit is the float64
-// path: the same semantics with double coordinates / features, written for correctness first.  No float32 data is
-// read here; the sort plan of the deterministic backwards (count / scan / place below) depends on the indices alone and
-// also serves the float32 deterministic mode (det.hip, through regnet_scatter_plan).
+// path of the forwards: the same semantics with double coordinates / features, written for correctness first.  No
+// float32 data is read here.  The float64 backwards are deterministic and live in scatter.hip with the float32
+// deterministic ones: the same sort plan and the same segment-sum kernels, instantiated for double.
 //
 // Reference behaviour restated (relative to multi_model/utils/pn2_utils/):
 //   FPS         csrc/sampling_kernel.cu:47-117      ball query  csrc/ball_query_kernel.cu:31-74
@@ -13,28 +13,13 @@
 //
 // Built with -ffp-contract=off (csrc/build.py): the indices depend on individually rounded distances
 // ((dx*dx) + (dy*dy)) + (dz*dz), and the interpolation sums add individually rounded products.
-//
-// Backward passes are DETERMINISTIC: each destination element is the sum of its contributions in ascending flattened
-// source position, starting from +0.0 (bit-identical to numpy's np.add.at in float64).  Per scene:
-//   count   -- contributions per destination (integer atomics: the counts do not depend on their order),
-//   scan    -- exclusive prefix sum of the counts -> segment offsets, and a cursor per destination,
-//   place   -- ONE wave walks the scene's sources in ascending order, 64 at a time; lanes that share a destination
-//              are matched with ballots over the destination's bits, ranked with mbcnt, and the group's first lane
-//              advances the destination's cursor: every segment lists its source positions in ascending order,
-//   segsum  -- a thread per destination walks its segment in order, a few channels at a time.
 #include "common.h"
-#include "scatter_plan.h"
 
 __device__ __forceinline__ double sqdist3_f64(double ax, double ay, double az, double bx, double by, double bz) {
   double dx = ax - bx, dy = ay - by, dz = az - bz;
   double xx = dx * dx, yy = dy * dy, zz = dz * dz;
   double s = xx + yy;
   return s + zz;
-}
-
-// number of set bits of `mask` below this lane
-__device__ __forceinline__ int mbcnt64(uint64_t mask) {
-  return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
 // =====================================================================================
@@ -334,218 +319,4 @@ extern "C" int regnet_gather_knn_fwd_f64(const double* input, int64_t sb, int64_
                                          int64_t B, int64_t C, int64_t N, int64_t NI, int64_t K, double* out,
                                          void* stream) {
   return regnet_group_points_fwd_f64(input, sb, sc, sn, index, B, C, N, NI, K, out, stream);
-}
-
-// =====================================================================================
-// Deterministic scatter-add (backward of group_points / gather_knn / interpolate)
-// =====================================================================================
-// Per scene: R destinations, L sources (flattened source positions p = row * inner + k, index[b, p] the destination).
-// Workspace (regnet_scatter_f64_workspace_bytes): cursor int32[B*R] | offset int32[B*(R+1)] | perm int32[B*L].
-#define SC64_T 256
-#define SCAN64_T 1024
-#define SEG64_CH 8
-
-__global__ __launch_bounds__(SC64_T) void scatter_count_kernel(const int64_t* __restrict__ index, int R, int64_t L,
-                                                               int* __restrict__ cnt) {
-  const int b = blockIdx.y;
-  const int64_t p = (int64_t)blockIdx.x * SC64_T + threadIdx.x;
-  if (p >= L) return;
-  const int64_t j = index[(int64_t)b * L + p];
-  if (j >= 0 && j < R) atomicAdd(&cnt[(int64_t)b * R + j], 1);
-}
-
-// one workgroup per scene: offset[n] = sum of cnt[< n], offset[R] = total; cnt becomes the placement cursor
-__global__ __launch_bounds__(SCAN64_T) void scatter_scan_kernel(int* __restrict__ cnt, int R, int* __restrict__ off) {
-  __shared__ int wsum[SCAN64_T / 64];
-  __shared__ int carry_s;
-  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
-  int* c = cnt + (int64_t)b * R;
-  int* o = off + (int64_t)b * (R + 1);
-  if (t == 0) carry_s = 0;
-  __syncthreads();
-  for (int base = 0; base < R; base += SCAN64_T) {
-    const int n = base + t;
-    const int v = n < R ? c[n] : 0;
-    int incl = v;   // inclusive scan inside the wave
-    for (int d = 1; d < 64; d <<= 1) {
-      const int u = __shfl_up(incl, d, 64);
-      if (lane >= d) incl += u;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    int before = carry_s;
-    for (int k = 0; k < w; ++k) before += wsum[k];
-    const int excl = before + incl - v;
-    if (n < R) { o[n] = excl; c[n] = excl; }
-    __syncthreads();
-    if (t == SCAN64_T - 1) carry_s = excl + v;
-    __syncthreads();
-  }
-  if (t == 0) o[R] = carry_s;
-}
-
-// one wave per scene, sources in ascending order: stable placement into the destinations' segments
-__global__ __launch_bounds__(64) void scatter_place_kernel(const int64_t* __restrict__ index, int R, int64_t L, int nbits,
-                                                           int* __restrict__ cursor, int* __restrict__ perm) {
-  const int b = blockIdx.x, lane = lane_id();
-  const int64_t* idx = index + (int64_t)b * L;
-  int* cur = cursor + (int64_t)b * R;
-  int* pm = perm + (int64_t)b * L;
-  for (int64_t p0 = 0; p0 < L; p0 += 64) {
-    const int64_t p = p0 + lane;
-    const int64_t j = p < L ? idx[p] : -1;
-    const bool valid = j >= 0 && j < R;
-    const int key = valid ? (int)j : 0;
-    uint64_t match = (uint64_t)__ballot(valid);
-    for (int bit = 0; bit < nbits; ++bit) {
-      const bool on = (key >> bit) & 1;
-      const uint64_t ones = (uint64_t)__ballot(valid && on);
-      match &= on ? ones : ~ones;
-    }
-    // (invalid lanes carry garbage in `match`; they neither lead nor place)
-    const int rank = mbcnt64(match);
-    const bool leader = valid && rank == 0;
-    int base = 0;
-    if (leader) base = atomicAdd(&cur[key], __popcll(match));
-    const int leader_lane = valid ? __ffsll((unsigned long long)match) - 1 : lane;
-    base = __shfl(base, leader_lane, 64);
-    if (valid) pm[base + rank] = (int)p;
-  }
-}
-
-// gi[b, c, n] = sum over the segment of n, in order, from +0.0.  WEIGHTED: interpolate (value g[row] * w[p], rows of
-// inner = 3); otherwise group / gather_knn (value g[row, k], p = row * inner + k).
-template <bool WEIGHTED>
-__global__ __launch_bounds__(SC64_T) void scatter_segsum_kernel(const double* __restrict__ go, int64_t sb, int64_t sc,
-                                                                int64_t s_hi, int64_t s_lo, int inner,
-                                                                const double* __restrict__ weight, int C, int R, int64_t L,
-                                                                const int* __restrict__ off, const int* __restrict__ perm,
-                                                                double* __restrict__ gi) {
-  const int b = blockIdx.z;
-  const int n = blockIdx.x * SC64_T + threadIdx.x;
-  if (n >= R) return;
-  const int c0 = blockIdx.y * SEG64_CH;
-  const int nc = min(SEG64_CH, C - c0);
-  const int* o = off + (int64_t)b * (R + 1);
-  const int* pm = perm + (int64_t)b * L;
-  const double* src = go + (int64_t)b * sb + (int64_t)c0 * sc;
-  double acc[SEG64_CH];
-#pragma unroll
-  for (int c = 0; c < SEG64_CH; ++c) acc[c] = 0.0;
-  const int beg = o[n], end = o[n + 1];
-  for (int i = beg; i < end; ++i) {
-    const int p = pm[i];
-    const int hi = p / inner, lo = p - hi * inner;
-    const double* e = src + (int64_t)hi * s_hi + (int64_t)lo * s_lo;
-    const double w = WEIGHTED ? weight[(int64_t)b * L + p] : 1.0;
-#pragma unroll
-    for (int c = 0; c < SEG64_CH; ++c) {
-      if (c < nc) {
-        const double g = e[(int64_t)c * sc];
-        if (WEIGHTED) {
-          const double v = g * w;
-          acc[c] = acc[c] + v;
-        } else {
-          acc[c] = acc[c] + g;
-        }
-      }
-    }
-  }
-  double* dst = gi + ((int64_t)b * C + c0) * R + n;
-#pragma unroll
-  for (int c = 0; c < SEG64_CH; ++c)
-    if (c < nc) dst[(int64_t)c * R] = acc[c];
-}
-
-extern "C" int64_t regnet_scatter_f64_workspace_bytes(int64_t B, int64_t num_dest, int64_t num_src) {
-  if (B <= 0 || num_dest <= 0) return 0;
-  if (num_src < 0) num_src = 0;
-  return round16(B * num_dest * 4) + round16(B * (num_dest + 1) * 4) + round16(B * num_src * 4);
-}
-
-// count -> scan -> place of `index` (B, L) into the plan in `workspace` (scatter_plan.h); the caller checked the limits
-static int build_scatter_plan(const int64_t* index, int64_t B, int64_t R, int64_t L, void* workspace, hipStream_t st) {
-  ScatterPlan pl = scatter_plan_parts(workspace, B, R);
-  hipError_t e = hipMemsetAsync(pl.cursor, 0, sizeof(int) * (size_t)(B * R), st);
-  if (e != hipSuccess) return (int)e;
-  if (L > 0) {
-    hipLaunchKernelGGL(scatter_count_kernel, dim3((unsigned)((L + SC64_T - 1) / SC64_T), (unsigned)B), dim3(SC64_T), 0, st,
-                       index, (int)R, L, pl.cursor);
-    REGNET_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(scatter_scan_kernel, dim3((unsigned)B), dim3(SCAN64_T), 0, st, pl.cursor, (int)R, pl.off);
-  REGNET_LAUNCH_CHECK();
-  if (L > 0) {
-    int nbits = 0;
-    while (((int64_t)1 << nbits) < R) ++nbits;
-    hipLaunchKernelGGL(scatter_place_kernel, dim3((unsigned)B), dim3(64), 0, st, index, (int)R, L, nbits, pl.cursor,
-                       pl.perm);
-    REGNET_LAUNCH_CHECK();
-  }
-  return REGNET_OK;
-}
-
-extern "C" int64_t regnet_scatter_plan_bytes(int64_t B, int64_t num_dest, int64_t num_src) {
-  return regnet_scatter_f64_workspace_bytes(B, num_dest, num_src);
-}
-
-extern "C" int regnet_scatter_plan(const int64_t* index, int64_t B, int64_t num_dest, int64_t num_src, void* plan,
-                                   void* stream) {
-  if (B < 0 || num_dest < 0 || num_src < 0) return REGNET_ERR_SHAPE;
-  if (B == 0 || num_dest == 0) return REGNET_OK;
-  if (!scatter_plan_dims_ok(B, num_dest, num_src)) return REGNET_ERR_UNSUPPORTED;
-  if (!plan || (num_src > 0 && !index)) return REGNET_ERR_NULL;
-  return build_scatter_plan(index, B, num_dest, num_src, plan, as_stream(stream));
-}
-
-template <bool WEIGHTED>
-static int scatter_f64(const double* go, int64_t sb, int64_t sc, int64_t s_hi, int64_t s_lo, int64_t inner,
-                       const int64_t* index, const double* weight, int64_t B, int64_t C, int64_t R, int64_t L,
-                       double* gi, void* workspace, hipStream_t st) {
-  if (L == 0) {
-    hipError_t e = hipMemsetAsync(gi, 0, sizeof(double) * (size_t)(B * C * R), st);
-    return e == hipSuccess ? REGNET_OK : (int)e;
-  }
-  if (R >= (int64_t)1 << 30 || L >= (int64_t)1 << 31 || B > 65535 || (C + SEG64_CH - 1) / SEG64_CH > 65535 ||
-      (L + SC64_T - 1) / SC64_T >= (int64_t)1 << 31)
-    return REGNET_ERR_UNSUPPORTED;
-  if (!go || !index || !workspace || (WEIGHTED && !weight)) return REGNET_ERR_NULL;
-  const int rc = build_scatter_plan(index, B, R, L, workspace, st);
-  if (rc != REGNET_OK) return rc;
-  const ScatterPlan pl = scatter_plan_parts(workspace, B, R);
-  int* off = pl.off;
-  int* perm = pl.perm;
-  dim3 grid((unsigned)((R + SC64_T - 1) / SC64_T), (unsigned)((C + SEG64_CH - 1) / SEG64_CH), (unsigned)B);
-  hipLaunchKernelGGL(scatter_segsum_kernel<WEIGHTED>, grid, dim3(SC64_T), 0, st, go, sb, sc, s_hi, s_lo, (int)inner,
-                     weight, (int)C, (int)R, L, off, perm, gi);
-  REGNET_LAUNCH_CHECK();
-  return REGNET_OK;
-}
-
-extern "C" int regnet_group_points_bwd_f64(const double* grad_out, int64_t sb, int64_t sc, int64_t sn2, int64_t sk,
-                                           const int64_t* index, int64_t B, int64_t C, int64_t N1, int64_t N2,
-                                           int64_t K, double* grad_in, void* workspace, void* stream) {
-  if (B < 0 || C < 0 || N1 < 0 || N2 < 0 || K < 0) return REGNET_ERR_SHAPE;
-  if (B == 0 || C == 0 || N1 == 0) return REGNET_OK;
-  if (!grad_in) return REGNET_ERR_NULL;
-  if (K >= (int64_t)1 << 31) return REGNET_ERR_UNSUPPORTED;
-  return scatter_f64<false>(grad_out, sb, sc, sn2, sk, K, index, nullptr, B, C, N1, N2 * K, grad_in, workspace,
-                            as_stream(stream));
-}
-
-extern "C" int regnet_gather_knn_bwd_f64(const double* grad_out, int64_t sb, int64_t sc, int64_t sn2, int64_t sk,
-                                         const int64_t* index, int64_t B, int64_t C, int64_t N, int64_t NI,
-                                         int64_t K, double* grad_in, void* workspace, void* stream) {
-  return regnet_group_points_bwd_f64(grad_out, sb, sc, sn2, sk, index, B, C, N, NI, K, grad_in, workspace, stream);
-}
-
-extern "C" int regnet_interpolate_bwd_f64(const double* grad_out, int64_t sb, int64_t sc, int64_t sn,
-                                          const int64_t* index, const double* weight, int64_t B, int64_t C, int64_t M,
-                                          int64_t N, double* grad_in, void* workspace, void* stream) {
-  if (B < 0 || C < 0 || M < 0 || N < 0) return REGNET_ERR_SHAPE;
-  if (B == 0 || C == 0 || M == 0) return REGNET_OK;
-  if (!grad_in) return REGNET_ERR_NULL;
-  // source position p = n * 3 + k: row n of grad_out (stride sn), no column stride
-  return scatter_f64<true>(grad_out, sb, sc, sn, 0, 3, index, weight, B, C, M, N * 3, grad_in, workspace,
-                           as_stream(stream));
 }

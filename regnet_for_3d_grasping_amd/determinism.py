@@ -1,9 +1,9 @@
 """Deterministic mode of the float32 training path.
 
 The mode is on exactly when ``torch.are_deterministic_algorithms_enabled()`` is true: there is no switch of this package's
-own.  Under it, every sum our kernels form in a training iteration is added in one fixed order (csrc/det.hip,
-csrc/bn_train.hip ``_det`` entry points, the sort plan of csrc/ops_f64.hip), so two runs from the same state and seeds
-agree bit for bit.  With the mode off nothing changes: the default kernels run as before.
+own.  Under it, every sum our kernels form in a training iteration is added in one fixed order (the sort plan and
+segment sums of csrc/scatter.hip, which the float64 backwards share; csrc/det.hip; csrc/bn_train.hip ``_det`` entry
+points), so two runs from the same state and seeds agree bit for bit.  With the mode off nothing changes: the default kernels run as before.
 
 An op that has no deterministic kernel for a shape raises RuntimeError naming itself, as torch's own ops do; under
 ``torch.use_deterministic_algorithms(True, warn_only=True)`` it warns once per op and runs its default kernel.

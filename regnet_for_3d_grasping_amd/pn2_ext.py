@@ -7,12 +7,13 @@ non-contiguous views, are never modified; outputs are freshly allocated; failed 
 RuntimeError.  Kernels are enqueued on torch's current stream of the input's device.
 
 dtypes: float32 or float64, like the reference's AT_DISPATCH_FLOATING_TYPES.  float32 runs the tuned kernels
-(csrc/geometry.hip, grid.hip, gather.hip); float64 runs csrc/ops_f64.hip (same semantics, deterministic
-backwards: see include/regnet_hip.h).  All float inputs of one call share one dtype (mixing raises, as the
-reference's ``data<scalar_t>()`` does); float outputs take it, index / count outputs are int64.
+(csrc/geometry.hip, grid.hip, gather.hip); float64 runs the forwards of csrc/ops_f64.hip (same semantics) and the
+deterministic backwards of csrc/scatter.hip (see include/regnet_hip.h).  All float inputs of one call share one dtype
+(mixing raises, as the reference's ``data<scalar_t>()`` does); float outputs take it, index / count outputs are int64.
 
 Under ``torch.use_deterministic_algorithms(True)`` the float32 backwards follow the float64 ones' contract in float32
-(each destination adds its contributions in ascending source position from +0.0; see determinism.py).
+(each destination adds its contributions in ascending source position from +0.0; see determinism.py): the same plan and
+segment-sum kernels of csrc/scatter.hip, instantiated for float.
 """
 import torch
 
@@ -55,6 +56,11 @@ def _need_float(t, name, like=None):
     return t.dtype == torch.float64
 
 
+def _entry(name, x):
+    """The entry point ``regnet_<name>_f64`` or ``_f32``, by the dtype of ``x``."""
+    return getattr(_L, "regnet_%s_%s" % (name, "f64" if x.dtype == torch.float64 else "f32"))
+
+
 def _need_i64(t, name):
     _need_gpu(t, name)
     if t.dtype != torch.int64:
@@ -89,35 +95,29 @@ def farthest_point_sample(points, num_centroids, chain=None):
         raise RuntimeError("num_centroids is not greater than 0")
     if not N >= M:
         raise RuntimeError("num_points is less than num_centroids")
-    if f64:
-        if chain is not None:
-            raise RuntimeError("FpsChain is a float32 mechanism; float64 points take no chain")
-        with torch.cuda.device(points.device):
-            index = torch.empty((B, M), dtype=torch.int64, device=points.device)
-            ws = torch.empty((max(_L.regnet_fps_f64_workspace_bytes(B, N, M) // 8, 1),), dtype=torch.float64,
-                             device=points.device)
-            _check(_L.regnet_fps_f64(points.data_ptr(), *points.stride(), B, N, M, index.data_ptr(), ws.data_ptr(),
-                                     _stream(points)), "farthest_point_sample")
-        return index
+    if f64 and chain is not None:
+        raise RuntimeError("FpsChain is a float32 mechanism; float64 points take no chain")
     with torch.cuda.device(points.device):
         index = torch.empty((B, M), dtype=torch.int64, device=points.device)
-        ws_bytes = _L.regnet_fps_workspace_bytes(B, N, M)
-        ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=points.device) if ws_bytes else None
+        ws_bytes = (_L.regnet_fps_f64_workspace_bytes if f64 else _L.regnet_fps_workspace_bytes)(B, N, M)
+        ws = torch.empty((ws_bytes // points.element_size(),), dtype=points.dtype, device=points.device) \
+            if ws_bytes else None
         sb, sc, sn = points.stride()
         if chain is None:
-            _check(_L.regnet_fps_f32(points.data_ptr(), sb, sc, sn, B, N, M, index.data_ptr(),
-                                     ws.data_ptr() if ws is not None else None, _stream(points)),
+            _check(_entry("fps", points)(points.data_ptr(), sb, sc, sn, B, N, M, index.data_ptr(),
+                                         ws.data_ptr() if ws is not None else None, _stream(points)),
                    "farthest_point_sample")
         else:
             prefix = chain.prefix_ok
             if prefix is not None and (prefix.dtype != torch.int32 or prefix.numel() != B or not prefix.is_cuda):
                 raise RuntimeError("FpsChain.prefix_ok must be a (B,) int32 GPU tensor")
+            prefix = prefix.contiguous() if prefix is not None else None   # held across the call
             chain.first_tie = torch.empty((B,), dtype=torch.int32, device=points.device)
             _check(_L.regnet_fps_chain_f32(points.data_ptr(), sb, sc, sn, B, N, M, index.data_ptr(),
                                            ws.data_ptr() if ws is not None else None,
-                                           prefix.contiguous().data_ptr() if prefix is not None else None,
+                                           prefix.data_ptr() if prefix is not None else None,
                                            chain.first_tie.data_ptr(), _stream(points)), "farthest_point_sample")
-        status_at = _L.regnet_fps_status_offset_bytes(B, N, M)
+        status_at = -1 if f64 else _L.regnet_fps_status_offset_bytes(B, N, M)
         if status_at >= 0:
             # cooperative sampling (N > 25 600): accumulate the launch's status word into the device's flag -- one tiny
             # launch on the same stream, no synchronisation; raise_if_fps_failed() reads it where the caller synchronises
@@ -200,26 +200,22 @@ def ball_query(points, centroids, radius, num_neighbours):
     with torch.cuda.device(points.device):
         index = torch.empty((B, N2, K), dtype=torch.int64, device=points.device)
         count = torch.empty((B, N2), dtype=torch.int64, device=points.device)
-        if f64:
-            _check(_L.regnet_ball_query_f64(points.data_ptr(), *points.stride(), centroids.data_ptr(),
-                                            *centroids.stride(), B, N1, N2, float(radius), K, index.data_ptr(),
-                                            count.data_ptr(), _stream(points)), "ball_query")
-        elif N1 >= GRID_MIN_POINTS_BALL and K <= 64 and B > 0 and float(radius) > 0:
+        if not f64 and N1 >= GRID_MIN_POINTS_BALL and K <= 64 and B > 0 and float(radius) > 0:
             ws = torch.empty((_L.regnet_grid_workspace_bytes(B, N1),), dtype=torch.uint8, device=points.device)
             _check(_L.regnet_ball_query_grid_f32(points.data_ptr(), *points.stride(), centroids.data_ptr(),
                                                  *centroids.stride(), B, N1, N2, float(radius), K,
                                                  index.data_ptr(), count.data_ptr(), ws.data_ptr(),
                                                  _stream(points)), "ball_query")
         else:
-            _check(_L.regnet_ball_query_f32(points.data_ptr(), *points.stride(), centroids.data_ptr(),
-                                            *centroids.stride(), B, N1, N2, float(radius), K, index.data_ptr(),
-                                            count.data_ptr(), _stream(points)), "ball_query")
+            _check(_entry("ball_query", points)(points.data_ptr(), *points.stride(), centroids.data_ptr(),
+                                                *centroids.stride(), B, N1, N2, float(radius), K, index.data_ptr(),
+                                                count.data_ptr(), _stream(points)), "ball_query")
     return [index, count]
 
 
 def group_points_forward(input, index):
     """input (B,C,N1), index (B,N2,K) -> (B,C,N2,K).  csrc/grouping_kernel.cu:29-51."""
-    f64 = _need_float(input, "input")
+    _need_float(input, "input")
     _need_i64(index, "index")
     _eq(input.dim(), 3, "input.dim() does not equal to 3")
     _eq(index.dim(), 3, "index.dim() does not equal to 3")
@@ -228,14 +224,9 @@ def group_points_forward(input, index):
     _, N2, K = index.shape
     with torch.cuda.device(input.device):
         idx = index.contiguous()
-        if f64:
-            out = torch.empty((B, C, N2, K), dtype=torch.float64, device=input.device)
-            _check(_L.regnet_group_points_fwd_f64(input.data_ptr(), *input.stride(), idx.data_ptr(), B, C, N1, N2, K,
-                                                  out.data_ptr(), _stream(input)), "group_points_forward")
-            return out
-        out = torch.empty((B, C, N2, K), dtype=torch.float32, device=input.device)
-        _check(_L.regnet_group_points_fwd_f32(input.data_ptr(), *input.stride(), idx.data_ptr(), B, C, N1, N2, K,
-                                              out.data_ptr(), _stream(input)), "group_points_forward")
+        out = torch.empty((B, C, N2, K), dtype=input.dtype, device=input.device)
+        _check(_entry("group_points_fwd", input)(input.data_ptr(), *input.stride(), idx.data_ptr(), B, C, N1, N2, K,
+                                                 out.data_ptr(), _stream(input)), "group_points_forward")
     return out
 
 
@@ -243,7 +234,7 @@ def group_points_backward(grad_output, index, num_points, plan=None):
     """grad_output (B,C,N2,K), index (B,N2,K) -> grad_input (B,C,N1).  csrc/grouping_kernel.cu:103-149.  float64, and
     float32 in deterministic mode: summed in ascending (n2, k) order per destination, run to run bit-identical.
     ``plan``: ``scatter_plan(index, num_points)`` when the caller already has it (deterministic mode; else built here)."""
-    f64 = _need_float(grad_output, "grad_output")
+    _need_float(grad_output, "grad_output")
     _need_i64(index, "index")
     _eq(grad_output.dim(), 4, "grad_output.dim() does not equal to 4")
     _eq(index.dim(), 3, "index.dim() does not equal to 3")
@@ -254,28 +245,17 @@ def group_points_backward(grad_output, index, num_points, plan=None):
     N1 = int(num_points)
     with torch.cuda.device(grad_output.device):
         idx = index.contiguous()
-        if f64:
-            grad_in = torch.empty((B, C, N1), dtype=torch.float64, device=grad_output.device)
-            ws = _scatter_workspace(B, N1, N2 * K, grad_output.device)
-            _check(_L.regnet_group_points_bwd_f64(grad_output.data_ptr(), *grad_output.stride(), idx.data_ptr(), B, C,
-                                                  N1, N2, K, grad_in.data_ptr(), ws.data_ptr(), _stream(grad_output)),
-                   "group_points_backward")
-            return grad_in
-        if determinism.enabled():
-            grad_in = _det_segsum("group_points_backward", grad_output, grad_output.stride(), index, idx, None, B, C, N1,
-                                  N2 * K, K, plan)
-            if grad_in is not None:
-                return grad_in
-        grad_in = torch.empty((B, C, N1), dtype=torch.float32, device=grad_output.device)
-        _check(_L.regnet_group_points_bwd_f32(grad_output.data_ptr(), *grad_output.stride(), idx.data_ptr(), B, C,
-                                              N1, N2, K, grad_in.data_ptr(), _stream(grad_output)),
-               "group_points_backward")
-    return grad_in
+        return _scatter_backward(
+            "group_points_backward", grad_output, idx, None, B, C, N1, N2 * K, K, plan,
+            lambda grad_in, *ws: _entry("group_points_bwd", grad_output)(
+                grad_output.data_ptr(), *grad_output.stride(), idx.data_ptr(), B, C, N1, N2, K, grad_in.data_ptr(), *ws,
+                _stream(grad_output)))
 
 
-def _scatter_workspace(B, num_dest, num_src, device):
-    """Scratch of the deterministic float64 backwards (include/regnet_hip.h: regnet_scatter_f64_workspace_bytes)."""
-    n = _L.regnet_scatter_f64_workspace_bytes(B, num_dest, num_src)
+def _plan_buffer(B, num_dest, num_src, device):
+    """Device buffer of a sort plan (include/regnet_hip.h: regnet_scatter_plan_bytes), which is also the workspace of the
+    float64 backwards (regnet_scatter_f64_workspace_bytes: the same size)."""
+    n = _L.regnet_scatter_plan_bytes(B, num_dest, num_src)
     return torch.empty((max(n, 16),), dtype=torch.uint8, device=device)
 
 
@@ -299,7 +279,7 @@ def scatter_plan(index, num_dest):
     L = idx.numel() // max(B, 1)
     R = int(num_dest)
     with torch.cuda.device(index.device):
-        buf = torch.empty((max(_L.regnet_scatter_plan_bytes(B, R, L), 16),), dtype=torch.uint8, device=index.device)
+        buf = _plan_buffer(B, R, L, index.device)
         _check(_L.regnet_scatter_plan(idx.data_ptr(), B, R, L, buf.data_ptr(), _stream(index)), "scatter_plan")
     PLANS["built"] += 1
     p = ScatterPlan()
@@ -307,27 +287,37 @@ def scatter_plan(index, num_dest):
     return p
 
 
-def _det_segsum(op, go, strides, index, idx, weight, B, C, R, L, inner, plan):
-    """Deterministic float32 scatter-add of ``go`` (strides (sb, sc, s_hi[, s_lo])) by ``index`` -> (B, C, R), or None after
-    determinism.unsupported (warn_only) when this shape has no deterministic kernel."""
-    if plan is not None and (plan.index is not index and plan.index is not idx or plan.num_dest != R or plan.num_src != L):
-        raise RuntimeError("%s: the plan was built for another table" % op)
-    try:
-        if plan is None:
-            plan = scatter_plan(idx, R)
-    except RuntimeError:
-        determinism.unsupported(op, "%d destinations / %d sources per scene" % (R, L))
-        return None
-    sb, sc, s_hi = strides[:3]
-    s_lo = strides[3] if len(strides) > 3 else 0
-    grad_in = torch.empty((B, C, R), dtype=torch.float32, device=go.device)
-    st = _L.regnet_scatter_segsum_f32(go.data_ptr(), sb, sc, s_hi, s_lo, inner,
-                                      weight.data_ptr() if weight is not None else None, B, C, R, L,
-                                      plan.buffer.data_ptr(), grad_in.data_ptr(), _stream(go))
-    if st == determinism.REGNET_ERR_UNSUPPORTED:
-        determinism.unsupported(op, "%d channels" % C)
-        return None
-    _check(st, op)
+def _scatter_backward(op, go, idx, weight, B, C, R, L, inner, plan, native):
+    """The backward of ``op`` -> grad_in (B, C, R): ``go`` (B, C, rows[, inner]) scatter-added by the contiguous index
+    ``idx`` (B, L = rows * inner), weighted by ``weight`` (B, L) for interpolate (inner = 3).  ``native(grad_in[, ws])``
+    calls the op's own entry point for the dtype of ``go`` and returns its status: float64 with the workspace pointer
+    ``ws``, float32 (the atomics kernel) without.  float64, and float32 in deterministic mode, sum each destination in
+    ascending source position (csrc/scatter.hip; float32 through ``plan``, ``scatter_plan(idx, R)`` when given, else
+    built here).  In deterministic mode a shape with no deterministic kernel goes to determinism.unsupported, which
+    raises or (warn_only) lets the default kernel run."""
+    grad_in = torch.empty((B, C, R), dtype=go.dtype, device=go.device)
+    if go.dtype == torch.float64:
+        ws = _plan_buffer(B, R, L, go.device)      # held until the call has enqueued every kernel that uses it
+        _check(native(grad_in, ws.data_ptr()), op)
+        return grad_in
+    if determinism.enabled():
+        if plan is not None and (plan.index is not idx or plan.num_dest != R or plan.num_src != L):
+            raise RuntimeError("%s: the plan was built for another table" % op)
+        try:
+            if plan is None:
+                plan = scatter_plan(idx, R)
+        except RuntimeError:
+            determinism.unsupported(op, "%d destinations / %d sources per scene" % (R, L))
+        else:
+            sb, sc, s_hi, s_lo = (go.stride() + (0,))[:4]
+            st = _L.regnet_scatter_segsum_f32(go.data_ptr(), sb, sc, s_hi, s_lo, inner,
+                                              weight.data_ptr() if weight is not None else None, B, C, R, L,
+                                              plan.buffer.data_ptr(), grad_in.data_ptr(), _stream(go))
+            if st != determinism.REGNET_ERR_UNSUPPORTED:
+                _check(st, op)
+                return grad_in
+            determinism.unsupported(op, "%d channels" % C)
+    _check(native(grad_in), op)
     return grad_in
 
 
@@ -346,22 +336,16 @@ def point_search(query_xyz, key_xyz, num_neighbours):
         raise RuntimeError("num_key is less than num_neighbours")
     with torch.cuda.device(query_xyz.device):
         index = torch.empty((B, N1, 3), dtype=torch.int64, device=query_xyz.device)
-        if f64:
-            dist = torch.empty((B, N1, 3), dtype=torch.float64, device=query_xyz.device)
-            _check(_L.regnet_three_nn_f64(query_xyz.data_ptr(), *query_xyz.stride(), key_xyz.data_ptr(),
-                                          *key_xyz.stride(), B, N1, N2, index.data_ptr(), dist.data_ptr(),
-                                          _stream(query_xyz)), "point_search")
-            return [index, dist]
-        dist = torch.empty((B, N1, 3), dtype=torch.float32, device=query_xyz.device)
-        if N2 >= GRID_MIN_POINTS and B > 0:
+        dist = torch.empty((B, N1, 3), dtype=query_xyz.dtype, device=query_xyz.device)
+        if not f64 and N2 >= GRID_MIN_POINTS and B > 0:
             ws = torch.empty((_L.regnet_grid_workspace_bytes(B, N2),), dtype=torch.uint8, device=query_xyz.device)
             _check(_L.regnet_three_nn_grid_f32(query_xyz.data_ptr(), *query_xyz.stride(), key_xyz.data_ptr(),
                                                *key_xyz.stride(), B, N1, N2, index.data_ptr(), dist.data_ptr(),
                                                ws.data_ptr(), _stream(query_xyz)), "point_search")
         else:
-            _check(_L.regnet_three_nn_f32(query_xyz.data_ptr(), *query_xyz.stride(), key_xyz.data_ptr(),
-                                          *key_xyz.stride(), B, N1, N2, index.data_ptr(), dist.data_ptr(),
-                                          _stream(query_xyz)), "point_search")
+            _check(_entry("three_nn", query_xyz)(query_xyz.data_ptr(), *query_xyz.stride(), key_xyz.data_ptr(),
+                                                 *key_xyz.stride(), B, N1, N2, index.data_ptr(), dist.data_ptr(),
+                                                 _stream(query_xyz)), "point_search")
     return [index, dist]
 
 
@@ -377,20 +361,15 @@ def _check_interp(first, index, weight, B, N):
 
 def interpolate_forward(input, index, weight):
     """input (B,C,M), index/weight (B,N,3) -> (B,C,N).  csrc/interpolate_kernel.cu:187-232."""
-    f64 = _need_float(input, "input")
+    _need_float(input, "input")
     B, C, M = input.shape
     N = index.size(1)
     _check_interp(input, index, weight, B, N)
     with torch.cuda.device(input.device):
         idx, w = index.contiguous(), weight.contiguous()
-        if f64:
-            out = torch.empty((B, C, N), dtype=torch.float64, device=input.device)
-            _check(_L.regnet_interpolate_fwd_f64(input.data_ptr(), *input.stride(), idx.data_ptr(), w.data_ptr(), B, C,
-                                                 M, N, out.data_ptr(), _stream(input)), "interpolate_forward")
-            return out
-        out = torch.empty((B, C, N), dtype=torch.float32, device=input.device)
-        _check(_L.regnet_interpolate_fwd_f32(input.data_ptr(), *input.stride(), idx.data_ptr(), w.data_ptr(), B, C,
-                                             M, N, out.data_ptr(), _stream(input)), "interpolate_forward")
+        out = torch.empty((B, C, N), dtype=input.dtype, device=input.device)
+        _check(_entry("interpolate_fwd", input)(input.data_ptr(), *input.stride(), idx.data_ptr(), w.data_ptr(), B, C,
+                                                M, N, out.data_ptr(), _stream(input)), "interpolate_forward")
     return out
 
 
@@ -398,26 +377,14 @@ def interpolate_backward(grad_output, index, weight, num_inst):
     """grad_output (B,C,N) -> grad_input (B,C,M).  csrc/interpolate_kernel.cu:292-337.  float64, and float32 in
     deterministic mode: summed in ascending (n, k) order per destination (adding the float32 products g * w), run to run
     bit-identical."""
-    f64 = _need_float(grad_output, "grad_output")
+    _need_float(grad_output, "grad_output")
     B, C, N = grad_output.shape
     _check_interp(grad_output, index, weight, B, N)
     M = int(num_inst)
     with torch.cuda.device(grad_output.device):
         idx, w = index.contiguous(), weight.contiguous()
-        if f64:
-            grad_in = torch.empty((B, C, M), dtype=torch.float64, device=grad_output.device)
-            ws = _scatter_workspace(B, M, N * 3, grad_output.device)
-            _check(_L.regnet_interpolate_bwd_f64(grad_output.data_ptr(), *grad_output.stride(), idx.data_ptr(),
-                                                 w.data_ptr(), B, C, M, N, grad_in.data_ptr(), ws.data_ptr(),
-                                                 _stream(grad_output)), "interpolate_backward")
-            return grad_in
-        if determinism.enabled():
-            grad_in = _det_segsum("interpolate_backward", grad_output, grad_output.stride(), index, idx, w, B, C, M, N * 3,
-                                  3, None)
-            if grad_in is not None:
-                return grad_in
-        grad_in = torch.empty((B, C, M), dtype=torch.float32, device=grad_output.device)
-        _check(_L.regnet_interpolate_bwd_f32(grad_output.data_ptr(), *grad_output.stride(), idx.data_ptr(),
-                                             w.data_ptr(), B, C, M, N, grad_in.data_ptr(), _stream(grad_output)),
-               "interpolate_backward")
-    return grad_in
+        return _scatter_backward(
+            "interpolate_backward", grad_output, idx, w, B, C, M, N * 3, 3, None,
+            lambda grad_in, *ws: _entry("interpolate_bwd", grad_output)(
+                grad_output.data_ptr(), *grad_output.stride(), idx.data_ptr(), w.data_ptr(), B, C, M, N,
+                grad_in.data_ptr(), *ws, _stream(grad_output)))

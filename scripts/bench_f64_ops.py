@@ -1,6 +1,6 @@
-"""Wall time of the float64 operators (csrc/ops_f64.hip) at configs[2]'s shapes -- 8 scenes x 25 600 points, levels of
-5 120 / 1 024 / 256 centroids -- and of one ``.double()`` ScoreNetwork forward (eval, no_grad) at 8 x 25 600.  The float64
-path is a correctness / compatibility path; these numbers describe it, they gate nothing.
+"""Wall time of the float64 operators (csrc/ops_f64.hip, scatter.hip) at configs[2]'s shapes -- 8 scenes x 25 600
+points, levels of 5 120 / 1 024 / 256 centroids -- and of one ``.double()`` ScoreNetwork forward (eval, no_grad) at
+8 x 25 600.  The float64 path is a correctness / compatibility path; these numbers describe it, they gate nothing.
 
     python scripts/bench_f64_ops.py [out.json]        (HIP events, median of 5 after one warm-up call)
 """

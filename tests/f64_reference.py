@@ -1,7 +1,7 @@
 """float64 restatement of the pn2_ext / dgcnn_ext operators in numpy (test helper, not a test module).
 
 Same surface as oracle/pn2_ext_oracle.py -- the reference's pybind entry points on CPU tensors -- for float64 data, with
-the arithmetic the GPU's float64 kernels (csrc/ops_f64.hip) promise:
+the arithmetic the GPU's float64 kernels (csrc/ops_f64.hip, csrc/scatter.hip) promise:
   * distances ((dx*dx) + (dy*dy)) + (dz*dz), each operation rounded in double (numpy does not contract);
   * furthest point sampling with the reference's tie order: get_block(N) (at least 16) lanes, lane t scans t, t + block,
     ... keeping its first strict maximum (from 0 with the previous pick), then a tree that keeps the lower lane on

@@ -1,6 +1,6 @@
-"""float64 operators on the MI355X (csrc/ops_f64.hip through pn2_ext / dgcnn_ext) against tests/f64_reference.py:
-indices, squared distances, gathers and the deterministic backwards compared bit for bit; gradcheck of the three
-differentiable autograd Functions; dtype / device errors; float32 still on the float32 kernels."""
+"""float64 operators on the MI355X (csrc/ops_f64.hip, csrc/scatter.hip through pn2_ext / dgcnn_ext) against
+tests/f64_reference.py: indices, squared distances, gathers and the deterministic backwards compared bit for bit;
+gradcheck of the three differentiable autograd Functions; dtype / device errors; float32 still on the float32 kernels."""
 import numpy as np
 import pytest
 import torch
@@ -88,8 +88,12 @@ def _indices(kind, B, N1, N2, K, seed):
     return torch.zeros((B, N2, K), dtype=torch.int64)      # every source on one destination
 
 
+# backward kernels in double (csrc/scatter.hip): one LDS chunk; several LDS chunks; several LDS chunks, nine channels;
+# 20 000 destinations, whose state does not fit in LDS -> the global-memory kernel; one chunk staging 8 channels per
+# workgroup (the last block 6)
 @pytest.mark.parametrize("kind", ["random", "padded", "collide"])
-@pytest.mark.parametrize("B,C,N1,N2,K", [(2, 7, 500, 128, 16), (1, 3, 5000, 1024, 64)])
+@pytest.mark.parametrize("B,C,N1,N2,K", [(2, 7, 500, 128, 16), (1, 3, 5000, 1024, 64), (2, 9, 2000, 640, 64),
+                                         (1, 5, 20000, 1024, 32), (4, 1030, 500, 128, 16)])
 def test_group_points_f64_bit_exact(kind, B, C, N1, N2, K):
     from regnet_for_3d_grasping_amd import dgcnn_ext, pn2_ext
     gen = torch.Generator().manual_seed(N1 + K)
@@ -126,7 +130,10 @@ def test_gather_knn_f64_bit_exact(kind):
     assert torch.equal(b1.cpu(), R.gather_knn_backward(g, idx)) and torch.equal(b1, b2)
 
 
-@pytest.mark.parametrize("B,C,M,N,kind", [(2, 9, 300, 1200, "nn"), (1, 4, 5120, 25600, "nn"), (2, 3, 50, 700, "collide")])
+# backward kernels in double: one LDS chunk; several LDS chunks; one chunk; the global-memory kernel (12 000 destinations
+# and 20 000 slots); one chunk staging 4 channels per workgroup (the last block 2)
+@pytest.mark.parametrize("B,C,M,N,kind", [(2, 9, 300, 1200, "nn"), (1, 4, 5120, 25600, "nn"), (2, 3, 50, 700, "collide"),
+                                          (1, 3, 12000, 20000, "random"), (2, 1030, 300, 1200, "nn")])
 def test_interpolate_f64_bit_exact(B, C, M, N, kind):
     from regnet_for_3d_grasping_amd import pn2_ext
     gen = torch.Generator().manual_seed(M)
@@ -137,6 +144,8 @@ def test_interpolate_f64_bit_exact(B, C, M, N, kind):
         w = inv / inv.sum(2, keepdim=True)
     else:
         idx = torch.zeros((B, N, 3), dtype=torch.int64)
+        if kind == "random":
+            idx = torch.randint(0, M, (B, N, 3), generator=gen)
         w = torch.rand((B, N, 3), generator=gen, dtype=torch.float64)
     g = torch.randn((B, C, N), generator=gen, dtype=torch.float64)
     xd, idxd, wd, gd = gpu(x, idx, w, g)
