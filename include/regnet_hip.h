@@ -316,6 +316,16 @@ int regnet_gather_points_f32(const float* points, int64_t pb, int64_t pc, int64_
  * second output), n <= 2^24.                                                                                                 */
 int regnet_class_order_i64(const int64_t* count, int64_t n, int64_t* order, void* stream);
 
+/* regnet_pair_order_i64: order (n) int64 = a processing order of the level-1 neighbourhoods for regnet_sa_chain3_f32's row
+ * packing (fused.chain3_pair_order).  With ft = (count - 1) / 32 full point tiles and rem = (count - 1) % 32 + 1 remainder rows
+ * per neighbourhood (count clamped to 1..64): neighbourhoods are paired greedily (ascending remainders; the smallest left
+ * with the largest left when rem + rem' <= 32, else the largest stays without a partner; those go side by side two and two),
+ * the pairs are sorted by their cost in point tiles (ft + ft' + 1 when they share a tile, ft + ft' + 2 otherwise; light first)
+ * and pair p sits at slots 8 (p / 4) + p % 4 and + 4 (waves w and w + 4 of a chain workgroup); the n % 8 trailing slots take
+ * the last pairs one after the other.  The result is a permutation of 0..n-1 and does not depend on timing.  One launch,
+ * one workgroup.  count (n) int64 device, work (n) int32 device scratch, n <= 2^24.                                         */
+int regnet_pair_order_i64(const int64_t* count, int64_t n, int64_t* order, int32_t* work, void* stream);
+
 /* regnet_grasp_collision_counts_f32 / regnet_grasp_antipodal_stats_f32: the per-grasp point scans of the reference's grasp
  * evaluation, dataset_utils/eval_score/eval.py:4-24 -> eval_utils/evaluation_data_generator.py (EvalDataTest /
  * EvalDataValidate .finger_hand_view :188-236 / :420-483, .finger_hand_scene :485-537, ._antipodal_score :392-418;

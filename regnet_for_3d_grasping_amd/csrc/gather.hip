@@ -386,3 +386,153 @@ extern "C" int regnet_class_order_i64(const int64_t* count, int64_t n, int64_t* 
   REGNET_LAUNCH_CHECK();
   return REGNET_OK;
 }
+
+// ---- processing order of the level-1 neighbourhoods for sa_chain_kernel's row packing (fused.chain3_pair_order) -------------
+// A neighbourhood of c members (1..64) is ft = (c - 1) / 32 full point tiles plus a remainder rem = (c - 1) % 32 + 1; waves w
+// and w + 4 of a chain workgroup share one tile for their remainders when rem + rem' <= 32 (csrc/sa_chain.hip).  The plan pairs
+// the neighbourhoods greedily -- remainders in ascending order, the smallest left with the largest left if the two fit, else
+// the largest stays without a partner (those are then put side by side two and two) --, sorts the pairs by the tiles they
+// cost (1..4, light first) and lays pair p out at slots 8 (p / 4) + p % 4 and + 4, so that whole workgroups are of one cost.
+// n % 8 trailing slots (a last, partial workgroup) take the last pairs one after the other.
+// One workgroup: a 64-bin counting sort by (rem, ft) (every wave owns a contiguous segment, ranks by ballots: the result
+// does not depend on timing), the greedy matching over the BINS by one lane (<= 64 steps, every step empties a bin; it emits
+// runs "q consecutive members of bin A with q consecutive members of bin B"), then every thread places pairs.
+#define PO_BINS 64
+#define PO_RUNS 192   // <= 64 greedy steps x 2 runs + 3
+__global__ __launch_bounds__(CO_THREADS) void pair_order_kernel(const long long* __restrict__ count, long long n_,
+                                                                long long* __restrict__ order, int* __restrict__ work) {
+  __shared__ int cnt[CO_WAVES][PO_BINS];     // per wave and bin: members (pass A), then position of the wave's next one (pass B)
+  __shared__ int binTot[PO_BINS], binBase[PO_BINS];
+  __shared__ int runA[PO_RUNS], runSA[PO_RUNS], runB[PO_RUNS], runSB[PO_RUNS], runCost[PO_RUNS], runDst[PO_RUNS], runP[PO_RUNS + 1];
+  __shared__ int clsCnt[4], nRuns, single;
+  const int n = (int)n_;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const unsigned long long lt_mask = (1ull << lane) - 1ull;
+  const int seg = ((n + CO_WAVES - 1) / CO_WAVES + 63) / 64 * 64;
+  const int lo = wave * seg, hi = lo + seg < n ? lo + seg : n;
+  volatile int* my = cnt[wave];
+  my[lane] = 0;
+  // pass A: the wave's members per bin.  same = the lanes of this step with my bin (six ballots)
+#define PO_BIN_AND_PEERS()                                                                          \
+    const int i = i0 + lane;                                                                        \
+    const bool in = i < hi;                                                                         \
+    long long c = in ? count[i] : 1;                                                                \
+    c = c < 1 ? 1 : c > 64 ? 64 : c;                                                                \
+    const int key = (int)c - 1, bin = ((key & 31) << 1) | (key >> 5);                               \
+    unsigned long long same = __ballot(in);                                                         \
+    _Pragma("unroll") for (int bit = 0; bit < 6; ++bit) {                                           \
+      const unsigned long long bb = __ballot((bin >> bit) & 1);                                     \
+      same &= ((bin >> bit) & 1) ? bb : ~bb;                                                        \
+    }                                                                                               \
+    const bool leader = in && (same & lt_mask) == 0
+  for (int i0 = lo; i0 < hi; i0 += 64) {
+    PO_BIN_AND_PEERS();
+    if (leader) my[bin] += (int)__popcll(same);
+  }
+  __syncthreads();
+  if (wave == 0) {   // lane = bin: totals, the waves' exclusive prefixes, the bins' bases
+    int tot = 0;
+#pragma unroll
+    for (int w = 0; w < CO_WAVES; ++w) { const int t = cnt[w][lane]; cnt[w][lane] = tot; tot += t; }
+    int incl = tot;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const int t = __shfl_up(incl, d, 64); if (lane >= d) incl += t; }
+    binTot[lane] = tot;
+    binBase[lane] = incl - tot;
+  }
+  __syncthreads();
+  if (tid == 0) {   // greedy matching over the bins (ascending remainder: bin = 2 (rem - 1) + ft)
+    int a = 0, z = PO_BINS - 1, fa = 0, kz = 0, R = 0, P = 0;
+    int carryBin = -1, carryPos = 0;
+    int c1 = 0, c2 = 0, c3 = 0, c4 = 0;
+#define PO_EMIT(A, SA, B, SB, Q, COST)                                                              \
+    if ((Q) > 0 && R < PO_RUNS) {                                                                   \
+      const int cost_ = (COST);                                                                     \
+      runA[R] = (A); runSA[R] = (SA); runB[R] = (B); runSB[R] = (SB); runCost[R] = cost_;           \
+      runDst[R] = cost_ == 1 ? c1 : cost_ == 2 ? c2 : cost_ == 3 ? c3 : c4; runP[R] = P;            \
+      c1 += cost_ == 1 ? (Q) : 0; c2 += cost_ == 2 ? (Q) : 0; c3 += cost_ == 3 ? (Q) : 0;           \
+      c4 += cost_ > 3 ? (Q) : 0; P += (Q); ++R;                                                     \
+    }
+    // members without a partner, two and two (a single one is carried to the next lot)
+#define PO_ALONE(BIN, START, CNT)                                                                   \
+    {                                                                                               \
+      int st_ = (START), n_left = (CNT);                                                            \
+      const int nt_ = ((BIN) & 1) + 1;                                                              \
+      if (carryBin >= 0 && n_left > 0) {                                                            \
+        PO_EMIT(carryBin, carryPos, (BIN), st_, 1, (carryBin & 1) + 1 + nt_);                       \
+        ++st_; --n_left; carryBin = -1;                                                             \
+      }                                                                                             \
+      const int q_ = n_left >> 1;                                                                   \
+      PO_EMIT((BIN), st_, (BIN), st_ + q_, q_, 2 * nt_);                                            \
+      if (n_left & 1) { carryBin = (BIN); carryPos = st_ + 2 * q_; }                                \
+    }
+    for (;;) {
+      while (a < z && binTot[a] - fa == 0) { ++a; fa = 0; }
+      while (z > a && binTot[z] - kz == 0) { --z; kz = 0; }
+      if (a == z) {   // one bin left: its members [fa, tot - kz)
+        int avail = binTot[a] - fa - kz;
+        if (avail >= 2 && 2 * ((a >> 1) + 1) <= 32) {
+          const int q = avail >> 1;
+          PO_EMIT(a, fa, a, fa + q, q, 2 * (a & 1) + 1);
+          fa += 2 * q; avail -= 2 * q;
+        }
+        if (avail > 0) PO_ALONE(a, fa, avail);
+        break;
+      }
+      const int ra = binTot[a] - fa, rz = binTot[z] - kz;
+      if ((a >> 1) + 1 + (z >> 1) + 1 <= 32) {
+        const int q = ra < rz ? ra : rz;
+        PO_EMIT(a, fa, z, rz - q, q, (a & 1) + (z & 1) + 1);
+        fa += q; kz += q;
+      } else {
+        PO_ALONE(z, 0, rz);
+        kz += rz;
+      }
+    }
+#undef PO_ALONE
+#undef PO_EMIT
+    runP[R] = P;
+    nRuns = R;
+    single = carryBin >= 0 ? binBase[carryBin] + carryPos : -1;
+    clsCnt[0] = 0; clsCnt[1] = c1; clsCnt[2] = c1 + c2; clsCnt[3] = c1 + c2 + c3;   // the classes' first pairs
+  }
+  // pass B: members sorted by bin (work), stable
+  for (int i0 = lo; i0 < hi; i0 += 64) {
+    PO_BIN_AND_PEERS();
+    const int base = in ? my[bin] : 0;
+    if (in) work[binBase[bin] + base + (int)__popcll(same & lt_mask)] = i;
+    if (leader) my[bin] = base + (int)__popcll(same);
+  }
+#undef PO_BIN_AND_PEERS
+  __syncthreads();
+  // pass C: pair p of run r -> its slots
+  const int R = nRuns, P = runP[R], full = (n >> 3) << 2;   // pairs that sit in whole workgroups
+  for (int p = tid; p < P; p += CO_THREADS) {
+    int r = 0;
+    for (int step = 128; step > 0; step >>= 1)
+      if (r + step < R && runP[r + step] <= p) r += step;
+    const int t = p - runP[r];
+    const long long host = work[binBase[runA[r]] + runSA[r] + t], guest = work[binBase[runB[r]] + runSB[r] + t];
+    const int pp = clsCnt[runCost[r] - 1] + runDst[r] + t;
+    if (pp < full) {
+      order[8 * (pp >> 2) + (pp & 3)] = host;
+      order[8 * (pp >> 2) + (pp & 3) + 4] = guest;
+    } else {
+      order[2 * full + 2 * (pp - full)] = host;
+      order[2 * full + 2 * (pp - full) + 1] = guest;
+    }
+  }
+  if (tid == 0 && single >= 0) order[n - 1] = work[single];
+}
+
+extern "C" int regnet_pair_order_i64(const int64_t* count, int64_t n, int64_t* order, int32_t* work, void* stream) {
+  if (n < 0) return REGNET_ERR_SHAPE;
+  if (n == 0) return REGNET_OK;
+  if (n > (1ll << 24)) return REGNET_ERR_UNSUPPORTED;
+  if (!count || !order || !work) return REGNET_ERR_NULL;
+  hipLaunchKernelGGL(pair_order_kernel, dim3(1), dim3(CO_THREADS), 0, as_stream(stream), (const long long*)count, (long long)n,
+                     (long long*)order, (int*)work);
+  REGNET_LAUNCH_CHECK();
+  return REGNET_OK;
+}

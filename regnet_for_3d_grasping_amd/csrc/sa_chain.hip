@@ -56,20 +56,23 @@ struct ChainArgs {
 // first hit), which cannot change a maximum, so the second tile's MFMAs are skipped altogether.  Both instantiations
 // execute the same barriers (one per W3 tile), so waves of one workgroup may take different ones.
 //
-// Paired neighbourhoods (role 1 = host, role 2 = guest).  Two neighbourhoods with 33..48 members each need THREE point
-// tiles between them, not four: waves w and w + 4 of a workgroup -- the two waves of one SIMD -- form a pair when both of
-// theirs are of that kind.  The host (w < 4) runs NPT = 2 with its second tile holding its own slots 32..47 in rows 0..15
-// and the GUEST's slots 32..47 in rows 16..31; the guest runs NPT = 1 on its slots 0..31.  Rows are accumulator registers
-// in the layer-3 product (rows 0..15 = registers 0..7), so the host pools the two halves of that tile separately at no
-// cost, leaves the guest's partial maximum in LDS (sPart, double-buffered by W3 tile) and the guest -- the lighter wave --
-// folds it into its own after the tile's barrier.  Every point's activations are the same MFMA chain as before and a
-// maximum does not care about grouping: bit-identical outputs, 3/4 of the matrix work for such a pair, and the SIMD's two
-// waves still add up to the same load on every SIMD of the workgroup (3 tiles each).
+// Paired neighbourhoods (role 1 = host, role 2 = guest).  A neighbourhood of c members is (c - 1) / 32 full point tiles plus a
+// remainder of 1..32 rows.  Waves w and w + 4 of a workgroup -- the two waves of one SIMD -- form a pair when their remainders
+// fit ONE 32-row tile together: the host's last tile holds its own last s rows in rows [0, s) and the guest's last t rows in
+// rows [s, s + t) (rows beyond repeat the guest's last real row), and the guest runs without its last tile -- NPT = 1 on its
+// slots 0..31, or no tile at all (chain_guest_only) when it has at most 32 members.  A SIMD pair costs 1..4 tiles instead of
+// 2..4.  The host is the wave with fewer full tiles (wave w on a tie), so the two waves of a SIMD stay as even as they can be.
+// Rows are accumulator registers in the layer-3 product (row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)), so the host pools the
+// two segments of that tile as two running maxima selected per register by row < s (s is wave-uniform), leaves the guest's
+// partial maximum in LDS (sPart, double-buffered by W3 tile) and the guest folds it into its own after the tile's barrier.
+// Every point's activations are the same MFMA chain as before and a maximum does not care about grouping: bit-identical
+// outputs.  Who sits at w and w + 4 is the caller's business (the processing order: fused.chain3_pair_order puts partners
+// there); the kernel pairs whatever fits, so any order is correct and a good one is fast.
 template <int NPT>
 __device__ __forceinline__ void chain_group(const ChainArgs& p, const float* __restrict__ sW2, float (*sW3)[32 * CH_LD],
                                             const float* __restrict__ sW1, const float* __restrict__ sS2,
                                             const float* __restrict__ sT2, float (*sPart)[4][32], const int role,
-                                            const float (&x)[2][8], long long gs, bool valid,
+                                            const int split, const float (&x)[2][8], long long gs, bool valid,
                                             float4 w3a, float4 w3b, int tid, int lane, int fr, int fh, int t_row0,
                                             int t_c4) {
   // ---- layer 2 (layer 1 on the fly): acc2[dt][pt] = W2[32 dt .., :] . h1[:, 32 pt ..] ------------------------------
@@ -164,25 +167,31 @@ __device__ __forceinline__ void chain_group(const ChainArgs& p, const float* __r
       for (int pt = 0; pt < NPT; ++pt) acc3[pt] = __builtin_amdgcn_mfma_f32_32x32x2f32(acc2[dt][pt][4 * q + 3], w.w, acc3[pt], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
-    // lane l holds channel et*32 + (l & 31) of 16 points per point tile (+ the other 16 in lane l ^ 32); registers 0..7
-    // are rows 0..15 of a tile, registers 8..15 rows 16..31
+    // lane l holds channel et*32 + (l & 31) of 16 points per point tile (+ the other 16 in lane l ^ 32); register r is
+    // row (r & 3) + 8 (r >> 2) + 4 fh of a tile
     float hold;
     {
       const float sc = p.scale3[et * 32 + fr], sh = p.shift3[et * 32 + fr];
-      float m = -__builtin_inff(), m2 = -__builtin_inff();
+      float m = -__builtin_inff();
 #pragma unroll
-      for (int r = 0; r < 16; ++r) m = fmaxf(m, acc3[0][r] * sc + sh);
-      if (NPT == 2) {
+      for (int pt = 0; pt < NPT - 1; ++pt)
 #pragma unroll
-        for (int r = 0; r < 8; ++r) m = fmaxf(m, acc3[NPT - 1][r] * sc + sh);
+        for (int r = 0; r < 16; ++r) m = fmaxf(m, acc3[pt][r] * sc + sh);
+      if (role == 1) {   // rows [0, split) of the last tile are mine, the others the guest's
+        const int mine = split - 4 * fh;
+        float m2 = -__builtin_inff();
 #pragma unroll
-        for (int r = 8; r < 16; ++r) m2 = fmaxf(m2, acc3[NPT - 1][r] * sc + sh);
-        if (role == 1) {   // rows 16..31 of the second tile are the guest's
-          m2 = fmaxf(m2, __shfl_xor(m2, 32, 64));
-          if (fh == 0) sPart[buf][tid >> 6][fr] = m2;
-        } else {
-          m = fmaxf(m, m2);
+        for (int r = 0; r < 16; ++r) {
+          const float v = acc3[NPT - 1][r] * sc + sh;
+          const bool own = (r & 3) + 8 * (r >> 2) < mine;
+          m = fmaxf(m, own ? v : -__builtin_inff());
+          m2 = fmaxf(m2, own ? -__builtin_inff() : v);
         }
+        m2 = fmaxf(m2, __shfl_xor(m2, 32, 64));
+        if (fh == 0) sPart[buf][(tid >> 6) & 3][fr] = m2;
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) m = fmaxf(m, acc3[NPT - 1][r] * sc + sh);
       }
       if (p.relu3) m = fmaxf(m, 0.f);
       m = fmaxf(m, __shfl_xor(m, 32, 64));
@@ -195,9 +204,30 @@ __device__ __forceinline__ void chain_group(const ChainArgs& p, const float* __r
     }
     __syncthreads();
     if (NPT == 1 && role == 2) {   // the host's next write to sPart[buf] is two barriers away
-      const float m = fmaxf(hold, sPart[buf][(tid >> 6) - 4][fr]);
+      const float m = fmaxf(hold, sPart[buf][(tid >> 6) & 3][fr]);
       if (fh == 0 && valid) orow[et * 32 + fr] = m;
     }
+  }
+}
+
+// A guest whose members all sit in its host's last tile: no point tile of its own, only the workgroup's W3 staging, its
+// barriers (one per W3 tile, as chain_group) and the host's maxima.
+__device__ __forceinline__ void chain_guest_only(const ChainArgs& p, float (*sW3)[32 * CH_LD], float (*sPart)[4][32], long long gs,
+                                                 bool valid, int tid, int fr, int fh, int t_row0, int t_c4) {
+  const int tiles = p.C3 / 32;
+  float* orow = p.out + gs * p.ldo;
+  for (int et = 0; et < tiles; ++et) {
+    const int buf = et & 1;
+    if (et + 1 < tiles) {
+      const float4 w3a = reinterpret_cast<const float4*>(p.W3)[(et + 1) * 1024 + tid];
+      const float4 w3b = reinterpret_cast<const float4*>(p.W3)[(et + 1) * 1024 + tid + CH_THREADS];
+      *reinterpret_cast<float4*>(&sW3[buf ^ 1][t_row0 * CH_LD + t_c4 * 4]) = w3a;
+      *reinterpret_cast<float4*>(&sW3[buf ^ 1][(t_row0 + 16) * CH_LD + t_c4 * 4]) = w3b;
+    }
+    __syncthreads();
+    float m = sPart[buf][(tid >> 6) & 3][fr];
+    if (p.relu3) m = fmaxf(m, 0.f);
+    if (fh == 0 && valid) orow[et * 32 + fr] = m;
   }
 }
 
@@ -247,19 +277,28 @@ __global__ __launch_bounds__(CH_THREADS, 2) void sa_chain_kernel(const ChainArgs
   const long long slot = (long long)blockIdx.x * CH_WAVES + wave;
   const bool valid = slot < p.groups;
   const long long gs = valid ? (p.order ? p.order[slot] : slot) : 0;
-  // pairing (see chain_group): waves w and w + 4 when both neighbourhoods have 33..48 members; all of it wave-uniform
-  int role = 0;
+  // pairing (see chain_group): waves w and w + 4 when their remainders fit one point tile; all of it wave-uniform
+  int role = 0, split = 32, g_base = 0, g_last = 0;   // a host's guest: first slot and last row of its remainder
   long long gm = gs;
-  const long long c_me = p.count ? p.count[gs] : 64;
+  long long c_me = p.count ? p.count[gs] : 64;
+  c_me = c_me < 1 ? 1 : c_me > 64 ? 64 : c_me;
+  const int ft_me = (int)(c_me - 1) >> 5, rem_me = ((int)(c_me - 1) & 31) + 1;
   if (p.count && valid) {
     const long long pslot = wave < 4 ? slot + 4 : slot - 4;
     if (pslot < p.groups) {
       const long long gp = p.order ? p.order[pslot] : pslot;
-      const long long c_p = p.count[gp];
-      if (c_me > 32 && c_me <= 48 && c_p > 32 && c_p <= 48) { role = wave < 4 ? 1 : 2; gm = gp; }
+      long long c_p = p.count[gp];
+      c_p = c_p < 1 ? 1 : c_p > 64 ? 64 : c_p;
+      const int ft_p = (int)(c_p - 1) >> 5, rem_p = ((int)(c_p - 1) & 31) + 1;
+      if (rem_me + rem_p <= 32) {
+        role = (ft_me != ft_p ? ft_me < ft_p : wave < 4) ? 1 : 2;
+        gm = gp; split = rem_me; g_base = 32 * ft_p; g_last = rem_p - 1;
+      }
     }
   }
-  const int npt = (c_me <= 32 || role == 2) ? 1 : 2;
+  role = __builtin_amdgcn_readfirstlane(role);
+  split = __builtin_amdgcn_readfirstlane(split);
+  const int npt = role == 2 ? ft_me : ft_me + 1;
   const long long b = gs / p.groups_per_scene;
   const float* xb = p.xyz + b * p.xb;
   const long long cj = p.ctr[gs];
@@ -267,8 +306,8 @@ __global__ __launch_bounds__(CH_THREADS, 2) void sa_chain_kernel(const ChainArgs
   float x[2][8];
 #pragma unroll
   for (int pt = 0; pt < 2; ++pt) {
-    // a host's second tile: rows 0..15 its own slots 32..47, rows 16..31 the guest's slots 32..47 (the guest's scene and centre)
-    const bool theirs = pt == 1 && role == 1 && fr >= 16;
+    // a host's last tile: rows [0, split) its own slots, the rows behind them the guest's remainder (the guest's scene and centre)
+    const bool theirs = role == 1 && pt == npt - 1 && fr >= split;
     const long long g = theirs ? gm : gs;
     const long long bg = theirs ? gm / p.groups_per_scene : b;
     const float* xg = p.xyz + bg * p.xb;
@@ -277,7 +316,8 @@ __global__ __launch_bounds__(CH_THREADS, 2) void sa_chain_kernel(const ChainArgs
       const long long cm = p.ctr[gm];
       ox = xg[cm * p.xn]; oy = xg[p.xc + cm * p.xn]; oz = xg[2 * p.xc + cm * p.xn];
     }
-    const long long j = p.nbr[g * 64 + pt * 32 + (theirs ? fr - 16 : fr)];
+    const int gslot = fr - split < g_last ? fr - split : g_last;
+    const long long j = p.nbr[g * 64 + (theirs ? g_base + gslot : pt * 32 + fr)];
     const float rx = xg[j * p.xn] - ox, ry = xg[p.xc + j * p.xn] - oy, rz = xg[2 * p.xc + j * p.xn] - oz;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
@@ -292,8 +332,9 @@ __global__ __launch_bounds__(CH_THREADS, 2) void sa_chain_kernel(const ChainArgs
   __syncthreads();
   CH_TRACE_MID();
 
-  if (npt == 2) chain_group<2>(p, sW2, sW3, sW1, sS2, sT2, sPart, role, x, gs, valid, w3a, w3b, tid, lane, fr, fh, t_row0, t_c4);
-  else chain_group<1>(p, sW2, sW3, sW1, sS2, sT2, sPart, role, x, gs, valid, w3a, w3b, tid, lane, fr, fh, t_row0, t_c4);
+  if (npt == 2) chain_group<2>(p, sW2, sW3, sW1, sS2, sT2, sPart, role, split, x, gs, valid, w3a, w3b, tid, lane, fr, fh, t_row0, t_c4);
+  else if (npt == 1) chain_group<1>(p, sW2, sW3, sW1, sS2, sT2, sPart, role, split, x, gs, valid, w3a, w3b, tid, lane, fr, fh, t_row0, t_c4);
+  else chain_guest_only(p, sW3, sPart, gs, valid, tid, fr, fh, t_row0, t_c4);
   CH_TRACE_END();
 }
 

@@ -299,6 +299,84 @@ def chain3_order(count):
     return torch.argsort((c > 32).to(torch.uint8) + (c > 48).to(torch.uint8), stable=True)
 
 
+def chain3_pair_cost(c_a, c_b):
+    """Point tiles that sa_chain3 executes for two neighbourhoods at waves w and w + 4 (int64 tensors of member counts):
+    their full tiles plus one shared tile when the two remainders fit 32 rows together, else one tile each."""
+    a, b = c_a.clamp(1, 64) - 1, c_b.clamp(1, 64) - 1
+    return (a >> 5) + (b >> 5) + 1 + ((a & 31) + (b & 31) + 2 > 32).to(a.dtype)
+
+
+def _pair_order_host(count):
+    """The plan of regnet_pair_order_i64 (csrc/gather.hip: pair_order_kernel) restated in numpy, run for run."""
+    import numpy as np
+    c = np.clip(np.asarray(count, dtype=np.int64).reshape(-1), 1, 64) - 1
+    n = c.size
+    bins = ((c & 31) << 1) | (c >> 5)                       # ascending remainder, then full tiles
+    work = np.argsort(bins, kind="stable")
+    tot = np.bincount(bins, minlength=64)
+    base = np.concatenate([[0], np.cumsum(tot)[:-1]])
+    runs, carry = [], None                                  # (bin A, start A, bin B, start B, pairs, cost)
+
+    def alone(b, start, left):
+        nonlocal carry
+        if carry is not None and left > 0:
+            runs.append((carry[0], carry[1], b, start, 1, (carry[0] & 1) + 1 + (b & 1) + 1))
+            start, left, carry = start + 1, left - 1, None
+        q = left >> 1
+        if q:
+            runs.append((b, start, b, start + q, q, 2 * ((b & 1) + 1)))
+        if left & 1:
+            carry = (b, start + 2 * q)
+
+    a, z, fa, kz = 0, 63, 0, 0
+    while True:
+        while a < z and tot[a] - fa == 0:
+            a, fa = a + 1, 0
+        while z > a and tot[z] - kz == 0:
+            z, kz = z - 1, 0
+        if a == z:
+            avail = tot[a] - fa - kz
+            if avail >= 2 and 2 * ((a >> 1) + 1) <= 32:
+                q = avail >> 1
+                runs.append((a, fa, a, fa + q, q, 2 * (a & 1) + 1))
+                fa, avail = fa + 2 * q, avail - 2 * q
+            if avail > 0:
+                alone(a, fa, avail)
+            break
+        ra, rz = tot[a] - fa, tot[z] - kz
+        if (a >> 1) + 1 + (z >> 1) + 1 <= 32:
+            q = min(ra, rz)
+            runs.append((a, fa, z, rz - q, q, (a & 1) + (z & 1) + 1))
+            fa, kz = fa + q, kz + q
+        else:
+            alone(z, 0, rz)
+            kz += rz
+    order = np.empty(n, dtype=np.int64)
+    full = (n >> 3) << 2
+    nxt = np.concatenate([[0], np.cumsum([sum(r[4] for r in runs if r[5] == k) for k in (1, 2, 3)])])
+    for ba, sa, bb, sb, q, cost in runs:
+        pp = nxt[cost - 1] + np.arange(q)
+        nxt[cost - 1] += q
+        host, guest = work[base[ba] + sa + np.arange(q)], work[base[bb] + sb + np.arange(q)]
+        slot = np.where(pp < full, 8 * (pp >> 2) + (pp & 3), 2 * full + 2 * (pp - full))
+        order[slot] = host
+        order[slot + np.where(pp < full, 4, 1)] = guest
+    if carry is not None:
+        order[n - 1] = work[base[carry[0]] + carry[1]]
+    return order
+
+
+def chain3_pair_order(count):
+    """Processing order of sa_chain3's neighbourhoods for its row packing: slots 8 g + w and 8 g + w + 4 (waves w and
+    w + 4 of a workgroup) hold two neighbourhoods whose remainders ``(count - 1) % 32 + 1`` share one point tile where the
+    greedy matching found a partner, and the pairs are sorted by cost in tiles (``chain3_pair_cost``), light ones first,
+    so that whole workgroups are of one cost.  A permutation; which one is sa_chain3's speed only, never its result."""
+    c = count.reshape(-1)
+    if c.is_cuda and c.dtype == torch.int64 and c.numel() <= (1 << 24):
+        return pn2_ext.pair_order(c)
+    return torch.from_numpy(_pair_order_host(c.cpu().numpy())).to(c.device)
+
+
 # EXPERIMENT (VERDICT r5 #6), off: the level-1 block with fp32-faithful products on the bf16 matrix pipe (csrc/sa_split.hip).  Never a
 # default path; bench.py reports it under its own name (value_split_products).
 SPLIT_PRODUCTS = False
@@ -493,12 +571,11 @@ def sa_group(module, xyz, ctr, first_tie=None):
         geo["first_tie"] = first_tie
     if (CHAIN3 and module.grouper.num_neighbours == 64 and len(module.mlp) == 3
             and module.mlp[0].conv.in_channels <= 8):
-        # for the register-chained block (narrow gathered input, sa_features): neighbourhoods with <= 32 members first
-        # (one point tile instead of two), then those with 33..48 (waves w and w + 4 of a workgroup share a third tile:
-        # three tiles per pair, csrc/sa_chain.hip), then the full ones, so that whole workgroups are of one kind;
-        # computed here, in the geometry stage, off the matrix cores' critical path
+        # for the register-chained block (narrow gathered input, sa_features): partners whose remainders fit one point
+        # tile at waves w and w + 4 of a workgroup (csrc/sa_chain.hip), pairs of 1, 2, 3, 4 tiles in that order so that
+        # whole workgroups are of one kind; computed here, in the geometry stage, off the matrix cores' critical path
         geo["count"] = count
-        geo["order"] = chain3_order(count)
+        geo["order"] = chain3_pair_order(count)
     elif (PREMUL and not module.training and not torch.is_grad_enabled() and module.use_xyz
           and module.mlp[0].conv.in_channels > 8 and len(module.mlp) >= 2):
         # wide gathered input (levels 2+, see sa_features): everything of the pre-multiplied first layer that depends on the

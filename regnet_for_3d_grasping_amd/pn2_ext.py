@@ -163,6 +163,21 @@ def class_order(count):
     return order
 
 
+def pair_order(count):
+    """count (...) int64 GPU tensor of ball-query member counts -> (count.numel(),) int64: the processing order that puts
+    neighbourhoods whose remainders share a point tile at slots 8 g + w and 8 g + w + 4, pairs sorted by cost in tiles
+    (regnet_pair_order_i64, one launch; ``fused.chain3_pair_order`` states the same plan in numpy)."""
+    _need_i64(count, "count")
+    flat = count.reshape(-1)
+    flat = flat if flat.is_contiguous() else flat.contiguous()
+    with torch.cuda.device(count.device):
+        order = torch.empty((flat.numel(),), dtype=torch.int64, device=count.device)
+        work = torch.empty((flat.numel(),), dtype=torch.int32, device=count.device)
+        _check(_L.regnet_pair_order_i64(flat.data_ptr(), flat.numel(), order.data_ptr(), work.data_ptr(), _stream(count)),
+               "pair_order")
+    return order
+
+
 _fps_flags = {}
 
 
