@@ -776,6 +776,50 @@ int regnet_dataset_resample_f32(const float* cloud, const float* color, const fl
                                 const int64_t* pick, int64_t N, const double* rand6, float* pc, float* score_out,
                                 float* label_out, int32_t* out_of_range, void* stream);
 
+/* ---- single-frame ingest (csrc/ingest.hip): the front end of the reference's test.py:101-129 on the device ----------
+ * regnet_ingest_crop_f32 / regnet_ingest_crop_f64: rigid transform into the table frame (test.py:104) + workspace crop
+ * (:114-118) of one raw camera frame as an order-preserving compaction.
+ *   xyz, rgb   (M,3) contiguous DEVICE arrays, float32 (_f32) or float64 (_f64); float32 input is widened exactly.
+ *   transform  HOST pointer, 16 doubles, row-major 4x4 (rows 0..2 are used: the reference's transform is rigid).
+ *   bounds     HOST pointer, 5 doubles {x_hi, x_lo, z_hi, y_hi, y_lo}: a point is kept when x < x_hi, x > x_lo, z < z_hi,
+ *              y < y_hi and y > y_lo, all strict, in the order of :114-118 (+-infinity switches a test off).
+ *   drop_nonfinite != 0 drops rows with a NaN / infinite INPUT coordinate before the tests.  An explicit guard only: such a
+ *              coordinate reaches x as NaN (also through 0 * inf) or as an infinity, and both fail a strict two-sided test.
+ * Arithmetic (the translation unit is built with -ffp-contract=off): every coordinate is
+ * ((T[r][0] x + T[r][1] y) + T[r][2] z) + T[r][3] in float64, each product and sum individually rounded; the tests are made
+ * on those float64 values (the reference compares the float64 array).  Kept rows are written IN INPUT ORDER --
+ * np.random.choice (:122-127) indexes this list:
+ *   kept_xyz64 (M,3) float64, kept_xyz32 (M,3) float32 = kept_xyz64 rounded to nearest (torch.Tensor(pc), :129),
+ *   kept_rgb (M,3) float64, kept_src (M) int32 source rows or NULL; rows from *count on are left untouched.
+ *   count      (1) int32 DEVICE: the number of kept rows.  No host read, no synchronisation.
+ *   workspace  regnet_ingest_crop_workspace_bytes(M) bytes, 8-byte aligned (per-wave ballots + per-workgroup counts).
+ * Three launches (flags + counts, a one-workgroup exclusive scan, placement); no workgroup waits for another.
+ * M == 0: *count = 0, nothing else touched (only `count`, `transform`, `bounds` must be non-NULL).  Nothing kept:
+ * *count = 0.  Errors: M < 0 -> REGNET_ERR_SHAPE; M > 2^21 -> REGNET_ERR_UNSUPPORTED (the workspace size is then -1);
+ * a NULL pointer for a required array -> REGNET_ERR_NULL.                                                              */
+int64_t regnet_ingest_crop_workspace_bytes(int64_t M);
+int regnet_ingest_crop_f32(const float* xyz, const float* rgb, int64_t M, const double* transform, const double* bounds,
+                           int drop_nonfinite, double* kept_xyz64, float* kept_xyz32, double* kept_rgb, int32_t* kept_src,
+                           int32_t* count, void* workspace, void* stream);
+int regnet_ingest_crop_f64(const double* xyz, const double* rgb, int64_t M, const double* transform, const double* bounds,
+                           int drop_nonfinite, double* kept_xyz64, float* kept_xyz32, double* kept_rgb, int32_t* kept_src,
+                           int32_t* count, void* workspace, void* stream);
+/* regnet_ingest_resample_f32: utils.noise_color (utils.py:426-431) + pc[select_point_index] + torch.Tensor(pc)
+ * (test.py:120-129) as one gather: xyz (rows,3) float32, rgb (rows,3) float64 (rgb_is_f64 != 0: the real_data branch,
+ * float64 product rounded to float32) or float32 (the record branch: numpy >= 2 multiplies the float32 column by the
+ * float64 gain in double and rounds back to float32 -- the same value), pick (N) int64 drawn with numpy's stream, rand3 =
+ * the three np.random.rand() values drawn BEFORE the choice (gain 1 - r / 5), float64; all device memory.  count (1) int32
+ * device or NULL: the number of valid rows (at most `rows`; NULL = rows).  pc (N,6) float32 = [xyz | rgb * gain].  A pick
+ * outside [0, count) -- the -1 rows an empty list draws, where np.random.choice raises -- writes a row of zeros and ORs 1
+ * into *out_of_range (may be NULL); nothing is read out of bounds.  Errors: rows < 0 or N < 0 -> REGNET_ERR_SHAPE.     */
+int regnet_ingest_resample_f32(const float* xyz, const void* rgb, int rgb_is_f64, const int32_t* count, int64_t rows,
+                               const int64_t* pick, int64_t N, const double* rand3, float* pc, int32_t* out_of_range,
+                               void* stream);
+/* regnet_lzf_decompress: HOST code, the LZF codec of PCD `DATA binary_compressed` bodies (what open3d.io.read_point_cloud
+ * does for test.py:102).  -> the number of bytes written to out (at most out_cap), or REGNET_ERR_SHAPE for a truncated /
+ * corrupt stream or one that does not fit, REGNET_ERR_NULL for a NULL buffer of non-zero length.                          */
+int64_t regnet_lzf_decompress(const uint8_t* in, int64_t in_len, uint8_t* out, int64_t out_cap);
+
 /* ---- deterministic mode (csrc/scatter.hip, csrc/det.hip, csrc/bn_train.hip) ------------------------------------------
  * The float32 kernels behind torch.use_deterministic_algorithms(True): every sum of the training backward is formed in one
  * fixed order, so runs agree bit for bit.  The default entry points above are unchanged.

@@ -158,6 +158,12 @@ SIGNATURES = {
     "regnet_np_choice_rows_dev": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp]),
     "regnet_np_rand_doubles_dev": (_int, [_vp, _vp, _i64, _vp, _vp]),
     "regnet_dataset_resample_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # single-frame ingest (test.py's front end)
+    "regnet_ingest_crop_workspace_bytes": (_i64, [_i64]),
+    "regnet_ingest_crop_f32": (_int, [_vp, _vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "regnet_ingest_crop_f64": (_int, [_vp, _vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "regnet_ingest_resample_f32": (_int, [_vp, _vp, _int, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "regnet_lzf_decompress": (_i64, [_vp, _i64, _vp, _i64]),
     # deterministic mode
     "regnet_scatter_plan_bytes": (_i64, [_i64, _i64, _i64]),
     "regnet_scatter_plan": (_int, [_vp, _i64, _i64, _i64, _vp, _vp]),

@@ -36,6 +36,7 @@ SOURCES = [
     ("ops_f64.hip", ["-ffp-contract=off"]),   # float64 operators: indices depend on individually rounded distances
     ("scatter.hip", ["-ffp-contract=off"]),   # deterministic scatter-adds: interpolate adds individually rounded products
     ("det.hip", ["-ffp-contract=off"]),   # deterministic mode: scatter_max_grad
+    ("ingest.hip", ["-ffp-contract=off"]),   # test.py's front end: crop predicates on individually rounded float64 coordinates
 ]
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc"]
@@ -65,7 +66,8 @@ REPO = os.path.dirname(os.path.dirname(HERE))
 # error, not a slow kernel found later in a profile (object file -> mangled-name fragments)
 NO_VGPR_SPILL = {"mlp.o": ["mlp_gemm_kernelILi0E", "gemm2_kernel"], "sa_chain.o": ["sa_chain_kernel"],
                  "heads.o": ["heads_chain_kernel", "heads_tree_kernel"], "ops_f64.o": ["_f64_kernel"],
-                 "scatter.o": ["scatter_", "segsum_"], "det.o": ["det_"]}
+                 "scatter.o": ["scatter_", "segsum_"], "det.o": ["det_"],
+                 "ingest.o": ["ingest_"]}
 
 
 def check_no_vgpr_spill(obj_path, fragments):

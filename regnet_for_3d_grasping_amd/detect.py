@@ -1,0 +1,165 @@
+"""Single-file inference, the reference's ``test.py`` (:94-164) + ``utils.eval_notruth`` (utils.py:391-424): a camera frame
+(``.pcd``) or a dataset record (``.p``) in, the ``*_data_predict/*.p`` file of collision-filtered grasps out.
+
+``GraspDetector.detect`` chains ``ingest`` (transform, crop, colour gains and the ``np.random.choice`` rows on the device)
+-> ScoreNet -> ``get_grasp_allobj`` -> the region network -> ``eval_collision.eval_test`` on each of the four grasp sets,
+inside one ``np_random.deferred()`` block.  What it adds to the host reads the grouping and region stages already make is a
+4-byte read of the kept count before the collision filter and the final download.  Run as a module for ``test.py``'s
+``main()``:
+
+    python -m regnet_for_3d_grasping_amd.detect --folder DIR [--file NAME] --load-score-path S --load-region-path R
+"""
+import argparse
+import contextlib
+import glob
+import io
+import os
+import pickle
+
+import numpy as np
+
+# test.py:61-81, :90
+ALL_POINTS_NUM = 25600
+OBJ_CLASS_NUM = 43
+WIDTH, HEIGHT, DEPTH = 0.08, 0.010, 0.06
+TABLE_HEIGHT = 0.75
+CENTER_NUM = 4000
+MODEL_PARAMS = [OBJ_CLASS_NUM, 256, 64, 0.5, DEPTH, 10]
+TEST_PARAMS = [CENTER_NUM, 0.5, 256, 0.1, 2048, 0.8, WIDTH, HEIGHT, DEPTH]
+GRIPPER_PARAMS = [WIDTH, HEIGHT, DEPTH]
+EVAL_PARAMS = [DEPTH, WIDTH, TABLE_HEIGHT, 0, CENTER_NUM]
+USE_THETA = True
+RESULT_KEYS = ("points", "colors", "scores", "grasp_stage2", "grasp_stage3_stage2", "grasp_stage3", "grasp_stage3_score")
+
+
+def save_path_for(pc_path, real_data):
+    """test.py:143-145: ``_data`` -> ``_data_predict`` anywhere in the path; camera frames also ``.pcd`` -> ``.p``."""
+    path = pc_path.replace("_data", "_data_predict")
+    return path.replace(".pcd", ".p") if real_data else path
+
+
+class GraspDetector:
+    """``GraspDetector(score_net, region_net)``: both networks on one GPU, in eval mode for the call.  ``params`` /
+    ``gripper_params`` / ``eval_params`` are test.py's lists (:78-81, :90; ``eval_params[3]`` is the GPU index of the
+    collision filter and follows the networks' device).  ``transform`` / ``bounds``: see ``ingest.ingest_frame``."""
+
+    def __init__(self, score_net, region_net, params=TEST_PARAMS, gripper_params=GRIPPER_PARAMS, eval_params=EVAL_PARAMS,
+                 transform=None, bounds=None, num_points=ALL_POINTS_NUM, use_theta=USE_THETA):
+        from . import ingest
+        self.score_net, self.region_net = score_net, region_net
+        self.params, self.gripper_params, self.eval_params = list(params), list(gripper_params), list(eval_params)
+        self.transform = ingest.table_frame_transform() if transform is None else np.asarray(transform, dtype=np.float64)
+        self.bounds = ingest.DEFAULT_BOUNDS if bounds is None else tuple(bounds)
+        self.num_points, self.use_theta = int(num_points), use_theta
+        self.device = next(score_net.parameters()).device
+        if self.device.type != "cuda":
+            raise RuntimeError("GraspDetector: the networks must be on a GPU (no CPU path)")
+
+    def ingest(self, frame):
+        """``frame``: an ``ingest.Frame``, an ``(xyz, rgb)`` pair of a camera frame, or a record dict -> ``ingest.Frame``."""
+        from . import ingest
+        if isinstance(frame, ingest.Frame):
+            return frame
+        if isinstance(frame, dict):
+            return ingest.ingest_record(frame, self.num_points, self.device)
+        xyz, rgb = frame
+        return ingest.ingest_frame(xyz, rgb, self.transform, self.bounds, self.num_points, self.device)
+
+    def detect(self, frame):
+        """test.py:97-148 for one frame -> ``eval_notruth``'s dict of numpy arrays: ``points`` / ``colors`` (the cropped,
+        un-jittered cloud: float64 for a camera frame, float32 for a record), ``scores`` (N,1) float32 and the four
+        collision-filtered grasp sets (k,8) float32."""
+        import torch
+        from . import eval_collision, np_random
+        from .get_regiondataset import get_grasp_allobj
+        depth, width, table_height, _, _ = self.eval_params
+        gpu = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        was_training = self.score_net.training, self.region_net.training
+        self.score_net.eval()
+        self.region_net.eval()
+        try:
+            # (the stages' progress prints stay off stdout: detect_file's three count lines are all a caller sees)
+            with np_random.deferred(), torch.no_grad(), torch.cuda.device(self.device), \
+                    contextlib.redirect_stdout(io.StringIO()):
+                fr = self.ingest(frame)
+                pc = fr.pc
+                all_feature, output_score, _ = self.score_net(pc)
+                g = get_grasp_allobj(pc, output_score, self.params, [], self.use_theta)
+                res = self.region_net(g[3], g[5], g[2], g[4], g[0], g[1], pc, all_feature, self.gripper_params, None, [])
+                # eval_notruth(pc_back, color_back, grasp_stage2, select_grasp_class, select_grasp_score,
+                #              select_grasp_class_stage2, output_score, ...): test.py:147 -> utils.py:391
+                sets = {"grasp_stage2": res[0], "grasp_stage3_stage2": res[8], "grasp_stage3": res[6],
+                        "grasp_stage3_score": res[7]}
+                kept = fr.kept()
+                points32 = fr.points32[:kept]
+                self.raw_counts = {}
+                for key, grasp in sets.items():
+                    if grasp is None:      # (the refine head saw no valid crop: an empty set)
+                        grasp = torch.zeros((0, 8), dtype=torch.float32, device=self.device)
+                    self.raw_counts[key] = int(grasp.shape[0])
+                    if grasp.shape[0] >= 1:
+                        grasp = eval_collision.eval_test(points32, grasp[:, :8], None, table_height, depth, width, gpu)
+                    sets[key] = grasp
+                points, colors = fr.download(kept)
+                out = {"points": points, "colors": colors, "scores": output_score.view(-1, 1).cpu().numpy()}
+                out.update({key: grasp.cpu().numpy() for key, grasp in sets.items()})
+        finally:
+            self.score_net.train(was_training[0])
+            self.region_net.train(was_training[1])
+        return {key: out[key] for key in RESULT_KEYS}
+
+    def detect_file(self, path, save_path=None, real_data=None):
+        """``test_one_file`` (test.py:94-148): ``.pcd`` -> camera frame, anything else -> dataset record, unless ``real_data``
+        says so.  The dict is pickled to ``save_path`` (default: the rule of :143-145; no file when that rule leaves the path
+        unchanged, which would overwrite the input).  Prints the reference's three count lines.  -> (dict, save path or None)."""
+        from . import ingest
+        if real_data is None:
+            real_data = path.lower().endswith(".pcd")
+        if real_data:
+            xyz, rgb, _ = ingest.read_pcd(path)
+            out = self.detect((xyz, rgb))
+        else:
+            with open(path, "rb") as f:
+                out = self.detect(pickle.load(f))
+        print("stage2 grasp num:", len(out["grasp_stage2"]))
+        print("stage3 grasp num:", len(out["grasp_stage2"]))        # (sic: utils.py:410 prints the stage-2 count twice)
+        print("stage3 grasp num (with scorethre):", len(out["grasp_stage3_score"]))
+        if save_path is None:
+            save_path = save_path_for(path, real_data)
+            if save_path == path:
+                return out, None
+        os.makedirs(os.path.dirname(os.path.abspath(save_path)), exist_ok=True)
+        with open(save_path, "wb") as f:
+            pickle.dump(out, f)
+        return out, save_path
+
+
+def main(argv=None):
+    """``main()`` of test.py:150-164."""
+    from . import checkpoint
+    parser = argparse.ArgumentParser(description="REGNet single-file inference (the reference's test.py)")
+    parser.add_argument("--folder", "--folder-name", dest="folder", required=True)
+    parser.add_argument("--file", "--file-name", dest="file", default="")
+    parser.add_argument("--load-score-path", required=True)
+    parser.add_argument("--load-region-path", required=True)
+    parser.add_argument("--gpu", type=int, default=0)
+    args = parser.parse_args(argv)
+    obj_class_num, group_num, gripper_num, score_thre, depth, reg_channel = MODEL_PARAMS
+    dev = "cuda:%d" % args.gpu
+    with contextlib.redirect_stdout(io.StringIO()):
+        score_net, _ = checkpoint.construct_scorenet(True, obj_class_num, args.load_score_path, args.gpu)
+        region_net, _ = checkpoint.construct_rnet(True, True, group_num, gripper_num, score_thre, depth, reg_channel,
+                                                  args.load_region_path, args.gpu)
+    eval_params = [DEPTH, WIDTH, TABLE_HEIGHT, args.gpu, CENTER_NUM]
+    detector = GraspDetector(score_net.to(dev), region_net.to(dev), eval_params=eval_params)
+    real_data = "real_data" in args.folder
+    if args.file:
+        paths = [os.path.join(args.folder, args.file)]
+    else:
+        paths = glob.glob(args.folder + ("/*.pcd" if real_data else "/*.p"), recursive=True)
+    for path in paths:
+        detector.detect_file(path, real_data=real_data)
+
+
+if __name__ == "__main__":
+    main()
