@@ -65,6 +65,8 @@ REPO = os.path.dirname(os.path.dirname(HERE))
 # kernels whose register budget is part of their design: a build in which one of them spills vector registers to scratch is an
 # error, not a slow kernel found later in a profile (object file -> mangled-name fragments)
 NO_VGPR_SPILL = {"mlp.o": ["mlp_gemm_kernelILi0E", "gemm2_kernel"], "sa_chain.o": ["sa_chain_kernel"],
+                 # (not fp_head_chain_kernel<true>: it spills a few registers in its interpolating prologue, DESIGN.md par. 5)
+                 "rowchain.o": ["sa_premul_chain_kernel", "sa3_premul_chain_kernel", "fp_head_chain_kernelILb0E"],
                  "heads.o": ["heads_chain_kernel", "heads_tree_kernel"], "ops_f64.o": ["_f64_kernel"],
                  "scatter.o": ["scatter_", "segsum_"], "det.o": ["det_"],
                  "ingest.o": ["ingest_"]}

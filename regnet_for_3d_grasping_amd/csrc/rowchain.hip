@@ -25,6 +25,10 @@
 //   is laid out on the host in consumption order, already swizzled: the fetch is a linear copy.
 //   One resident workgroup per CU draws 128-row blocks from a ticket counter (a block = one pass over the stream), so a
 //   CU that another stream's kernel keeps busy simply takes fewer blocks.
+// Measured slower and not kept (DESIGN.md par. 5, docs/history/DESIGN_rounds1-5.md par. 5.3b; such switches live in
+// scripts/ablate/*.patch, not here): a stage's LDS-DMA pieces issued between its MFMA steps instead of all right behind the
+// barrier (2 % per kernel, same step time); the last round of a launch handed out as half blocks on waves 0-3 (1.74-1.83 vs
+// 1.65-1.67 ms inside the pipeline: a pass costs its weight stream however few rows it holds).
 #include "common.h"
 
 typedef float rc_f32x4 __attribute__((ext_vector_type(4)));
@@ -39,16 +43,8 @@ typedef float rc_f32x4 __attribute__((ext_vector_type(4)));
 #define RC_STAGES (RC_WAVES == 8 ? 3 : 2)      // ring depth (two workgroups per CU: 2 x 2 x 32 KiB)
 #endif
 #define RC_PIECES (32 / RC_WAVES)              // 1 KiB LDS-DMA pieces per wave per stage
-#ifndef RC_TAIL_HALF
-#define RC_TAIL_HALF 0                         // 1: the last 128 blocks of a launch are handed out as half blocks (waves 0-3;
-                                               // measured SLOWER inside the pipeline: 1.74-1.83 vs 1.65-1.67 ms, A/B on one box)
-#endif
-#ifndef RC_SPREAD_FETCH
-#define RC_SPREAD_FETCH 0                      // 1: a stage's LDS-DMA pieces are issued between its MFMA steps (measured 2 %
-                                               // SLOWER per kernel, same step time); 0: all right behind the barrier
-#endif
 #ifndef RC_MIDSYNC
-#define RC_MIDSYNC (RC_WAVES == 8 && !RC_SPREAD_FETCH)   // 1: fp_head_chain / sa_premul_chain meet in the MIDDLE of a stage (ring of 4)
+#define RC_MIDSYNC (RC_WAVES == 8)             // 1: fp_head_chain / sa3_premul_chain meet in the MIDDLE of a stage (ring of 4)
 #endif
 #define RC_MID_STAGES (RC_MIDSYNC ? 4 : RC_STAGES)
 #ifndef RC_SYNC_STEP
@@ -56,30 +52,6 @@ typedef float rc_f32x4 __attribute__((ext_vector_type(4)));
 #endif
 #define RC_AFFINE_MAX 4096                     // floats of folded BN affine kept in LDS
 #define RC_INTERP_FLOATS 1536                  // + the interpolating prologue's tables: Wd4 (256 x 4) | scale1 (256) | shift1 (256)
-
-struct RcArgs {
-  const float* X;  long long ldx;              // (P, 256) first-layer activation (channels-last), 16-byte aligned rows
-  float* F;        long long ldf;              // (P, 256) point feature out
-  float* score;                                // (P)
-  long long P;
-  const float* stream;                         // weight stream: n_stages x 32 KiB, consumption order, swizzled
-  int n_stages;                                // stages per pass over a row block (the chain's total)
-  const float* affine;                         // per layer [scale(N) | shift(N)], concatenated in layer order
-  int affine_floats;
-  const float* wscore;                         // conv_score weight (128)
-  float score_bias, score_bn_scale, score_bn_shift;
-  int* ticket;                                 // work queue head (zeroed by the caller before the launch)
-  long long n_blocks;                          // tickets to hand out: n_full whole blocks (8 waves) + half blocks (waves 0-3)
-  long long n_full;                            // tickets < n_full are whole blocks; ticket t >= n_full: half block t - n_full
-  long long blk_first, blk_count;              // this LAUNCH hands out blocks [blk_first, blk_first + blk_count) (a launch may be
-                                               // split: the last partial round of blocks on a side stream, fused.py)
-  // ---- interpolating prologue (fp_head_chain_kernel<true>): the first FP layer is evaluated right here, X is not read
-  const float* ys; long long ys_sb, ys_sn;     // (B, Ns, 256) sparse rows already multiplied by the layer's W[:, :Cs]
-  const long long* idx; const float* dist2;    // (P, 3) three nearest sparse points and their SQUARED distances
-  float eps; long long Nd;                     // weights 1 / max(d2, eps), normalised (modules.py:117-122); points per scene
-  const float* dsm; long long db, dn, dc; int Cdsm;   // narrow skip input (B, Cd <= 4, Nd), element strides (rgb)
-  const float* tables;                         // Wd4 (256 x 4) | scale1 (256) | shift1 (256)
-};
 
 __device__ __forceinline__ void rc_glds16(const float* gsrc, unsigned lds_dst) {
   unsigned keep;
@@ -95,20 +67,19 @@ __device__ __forceinline__ void rc_barrier_lds() { asm volatile("s_waitcnt lgkmc
 
 // The weight-stream ring.  Stage s of the (periodic) stream lives in ring slot s % STAGES.
 //
-// Two hand-over schemes (round 5):
-//  MID = false (3 slots; rounds 2-4, still sa_premul_chain_kernel): the barrier sits at the
+// Two hand-over schemes:
+//  MID = false (RcRingEdge, 3 slots: sa_premul_chain_kernel, for the reason given there): the barrier sits at the
 //    stage BOUNDARY -- acquire() waits for the next stage, everybody meets, the stage behind the ones in flight is fetched into
 //    the slot consumed last.  Every stage then starts with the matrix pipe empty: barrier, four LDS-DMA issues with their
 //    address arithmetic, the first fragment's LDS round trip -- on both waves of a SIMD at once, because the barrier released
-//    them together (measured: 14 % of fp_head_chain_kernel's shader cycles per block are not MFMA issue, ~1 300 per stage).
-//  MID = true (4 slots; fp_head_chain_kernel, sa3_premul_chain_kernel): the barrier sits in the MIDDLE of a stage (step
-//    RC_SYNC_STEP of 16).  At that point every wave is inside stage s, so the slot of stage s - 1 is free: the fetch of stage
-//    s + 3 goes there; and the counted wait in front of the barrier makes stage s + 1 readable for everybody.  The stage
+//    them together (measured: 14 % of fp_head_chain_kernel's shader cycles per block were not MFMA issue, ~1 300 per stage).
+//  MID = true (RcRingMid, 4 slots: fp_head_chain_kernel, sa3_premul_chain_kernel): the barrier sits in the MIDDLE of a stage
+//    (step RC_SYNC_STEP of 16).  At that point every wave is inside stage s, so the slot of stage s - 1 is free: the fetch of
+//    stage s + 3 goes there; and the counted wait in front of the barrier makes stage s + 1 readable for everybody.  The stage
 //    boundary itself needs nothing: a wave runs from the last MFMA of stage s into the first fragment reads of stage s + 1
 //    without meeting anyone, and the DMA issue + barrier happen between two MFMA steps whose operands are already in registers.
 template <int STAGES, bool MID>
 struct RcRing {
-  static constexpr bool mid = MID;
   const float* src;        // this lane's source of piece 0 of the next stage to fetch
   const float* src_begin;  // ... of stream stage 0
   int fetch_idx;           // stream index (0 .. n_stages) of the next stage to fetch
@@ -116,6 +87,7 @@ struct RcRing {
   unsigned lds_fetch;      // LDS byte address of this wave's piece 0 in the slot the next fetch goes to
   unsigned lds_lo, lds_hi; // ... in slot 0 / one past the last slot
   int slot;                // ring slot of the stage to be consumed next
+  bool primed;             // the first block of this workgroup has started the ring
 
   __device__ __forceinline__ void init(const float* stream, int n, float* smem, int wave, int lane) {
     n_stages = n;
@@ -126,19 +98,15 @@ struct RcRing {
     lds_hi = lds_lo + STAGES * RC_STAGE_FLOATS * 4;
     lds_fetch = lds_lo;
     slot = 0;
-  }
-  __device__ __forceinline__ void fetch_piece(int j) {   // j = 0 .. RC_PIECES - 1, in order; the last one advances the ring
-    rc_glds16(src + j * 256, lds_fetch + j * 1024);
-    if (j == RC_PIECES - 1) {
-      src += RC_STAGE_FLOATS;
-      if (++fetch_idx == n_stages) { fetch_idx = 0; src = src_begin; }
-      lds_fetch += RC_STAGE_FLOATS * 4;
-      if (lds_fetch == lds_hi) lds_fetch = lds_lo;
-    }
+    primed = false;
   }
   __device__ __forceinline__ void fetch() {
 #pragma unroll
-    for (int j = 0; j < RC_PIECES; ++j) fetch_piece(j);
+    for (int j = 0; j < RC_PIECES; ++j) rc_glds16(src + j * 256, lds_fetch + j * 1024);
+    src += RC_STAGE_FLOATS;
+    if (++fetch_idx == n_stages) { fetch_idx = 0; src = src_begin; }
+    lds_fetch += RC_STAGE_FLOATS * 4;
+    if (lds_fetch == lds_hi) lds_fetch = lds_lo;
   }
   // Start of the ring: STAGES - 1 stages in flight; MID: stage 0 must be readable before its first fragment read (later
   // stages become readable at the barrier in the middle of the stage before them).
@@ -146,25 +114,23 @@ struct RcRing {
 #pragma unroll
     for (int d = 0; d < STAGES - 1; ++d) fetch();
     if (MID) rc_wait_barrier<(STAGES - 2) * RC_PIECES>();
+    primed = true;
   }
   // Make the next stage readable (mine: counted wait; everybody's: barrier -- which also says that nobody reads the
-  // slot consumed last any more, so the stage behind the ones in flight is fetched into it: right here, or -- with
-  // RC_SPREAD_FETCH -- one LDS-DMA piece at a time between the stage's MFMA steps (RC_FETCH_AT)).  MID: nothing to wait for.
+  // slot consumed last any more, so the stage behind the ones in flight is fetched into it right here) and return it.
+  // MID: nothing to wait for.
   // The counted wait stays correct with other vector memory operations outstanding (activation loads, feature
   // stores, issued after the newest fetch): loads return in order among loads, so "at most RC_PIECES operations
   // outstanding" implies that at most the RC_PIECES newest LOADS are -- every piece of the stage wanted here is older
-  // than those; extra operations only make the wait longer.  DRAIN (vmcnt(0)) is kept as a debugging switch.
-  template <bool DRAIN> __device__ __forceinline__ int acquire() {
+  // than those; extra operations only make the wait longer.
+  __device__ __forceinline__ const float* acquire(const float* smem) {
     if (!MID) {
-      if (DRAIN) rc_wait_barrier<0>();
-      else rc_wait_barrier<(STAGES - 2) * RC_PIECES>();
-#if !RC_SPREAD_FETCH
+      rc_wait_barrier<(STAGES - 2) * RC_PIECES>();
       fetch();
-#endif
     }
     const int s = slot;
     slot = (slot + 1 == STAGES) ? 0 : slot + 1;
-    return s;
+    return smem + s * RC_STAGE_FLOATS;
   }
   // MID, called behind step `step` of the 16 steps of EVERY stage: in flight are the stages s + 1 .. s + STAGES - 2; all but
   // the newest STAGES - 3 of them must have landed (s + 1 is consumed next, without another meeting).
@@ -180,13 +146,20 @@ typedef RcRing<RC_MID_STAGES, (RC_MIDSYNC != 0)> RcRingMid;    // fp_head_chain_
 typedef RcRing<RC_STAGES, false> RcRingEdge;                    // sa_premul_chain_kernel (and RC_MIDSYNC=0 builds)
 #define RC_SA3_POOL_FLOATS (2 * RC_WAVES * 256)
 
-// One LDS-DMA piece of the next fetch behind step STEP_ of a 16-step stage (pieces spread evenly over the steps).
-#if RC_SPREAD_FETCH
-#define RC_FETCH_AT(RING_, STEP_)                                                              \
-  if (((STEP_) + 1) % (16 / RC_PIECES) == 0) (RING_).fetch_piece(((STEP_) + 1) / (16 / RC_PIECES) - 1);
-#else
-#define RC_FETCH_AT(RING_, STEP_) (RING_).at_step(STEP_);
-#endif
+// Head of the block loop.  Row blocks (128 rows = one pass of the 8 waves over the whole weight stream) are handed out
+// through a ticket counter: workgroups that start late -- their CU was busy with another stream's kernel, e.g. a 10 ms
+// furthest-point-sampling workgroup -- simply take fewer.  (A static split over 256 workgroups ran 2.86 ms inside the
+// pipeline against 1.55 ms stand-alone: the workgroups whose CU was taken ran as a second round.)
+// Returns this workgroup's next ticket, or -1 when the launch's `count` blocks are used up; the first ticket starts the ring.
+template <class Ring>
+__device__ __forceinline__ long long rc_next_block(int* ticket, long long count, int* s_blk, Ring& ring) {
+  if (threadIdx.x == 0) *s_blk = atomicAdd(ticket, 1);
+  rc_barrier_lds();                          // (thread 0's wave waited for its atomic; nobody else drains anything)
+  const long long tick = __builtin_amdgcn_readfirstlane(*s_blk);
+  if (tick >= count) return -1;
+  if (!ring.primed) ring.prime();
+  return tick;
+}
 
 // Per-lane fragment offsets (floats) inside a stage.  A-stages are [32 rows][256 k], B-stages [64 rows][128 k]; in both
 // the logical 16-byte chunk 4 kt + g of row (16 t + j) is stored at physical chunk (4 kt + g) ^ j =
@@ -210,48 +183,99 @@ __device__ __forceinline__ RcFrag rc_frag_offsets() {
 // front of their first use, so the two waves of a SIMD -- released by the same barrier, running the same code -- sit
 // out every LDS round trip together (67 TFLOP/s).  The stage loops below are software-pipelined at source level: the
 // reads of step k + 1 are issued in front of the MFMAs of step k.
+// TRANSPOSED swaps the roles: the activation registers as the A operand (rows = points), the weight fragment as the B
+// operand (columns = output channels) -> D[point 4 g + r][channel l & 15].
 #define RC_PIN() __builtin_amdgcn_sched_barrier(0)
-#define RC_MFMA8(W0, W1, X, A0, A1)                                        \
-  A0 = __builtin_amdgcn_mfma_f32_16x16x4f32(W0.x, X.x, A0, 0, 0, 0);       \
-  A1 = __builtin_amdgcn_mfma_f32_16x16x4f32(W1.x, X.x, A1, 0, 0, 0);       \
-  RC_PIN();                                                                \
-  A0 = __builtin_amdgcn_mfma_f32_16x16x4f32(W0.y, X.y, A0, 0, 0, 0);       \
-  A1 = __builtin_amdgcn_mfma_f32_16x16x4f32(W1.y, X.y, A1, 0, 0, 0);       \
-  RC_PIN();                                                                \
-  A0 = __builtin_amdgcn_mfma_f32_16x16x4f32(W0.z, X.z, A0, 0, 0, 0);       \
-  A1 = __builtin_amdgcn_mfma_f32_16x16x4f32(W1.z, X.z, A1, 0, 0, 0);       \
-  RC_PIN();                                                                \
-  A0 = __builtin_amdgcn_mfma_f32_16x16x4f32(W0.w, X.w, A0, 0, 0, 0);       \
-  A1 = __builtin_amdgcn_mfma_f32_16x16x4f32(W1.w, X.w, A1, 0, 0, 0);       \
-  RC_PIN();
+template <bool TRANSPOSED>
+__device__ __forceinline__ void rc_mfma8(const rc_f32x4& w0, const rc_f32x4& w1, const rc_f32x4& x, rc_f32x4& a0, rc_f32x4& a1) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    a0 = TRANSPOSED ? __builtin_amdgcn_mfma_f32_16x16x4f32(x[r], w0[r], a0, 0, 0, 0)
+                    : __builtin_amdgcn_mfma_f32_16x16x4f32(w0[r], x[r], a0, 0, 0, 0);
+    a1 = TRANSPOSED ? __builtin_amdgcn_mfma_f32_16x16x4f32(x[r], w1[r], a1, 0, 0, 0)
+                    : __builtin_amdgcn_mfma_f32_16x16x4f32(w1[r], x[r], a1, 0, 0, 0);
+    RC_PIN();
+  }
+}
 
-// The same step with the roles swapped: the activation registers as the A operand (rows = points), the weight fragment as
-// the B operand (columns = output channels) -> D[point 4 g + r][channel l & 15].
-#define RC_MFMA8_T(W0, W1, X, A0, A1)                                      \
-  A0 = __builtin_amdgcn_mfma_f32_16x16x4f32(X.x, W0.x, A0, 0, 0, 0);       \
-  A1 = __builtin_amdgcn_mfma_f32_16x16x4f32(X.x, W1.x, A1, 0, 0, 0);       \
-  RC_PIN();                                                                \
-  A0 = __builtin_amdgcn_mfma_f32_16x16x4f32(X.y, W0.y, A0, 0, 0, 0);       \
-  A1 = __builtin_amdgcn_mfma_f32_16x16x4f32(X.y, W1.y, A1, 0, 0, 0);       \
-  RC_PIN();                                                                \
-  A0 = __builtin_amdgcn_mfma_f32_16x16x4f32(X.z, W0.z, A0, 0, 0, 0);       \
-  A1 = __builtin_amdgcn_mfma_f32_16x16x4f32(X.z, W1.z, A1, 0, 0, 0);       \
-  RC_PIN();                                                                \
-  A0 = __builtin_amdgcn_mfma_f32_16x16x4f32(X.w, W0.w, A0, 0, 0, 0);       \
-  A1 = __builtin_amdgcn_mfma_f32_16x16x4f32(X.w, W1.w, A1, 0, 0, 0);       \
-  RC_PIN();
+// One A-stage ([32 rows][256 k] at st): acc0 / acc1 += the stage's two 16-row tiles times the 16 operand registers x16[0 .. 15]
+// (compile-time indices: x16 must point into a register array).  Waves without rows in the last pass compute on row 0's
+// data: no branch around the MFMA stream.
+template <bool TRANSPOSED, class Ring>
+__device__ __forceinline__ void rc_stage_a(const float* st, const RcFrag& fo, const rc_f32x4* x16, rc_f32x4& acc0,
+                                           rc_f32x4& acc1, Ring& ring) {
+  rc_f32x4 w0n = *reinterpret_cast<const rc_f32x4*>(st + fo.a[0]);
+  rc_f32x4 w1n = *reinterpret_cast<const rc_f32x4*>(st + fo.a[0] + 16 * 256);
+#pragma unroll
+  for (int kt = 0; kt < 16; ++kt) {
+    const rc_f32x4 w0 = w0n, w1 = w1n;
+    if (kt + 1 < 16) {
+      const float* wp = st + fo.a[(kt + 1) & 3] + 64 * ((kt + 1) >> 2);
+      w0n = *reinterpret_cast<const rc_f32x4*>(wp);
+      w1n = *reinterpret_cast<const rc_f32x4*>(wp + 16 * 256);
+    }
+    RC_PIN();
+    const rc_f32x4 x = x16[kt];
+    rc_mfma8<TRANSPOSED>(w0, w1, x, acc0, acc1);
+    ring.at_step(kt);
+  }
+}
+
+// Channel-major epilogue: register r of a tile = channel c + r of the table at a = table + c (scale; shift `n` floats on);
+// folded BN + ReLU in place turn the accumulator into the next layer's operand.
+__device__ __forceinline__ void rc_affine_relu(rc_f32x4& acc, const float* a, int n) {
+  const rc_f32x4 s = *reinterpret_cast<const rc_f32x4*>(a), t = *reinterpret_cast<const rc_f32x4*>(a + n);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) acc[r] = fmaxf(acc[r] * s[r] + t[r], 0.f);
+}
+
+// Point-major epilogue (TRANSPOSED stages): folded BN affine (+ ReLU) of this lane's channel in each tile (scale at a[0] /
+// a[16], shift `n` floats on), max over this wave's 16 points: the 4 registers, then two lane-group exchanges.
+__device__ __forceinline__ void rc_affine_max16(const rc_f32x4& acc0, const rc_f32x4& acc1, const float* a, int n, int relu,
+                                                float& m0, float& m1) {
+  const float sc0 = a[0], sc1 = a[16];
+  const float sh0 = a[n], sh1 = a[n + 16];
+  m0 = -__builtin_inff(); m1 = -__builtin_inff();
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    m0 = fmaxf(m0, acc0[r] * sc0 + sh0);
+    m1 = fmaxf(m1, acc1[r] * sc1 + sh1);
+  }
+  if (relu) { m0 = fmaxf(m0, 0.f); m1 = fmaxf(m1, 0.f); }
+  m0 = fmaxf(m0, __shfl_xor(m0, 16, 64)); m1 = fmaxf(m1, __shfl_xor(m1, 16, 64));
+  m0 = fmaxf(m0, __shfl_xor(m0, 32, 64)); m1 = fmaxf(m1, __shfl_xor(m1, 32, 64));
+}
+
+// x0[kt] = relu(U row - V row)[16 kt + 4 g ..] over 256 channels (ur, vr already point at this lane's 4 g): four loads of
+// each kind in flight at a time (all 32 at once spill).
+__device__ __forceinline__ void rc_load_uv(const float* ur, const float* vr, rc_f32x4 (&x0)[16]) {
+#pragma unroll
+  for (int kq = 0; kq < 4; ++kq) {
+    rc_f32x4 u[4], v[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      u[t] = *reinterpret_cast<const rc_f32x4*>(ur + 16 * (4 * kq + t));
+      v[t] = *reinterpret_cast<const rc_f32x4*>(vr + 16 * (4 * kq + t));
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) x0[4 * kq + t][r] = fmaxf(u[t][r] - v[t][r], 0.f);
+    RC_PIN();
+  }
+}
 
 // Two consecutive layers  A: 256 -> M  and  B: M -> N  as one loop over the 128-channel groups of M:
-//     mid = actA(affA(W_A[group rows] . xin))          4 A-stages ([32 rows][256 k]),  32 registers
+//     mid = relu(affA(W_A[group rows] . xin))          4 A-stages ([32 rows][256 k]),  32 registers
 //     acc += W_B[:, group columns] . mid               N/64 B-stages ([64 rows][128 k])
-// and xout = actB(affB(acc)) at the end.  Nothing in here is indexed by a loop counter except memory: xin, mid and
+// and xout = relu(affB(acc)) at the end.  Nothing in here is indexed by a loop counter except memory: xin, mid and
 // the N/16 accumulators are compile-time register arrays (a register array written at a run-time index would be
 // spilled), and the loop body -- 8 or 6 stages, 128 MFMAs each -- is small enough for the whole chain to stay in the
 // instruction cache.  Stream order: for each group, its A-stages then its B-stages.
-template <int M, int N, bool RELU_B, class Ring>
+template <int M, int N, class Ring>
 __device__ __forceinline__ void rc_pair(const rc_f32x4 (&xin)[16], rc_f32x4 (&xout)[N / 16], Ring& ring,
                                         const float* __restrict__ smem, const float* __restrict__ affA,
-                                        const float* __restrict__ affB, bool active, const RcFrag& fo) {
+                                        const float* __restrict__ affB, const RcFrag& fo) {
   static_assert(M % 128 == 0 && N % 64 == 0, "groups of 128 mid channels; B-stages of 64 output channels");
   const int g4 = ((threadIdx.x & 63) >> 4) * 4;
 #pragma unroll
@@ -262,72 +286,37 @@ __device__ __forceinline__ void rc_pair(const rc_f32x4 (&xin)[16], rc_f32x4 (&xo
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       rc_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-      const int slot = ring.template acquire<false>();
-      {   // (waves without rows in the last pass compute on row 0's data: no branch around the MFMA stream)
-        const float* st = smem + slot * RC_STAGE_FLOATS;
-        rc_f32x4 w0n = *reinterpret_cast<const rc_f32x4*>(st + fo.a[0]);
-        rc_f32x4 w1n = *reinterpret_cast<const rc_f32x4*>(st + fo.a[0] + 16 * 256);
-#pragma unroll
-        for (int kt = 0; kt < 16; ++kt) {
-          const rc_f32x4 w0 = w0n, w1 = w1n;
-          if (kt + 1 < 16) {
-            const float* wp = st + fo.a[(kt + 1) & 3] + 64 * ((kt + 1) >> 2);
-            w0n = *reinterpret_cast<const rc_f32x4*>(wp);
-            w1n = *reinterpret_cast<const rc_f32x4*>(wp + 16 * 256);
-          }
-          RC_PIN();
-          const rc_f32x4 x = xin[kt];
-          RC_MFMA8(w0, w1, x, acc0, acc1)
-          RC_FETCH_AT(ring, kt)
-        }
-      }
+      rc_stage_a<false>(ring.acquire(smem), fo, xin, acc0, acc1, ring);
       const float* a = affA + 128 * ob + 32 * u + g4;   // register r of tile t = channel 16 t + 4 g + r
-      const rc_f32x4 s0 = *reinterpret_cast<const rc_f32x4*>(a), s1 = *reinterpret_cast<const rc_f32x4*>(a + 16);
-      const rc_f32x4 t0 = *reinterpret_cast<const rc_f32x4*>(a + M), t1 = *reinterpret_cast<const rc_f32x4*>(a + M + 16);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        acc0[r] = fmaxf(acc0[r] * s0[r] + t0[r], 0.f);
-        acc1[r] = fmaxf(acc1[r] * s1[r] + t1[r], 0.f);
-      }
+      rc_affine_relu(acc0, a, M);
+      rc_affine_relu(acc1, a + 16, M);
       mid[2 * u] = acc0; mid[2 * u + 1] = acc1;
     }
     // ---- layer B, k-slice [128 ob, 128 ob + 128) for all N outputs
 #pragma unroll
     for (int v = 0; v < N / 64; ++v) {
-      const int slot = ring.template acquire<false>();
-      {   // (waves without rows in the last pass compute on row 0's data: no branch around the MFMA stream)
-        const float* st = smem + slot * RC_STAGE_FLOATS;
-        rc_f32x4 w0n = *reinterpret_cast<const rc_f32x4*>(st + fo.b[0]);
-        rc_f32x4 w1n = *reinterpret_cast<const rc_f32x4*>(st + fo.b[0] + 16 * 128);
+      const float* st = ring.acquire(smem);
+      rc_f32x4 w0n = *reinterpret_cast<const rc_f32x4*>(st + fo.b[0]);
+      rc_f32x4 w1n = *reinterpret_cast<const rc_f32x4*>(st + fo.b[0] + 16 * 128);
 #pragma unroll
-        for (int step = 0; step < 16; ++step) {   // tile pair tp = step / 8 (tiles 4 v + 2 tp, + 1), k-step kt = step % 8
-          constexpr int dummy = 0; (void)dummy;
-          const int tp = step >> 3, kt = step & 7;
-          const rc_f32x4 w0 = w0n, w1 = w1n;
-          if (step + 1 < 16) {
-            const int tpn = (step + 1) >> 3, ktn = (step + 1) & 7;
-            const float* wp = st + (2 * tpn) * 16 * 128 + fo.b[ktn & 3] + 64 * (ktn >> 2);
-            w0n = *reinterpret_cast<const rc_f32x4*>(wp);
-            w1n = *reinterpret_cast<const rc_f32x4*>(wp + 16 * 128);
-          }
-          RC_PIN();
-          const rc_f32x4 x = mid[kt];
-          RC_MFMA8(w0, w1, x, xout[4 * v + 2 * tp], xout[4 * v + 2 * tp + 1])
-          RC_FETCH_AT(ring, step)
+      for (int step = 0; step < 16; ++step) {   // tile pair tp = step / 8 (tiles 4 v + 2 tp, + 1), k-step kt = step % 8
+        const int tp = step >> 3, kt = step & 7;
+        const rc_f32x4 w0 = w0n, w1 = w1n;
+        if (step + 1 < 16) {
+          const int tpn = (step + 1) >> 3, ktn = (step + 1) & 7;
+          const float* wp = st + (2 * tpn) * 16 * 128 + fo.b[ktn & 3] + 64 * (ktn >> 2);
+          w0n = *reinterpret_cast<const rc_f32x4*>(wp);
+          w1n = *reinterpret_cast<const rc_f32x4*>(wp + 16 * 128);
         }
+        RC_PIN();
+        const rc_f32x4 x = mid[kt];
+        rc_mfma8<false>(w0, w1, x, xout[4 * v + 2 * tp], xout[4 * v + 2 * tp + 1]);
+        ring.at_step(step);
       }
     }
   }
 #pragma unroll
-  for (int ot = 0; ot < N / 16; ++ot) {
-    const float* a = affB + 16 * ot + g4;
-    const rc_f32x4 s = *reinterpret_cast<const rc_f32x4*>(a), t = *reinterpret_cast<const rc_f32x4*>(a + N);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float y = xout[ot][r] * s[r] + t[r];
-      xout[ot][r] = RELU_B ? fmaxf(y, 0.f) : y;
-    }
-  }
+  for (int ot = 0; ot < N / 16; ++ot) rc_affine_relu(xout[ot], affB + 16 * ot + g4, N);
 }
 
 // FP3 tail + segmentation head: 256 -> 256 -> [F] 256 -> 512 -> 256 -> 256 -> 128 -> score, as three layer pairs.
@@ -336,49 +325,49 @@ __device__ __forceinline__ void rc_pair(const rc_f32x4 (&xin)[16], rc_f32x4 (&xo
 // INTERP: the block's first layer (pn2_utils/modules.py:104-131 + the first SharedMLP layer, evaluated on the sparse rows:
 // fused._fp_first_layer) happens in the prologue -- x0 = relu(scale1 (sum_k w_k Ys[idx_k] + Wd4 . rgb) + shift1) -- instead
 // of in interp_affine_kernel, whose (P x 256) output (210 MB per batch of 8 written, then read here) never exists.
+struct RcArgs {
+  const float* X;  long long ldx;              // (P, 256) first-layer activation (channels-last), 16-byte aligned rows
+  float* F;        long long ldf;              // (P, 256) point feature out
+  float* score;                                // (P)
+  long long P;
+  const float* stream;                         // weight stream: n_stages x 32 KiB, consumption order, swizzled
+  int n_stages;                                // stages per pass over a row block (the chain's total)
+  const float* affine;                         // per layer [scale(N) | shift(N)], concatenated in layer order
+  int affine_floats;
+  const float* wscore;                         // conv_score weight (128)
+  float score_bias, score_bn_scale, score_bn_shift;
+  int* ticket;                                 // work queue head (zeroed by the caller before the launch)
+  long long blk_first, blk_count;              // this LAUNCH hands out blocks [blk_first, blk_first + blk_count) (a launch may be
+                                               // split: the last partial round of blocks on a side stream, fused.py)
+  // ---- interpolating prologue (fp_head_chain_kernel<true>): the first FP layer is evaluated right here, X is not read
+  const float* ys; long long ys_sb, ys_sn;     // (B, Ns, 256) sparse rows already multiplied by the layer's W[:, :Cs]
+  const long long* idx; const float* dist2;    // (P, 3) three nearest sparse points and their SQUARED distances
+  float eps; long long Nd;                     // weights 1 / max(d2, eps), normalised (modules.py:117-122); points per scene
+  const float* dsm; long long db, dn, dc; int Cdsm;   // narrow skip input (B, Cd <= 4, Nd), element strides (rgb)
+  const float* tables;                         // Wd4 (256 x 4) | scale1 (256) | shift1 (256)
+};
+
 template <bool INTERP>
 __global__ __launch_bounds__(RC_THREADS, 2) void fp_head_chain_kernel(const RcArgs p) {
   extern __shared__ __attribute__((aligned(1024))) float smem[];   // ring | affine | wscore | ticket | (interp tables)
   float* const aff = smem + RC_MID_STAGES * RC_STAGE_FLOATS;
   float* const wsc = aff + RC_AFFINE_MAX;
+  int* const s_blk = reinterpret_cast<int*>(wsc + 128);
   float* const itab = wsc + 128 + 4;
   const int tid = threadIdx.x, lane = tid & 63, j = lane & 15, g = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   for (int i = tid; i < p.affine_floats; i += RC_THREADS) aff[i] = p.affine[i];
   for (int i = tid; i < 128; i += RC_THREADS) wsc[i] = p.wscore[i];
   if (INTERP) for (int i = tid; i < RC_INTERP_FLOATS; i += RC_THREADS) itab[i] = p.tables[i];
-#ifndef RC_NO_TABLE_SYNC
   __syncthreads();   // the tables are read after the ring's barriers, which do not wait for LDS writes (lgkmcnt)
-#endif
 
   RcRingMid ring;
   ring.init(p.stream, p.n_stages, smem, wave, lane);
   const RcFrag fo = rc_frag_offsets();
 
-  // Row blocks (128 rows = one pass of the 8 waves over the whole weight stream) are handed out through a ticket
-  // counter: workgroups that start late -- their CU was busy with another stream's kernel, e.g. a 10 ms furthest-
-  // point-sampling workgroup -- simply take fewer.  (A static split over 256 workgroups ran 2.86 ms inside the
-  // pipeline against 1.55 ms stand-alone: the workgroups whose CU was taken ran as a second round.)
-  int* const s_blk = reinterpret_cast<int*>(wsc + 128);
-  const long long units_total = (p.P + 15) / 16;
-  bool primed = false;
-  for (;;) {
-    if (tid == 0) *s_blk = atomicAdd(p.ticket, 1);
-    rc_barrier_lds();                          // (thread 0's wave waited for its atomic; nobody else drains anything)
-    const long long tick = __builtin_amdgcn_readfirstlane(*s_blk);
-    if (tick >= p.blk_count) break;
-    const long long blk = p.blk_first + tick;
-    if (!primed) {   // prologue of the ring: RC_STAGES - 1 stages in flight
-      ring.prime();
-      primed = true;
-    }
-    // whole block: 8 waves x 16 rows; half block (the last round's worth of rows, so that the launch's tail is made of
-    // half-length passes): waves 0-3 only -- one wave per SIMD, which then has the matrix pipe to itself
-    const bool half = blk >= p.n_full;
-    const long long unit = half ? p.n_full * RC_WAVES + (blk - p.n_full) * (RC_WAVES / 2) + wave : blk * RC_WAVES + wave;
-    const bool active = unit < units_total && !(half && wave >= RC_WAVES / 2);   // wave-uniform
-    long long row = unit * 16 + j;
-    const bool row_ok = active && row < p.P;
+  for (long long tick; (tick = rc_next_block(p.ticket, p.blk_count, s_blk, ring)) >= 0;) {
+    long long row = ((p.blk_first + tick) * RC_WAVES + wave) * 16 + j;   // a block = 8 waves x 16 rows
+    const bool row_ok = row < p.P;
     if (!row_ok) row = 0;
     // ---- h1: x0[kt] = X[row][16 kt + 4 g ..]
     rc_f32x4 x0[16];
@@ -428,7 +417,7 @@ __global__ __launch_bounds__(RC_THREADS, 2) void fp_head_chain_kernel(const RcAr
       }
     }
     rc_f32x4 x2[16];
-    rc_pair<256, 256, true>(x0, x2, ring, smem, aff + 0, aff + 512, active, fo);
+    rc_pair<256, 256>(x0, x2, ring, smem, aff + 0, aff + 512, fo);
     // ---- F out
     if (row_ok) {
       float* fr = p.F + row * p.ldf + 4 * g;
@@ -436,9 +425,9 @@ __global__ __launch_bounds__(RC_THREADS, 2) void fp_head_chain_kernel(const RcAr
       for (int ot = 0; ot < 16; ++ot) *reinterpret_cast<rc_f32x4*>(fr + 16 * ot) = x2[ot];
     }
     rc_f32x4 x4[16];
-    rc_pair<512, 256, true>(x2, x4, ring, smem, aff + 1024, aff + 2048, active, fo);
+    rc_pair<512, 256>(x2, x4, ring, smem, aff + 1024, aff + 2048, fo);
     rc_f32x4 x6[8];
-    rc_pair<256, 128, true>(x4, x6, ring, smem, aff + 2560, aff + 3072, active, fo);
+    rc_pair<256, 128>(x4, x6, ring, smem, aff + 2560, aff + 3072, fo);
     // ---- conv_score + bn_score + sigmoid
     float acc = 0.f;
 #pragma unroll
@@ -457,9 +446,22 @@ __global__ __launch_bounds__(RC_THREADS, 2) void fp_head_chain_kernel(const RcAr
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Level-2 set-abstraction block of PointNet2Seg on pre-multiplied layer-1 rows (pointnet2.py:40-42: 259 -> 256 -> 256
-// -> 512 over 1024 x 64 rows per scene; pn2_utils/modules.py:39-56, :244-245), layers 2 + 3 + the max over the 64
-// neighbours in one kernel:
+// Level-2 and level-3 set-abstraction blocks of PointNet2Seg on pre-multiplied layer-1 rows (pointnet2.py:40-42;
+// pn2_utils/modules.py:39-56, :244-245), layers 2 + 3 + the max over the 64 neighbours in one kernel.  A block = 128 rows =
+// 2 neighbourhoods, 4 waves each; all stages are [32 output channels][256 k].
+struct ScArgs {
+  const float* U; long long ldu, scene_stride;   // U row of source point j of scene b: U + b * scene_stride + j * ldu
+  const float* V; long long ldv;                 // V row of neighbourhood g
+  const long long* nbr;                          // (groups, 64)
+  long long groups, groups_per_scene;
+  const float* stream; int n_stages;
+  const float* affine; int affine_floats;        // [scale2(C) | shift2(C) | scale3(2 C) | shift3(2 C)], C = 256 / 512
+  int relu3;
+  float* out; long long ldo;                     // (groups, 2 C)
+  int* ticket; long long n_blocks;
+};
+
+// Level 2 (259 -> 256 -> 256 -> 512 over 1024 x 64 rows per scene):
 //     x0[p] = relu(U[b, nbr[p]] - V[p / 64])        (layer 1, evaluated per source point / per centre: fused.sa_features)
 //     x1 = relu(aff2(W2 . x0))   256 -> 256         channel-major, as in rc_pair's layer A
 //     y  = relu(aff3(x1 . W3^T)) 256 -> 512         POINT-major: x1's registers are just as well the A operand
@@ -467,20 +469,7 @@ __global__ __launch_bounds__(RC_THREADS, 2) void fp_head_chain_kernel(const RcAr
 //                                                   operand; D[point 4 g + r][channel j'] -- the max over the points is then
 //                                                   a max over the 4 registers + two lane-group exchanges, no 16-lane reduction
 //     out[p / 64] = max over the neighbourhood's 4 waves (LDS)
-// The 537 MB (batch of 8) layer-2 activation the two-launch path writes and re-reads never exists.  24 stages per pass,
-// all [32 output channels][256 k]; a block = 128 rows = 2 neighbourhoods.
-struct ScArgs {
-  const float* U; long long ldu, scene_stride;   // U row of source point j of scene b: U + b * scene_stride + j * ldu
-  const float* V; long long ldv;                 // V row of neighbourhood g
-  const long long* nbr;                          // (groups, 64)
-  long long groups, groups_per_scene;
-  const float* stream; int n_stages;
-  const float* affine; int affine_floats;        // [scale2(256) | shift2(256) | scale3(512) | shift3(512)]
-  int relu3;
-  float* out; long long ldo;                     // (groups, 512)
-  int* ticket; long long n_blocks, n_full;     // as RcArgs: whole blocks first, then half blocks
-};
-
+// The 537 MB (batch of 8) layer-2 activation the two-launch path writes and re-reads never exists.  24 stages per pass.
 __global__ __launch_bounds__(RC_THREADS, 2) void sa_premul_chain_kernel(const ScArgs p) {
   extern __shared__ __attribute__((aligned(1024))) float smem[];   // ring | affine (1536) | pool (8 x 512) | ticket
   float* const aff = smem + RC_STAGES * RC_STAGE_FLOATS;
@@ -491,7 +480,7 @@ __global__ __launch_bounds__(RC_THREADS, 2) void sa_premul_chain_kernel(const Sc
   for (int i = tid; i < p.affine_floats; i += RC_THREADS) aff[i] = p.affine[i];
   __syncthreads();
 
-  // (the round-2 hand-over, three slots: this kernel's 174 VGPRs leave room for other streams' waves on its CUs -- the region
+  // (the boundary hand-over, three slots: this kernel's 174 VGPRs leave room for other streams' waves on its CUs -- the region
   // stage's and the geometry's small kernels -- as long as its LDS does too: with a fourth slot (150 KB) they lost that place,
   // their launches took 3 x longer and the step gained nothing from this kernel's 1.5 %)
   RcRingEdge ring;
@@ -499,114 +488,37 @@ __global__ __launch_bounds__(RC_THREADS, 2) void sa_premul_chain_kernel(const Sc
   const RcFrag fo = rc_frag_offsets();
   const int g4 = 4 * g;
 
-  bool primed = false;
-  for (;;) {
-    if (tid == 0) *s_blk = atomicAdd(p.ticket, 1);
-    rc_barrier_lds();                          // (thread 0's wave waited for its atomic; nobody else drains anything)
-    const long long blk = __builtin_amdgcn_readfirstlane(*s_blk);
-    if (blk >= p.n_blocks) break;
-    if (!primed) {
-      ring.prime();
-      primed = true;
-    }
-    const bool half = blk >= p.n_full;                         // half block: one neighbourhood on waves 0-3
-    const long long grp0 = half ? p.n_full * (RC_WAVES / 4) + (blk - p.n_full) * (RC_WAVES / 8) : blk * (RC_WAVES / 4);
+  for (long long blk; (blk = rc_next_block(p.ticket, p.n_blocks, s_blk, ring)) >= 0;) {
+    const long long grp0 = blk * (RC_WAVES / 4);
     const long long grp = grp0 + (wave >> 2);                  // this wave's neighbourhood
-    const bool active = grp < p.groups && !(half && wave >= RC_WAVES / 2);   // wave-uniform
-    const long long gs = active ? grp : 0;
+    const long long gs = grp < p.groups ? grp : 0;             // wave-uniform
     // ---- layer-1 rows of this wave's 16 points
     rc_f32x4 x0[16];
     {
       const long long b = gs / p.groups_per_scene;
       const long long src = p.nbr[gs * 64 + (wave & 3) * 16 + j];
-      const float* ur = p.U + b * p.scene_stride + src * p.ldu + g4;
-      const float* vr = p.V + gs * p.ldv + g4;
-#pragma unroll
-      for (int kq = 0; kq < 4; ++kq) {     // four loads of each kind in flight at a time (all 32 at once spill)
-        rc_f32x4 u[4], v[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          u[t] = *reinterpret_cast<const rc_f32x4*>(ur + 16 * (4 * kq + t));
-          v[t] = *reinterpret_cast<const rc_f32x4*>(vr + 16 * (4 * kq + t));
-        }
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) x0[4 * kq + t][r] = fmaxf(u[t][r] - v[t][r], 0.f);
-        RC_PIN();
-      }
+      rc_load_uv(p.U + b * p.scene_stride + src * p.ldu + g4, p.V + gs * p.ldv + g4, x0);
     }
     // ---- layer 2: 8 stages, fully unrolled (x1 is a compile-time register array)
     rc_f32x4 x1[16];
 #pragma unroll
     for (int st8 = 0; st8 < 8; ++st8) {
       rc_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-      const int slot = ring.template acquire<false>();
-      {   // (waves without rows in the last pass compute on row 0's data: no branch around the MFMA stream)
-        const float* st = smem + slot * RC_STAGE_FLOATS;
-        rc_f32x4 w0n = *reinterpret_cast<const rc_f32x4*>(st + fo.a[0]);
-        rc_f32x4 w1n = *reinterpret_cast<const rc_f32x4*>(st + fo.a[0] + 16 * 256);
-#pragma unroll
-        for (int kt = 0; kt < 16; ++kt) {
-          const rc_f32x4 w0 = w0n, w1 = w1n;
-          if (kt + 1 < 16) {
-            const float* wp = st + fo.a[(kt + 1) & 3] + 64 * ((kt + 1) >> 2);
-            w0n = *reinterpret_cast<const rc_f32x4*>(wp);
-            w1n = *reinterpret_cast<const rc_f32x4*>(wp + 16 * 256);
-          }
-          RC_PIN();
-          const rc_f32x4 x = x0[kt];
-          RC_MFMA8(w0, w1, x, acc0, acc1)
-          RC_FETCH_AT(ring, kt)
-        }
-      }
+      rc_stage_a<false>(ring.acquire(smem), fo, x0, acc0, acc1, ring);
       const float* a = aff + 32 * st8 + g4;
-      const rc_f32x4 s0 = *reinterpret_cast<const rc_f32x4*>(a), s1 = *reinterpret_cast<const rc_f32x4*>(a + 16);
-      const rc_f32x4 t0 = *reinterpret_cast<const rc_f32x4*>(a + 256), t1 = *reinterpret_cast<const rc_f32x4*>(a + 256 + 16);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        acc0[r] = fmaxf(acc0[r] * s0[r] + t0[r], 0.f);
-        acc1[r] = fmaxf(acc1[r] * s1[r] + t1[r], 0.f);
-      }
+      rc_affine_relu(acc0, a, 256);
+      rc_affine_relu(acc1, a + 16, 256);
       x1[2 * st8] = acc0; x1[2 * st8 + 1] = acc1;
     }
-    // ---- layer 3 + max over the points, one stage (32 channels) at a time
+    // ---- layer 3 + max over the points, one stage (32 channels: 32 s3 + 16 t + j) at a time
     for (int s3 = 0; s3 < 16; ++s3) {
       rc_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-      const int slot = ring.template acquire<false>();
-      {   // (waves without rows in the last pass compute on row 0's data: no branch around the MFMA stream)
-        const float* st = smem + slot * RC_STAGE_FLOATS;
-        rc_f32x4 w0n = *reinterpret_cast<const rc_f32x4*>(st + fo.a[0]);
-        rc_f32x4 w1n = *reinterpret_cast<const rc_f32x4*>(st + fo.a[0] + 16 * 256);
-#pragma unroll
-        for (int kt = 0; kt < 16; ++kt) {
-          const rc_f32x4 w0 = w0n, w1 = w1n;
-          if (kt + 1 < 16) {
-            const float* wp = st + fo.a[(kt + 1) & 3] + 64 * ((kt + 1) >> 2);
-            w0n = *reinterpret_cast<const rc_f32x4*>(wp);
-            w1n = *reinterpret_cast<const rc_f32x4*>(wp + 16 * 256);
-          }
-          RC_PIN();
-          const rc_f32x4 x = x1[kt];
-          RC_MFMA8_T(w0, w1, x, acc0, acc1)
-          RC_FETCH_AT(ring, kt)
-        }
-        // folded BN affine (+ ReLU) per channel (32 s3 + 16 t + j), max over this wave's 16 points: registers, then lane groups
-        const float sc0 = aff[512 + 32 * s3 + j], sc1 = aff[512 + 32 * s3 + 16 + j];
-        const float sh0 = aff[1024 + 32 * s3 + j], sh1 = aff[1024 + 32 * s3 + 16 + j];
-        float m0 = -__builtin_inff(), m1 = -__builtin_inff();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          m0 = fmaxf(m0, acc0[r] * sc0 + sh0);
-          m1 = fmaxf(m1, acc1[r] * sc1 + sh1);
-        }
-        if (p.relu3) { m0 = fmaxf(m0, 0.f); m1 = fmaxf(m1, 0.f); }
-        m0 = fmaxf(m0, __shfl_xor(m0, 16, 64)); m1 = fmaxf(m1, __shfl_xor(m1, 16, 64));
-        m0 = fmaxf(m0, __shfl_xor(m0, 32, 64)); m1 = fmaxf(m1, __shfl_xor(m1, 32, 64));
-        if (g == 0) {
-          pool[wave * 512 + 32 * s3 + j] = m0;
-          pool[wave * 512 + 32 * s3 + 16 + j] = m1;
-        }
+      rc_stage_a<true>(ring.acquire(smem), fo, x1, acc0, acc1, ring);
+      float m0, m1;
+      rc_affine_max16(acc0, acc1, aff + 512 + 32 * s3 + j, 512, p.relu3, m0, m1);
+      if (g == 0) {
+        pool[wave * 512 + 32 * s3 + j] = m0;
+        pool[wave * 512 + 32 * s3 + 16 + j] = m1;
       }
     }
     // ---- max over the 4 waves of each neighbourhood (the ring's next barriers separate this from the next pass's writes)
@@ -614,7 +526,7 @@ __global__ __launch_bounds__(RC_THREADS, 2) void sa_premul_chain_kernel(const Sc
 #pragma unroll
     for (int n = 0; n < RC_WAVES / 4; ++n) {
       const long long gn = grp0 + n;
-      if (gn < p.groups && !(half && n >= RC_WAVES / 8))
+      if (gn < p.groups)
         for (int c = tid; c < 512; c += RC_THREADS) {
           const float* q = pool + (4 * n) * 512 + c;
           p.out[gn * p.ldo + c] = fmaxf(fmaxf(q[0], q[512]), fmaxf(q[1024], q[1536]));
@@ -624,29 +536,15 @@ __global__ __launch_bounds__(RC_THREADS, 2) void sa_premul_chain_kernel(const Sc
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// Level-3 set-abstraction block of PointNet2Seg on pre-multiplied layer-1 rows (pointnet2.py:40-42: 515 -> 512 -> 512 ->
-// 1024 over 256 x 64 rows per scene; pn2_utils/modules.py:39-56, :244-245): layers 2 + 3 + the max over the 64 neighbours
-// in one kernel, like sa_premul_chain_kernel but with 512-wide activations -- 128 registers per 16 points, so layer 1 and
-// layer 2 cannot both be resident.  Layer 2 therefore runs as two K-halves:
+// Level 3 (515 -> 512 -> 512 -> 1024 over 256 x 64 rows per scene): like sa_premul_chain_kernel but with 512-wide
+// activations -- 128 registers per 16 points, so layer 1 and layer 2 cannot both be resident.  Layer 2 therefore runs as two
+// K-halves:
 //     for kh in {0, 1}:  x0h = relu(U[b, nbr[p]][256 kh ..] - V[p / 64][256 kh ..])       64 registers, re-gathered per half
 //                        x1 += W2[:, 256 kh ..] . x0h                                      128 accumulator registers (all 512)
 //     x1 = relu(aff2(x1));   y = relu(aff3(x1 . W3^T)) point-major, 32 channels per step, two K-half stages each;  max.
 // The 268 MB (batch of 8) layer-2 activation that regnet_sa_premul_layer_f32 wrote and the pooling GEMM re-read never
-// exists.  96 stages per pass ([32 output channels][256 k] each): W2 as (kh, 16 row blocks), W3 as (32 row blocks, kh).
-struct Sc3Args {
-  const float* U; long long ldu, scene_stride;
-  const float* V; long long ldv;
-  const long long* nbr;
-  long long groups, groups_per_scene;
-  const float* stream; int n_stages;
-  const float* affine; int affine_floats;        // [scale2(512) | shift2(512) | scale3(1024) | shift3(1024)]
-  int relu3;
-  float* out; long long ldo;                     // (groups, 1024)
-  int* ticket; long long n_blocks;
-};
-
-__global__ __launch_bounds__(RC_THREADS, 2) void sa3_premul_chain_kernel(const Sc3Args p) {
+// exists.  96 stages per pass: W2 as (kh, 16 row blocks), W3 as (32 row blocks, kh).
+__global__ __launch_bounds__(RC_THREADS, 2) void sa3_premul_chain_kernel(const ScArgs p) {
   extern __shared__ __attribute__((aligned(1024))) float smem[];   // ring | affine (3072) | pool (2 x 8 x 256) | ticket
   float* const aff = smem + RC_MID_STAGES * RC_STAGE_FLOATS;
   float* const pool = aff + 3072;
@@ -661,20 +559,10 @@ __global__ __launch_bounds__(RC_THREADS, 2) void sa3_premul_chain_kernel(const S
   const RcFrag fo = rc_frag_offsets();
   const int g4 = 4 * g;
 
-  bool primed = false;
-  for (;;) {
-    if (tid == 0) *s_blk = atomicAdd(p.ticket, 1);
-    rc_barrier_lds();                          // (thread 0's wave waited for its atomic; nobody else drains anything)
-    const long long blk = __builtin_amdgcn_readfirstlane(*s_blk);
-    if (blk >= p.n_blocks) break;
-    if (!primed) {
-      ring.prime();
-      primed = true;
-    }
+  for (long long blk; (blk = rc_next_block(p.ticket, p.n_blocks, s_blk, ring)) >= 0;) {
     const long long grp0 = blk * (RC_WAVES / 4);
     const long long grp = grp0 + (wave >> 2);                  // this wave's neighbourhood
-    const bool active = grp < p.groups;                        // wave-uniform
-    const long long gs = active ? grp : 0;
+    const long long gs = grp < p.groups ? grp : 0;             // wave-uniform
     const long long b = gs / p.groups_per_scene;
     const long long src = p.nbr[gs * 64 + (wave & 3) * 16 + j];
     const float* const ur = p.U + b * p.scene_stride + src * p.ldu + g4;
@@ -686,87 +574,19 @@ __global__ __launch_bounds__(RC_THREADS, 2) void sa3_premul_chain_kernel(const S
     for (int t = 0; t < 32; ++t) x1[t] = rc_f32x4{0.f, 0.f, 0.f, 0.f};
     for (int kh = 0; kh < 2; ++kh) {
       rc_f32x4 x0[16];
-      {
-        const float* urh = ur + 256 * kh;
-        const float* vrh = vr + 256 * kh;
+      rc_load_uv(ur + 256 * kh, vr + 256 * kh, x0);
 #pragma unroll
-        for (int kq = 0; kq < 4; ++kq) {     // four loads of each kind in flight at a time
-          rc_f32x4 u[4], v[4];
-#pragma unroll
-          for (int t = 0; t < 4; ++t) {
-            u[t] = *reinterpret_cast<const rc_f32x4*>(urh + 16 * (4 * kq + t));
-            v[t] = *reinterpret_cast<const rc_f32x4*>(vrh + 16 * (4 * kq + t));
-          }
-#pragma unroll
-          for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) x0[4 * kq + t][r] = fmaxf(u[t][r] - v[t][r], 0.f);
-          RC_PIN();
-        }
-      }
-#pragma unroll
-      for (int rg = 0; rg < 16; ++rg) {
-        const int slot = ring.template acquire<false>();
-        const float* st = smem + slot * RC_STAGE_FLOATS;
-        rc_f32x4 w0n = *reinterpret_cast<const rc_f32x4*>(st + fo.a[0]);
-        rc_f32x4 w1n = *reinterpret_cast<const rc_f32x4*>(st + fo.a[0] + 16 * 256);
-#pragma unroll
-        for (int kt = 0; kt < 16; ++kt) {
-          const rc_f32x4 w0 = w0n, w1 = w1n;
-          if (kt + 1 < 16) {
-            const float* wp = st + fo.a[(kt + 1) & 3] + 64 * ((kt + 1) >> 2);
-            w0n = *reinterpret_cast<const rc_f32x4*>(wp);
-            w1n = *reinterpret_cast<const rc_f32x4*>(wp + 16 * 256);
-          }
-          RC_PIN();
-          const rc_f32x4 x = x0[kt];
-          RC_MFMA8(w0, w1, x, x1[2 * rg], x1[2 * rg + 1])
-          RC_FETCH_AT(ring, kt)
-        }
-      }
+      for (int rg = 0; rg < 16; ++rg) rc_stage_a<false>(ring.acquire(smem), fo, x0, x1[2 * rg], x1[2 * rg + 1], ring);
     }
 #pragma unroll
-    for (int t = 0; t < 32; ++t) {
-      const float* a = aff + 16 * t + g4;
-      const rc_f32x4 sc = *reinterpret_cast<const rc_f32x4*>(a), sh = *reinterpret_cast<const rc_f32x4*>(a + 512);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) x1[t][r] = fmaxf(x1[t][r] * sc[r] + sh[r], 0.f);
-    }
-    // ---- layer 3 + max over the points: 32 channels per step, the two K-halves as two stages
+    for (int t = 0; t < 32; ++t) rc_affine_relu(x1[t], aff + 16 * t + g4, 512);
+    // ---- layer 3 + max over the points: 32 channels (32 s3 + 16 t + j) per step, the two K-halves as two stages
     for (int s3 = 0; s3 < 32; ++s3) {
       rc_f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int kh = 0; kh < 2; ++kh) {
-        const int slot = ring.template acquire<false>();
-        const float* st = smem + slot * RC_STAGE_FLOATS;
-        rc_f32x4 w0n = *reinterpret_cast<const rc_f32x4*>(st + fo.a[0]);
-        rc_f32x4 w1n = *reinterpret_cast<const rc_f32x4*>(st + fo.a[0] + 16 * 256);
-#pragma unroll
-        for (int kt = 0; kt < 16; ++kt) {
-          const rc_f32x4 w0 = w0n, w1 = w1n;
-          if (kt + 1 < 16) {
-            const float* wp = st + fo.a[(kt + 1) & 3] + 64 * ((kt + 1) >> 2);
-            w0n = *reinterpret_cast<const rc_f32x4*>(wp);
-            w1n = *reinterpret_cast<const rc_f32x4*>(wp + 16 * 256);
-          }
-          RC_PIN();
-          const rc_f32x4 x = x1[16 * kh + kt];
-          RC_MFMA8_T(w0, w1, x, acc0, acc1)
-          RC_FETCH_AT(ring, kt)
-        }
-      }
-      // folded BN affine (+ ReLU) per channel (32 s3 + 16 t + j), max over this wave's 16 points: registers, then lane groups
-      const float sc0 = aff[1024 + 32 * s3 + j], sc1 = aff[1024 + 32 * s3 + 16 + j];
-      const float sh0 = aff[2048 + 32 * s3 + j], sh1 = aff[2048 + 32 * s3 + 16 + j];
-      float m0 = -__builtin_inff(), m1 = -__builtin_inff();
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        m0 = fmaxf(m0, acc0[r] * sc0 + sh0);
-        m1 = fmaxf(m1, acc1[r] * sc1 + sh1);
-      }
-      if (p.relu3) { m0 = fmaxf(m0, 0.f); m1 = fmaxf(m1, 0.f); }
-      m0 = fmaxf(m0, __shfl_xor(m0, 16, 64)); m1 = fmaxf(m1, __shfl_xor(m1, 16, 64));
-      m0 = fmaxf(m0, __shfl_xor(m0, 32, 64)); m1 = fmaxf(m1, __shfl_xor(m1, 32, 64));
+      for (int kh = 0; kh < 2; ++kh) rc_stage_a<true>(ring.acquire(smem), fo, x1 + 16 * kh, acc0, acc1, ring);
+      float m0, m1;
+      rc_affine_max16(acc0, acc1, aff + 1024 + 32 * s3 + j, 1024, p.relu3, m0, m1);
       // The per-wave maxima of 256 channels (8 steps) at a time, double-buffered: after every eighth step the four waves of a
       // neighbourhood meet (LDS-only barrier) and 512 threads write 2 x 256 pooled values; the buffer is written again two
       // chunks later, behind the next chunk's barrier.  (One 8 x 1024 buffer reduced at the end of the pass -- 32 KB -- left no
@@ -808,14 +628,15 @@ static int rc_allow_lds(const void* kernel, size_t bytes) {
   return REGNET_OK;
 }
 
-extern "C" int64_t regnet_sa_premul_chain_stream_floats(void) { return 24ll * RC_STAGE_FLOATS; }
-
-extern "C" int regnet_sa_premul_chain_f32(const float* U, int64_t ldu, const float* V, int64_t ldv, const int64_t* nbr,
-                                          int64_t B, int64_t Nsrc, int64_t M, const float* stream, int64_t n_stages,
-                                          const float* affine, int64_t affine_floats, int relu3, float* out, int64_t ldo,
-                                          int32_t* ticket, void* stream_handle) {
-  if (B < 0 || M < 0 || Nsrc <= 0 || ldu < 256 || ldv < 256 || (ldu & 3) || (ldv & 3) || ldo < 512 || n_stages != 24 ||
-      affine_floats != 1536)
+// Both SA chains: activations C wide in, 2 C out, `stages` stages per pass, an affine table of 6 C floats; LDS = ring of
+// `ring_slots` | affine | `pool_floats` | ticket.
+static int rc_launch_sa_chain(void (*kernel)(const ScArgs), int C, int stages, int ring_slots, int pool_floats,
+                              const float* U, int64_t ldu, const float* V, int64_t ldv, const int64_t* nbr, int64_t B,
+                              int64_t Nsrc, int64_t M, const float* stream, int64_t n_stages, const float* affine,
+                              int64_t affine_floats, int relu3, float* out, int64_t ldo, int32_t* ticket,
+                              void* stream_handle) {
+  if (B < 0 || M < 0 || Nsrc <= 0 || ldu < C || ldv < C || (ldu & 3) || (ldv & 3) || ldo < 2 * C || n_stages != stages ||
+      affine_floats != 6 * C)
     return REGNET_ERR_SHAPE;
   const long long groups = B * M;
   if (groups == 0) return REGNET_OK;
@@ -825,22 +646,27 @@ extern "C" int regnet_sa_premul_chain_f32(const float* U, int64_t ldu, const flo
   a.U = U; a.ldu = ldu; a.scene_stride = Nsrc * ldu; a.V = V; a.ldv = ldv; a.nbr = (const long long*)nbr;
   a.groups = groups; a.groups_per_scene = M; a.stream = stream; a.n_stages = (int)n_stages;
   a.affine = affine; a.affine_floats = (int)affine_floats; a.relu3 = relu3; a.out = out; a.ldo = ldo;
-  {   // the last ~half round of blocks is handed out as half blocks (see the kernel)
-    const long long gpb = RC_WAVES / 4, blocks = (groups + gpb - 1) / gpb;
-    const long long split = (RC_WAVES == 8 && RC_TAIL_HALF) ? (blocks < 128 ? blocks : 128) : 0;
-    a.n_full = blocks - split;
-    const long long rest = groups - a.n_full * gpb;            // neighbourhoods left for half blocks (one each)
-    a.n_blocks = a.n_full + (rest > 0 ? rest : 0);
-  }
+  const long long gpb = RC_WAVES / 4;                          // neighbourhoods per block
+  a.n_blocks = (groups + gpb - 1) / gpb;
   a.ticket = ticket;
   const int cus = 256 * RC_WG_PER_CU;
   const long long wgs = a.n_blocks < cus ? a.n_blocks : cus;
-  const size_t lds = (size_t)(RC_STAGES * RC_STAGE_FLOATS + 1536 + RC_WAVES * 512 + 4) * sizeof(float);
-  int rc_attr = rc_allow_lds(reinterpret_cast<const void*>(sa_premul_chain_kernel), lds);
+  const size_t lds = (size_t)(ring_slots * RC_STAGE_FLOATS + 6 * C + pool_floats + 4) * sizeof(float);
+  int rc_attr = rc_allow_lds(reinterpret_cast<const void*>(kernel), lds);
   if (rc_attr) return rc_attr;
-  hipLaunchKernelGGL(sa_premul_chain_kernel, dim3((unsigned)wgs), dim3(RC_THREADS), lds, as_stream(stream_handle), a);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)wgs), dim3(RC_THREADS), lds, as_stream(stream_handle), a);
   REGNET_LAUNCH_CHECK();
   return REGNET_OK;
+}
+
+extern "C" int64_t regnet_sa_premul_chain_stream_floats(void) { return 24ll * RC_STAGE_FLOATS; }
+
+extern "C" int regnet_sa_premul_chain_f32(const float* U, int64_t ldu, const float* V, int64_t ldv, const int64_t* nbr,
+                                          int64_t B, int64_t Nsrc, int64_t M, const float* stream, int64_t n_stages,
+                                          const float* affine, int64_t affine_floats, int relu3, float* out, int64_t ldo,
+                                          int32_t* ticket, void* stream_handle) {
+  return rc_launch_sa_chain(sa_premul_chain_kernel, 256, 24, RC_STAGES, RC_WAVES * 512, U, ldu, V, ldv, nbr, B, Nsrc, M,
+                            stream, n_stages, affine, affine_floats, relu3, out, ldo, ticket, stream_handle);
 }
 
 extern "C" int64_t regnet_sa3_premul_chain_stream_floats(void) { return 96ll * RC_STAGE_FLOATS; }
@@ -849,56 +675,30 @@ extern "C" int regnet_sa3_premul_chain_f32(const float* U, int64_t ldu, const fl
                                            int64_t B, int64_t Nsrc, int64_t M, const float* stream, int64_t n_stages,
                                            const float* affine, int64_t affine_floats, int relu3, float* out, int64_t ldo,
                                            int32_t* ticket, void* stream_handle) {
-  if (B < 0 || M < 0 || Nsrc <= 0 || ldu < 512 || ldv < 512 || (ldu & 3) || (ldv & 3) || ldo < 1024 || n_stages != 96 ||
-      affine_floats != 3072 || RC_WAVES != 8)
-    return REGNET_ERR_SHAPE;
-  const long long groups = B * M;
-  if (groups == 0) return REGNET_OK;
-  if (!U || !V || !nbr || !stream || !affine || !out || !ticket) return REGNET_ERR_NULL;
-  if (!rc_aligned16(U) || !rc_aligned16(V) || !rc_aligned16(stream) || !rc_aligned16(affine)) return REGNET_ERR_SHAPE;
-  Sc3Args a = {};
-  a.U = U; a.ldu = ldu; a.scene_stride = Nsrc * ldu; a.V = V; a.ldv = ldv; a.nbr = (const long long*)nbr;
-  a.groups = groups; a.groups_per_scene = M; a.stream = stream; a.n_stages = (int)n_stages;
-  a.affine = affine; a.affine_floats = (int)affine_floats; a.relu3 = relu3; a.out = out; a.ldo = ldo;
-  a.n_blocks = (groups + 1) / 2;
-  a.ticket = ticket;
-  const long long wgs = a.n_blocks < 256 ? a.n_blocks : 256;
-  const size_t lds = (size_t)(RC_MID_STAGES * RC_STAGE_FLOATS + 3072 + RC_SA3_POOL_FLOATS + 4) * sizeof(float);
-  int rc_attr = rc_allow_lds(reinterpret_cast<const void*>(sa3_premul_chain_kernel), lds);
-  if (rc_attr) return rc_attr;
-  hipLaunchKernelGGL(sa3_premul_chain_kernel, dim3((unsigned)wgs), dim3(RC_THREADS), lds, as_stream(stream_handle), a);
-  REGNET_LAUNCH_CHECK();
-  return REGNET_OK;
+  if (RC_WAVES != 8) return REGNET_ERR_SHAPE;                  // (its pooling assigns 512 threads to 2 x 256 channels)
+  return rc_launch_sa_chain(sa3_premul_chain_kernel, 512, 96, RC_MID_STAGES, RC_SA3_POOL_FLOATS, U, ldu, V, ldv, nbr, B,
+                            Nsrc, M, stream, n_stages, affine, affine_floats, relu3, out, ldo, ticket, stream_handle);
 }
 
 extern "C" int64_t regnet_fp_head_chain_stream_floats(void) { return 60ll * RC_STAGE_FLOATS; }
 
-static long long rc_fp_head_blocks(long long P, long long* n_full) {
-  const long long units = (P + 15) / 16, blocks = (units + RC_WAVES - 1) / RC_WAVES;
-  const long long split = (RC_WAVES == 8 && RC_TAIL_HALF) ? (blocks < 128 ? blocks : 128) : 0;
-  const long long full = blocks - split;
-  const long long rest = units - full * RC_WAVES;              // 16-row units left for half blocks (4 each)
-  if (n_full) *n_full = full;
-  return full + (rest > 0 ? (rest + RC_WAVES / 2 - 1) / (RC_WAVES / 2) : 0);
+extern "C" int64_t regnet_fp_head_chain_blocks(int64_t P) {
+  return P <= 0 ? 0 : ((P + 15) / 16 + RC_WAVES - 1) / RC_WAVES;   // 16-row units, RC_WAVES of them to a block
 }
 
-extern "C" int64_t regnet_fp_head_chain_blocks(int64_t P) { return P <= 0 ? 0 : rc_fp_head_blocks(P, nullptr); }
-
 static int rc_launch_fp_head(RcArgs& a, bool interp, int64_t block_first, int64_t block_count, void* stream_handle) {
-  a.n_blocks = rc_fp_head_blocks(a.P, &a.n_full);
-  if (block_count < 0) { block_first = 0; block_count = a.n_blocks; }
-  if (block_first < 0 || block_first + block_count > a.n_blocks) return REGNET_ERR_SHAPE;
+  const int64_t n_blocks = regnet_fp_head_chain_blocks(a.P);
+  if (block_count < 0) { block_first = 0; block_count = n_blocks; }
+  if (block_first < 0 || block_first + block_count > n_blocks) return REGNET_ERR_SHAPE;
   if (block_count == 0) return REGNET_OK;
   a.blk_first = block_first; a.blk_count = block_count;
   const int cus = 256 * RC_WG_PER_CU;
   const long long wgs = block_count < cus ? block_count : cus;
   const size_t lds = (size_t)(RC_MID_STAGES * RC_STAGE_FLOATS + RC_AFFINE_MAX + 128 + 4 + (interp ? RC_INTERP_FLOATS : 0)) * sizeof(float);
-  const void* kernel = interp ? reinterpret_cast<const void*>(fp_head_chain_kernel<true>)
-                              : reinterpret_cast<const void*>(fp_head_chain_kernel<false>);
-  int rc_attr = rc_allow_lds(kernel, lds);
+  void (*kernel)(const RcArgs) = interp ? fp_head_chain_kernel<true> : fp_head_chain_kernel<false>;
+  int rc_attr = rc_allow_lds(reinterpret_cast<const void*>(kernel), lds);
   if (rc_attr) return rc_attr;
-  if (interp) hipLaunchKernelGGL(fp_head_chain_kernel<true>, dim3((unsigned)wgs), dim3(RC_THREADS), lds, as_stream(stream_handle), a);
-  else hipLaunchKernelGGL(fp_head_chain_kernel<false>, dim3((unsigned)wgs), dim3(RC_THREADS), lds, as_stream(stream_handle), a);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)wgs), dim3(RC_THREADS), lds, as_stream(stream_handle), a);
   REGNET_LAUNCH_CHECK();
   return REGNET_OK;
 }

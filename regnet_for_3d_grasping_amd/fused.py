@@ -212,14 +212,16 @@ def mlp_layer(A, Ka, layer, P, pool_group=0):
     return out
 
 
+def _strided3(t):
+    """(pointer, batch stride, channel stride, point stride, channels) of a (B,C,N) tensor of any strides; zeros for None."""
+    return (None, 0, 0, 0, 0) if t is None else (t.data_ptr(),) + tuple(t.stride()) + (t.size(1),)
+
+
 @_on_tensor_device
 def sa_layer1(feature, xyz, nbr, ctr, layer, B, M, group):
     """Gather-fused first SA layer.  feature (B,Cf,N) any strides or None; xyz (B,3,N) any strides."""
     out = torch.empty((B * M * group, layer.N), dtype=torch.float32, device=xyz.device)
-    if feature is None:
-        fptr, fb, fn, fc, Cf = None, 0, 0, 0, 0
-    else:
-        fptr, (fb, fc, fn), Cf = feature.data_ptr(), feature.stride(), feature.size(1)
+    fptr, fb, fc, fn, Cf = _strided3(feature)
     _check(_L.regnet_sa_layer1_f32(fptr, fb, fn, fc, Cf, xyz.data_ptr(), *xyz.stride(), nbr.data_ptr(), ctr.data_ptr(),
                                    B, M, group, layer.W.data_ptr(), layer.Kpad, layer.scale.data_ptr(),
                                    layer.shift.data_ptr(), out.data_ptr(), out.stride(0), layer.N, layer.relu,
@@ -233,10 +235,7 @@ def sa_layer12(feature, xyz, nbr, ctr, first, layer, B, M, group, pool_group=0):
     P = B * M * group
     rows = P // pool_group if pool_group else P
     out = torch.empty((rows, layer.N), dtype=torch.float32, device=xyz.device)
-    if feature is None:
-        fptr, fb, fn, fc, Cf = None, 0, 0, 0, 0
-    else:
-        fptr, (fb, fc, fn), Cf = feature.data_ptr(), feature.stride(), feature.size(1)
+    fptr, fb, fc, fn, Cf = _strided3(feature)
     _check(_L.regnet_sa_layer12_f32(fptr, fb, fn, fc, Cf, xyz.data_ptr(), *xyz.stride(), nbr.data_ptr(),
                                     ctr.data_ptr(), B, M, group, first.W8.data_ptr(), first.scale.data_ptr(),
                                     first.shift.data_ptr(), first.N, layer.W.data_ptr(), layer.Kpad,
@@ -264,10 +263,7 @@ def pack_rows(feature, xyz, width, mu=None):
     -> (B*N, width)."""
     B, _, N = xyz.shape
     out = torch.empty((B * N, width), dtype=torch.float32, device=xyz.device)
-    if feature is None:
-        fptr, fb, fc, fn, Cf = None, 0, 0, 0, 0
-    else:
-        fptr, (fb, fc, fn), Cf = feature.data_ptr(), feature.stride(), feature.size(1)
+    fptr, fb, fc, fn, Cf = _strided3(feature)
     if mu is not None:
         mu = mu.reshape(B, 3)
         mu = mu if mu.is_contiguous() else mu.contiguous()
@@ -387,10 +383,7 @@ def sa_chain3_split(feature, xyz, nbr, ctr, l1, l2, l3, B, M, group, count=None,
     """``sa_chain3`` by ``regnet_sa_chain3_split_f32``; the weights' bf16 pieces are built by the kernel's first launch on
     a layer pack (both layers are of the same stack pack: the planes are kept on ``l3``)."""
     out = torch.empty((B * M, l3.N), dtype=torch.float32, device=xyz.device)
-    if feature is None:
-        fptr, fb, fn, fc, Cf = None, 0, 0, 0, 0
-    else:
-        fptr, (fb, fc, fn), Cf = feature.data_ptr(), feature.stride(), feature.size(1)
+    fptr, fb, fc, fn, Cf = _strided3(feature)
     planes = l3.derived.get("split_planes")
     build = planes is None
     if build:
@@ -414,10 +407,7 @@ def sa_chain3(feature, xyz, nbr, ctr, l1, l2, l3, B, M, group, count=None, order
             and feature.size(1) == 3):      # (the shapes of the level-1 block, the only ones the experiment's kernel is built for)
         return sa_chain3_split(feature, xyz, nbr, ctr, l1, l2, l3, B, M, group, count, order)
     out = torch.empty((B * M, l3.N), dtype=torch.float32, device=xyz.device)
-    if feature is None:
-        fptr, fb, fn, fc, Cf = None, 0, 0, 0, 0
-    else:
-        fptr, (fb, fc, fn), Cf = feature.data_ptr(), feature.stride(), feature.size(1)
+    fptr, fb, fc, fn, Cf = _strided3(feature)
     _check(_L.regnet_sa_chain3_f32(fptr, fb, fn, fc, Cf, xyz.data_ptr(), *xyz.stride(), nbr.data_ptr(), ctr.data_ptr(),
                                    None if count is None else count.data_ptr(),
                                    None if order is None else order.data_ptr(), B, M, group, l1.W8.data_ptr(), l1.scale.data_ptr(), l1.shift.data_ptr(), l1.N,
@@ -435,10 +425,7 @@ def interp_concat(sparse_cl, idx, dist2, eps, dense_feature, B, Nd):
     Cd = 0 if dense_feature is None else dense_feature.size(1)
     width = _round_up(Cs + Cd, 4)
     out = torch.empty((B * Nd, width), dtype=torch.float32, device=sparse_cl.device)
-    if dense_feature is None:
-        dptr, db, dn, dc = None, 0, 0, 0
-    else:
-        dptr, (db, dc, dn) = dense_feature.data_ptr(), dense_feature.stride()
+    dptr, db, dc, dn, _ = _strided3(dense_feature)
     _check(_L.regnet_interp_concat_f32(sparse_cl.data_ptr(), sparse_cl.stride(0), sparse_cl.stride(1), Cs,
                                        idx.data_ptr(), dist2.data_ptr(), float(eps), dptr, db, dn, dc, Cd, B, Nd,
                                        out.data_ptr(), out.stride(0), width, _stream(sparse_cl)), "interp_concat")
@@ -480,10 +467,8 @@ def interp_affine(Ys, idx, dist2, eps, Yd, dense_small, wd4, layer, B, Ns, Nd):
     pre-multiplied sparse rows.  ``dense_small``: (B,Cd<=4,Nd) any strides, or None."""
     C = layer.N
     out = torch.empty((B * Nd, C), dtype=torch.float32, device=Ys.device)
-    if dense_small is None:
-        dptr, db, dc, dn, Cd, wptr = None, 0, 0, 0, 0, None
-    else:
-        dptr, (db, dc, dn), Cd, wptr = dense_small.data_ptr(), dense_small.stride(), dense_small.size(1), wd4.data_ptr()
+    dptr, db, dc, dn, Cd = _strided3(dense_small)
+    wptr = None if dense_small is None else wd4.data_ptr()
     _check(_L.regnet_interp_affine_f32(Ys.data_ptr(), Ns * Ys.stride(0), Ys.stride(0), idx.data_ptr(),
                                        dist2.data_ptr(), float(eps), None if Yd is None else Yd.data_ptr(),
                                        0 if Yd is None else Yd.stride(0), dptr, db, dn, dc, Cd, wptr,
@@ -713,17 +698,12 @@ def fp_features(module, dense_xyz, dense_feature, sparse_feature, geo):
     layers = _packed_stack(module, module.mlp)
     h = _fp_first_layer(module, layers, dense_xyz, dense_feature, sparse_feature, geo)
     if h is not None:
-        Ka, P = layers[0].N, B * Nd
-        for layer in layers[1:]:
-            h = mlp_layer(h, Ka, layer, P)
-            Ka = layer.N
-        return h.view(B, Nd, -1).transpose(1, 2)
-    A, width = interp_concat(_as_channels_last(sparse_feature), geo["idx"], geo["dist2"], module.interpolator._eps,
-                             dense_feature, B, Nd)
-    P = B * Nd
-    h, Ka = A, width
+        Ka, layers = layers[0].N, layers[1:]
+    else:
+        h, Ka = interp_concat(_as_channels_last(sparse_feature), geo["idx"], geo["dist2"], module.interpolator._eps,
+                              dense_feature, B, Nd)
     for layer in layers:
-        h = mlp_layer(h, Ka, layer, P)
+        h = mlp_layer(h, Ka, layer, B * Nd)
         Ka = layer.N
     return h.view(B, Nd, -1).transpose(1, 2)
 
@@ -749,51 +729,47 @@ def head_forward(seg, sparse_feature):
     return score_head(h, seg, B * N).view(B, N)
 
 
-# ---- level-2 set-abstraction block: layers 2 + 3 + pooling as ONE kernel (csrc/rowchain.hip) ---------------------------
-def _packed_sa_chain(module, layers):
-    """Weight stream (24 stages [32 rows][256 k], layer 2 then layer 3) + affine table of sa_premul_chain."""
+# ---- level-2 / level-3 set-abstraction blocks: layers 2 + 3 + pooling as ONE kernel (csrc/rowchain.hip) ----------------
+def _packed_premul_chain(module, layers, C):
+    """Weight stream of [32 rows][256 k] stages + affine table of the SA chain with C-wide activations.  C = 256 (level 2,
+    cache slot "sa_chain"): 24 stages, layer 2 then layer 3.  C = 512 (level 3, "sa3_chain"): 96 stages, W2 as (K-half, 16 row
+    blocks), W3 as (32 row blocks, K-half)."""
     def build():
         l2, l3 = layers[1], layers[2]
-        stages = [_swizzle_stage(l2.W[32 * s:32 * s + 32, :256]) for s in range(8)]
-        stages += [_swizzle_stage(l3.W[32 * s:32 * s + 32, :256]) for s in range(16)]
+        halves = range(C // 256)
+        stages = [_swizzle_stage(l2.W[32 * rg:32 * rg + 32, 256 * kh:256 * kh + 256]) for kh in halves for rg in range(C // 32)]
+        stages += [_swizzle_stage(l3.W[32 * s:32 * s + 32, 256 * kh:256 * kh + 256]) for s in range(C // 16) for kh in halves]
         stream = torch.cat(stages).contiguous()
-        affine = torch.cat([l2.scale[:256], l2.shift[:256], l3.scale[:512], l3.shift[:512]]).contiguous()
-        assert stream.numel() == _L.regnet_sa_premul_chain_stream_floats() and affine.numel() == 1536
+        affine = torch.cat([l2.scale[:C], l2.shift[:C], l3.scale[:2 * C], l3.shift[:2 * C]]).contiguous()
+        floats = _L.regnet_sa_premul_chain_stream_floats() if C == 256 else _L.regnet_sa3_premul_chain_stream_floats()
+        assert stream.numel() == floats and affine.numel() == 6 * C
         return stream, affine
-    return _cached(module, "sa_chain", _signature(module.mlp), build)
+    return _cached(module, "sa_chain" if C == 256 else "sa3_chain", _signature(module.mlp), build)
+
+
+def _premul_chain(C, U, V, nbr, module, layers, B, Nsrc, M):
+    stream, affine = _packed_premul_chain(module, layers, C)
+    entry, name = ((_L.regnet_sa_premul_chain_f32, "sa_premul_chain") if C == 256 else
+                   (_L.regnet_sa3_premul_chain_f32, "sa3_premul_chain"))
+    out = torch.empty((B * M, 2 * C), dtype=torch.float32, device=U.device)
+    ticket = _tickets(U.device)
+    _check(entry(U.data_ptr(), U.stride(0), V.data_ptr(), V.stride(0), nbr.data_ptr(), B, Nsrc, M, stream.data_ptr(),
+                 stream.numel() // 8192, affine.data_ptr(), affine.numel(), layers[2].relu, out.data_ptr(), out.stride(0),
+                 ticket.data_ptr(), _stream(U)), name)
+    return out
+
+
+def _packed_sa_chain(module, layers):
+    return _packed_premul_chain(module, layers, 256)
+
+
+def _packed_sa3_chain(module, layers):
+    return _packed_premul_chain(module, layers, 512)
 
 
 def supports_sa_chain(layers):
     return (ROWCHAIN and len(layers) == 3 and layers[0].N == 256 and layers[1].K == 256 and layers[1].N == 256
             and layers[1].relu and layers[2].K == 256 and layers[2].N == 512)
-
-
-@_on_tensor_device
-def sa_premul_chain(U, V, nbr, module, layers, B, Nsrc, M):
-    """relu(U[nbr] - V[centre]) -> 256 -> 512 -> max over the 64 neighbours, one launch; -> (B*M, 512)."""
-    stream, affine = _packed_sa_chain(module, layers)
-    out = torch.empty((B * M, 512), dtype=torch.float32, device=U.device)
-    ticket = _tickets(U.device)
-    _check(_L.regnet_sa_premul_chain_f32(U.data_ptr(), U.stride(0), V.data_ptr(), V.stride(0), nbr.data_ptr(), B, Nsrc,
-                                         M, stream.data_ptr(), 24, affine.data_ptr(), affine.numel(), layers[2].relu,
-                                         out.data_ptr(), out.stride(0), ticket.data_ptr(), _stream(U)),
-           "sa_premul_chain")
-    return out
-
-
-# ---- level-3 set-abstraction block: layers 2 + 3 + pooling as ONE kernel, 512-wide (csrc/rowchain.hip) ------------------
-def _packed_sa3_chain(module, layers):
-    """Weight stream (96 stages [32 rows][256 k]: W2 as (K-half, 16 row blocks), W3 as (32 row blocks, K-half)) + affine
-    table of sa3_premul_chain."""
-    def build():
-        l2, l3 = layers[1], layers[2]
-        stages = [_swizzle_stage(l2.W[32 * rg:32 * rg + 32, 256 * kh:256 * kh + 256]) for kh in range(2) for rg in range(16)]
-        stages += [_swizzle_stage(l3.W[32 * s:32 * s + 32, 256 * kh:256 * kh + 256]) for s in range(32) for kh in range(2)]
-        stream = torch.cat(stages).contiguous()
-        affine = torch.cat([l2.scale[:512], l2.shift[:512], l3.scale[:1024], l3.shift[:1024]]).contiguous()
-        assert stream.numel() == _L.regnet_sa3_premul_chain_stream_floats() and affine.numel() == 3072
-        return stream, affine
-    return _cached(module, "sa3_chain", _signature(module.mlp), build)
 
 
 def supports_sa3_chain(layers):
@@ -802,16 +778,15 @@ def supports_sa3_chain(layers):
 
 
 @_on_tensor_device
+def sa_premul_chain(U, V, nbr, module, layers, B, Nsrc, M):
+    """relu(U[nbr] - V[centre]) -> 256 -> 512 -> max over the 64 neighbours, one launch; -> (B*M, 512)."""
+    return _premul_chain(256, U, V, nbr, module, layers, B, Nsrc, M)
+
+
+@_on_tensor_device
 def sa3_premul_chain(U, V, nbr, module, layers, B, Nsrc, M):
     """relu(U[nbr] - V[centre]) -> 512 -> 1024 -> max over the 64 neighbours, one launch; -> (B*M, 1024)."""
-    stream, affine = _packed_sa3_chain(module, layers)
-    out = torch.empty((B * M, 1024), dtype=torch.float32, device=U.device)
-    ticket = _tickets(U.device)
-    _check(_L.regnet_sa3_premul_chain_f32(U.data_ptr(), U.stride(0), V.data_ptr(), V.stride(0), nbr.data_ptr(), B, Nsrc,
-                                          M, stream.data_ptr(), 96, affine.data_ptr(), affine.numel(), layers[2].relu,
-                                          out.data_ptr(), out.stride(0), ticket.data_ptr(), _stream(U)),
-           "sa3_premul_chain")
-    return out
+    return _premul_chain(512, U, V, nbr, module, layers, B, Nsrc, M)
 
 
 # ---- FP3 tail + segmentation head as ONE kernel (csrc/rowchain.hip) --------------------------------------------------
@@ -910,10 +885,7 @@ def fp_head_chain_interp(Ys, idx, dist2, eps, dense_small, wd4, first, seg, fp_l
     F = torch.empty((P, 256), dtype=torch.float32, device=Ys.device)
     score = torch.empty((P,), dtype=torch.float32, device=Ys.device)
     tickets = _tickets(Ys.device, 2)
-    if dense_small is None:
-        dptr, db, dc, dn, Cd = None, 0, 0, 0, 0
-    else:
-        dptr, (db, dc, dn), Cd = dense_small.data_ptr(), dense_small.stride(), dense_small.size(1)
+    dptr, db, dc, dn, Cd = _strided3(dense_small)
 
     def launch(first, count, ticket, stream_handle):
         _check(_L.regnet_fp_head_chain_interp_f32(Ys.data_ptr(), Ns * Ys.stride(0), Ys.stride(0), idx.data_ptr(),
@@ -1123,23 +1095,17 @@ def twostage_forward(net, mp_x, raw_reg=False):
     x = mp_x.reshape(n, -1).contiguous()
     if HEADS_CHAIN and n <= HEADS_CHAIN_MAX_ROWS and x.shape[1] % 16 == 0:
         x_cls, x_reg = _heads_chain(x, L, _TWOSTAGE_PLAN, L["conv_cls4"].N, L["conv_reg4"].N)
-        x_reg = x_reg.view(n, -1, net.k_reg_no_anchor)
-        if not raw_reg:
-            x_reg[:, :, 7:] = torch.sigmoid(x_reg[:, :, 7:])
-        return x_cls, x_reg
-    if _tree_ok(L, _TWOSTAGE_TREE, x) and L["conv_cls3"].K == L["conv_cls2"].N:
+    elif _tree_ok(L, _TWOSTAGE_TREE, x) and L["conv_cls3"].K == L["conv_cls2"].N:
         n2, n3 = L["conv_cls2"].N, L["conv_cls3"].N
         x_cls, x_reg = _heads_tree(x, L, _TWOSTAGE_TREE,
                                    [("conv_cls3", 0, 0, 1, 0), ("conv_reg3", 0, n2, 1, _round_up(n3, 16)),
                                     ("conv_cls4", 1, 0, 4, 0), ("conv_reg4", 1, _round_up(n3, 16), 5, 0)],
                                    L["conv_cls4"].N, L["conv_reg4"].N)
-        x_reg = x_reg.view(n, -1, net.k_reg_no_anchor)
-        if not raw_reg:
-            x_reg[:, :, 7:] = torch.sigmoid(x_reg[:, :, 7:])
-        return x_cls, x_reg
-    h = mlp_layer(x, L["conv"].K, L["conv"], n)
-    x_cls = _chain(h, L, ["conv_cls2", "conv_cls3", "conv_cls4"])
-    x_reg = _chain(h, L, ["conv_reg2", "conv_reg3", "conv_reg4"]).view(n, -1, net.k_reg_no_anchor)
+    else:
+        h = mlp_layer(x, L["conv"].K, L["conv"], n)
+        x_cls = _chain(h, L, ["conv_cls2", "conv_cls3", "conv_cls4"])
+        x_reg = _chain(h, L, ["conv_reg2", "conv_reg3", "conv_reg4"])
+    x_reg = x_reg.view(n, -1, net.k_reg_no_anchor)
     if not raw_reg:
         x_reg[:, :, 7:] = torch.sigmoid(x_reg[:, :, 7:])
     return x_cls, x_reg
