@@ -820,6 +820,31 @@ int regnet_ingest_resample_f32(const float* xyz, const void* rgb, int rgb_is_f64
  * corrupt stream or one that does not fit, REGNET_ERR_NULL for a NULL buffer of non-zero length.                          */
 int64_t regnet_lzf_decompress(const uint8_t* in, int64_t in_len, uint8_t* out, int64_t out_cap);
 
+/* ---- pose non-maximum suppression + top-K (csrc/nms.hip): the K best DISTINCT grasps of one set, on the device -------------
+ * regnet_grasp_nms_f32: center (n,3) and frame (n,3,3) float32 contiguous -- eval_collision.grasp_frames' output, the frame's
+ * COLUMNS being approach a, axis_y b and minor normal m --, order (n) int64 = the input row of every rank, best first (the
+ * caller ranks: descending score, NaN as -inf, equal scores by lower row; entries outside [0, n) are never the same grasp as
+ * anything).  Two grasps are the same grasp when they are close AND aligned, in individually rounded fp32 operations in the
+ * written order (the translation unit is built with -ffp-contract=off):
+ *   close    d2 = ((dx dx) + (dy dy)) + (dz dz) <= T2                      T2 = float32(t) * float32(t), inclusive
+ *   aligned  tr = (da + db) + dm >= C, da = ((ax ax') + (ay ay')) + (az az') and likewise db, dm;
+ *            C = 1 + 2 cos(theta) evaluated in float64 and rounded once to float32
+ *            symmetric != 0: tr2 = (da - db) - dm, max(tr, tr2) >= C (a NaN in either fails it, as np.maximum): the gripper
+ *            turned 180 degrees about its approach axis is the same grasp.
+ * The ranks are walked in order; a rank is kept unless an already kept one is the same grasp; the walk stops once top_k are
+ * kept (top_k <= 0: no limit).
+ *   keep      (n) int64: the input rows of the kept grasps in rank order, then -1 up to n.
+ *   count     (1) int32 DEVICE: how many were kept.  No host read, no synchronisation, no allocation: capturable.
+ *   workspace regnet_grasp_nms_workspace_bytes(n) = nb (nb + 1) / 2 * 64 * 8 bytes with nb = ceil(n / 64), 8-byte aligned:
+ *             one 64-bit word per (rank, later-or-own block of 64 ranks), the upper triangle of the pair mask; -1 for an
+ *             unsupported n.  The callee writes all of it before reading.
+ * Two launches (64 x 64 pair-mask tiles; a one-workgroup greedy scan that leaves early at top_k); no workgroup waits for
+ * another.  n == 0: success, no pointer touched.  Errors: n < 0 -> REGNET_ERR_SHAPE; n > 32768 -> REGNET_ERR_UNSUPPORTED
+ * (the workspace is 64.1 MiB there); a NULL pointer with n > 0 -> REGNET_ERR_NULL.  Validation precedes any launch.      */
+int64_t regnet_grasp_nms_workspace_bytes(int64_t n);
+int regnet_grasp_nms_f32(const float* center, const float* frame, const int64_t* order, int64_t n, float T2, float C,
+                         int symmetric, int64_t top_k, int64_t* keep, int32_t* count, void* workspace, void* stream);
+
 /* ---- deterministic mode (csrc/scatter.hip, csrc/det.hip, csrc/bn_train.hip) ------------------------------------------
  * The float32 kernels behind torch.use_deterministic_algorithms(True): every sum of the training backward is formed in one
  * fixed order, so runs agree bit for bit.  The default entry points above are unchanged.

@@ -164,6 +164,9 @@ SIGNATURES = {
     "regnet_ingest_crop_f64": (_int, [_vp, _vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "regnet_ingest_resample_f32": (_int, [_vp, _vp, _int, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "regnet_lzf_decompress": (_i64, [_vp, _i64, _vp, _i64]),
+    # pose NMS + top-K (grasp_select.py)
+    "regnet_grasp_nms_workspace_bytes": (_i64, [_i64]),
+    "regnet_grasp_nms_f32": (_int, [_vp, _vp, _vp, _i64, _f32, _f32, _int, _i64, _vp, _vp, _vp, _vp]),
     # deterministic mode
     "regnet_scatter_plan_bytes": (_i64, [_i64, _i64, _i64]),
     "regnet_scatter_plan": (_int, [_vp, _i64, _i64, _i64, _vp, _vp]),

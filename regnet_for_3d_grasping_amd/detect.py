@@ -8,6 +8,10 @@ inside one ``np_random.deferred()`` block.  What it adds to the host reads the g
 ``main()``:
 
     python -m regnet_for_3d_grasping_amd.detect --folder DIR [--file NAME] --load-score-path S --load-region-path R
+
+With ``select`` (``--top-k`` / ``--nms-translation`` / ``--nms-rotation`` / ``--select-from``) the record additionally carries the
+best distinct grasps of one of the four sets: pose non-maximum suppression + top-K on the device (``grasp_select.pose_nms``),
+before the final download.  Without it nothing changes.
 """
 import argparse
 import contextlib
@@ -30,6 +34,7 @@ GRIPPER_PARAMS = [WIDTH, HEIGHT, DEPTH]
 EVAL_PARAMS = [DEPTH, WIDTH, TABLE_HEIGHT, 0, CENTER_NUM]
 USE_THETA = True
 RESULT_KEYS = ("points", "colors", "scores", "grasp_stage2", "grasp_stage3_stage2", "grasp_stage3", "grasp_stage3_score")
+SELECT_KEYS = ("grasp_selected", "grasp_selected_index")       # added to the record when the detector has ``select``
 
 
 def save_path_for(pc_path, real_data):
@@ -41,11 +46,16 @@ def save_path_for(pc_path, real_data):
 class GraspDetector:
     """``GraspDetector(score_net, region_net)``: both networks on one GPU, in eval mode for the call.  ``params`` /
     ``gripper_params`` / ``eval_params`` are test.py's lists (:78-81, :90; ``eval_params[3]`` is the GPU index of the
-    collision filter and follows the networks' device).  ``transform`` / ``bounds``: see ``ingest.ingest_frame``."""
+    collision filter and follows the networks' device).  ``transform`` / ``bounds``: see ``ingest.ingest_frame``.
+    ``select``: None, or a ``grasp_select.SelectParams`` / a dict of its fields (``source``, ``top_k``,
+    ``translation_thresh``, ``rotation_thresh_deg``, ``symmetric``): the record then also carries ``grasp_selected`` (k,8),
+    the best distinct grasps of the collision-filtered set ``source``, and ``grasp_selected_index`` (k,) int64, their rows in
+    that set."""
 
     def __init__(self, score_net, region_net, params=TEST_PARAMS, gripper_params=GRIPPER_PARAMS, eval_params=EVAL_PARAMS,
-                 transform=None, bounds=None, num_points=ALL_POINTS_NUM, use_theta=USE_THETA):
-        from . import ingest
+                 transform=None, bounds=None, num_points=ALL_POINTS_NUM, use_theta=USE_THETA, select=None):
+        from . import grasp_select, ingest
+        self.select = grasp_select.SelectParams.coerce(select)
         self.score_net, self.region_net = score_net, region_net
         self.params, self.gripper_params, self.eval_params = list(params), list(gripper_params), list(eval_params)
         self.transform = ingest.table_frame_transform() if transform is None else np.asarray(transform, dtype=np.float64)
@@ -68,9 +78,9 @@ class GraspDetector:
     def detect(self, frame):
         """test.py:97-148 for one frame -> ``eval_notruth``'s dict of numpy arrays: ``points`` / ``colors`` (the cropped,
         un-jittered cloud: float64 for a camera frame, float32 for a record), ``scores`` (N,1) float32 and the four
-        collision-filtered grasp sets (k,8) float32."""
+        collision-filtered grasp sets (k,8) float32; with ``select`` also ``SELECT_KEYS``."""
         import torch
-        from . import eval_collision, np_random
+        from . import eval_collision, grasp_select, np_random
         from .get_regiondataset import get_grasp_allobj
         depth, width, table_height, _, _ = self.eval_params
         gpu = self.device.index if self.device.index is not None else torch.cuda.current_device()
@@ -100,18 +110,24 @@ class GraspDetector:
                     if grasp.shape[0] >= 1:
                         grasp = eval_collision.eval_test(points32, grasp[:, :8], None, table_height, depth, width, gpu)
                     sets[key] = grasp
+                sel = self.select
+                if sel is not None:         # on the device, before the download; draws nothing from numpy's stream
+                    sets["grasp_selected"], sets["grasp_selected_index"] = grasp_select.pose_nms(
+                        sets[sel.source], sel.translation_thresh, sel.rotation_thresh_deg, sel.top_k, sel.symmetric,
+                        return_index=True)
                 points, colors = fr.download(kept)
                 out = {"points": points, "colors": colors, "scores": output_score.view(-1, 1).cpu().numpy()}
                 out.update({key: grasp.cpu().numpy() for key, grasp in sets.items()})
         finally:
             self.score_net.train(was_training[0])
             self.region_net.train(was_training[1])
-        return {key: out[key] for key in RESULT_KEYS}
+        return {key: out[key] for key in (RESULT_KEYS if self.select is None else RESULT_KEYS + SELECT_KEYS)}
 
     def detect_file(self, path, save_path=None, real_data=None):
         """``test_one_file`` (test.py:94-148): ``.pcd`` -> camera frame, anything else -> dataset record, unless ``real_data``
         says so.  The dict is pickled to ``save_path`` (default: the rule of :143-145; no file when that rule leaves the path
-        unchanged, which would overwrite the input).  Prints the reference's three count lines.  -> (dict, save path or None)."""
+        unchanged, which would overwrite the input).  Prints the reference's three count lines, and the selected count when
+        the detector has ``select``.  -> (dict, save path or None)."""
         from . import ingest
         if real_data is None:
             real_data = path.lower().endswith(".pcd")
@@ -124,6 +140,8 @@ class GraspDetector:
         print("stage2 grasp num:", len(out["grasp_stage2"]))
         print("stage3 grasp num:", len(out["grasp_stage2"]))        # (sic: utils.py:410 prints the stage-2 count twice)
         print("stage3 grasp num (with scorethre):", len(out["grasp_stage3_score"]))
+        if self.select is not None:
+            print("selected grasp num (%s):" % self.select.source, len(out["grasp_selected"]))
         if save_path is None:
             save_path = save_path_for(path, real_data)
             if save_path == path:
@@ -132,6 +150,14 @@ class GraspDetector:
         with open(save_path, "wb") as f:
             pickle.dump(out, f)
         return out, save_path
+
+
+def select_from_args(args):
+    """The CLI's four selection flags -> a ``select`` dict, or None when none of them was given."""
+    given = {"top_k": args.top_k, "translation_thresh": args.nms_translation, "rotation_thresh_deg": args.nms_rotation,
+             "source": args.select_from}
+    given = {key: value for key, value in given.items() if value is not None}
+    return given if given else None
 
 
 def main(argv=None):
@@ -143,7 +169,13 @@ def main(argv=None):
     parser.add_argument("--load-score-path", required=True)
     parser.add_argument("--load-region-path", required=True)
     parser.add_argument("--gpu", type=int, default=0)
+    # pose NMS + top-K on one of the four sets (grasp_select.pose_nms); giving any of the four turns the selection on
+    parser.add_argument("--top-k", type=int, default=None, help="keep the K best distinct grasps (default: every distinct one)")
+    parser.add_argument("--nms-translation", type=float, default=None, help="centres this close are the same grasp [m] (0.03)")
+    parser.add_argument("--nms-rotation", type=float, default=None, help="frames this close are the same grasp [deg] (30)")
+    parser.add_argument("--select-from", choices=list(RESULT_KEYS[3:]), default=None, help="the set to select from (grasp_stage3)")
     args = parser.parse_args(argv)
+    select = select_from_args(args)
     obj_class_num, group_num, gripper_num, score_thre, depth, reg_channel = MODEL_PARAMS
     dev = "cuda:%d" % args.gpu
     with contextlib.redirect_stdout(io.StringIO()):
@@ -151,7 +183,7 @@ def main(argv=None):
         region_net, _ = checkpoint.construct_rnet(True, True, group_num, gripper_num, score_thre, depth, reg_channel,
                                                   args.load_region_path, args.gpu)
     eval_params = [DEPTH, WIDTH, TABLE_HEIGHT, args.gpu, CENTER_NUM]
-    detector = GraspDetector(score_net.to(dev), region_net.to(dev), eval_params=eval_params)
+    detector = GraspDetector(score_net.to(dev), region_net.to(dev), eval_params=eval_params, select=select)
     real_data = "real_data" in args.folder
     if args.file:
         paths = [os.path.join(args.folder, args.file)]

@@ -38,10 +38,13 @@ NORMAL_MAX_NN = 30
 
 
 def _unit_or(v, fallback):
-    """v / |v| with rows of zero norm replaced by ``fallback`` (the reference's div + nonzero(eq(norm, 0)) pattern)."""
+    """v / |v| with rows of zero norm replaced by ``fallback`` (the reference's div + nonzero(eq(norm, 0)) pattern).  The
+    fallback enters as scalars, not as a tensor uploaded from the host: nothing here waits for the device, so the function can
+    be captured into a graph (grasp_select.pose_nms_device)."""
     norm = torch.norm(v, dim=1)
     out = torch.div(v, norm.view(-1, 1))
-    return torch.where((norm == 0).view(-1, 1), v.new_tensor(fallback).expand_as(out), out)
+    zero = norm == 0
+    return torch.stack([torch.where(zero, float(f), out[:, k]) for k, f in enumerate(fallback)], dim=1)
 
 
 def grasp_frames(grasp):
