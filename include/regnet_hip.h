@@ -845,6 +845,45 @@ int64_t regnet_grasp_nms_workspace_bytes(int64_t n);
 int regnet_grasp_nms_f32(const float* center, const float* frame, const int64_t* order, int64_t n, float T2, float C,
                          int symmetric, int64_t top_k, int64_t* keep, int32_t* count, void* workspace, void* stream);
 
+/* ---- table plane (csrc/plane.hip): the dominant support plane of one camera frame, on the device ---------------------------
+ * regnet_plane_estimate_f32 / _f64: xyz (M,3) contiguous, float32 or float64 (a float64 value is rounded once to float32, to
+ * nearest; everything below is on the float32 values).  A row with a non-finite float32 coordinate takes no part.  Canonical
+ * fp32 arithmetic: individually rounded binary32 operations in the written order (-ffp-contract=off); dot(a, b) stands for
+ * ((ax bx) + (ay by)) + (az bz).
+ *   hypotheses  H of them, a multiple of 64, at most 4096.  Hypothesis h draws three rows: slot k = 0, 1, 2, attempt r = 0..7,
+ *               z = splitmix64(seed * 2^32 + (3 h + k) * 8 + r) in uint64 arithmetic (x += 0x9E3779B97F4A7C15;
+ *               x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB; z = x ^ x >> 31),
+ *               row = ((z >> 32) * M) >> 32; the first attempt that hits a finite row fills the slot.  With an unfilled slot
+ *               the hypothesis is invalid and its table row is zero.  Else a = p1 - p0, b = p2 - p0,
+ *               n = ((ay bz) - (az by), (az bx) - (ax bz), (ax by) - (ay bx)), nn = dot(n, n); valid when 1e-12f < nn < inf.
+ *   range gate  g = dot(p0, n): eligible when (lo lo) nn <= g g <= (hi hi) nn (float32 products; lo = 0, hi = inf: no gate).
+ *   tilt gate   up_hint (3) float32 HOST memory or NULL (no gate): with d = dot(n, u), uu = dot(u, u) eligible when
+ *               d d >= (cos2_tilt nn) uu; cos2_tilt = cos^2 of the largest tilt, evaluated in float64 and rounded once.
+ *   inlier      s = dot(p - p0, n); s s <= (t t) nn, inclusive, t = threshold.
+ *   winner      the valid eligible hypothesis with the most inliers, ties to the lower h; fewer than 3 inliers: no plane.
+ * Outputs, all DEVICE memory, written whole (no host read, no synchronisation, no allocation):
+ *   hypotheses (H,8) float32: n (3), p0 (3), nn, flag (0 invalid, 1 valid but gated out, 2 valid and eligible)
+ *   counts     (H) int32: the inlier count of every flag-2 hypothesis, -1 for the others
+ *   inlier     (M) uint8: 1 for the winner's inliers (all 0 without a plane)
+ *   moments    (10) float64 over the winner's inliers, coordinates widened from float32: n, Sx, Sy, Sz, Sxx, Sxy, Sxz, Syy,
+ *              Syz, Szz.  Float64 atomics: the order of the additions is not fixed -- the one non-bitwise output.
+ *   winner     (2) int32: the winning h (or -1) and its count (or 0)
+ *   workspace  regnet_plane_workspace_bytes(M, H) = 32 H bytes, 16-byte aligned (the count kernel's parameter rows); -1 for
+ *              unsupported sizes.  hypotheses must be 16-byte aligned too.
+ *   stages     15 = all four launches.  Bits 1 / 2 / 4 / 8 = hypotheses / counts / selection / mask + moments on their own,
+ *              each reading what the earlier ones left in the outputs: for measurements.
+ * Four launches ordered by the stream; no workgroup waits for another.  M == 0: every hypothesis invalid (zero rows, counts
+ * -1), winner -1, moments 0; xyz / inlier may be NULL.  Errors, all before any launch: M < 0, H <= 0, H % 64 != 0 or stages
+ * outside 1..15 -> REGNET_ERR_SHAPE; M > 2^21 or H > 4096 -> REGNET_ERR_UNSUPPORTED; a NULL pointer for a required array ->
+ * REGNET_ERR_NULL.                                                                                                        */
+int64_t regnet_plane_workspace_bytes(int64_t M, int64_t H);
+int regnet_plane_estimate_f32(const float* xyz, int64_t M, int64_t H, uint64_t seed, float threshold, float range_lo,
+                              float range_hi, const float* up_hint, float cos2_tilt, float* hypotheses, int32_t* counts,
+                              uint8_t* inlier, double* moments, int32_t* winner, void* workspace, int stages, void* stream);
+int regnet_plane_estimate_f64(const double* xyz, int64_t M, int64_t H, uint64_t seed, float threshold, float range_lo,
+                              float range_hi, const float* up_hint, float cos2_tilt, float* hypotheses, int32_t* counts,
+                              uint8_t* inlier, double* moments, int32_t* winner, void* workspace, int stages, void* stream);
+
 /* ---- deterministic mode (csrc/scatter.hip, csrc/det.hip, csrc/bn_train.hip) ------------------------------------------
  * The float32 kernels behind torch.use_deterministic_algorithms(True): every sum of the training backward is formed in one
  * fixed order, so runs agree bit for bit.  The default entry points above are unchanged.

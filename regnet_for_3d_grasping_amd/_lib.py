@@ -167,6 +167,12 @@ SIGNATURES = {
     # pose NMS + top-K (grasp_select.py)
     "regnet_grasp_nms_workspace_bytes": (_i64, [_i64]),
     "regnet_grasp_nms_f32": (_int, [_vp, _vp, _vp, _i64, _f32, _f32, _int, _i64, _vp, _vp, _vp, _vp]),
+    # table plane (table_plane.py)
+    "regnet_plane_workspace_bytes": (_i64, [_i64, _i64]),
+    "regnet_plane_estimate_f32": (_int, [_vp, _i64, _i64, ctypes.c_uint64, _f32, _f32, _f32, _vp, _f32, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _int, _vp]),
+    "regnet_plane_estimate_f64": (_int, [_vp, _i64, _i64, ctypes.c_uint64, _f32, _f32, _f32, _vp, _f32, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _int, _vp]),
     # deterministic mode
     "regnet_scatter_plan_bytes": (_i64, [_i64, _i64, _i64]),
     "regnet_scatter_plan": (_int, [_vp, _i64, _i64, _i64, _vp, _vp]),

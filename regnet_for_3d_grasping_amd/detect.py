@@ -12,6 +12,11 @@ inside one ``np_random.deferred()`` block.  What it adds to the host reads the g
 With ``select`` (``--top-k`` / ``--nms-translation`` / ``--nms-rotation`` / ``--select-from``) the record additionally carries the
 best distinct grasps of one of the four sets: pose non-maximum suppression + top-K on the device (``grasp_select.pose_nms``),
 before the final download.  Without it nothing changes.
+
+With ``transform="auto"`` (``--auto-table``, ``--table-range LO HI``, ``--plane-threshold``) the camera -> table transform is not
+the reference lab's hard-coded camera pose but is estimated on every camera frame: the dominant plane found on the device
+(``table_plane.estimate_plane``) becomes the table at ``eval_params[2]``, and the record additionally carries ``TABLE_KEYS``.
+``GraspDetector.calibrate(frame)`` does it once and keeps the transform.  Dataset records are never transformed.
 """
 import argparse
 import contextlib
@@ -35,6 +40,7 @@ EVAL_PARAMS = [DEPTH, WIDTH, TABLE_HEIGHT, 0, CENTER_NUM]
 USE_THETA = True
 RESULT_KEYS = ("points", "colors", "scores", "grasp_stage2", "grasp_stage3_stage2", "grasp_stage3", "grasp_stage3_score")
 SELECT_KEYS = ("grasp_selected", "grasp_selected_index")       # added to the record when the detector has ``select``
+TABLE_KEYS = ("table_transform", "table_plane")                # added when the transform is estimated per frame ("auto")
 
 
 def save_path_for(pc_path, real_data):
@@ -50,7 +56,10 @@ class GraspDetector:
     ``select``: None, or a ``grasp_select.SelectParams`` / a dict of its fields (``source``, ``top_k``,
     ``translation_thresh``, ``rotation_thresh_deg``, ``symmetric``): the record then also carries ``grasp_selected`` (k,8),
     the best distinct grasps of the collision-filtered set ``source``, and ``grasp_selected_index`` (k,) int64, their rows in
-    that set."""
+    that set.  ``transform``: a 4x4 (default ``ingest.table_frame_transform()``), or ``"auto"`` / a dict of
+    ``table_plane.estimate_plane`` keywords: the table plane is then estimated on every camera frame and placed at
+    ``eval_params[2]``, and the record also carries ``table_transform`` (4,4) float64 and ``table_plane`` (5,) float64 =
+    normal, offset, rms."""
 
     def __init__(self, score_net, region_net, params=TEST_PARAMS, gripper_params=GRIPPER_PARAMS, eval_params=EVAL_PARAMS,
                  transform=None, bounds=None, num_points=ALL_POINTS_NUM, use_theta=USE_THETA, select=None):
@@ -58,7 +67,15 @@ class GraspDetector:
         self.select = grasp_select.SelectParams.coerce(select)
         self.score_net, self.region_net = score_net, region_net
         self.params, self.gripper_params, self.eval_params = list(params), list(gripper_params), list(eval_params)
+        self.auto_table = None                    # estimate_plane's keywords when the transform is estimated per frame
+        if isinstance(transform, str):
+            if transform != "auto":
+                raise ValueError("transform must be a 4x4, None, \"auto\" or a dict of estimate_plane keywords")
+            transform = {}
+        if isinstance(transform, dict):
+            self.auto_table, transform = dict(transform), None
         self.transform = ingest.table_frame_transform() if transform is None else np.asarray(transform, dtype=np.float64)
+        self.table = None                         # (transform, plane) of the last automatically calibrated frame
         self.bounds = ingest.DEFAULT_BOUNDS if bounds is None else tuple(bounds)
         self.num_points, self.use_theta = int(num_points), use_theta
         self.device = next(score_net.parameters()).device
@@ -73,7 +90,26 @@ class GraspDetector:
         if isinstance(frame, dict):
             return ingest.ingest_record(frame, self.num_points, self.device)
         xyz, rgb = frame
-        return ingest.ingest_frame(xyz, rgb, self.transform, self.bounds, self.num_points, self.device)
+        transform = self.transform
+        if self.auto_table is not None:           # draws nothing from numpy's stream; one 96-byte read
+            from . import table_plane
+            xyz, rgb = ingest._to_device(xyz, self.device), ingest._to_device(rgb, self.device)
+            transform, plane = table_plane.calibrate(xyz, self.eval_params[2], **self.auto_table)
+            self.table = (transform, plane)
+        return ingest.ingest_frame(xyz, rgb, transform, self.bounds, self.num_points, self.device)
+
+    def calibrate(self, frame, **estimate_kwargs):
+        """Estimate the table plane of ``frame`` (an ``(xyz, rgb)`` pair or just ``xyz``) once and keep the transform for every
+        later call: ``self.transform`` is replaced and the per-frame estimation, if it was on, is switched off.
+        ``estimate_kwargs`` default to the ones the detector was built with.  -> (transform, plane)."""
+        from . import table_plane
+        xyz = frame[0] if isinstance(frame, (tuple, list)) else frame
+        kwargs = dict(self.auto_table or {})
+        kwargs.update(estimate_kwargs)
+        kwargs.setdefault("device", self.device)
+        self.transform, plane = table_plane.calibrate(xyz, self.eval_params[2], **kwargs)
+        self.auto_table = None
+        return self.transform, plane
 
     def detect(self, frame):
         """test.py:97-148 for one frame -> ``eval_notruth``'s dict of numpy arrays: ``points`` / ``colors`` (the cropped,
@@ -91,6 +127,7 @@ class GraspDetector:
             # (the stages' progress prints stay off stdout: detect_file's three count lines are all a caller sees)
             with np_random.deferred(), torch.no_grad(), torch.cuda.device(self.device), \
                     contextlib.redirect_stdout(io.StringIO()):
+                self.table = None
                 fr = self.ingest(frame)
                 pc = fr.pc
                 all_feature, output_score, _ = self.score_net(pc)
@@ -121,7 +158,13 @@ class GraspDetector:
         finally:
             self.score_net.train(was_training[0])
             self.region_net.train(was_training[1])
-        return {key: out[key] for key in (RESULT_KEYS if self.select is None else RESULT_KEYS + SELECT_KEYS)}
+        keys = RESULT_KEYS if self.select is None else RESULT_KEYS + SELECT_KEYS
+        if self.table is not None:
+            transform, plane = self.table
+            out["table_transform"] = np.array(transform, dtype=np.float64)
+            out["table_plane"] = np.array(list(plane.normal) + [plane.offset, plane.rms], dtype=np.float64)
+            keys = keys + TABLE_KEYS
+        return {key: out[key] for key in keys}
 
     def detect_file(self, path, save_path=None, real_data=None):
         """``test_one_file`` (test.py:94-148): ``.pcd`` -> camera frame, anything else -> dataset record, unless ``real_data``
@@ -160,6 +203,18 @@ def select_from_args(args):
     return given if given else None
 
 
+def transform_from_args(args):
+    """The CLI's three table flags -> ``GraspDetector``'s ``transform``: None (the default transform) unless one was given."""
+    if not (args.auto_table or args.table_range is not None or args.plane_threshold is not None):
+        return None
+    given = {}
+    if args.table_range is not None:
+        given["range"] = (float(args.table_range[0]), float(args.table_range[1]))
+    if args.plane_threshold is not None:
+        given["threshold"] = float(args.plane_threshold)
+    return given if given else "auto"
+
+
 def main(argv=None):
     """``main()`` of test.py:150-164."""
     from . import checkpoint
@@ -174,6 +229,11 @@ def main(argv=None):
     parser.add_argument("--nms-translation", type=float, default=None, help="centres this close are the same grasp [m] (0.03)")
     parser.add_argument("--nms-rotation", type=float, default=None, help="frames this close are the same grasp [deg] (30)")
     parser.add_argument("--select-from", choices=list(RESULT_KEYS[3:]), default=None, help="the set to select from (grasp_stage3)")
+    # the table plane estimated on every camera frame (table_plane.estimate_plane); giving any of the three turns it on
+    parser.add_argument("--auto-table", action="store_true", help="estimate the camera -> table transform on every frame")
+    parser.add_argument("--table-range", type=float, nargs=2, metavar=("LO", "HI"), default=None,
+                        help="the table plane lies between LO and HI metres from the camera")
+    parser.add_argument("--plane-threshold", type=float, default=None, help="inlier distance of the table plane [m] (0.005)")
     args = parser.parse_args(argv)
     select = select_from_args(args)
     obj_class_num, group_num, gripper_num, score_thre, depth, reg_channel = MODEL_PARAMS
@@ -183,7 +243,8 @@ def main(argv=None):
         region_net, _ = checkpoint.construct_rnet(True, True, group_num, gripper_num, score_thre, depth, reg_channel,
                                                   args.load_region_path, args.gpu)
     eval_params = [DEPTH, WIDTH, TABLE_HEIGHT, args.gpu, CENTER_NUM]
-    detector = GraspDetector(score_net.to(dev), region_net.to(dev), eval_params=eval_params, select=select)
+    detector = GraspDetector(score_net.to(dev), region_net.to(dev), eval_params=eval_params, select=select,
+                             transform=transform_from_args(args))
     real_data = "real_data" in args.folder
     if args.file:
         paths = [os.path.join(args.folder, args.file)]
