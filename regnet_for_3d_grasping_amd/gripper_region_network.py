@@ -149,7 +149,8 @@ class GripperRegionNetwork(nn.Module):
         gt7, gt_score = labels[:, :7], labels[:, 7:]
         # anchor whose orientation template is most similar to the label's closing axis
         sim = torch.stack([compute_cos_sim(anchors[:, a, 3:6], gt7[:, 3:6]).view(-1) for a in range(A)], dim=1)
-        ground_8 = torch.sort(sim, dim=1, descending=False)[1][:, 0]
+        # (stable: of tied templates -- an axis-aligned label ties two or four -- the first, as csrc/losses.hip documents)
+        ground_8 = torch.sort(sim, dim=1, descending=False, stable=True)[1][:, 0]
 
         # class-balanced subset: the same number of centres per (non-empty) anchor class.  ONE device->host read (the
         # <= B*64 class ids) instead of a count + a nonzero per class; the draws stay on numpy's global stream, in class order
