@@ -1,190 +1,65 @@
 """ctypes loader for ``csrc/libregnet_hip.so`` (the C ABI declared in include/regnet_hip.h).
 
+The header is the only declaration of an entry point: its prototypes are parsed at import into the ctypes signatures
+(``parse_header``), and ``call`` is the one way to launch (device, stream, status).
+
 Fails loudly: a missing library raises ImportError at import time and a non-zero status from
 any entry point raises RuntimeError (the reference's TORCH_CHECK / THCudaCheck convention,
 e.g. csrc/sampling_kernel.cu:134-137,167).
 """
 import ctypes
 import os
+import re
+
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("REGNET_HIP_LIB") or os.path.join(_HERE, "csrc", "libregnet_hip.so")   # override: A/B builds only
 
-_i64, _f32, _f64, _vp, _int = ctypes.c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_void_p, ctypes.c_int
+HEADER_PATH = os.path.join(_HERE, "..", "include", "regnet_hip.h")
 
-# name -> (restype, argtypes); mirrors include/regnet_hip.h one to one.
-SIGNATURES = {
-    "regnet_abi_version": (_int, []),
-    "regnet_build_info": (ctypes.c_char_p, []),
-    "regnet_strerror": (ctypes.c_char_p, [_int]),
-    "regnet_fps_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
-    "regnet_fps_chain_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "regnet_fps_workspace_bytes": (_i64, [_i64, _i64, _i64]),
-    "regnet_fps_status_offset_bytes": (_i64, [_i64, _i64, _i64]),
-    "regnet_ball_query_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i64,
-                                     _vp, _vp, _vp]),
-    "regnet_grid_workspace_bytes": (_i64, [_i64, _i64]),
-    "regnet_three_nn_grid_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp,
-                                        _vp]),
-    "regnet_ball_query_grid_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i64,
-                                          _vp, _vp, _vp, _vp]),
-    "regnet_group_points_fwd_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
-    "regnet_group_points_bwd_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp,
-                                           _vp]),
-    "regnet_three_nn_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
-    "regnet_interpolate_fwd_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
-    "regnet_interpolate_bwd_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
-    "regnet_gather_knn_fwd_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
-    "regnet_gather_knn_bwd_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
-    "regnet_fps_f64_workspace_bytes": (_i64, [_i64, _i64, _i64]),
-    "regnet_fps_f64": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
-    "regnet_ball_query_f64": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i64,
-                                     _vp, _vp, _vp]),
-    "regnet_three_nn_f64": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
-    "regnet_scatter_f64_workspace_bytes": (_i64, [_i64, _i64, _i64]),
-    "regnet_group_points_fwd_f64": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
-    "regnet_group_points_bwd_f64": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp,
-                                           _vp, _vp]),
-    "regnet_interpolate_fwd_f64": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
-    "regnet_interpolate_bwd_f64": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
-    "regnet_gather_knn_fwd_f64": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
-    "regnet_gather_knn_bwd_f64": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp,
-                                         _vp]),
-    "regnet_radius_group_f32":(_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _f32, _i64, _vp, _vp,
-                                       _vp]),
-    "regnet_select_positive_f32": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _f32, _vp, _vp, _vp, _vp]),
-    "regnet_box_crop_f32": (_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _f32, _i64, _i64, _vp, _vp, _vp]),
-    "regnet_gather_max_f32": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp]),
-    "regnet_gather_max_scene_f32": (_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
-    "regnet_gripper_frame_f32": (_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
-    "regnet_stage2_loss_rows_f32": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _f32, _vp, _vp, _i64, _vp, _vp, _vp,
-                                           _vp, _vp, _vp, _vp]),
-    "regnet_label_match_f32": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _f32, _f64, _vp, _vp, _vp]),
-    "regnet_ce_rows_f32": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp]),
-    "regnet_refine_loss_rows_f32": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _f32, _f32, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "regnet_heads_chain_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
-    "regnet_heads_tree_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
-    "regnet_head_layer_train_supported": (_int, [_i64, _i64, _i64]),
-    "regnet_head_layer_train_fwd_f32": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _i64, _i64, _i64, _int,
-                                               _vp, _vp, _vp, _vp]),
-    "regnet_head_layer_train_bwd_f32": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _int, _vp, _vp,
-                                               _vp, _vp, _vp, _vp, _i64, _int, _vp]),
-    "regnet_stage2_decode_f32": (_int, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _f32, _int, _i64, _vp, _vp]),
-    "regnet_refine_decode_f32": (_int, [_vp, _i64, _vp, _vp, _i64, _f32, _f32, _i64, _vp, _vp, _vp]),
-    "regnet_crop_pick": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
-    "regnet_gather_max_arg_f32": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
-    "regnet_scatter_max_grad_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
-    "regnet_rowsum_neg_f32": (_int, [_vp, _i64, _i64, _vp, _vp]),
-    "regnet_mlp_layer_f32": (_int, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _int, _int, _vp]),
-    "regnet_mlp_splitk_workspace_bytes": (_i64, [_i64, _i64, _i64]),
-    "regnet_mlp_layer_splitk_f32": (_int, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _int, _i64, _vp,
-                                           _vp]),
-    "regnet_sa_layer1_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64,
-                                    _vp, _i64, _vp, _vp, _vp, _i64, _i64, _int, _vp]),
-    "regnet_sa_chain3_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp,
-                                    _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _int, _vp, _i64,
-                                    _vp]),
-    "regnet_grasp_collision_counts_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _f32, _f32, _vp, _f32, _f32, _f32, _f32,
-                                                 _vp, _vp]),
-    "regnet_grasp_antipodal_stats_f32": (_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _f32, _f32, _vp, _f32,
-                                                _f32, _f32, _f32, _f32, _vp, _vp, _vp]),
-    "regnet_resample_groups_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
-    "regnet_normals_workspace_bytes": (_i64, [_i64]),
-    "regnet_estimate_normals_f32": (_int, [_vp, _i64, _f64, _i64, _f64, _f64, _f64, _vp, _vp, _vp, _vp]),
-    "regnet_bn_workspace_bytes": (_i64, [_i64]),
-    "regnet_bn_relu_train_fwd_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _f32, _f32, _vp, _vp, _int, _i64, _vp, _vp, _vp,
-                                            _vp, _vp, _vp]),
-    "regnet_bn_relu_train_bwd_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _int, _i64, _vp, _vp,
-                                            _vp, _vp, _vp]),
-    "regnet_bn_train_stats_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "regnet_bn_relu_train_fwd_from_sums_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _f32, _f32, _vp, _vp, _int, _i64, _vp, _vp,
-                                                      _vp, _vp, _vp, _vp]),
-    "regnet_bn_train_stats_from_sums_f32": (_int, [_i64, _i64, _i64, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "regnet_pack_rows_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
-    "regnet_pack_rows_centred_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp]),
-    "regnet_gather_points_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp]),
-    "regnet_class_order_i64": (_int, [_vp, _i64, _vp, _vp]),
-    "regnet_pair_order_i64": (_int, [_vp, _i64, _vp, _vp, _vp]),
-    "regnet_sa_premul_layer_f32": (_int, [_vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp,
-                                          _vp, _i64, _i64, _int, _int, _vp]),
-    "regnet_sa_layer12_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64,
-                                     _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _int, _int, _vp]),
-    "regnet_interp_concat_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _f32, _vp, _i64, _i64, _i64, _i64, _i64,
-                                        _i64, _vp, _i64, _i64, _vp]),
-    "regnet_interp_affine_f32": (_int, [_vp, _i64, _i64, _vp, _vp, _f32, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp,
-                                        _vp, _vp, _int, _i64, _i64, _i64, _vp, _i64, _vp]),
-    "regnet_score_head_f32": (_int, [_vp, _i64, _i64, _vp, _f32, _f32, _f32, _vp, _i64, _vp]),
-    "regnet_sa_premul_chain_stream_floats": (_i64, []),
-    "regnet_sa_premul_chain_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _int, _vp, _i64,
-                                          _vp, _vp]),
-    "regnet_sa3_premul_chain_stream_floats": (_i64, []),
-    "regnet_sa3_premul_chain_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _int, _vp, _i64,
-                                           _vp, _vp]),
-    "regnet_fp_head_chain_stream_floats": (_i64, []),
-    "regnet_fp_head_chain_blocks": (_i64, [_i64]),
-    "regnet_fp_head_chain_f32": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _f32, _f32, _f32, _vp, _i64, _vp, _i64, _vp,
-                                        _i64, _i64, _vp]),
-    "regnet_fp_head_chain_interp_f32": (_int, [_vp, _i64, _i64, _vp, _vp, _f32, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64,
-                                               _vp, _i64, _vp, _i64, _vp, _f32, _f32, _f32, _vp, _i64, _vp, _vp, _i64, _i64,
-                                               _vp]),
-    "regnet_conv1x1_train_supported": (_int, [_i64, _i64, _i64]),
-    "regnet_conv1x1_fwd_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
-    "regnet_conv1x1_dgrad_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
-    "regnet_conv1x1_fwd_stream_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
-    "regnet_conv1x1_dgrad_stream_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
-    "regnet_conv1x1_fwd_smallci_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
-    "regnet_conv1x1_smallci_stats_workspace_bytes": (_i64, [_i64, _i64, _i64]),
-    "regnet_conv1x1_fwd_smallci_stats_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
-    "regnet_conv1x1_wgrad_smallci_partials": (_i64, [_i64, _i64, _i64]),
-    "regnet_conv1x1_wgrad_smallci_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
-    "regnet_conv1x1_smallco_f32": (_int, [_int, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
-    "regnet_conv1x1_stream_reserve_slots": (_int, [_int]),
-    "regnet_sa_chain3_split_plane_bytes": (_i64, [_i64]),
-    "regnet_sa_chain3_split_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp,
-                                         _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _vp, _int, _vp, _i64, _vp, _vp]),
-    "regnet_conv1x1_split_supported": (_int, [_i64, _i64, _i64]),
-    "regnet_conv1x1_split_workspace_bytes": (_i64, [_i64, _i64, _i64]),
-    "regnet_conv1x1_split_f32": (_int, [_int, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _int, _vp, _vp]),
-    "regnet_conv1x1_bnrelu_supported": (_int, [_i64, _i64, _i64]),
-    "regnet_conv1x1_fwd_bnrelu_stream_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _int, _vp, _vp]),
-    "regnet_conv1x1_fwd_stats_supported": (_int, [_i64, _i64, _i64, _int]),
-    "regnet_conv1x1_fwd_stats_stream_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _int, _vp, _vp, _vp]),
-    "regnet_conv1x1_wgrad_bnrelu_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _int, _vp, _vp]),
-    "regnet_conv1x1_wgrad_slices": (_i64, [_i64, _i64, _i64, _i64]),
-    "regnet_conv1x1_wgrad_workspace_bytes": (_i64, [_i64, _i64, _i64, _i64]),
-    "regnet_conv1x1_wgrad_f32": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
-    "regnet_np_choice_rows": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp, _vp]),
-    "regnet_np_choice_rows_dev_workspace_ints": (_i64, [_i64, _i64]),
-    "regnet_np_choice_rows_dev": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp]),
-    "regnet_np_rand_doubles_dev": (_int, [_vp, _vp, _i64, _vp, _vp]),
-    "regnet_dataset_resample_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
-    # single-frame ingest (test.py's front end)
-    "regnet_ingest_crop_workspace_bytes": (_i64, [_i64]),
-    "regnet_ingest_crop_f32": (_int, [_vp, _vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "regnet_ingest_crop_f64": (_int, [_vp, _vp, _i64, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "regnet_ingest_resample_f32": (_int, [_vp, _vp, _int, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
-    "regnet_lzf_decompress": (_i64, [_vp, _i64, _vp, _i64]),
-    # pose NMS + top-K (grasp_select.py)
-    "regnet_grasp_nms_workspace_bytes": (_i64, [_i64]),
-    "regnet_grasp_nms_f32": (_int, [_vp, _vp, _vp, _i64, _f32, _f32, _int, _i64, _vp, _vp, _vp, _vp]),
-    # table plane (table_plane.py)
-    "regnet_plane_workspace_bytes": (_i64, [_i64, _i64]),
-    "regnet_plane_estimate_f32": (_int, [_vp, _i64, _i64, ctypes.c_uint64, _f32, _f32, _f32, _vp, _f32, _vp, _vp, _vp, _vp, _vp,
-                                         _vp, _int, _vp]),
-    "regnet_plane_estimate_f64": (_int, [_vp, _i64, _i64, ctypes.c_uint64, _f32, _f32, _f32, _vp, _f32, _vp, _vp, _vp, _vp, _vp,
-                                         _vp, _int, _vp]),
-    # deterministic mode
-    "regnet_scatter_plan_bytes": (_i64, [_i64, _i64, _i64]),
-    "regnet_scatter_plan": (_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
-    "regnet_scatter_segsum_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
-    "regnet_scatter_max_grad_det_f32": (_int, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp]),
-    "regnet_bn_det_workspace_bytes": (_i64, [_i64, _i64, _i64]),
-    "regnet_bn_relu_train_fwd_det_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _f32, _f32, _vp, _vp, _int, _i64, _vp, _vp, _vp,
-                                                _vp, _vp, _vp]),
-    "regnet_bn_relu_train_bwd_det_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _int, _i64, _vp, _vp,
-                                                _vp, _vp, _vp]),
-    "regnet_bn_train_stats_det_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-}
+_CTYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "float": ctypes.c_float,
+           "double": ctypes.c_double}
+_PROTOTYPE = re.compile(r"([^;{}()]*?)\b(regnet_\w+)\s*\(([^()]*)\)\s*;")
+
+
+def parse_header(text):
+    """The prototypes ``<ret> regnet_<name>(<params>);`` of a C header -> (SIGNATURES, PARAMS): name -> (restype, argtypes)
+    and name -> parameter names.  Any pointer parameter is a ``c_void_p``, a ``const char*`` return a ``c_char_p``, scalars
+    go through ``_CTYPES``; anything else raises ImportError naming the prototype -- the binding never guesses a type."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    signatures, params = {}, {}
+    for ret, name, plist in _PROTOTYPE.findall(text):
+        ret = " ".join(ret.split()).replace(" *", "*")
+        if ret == "const char*":
+            restype = ctypes.c_char_p
+        elif ret in _CTYPES:
+            restype = _CTYPES[ret]
+        else:
+            raise ImportError("%s: return type %r has no ctypes mapping" % (name, ret))
+        argtypes, names = [], []
+        plist = plist.strip()
+        for param in (plist.split(",") if plist != "void" else []):
+            m = re.fullmatch(r"(.*?)(\w+)", " ".join(param.split()))
+            ctype = m and (m.group(1).replace("const ", "").strip())
+            if not ctype or not ("*" in ctype or ctype in _CTYPES):
+                raise ImportError("%s: parameter %r has no ctypes mapping" % (name, param.strip()))
+            argtypes.append(ctypes.c_void_p if "*" in ctype else _CTYPES[ctype])
+            names.append(m.group(2))
+        signatures[name], params[name] = (restype, argtypes), names
+    if len(signatures) != len(set(re.findall(r"\b(regnet_\w+)\s*\(", text))):
+        raise ImportError("a regnet_* declaration in the header is not a prototype this parser reads")
+    if not signatures:
+        raise ImportError("no regnet_* prototype found in the header")
+    return signatures, params
+
+
+# name -> (restype, argtypes) and name -> parameter names: include/regnet_hip.h is the only declaration of an entry point.
+with open(HEADER_PATH) as _f:
+    SIGNATURES, PARAMS = parse_header(_f.read())
+# the launching entry points: their last parameter is the hipStream_t (the others are size, support and host-side queries)
+HAS_STREAM = {name: names[-1:] == ["stream"] for name, names in PARAMS.items()}
 
 
 def _load():
@@ -208,3 +83,25 @@ def check(status, what):
     if status != 0:
         msg = lib.regnet_strerror(int(status)).decode()
         raise RuntimeError("%s failed: %s (code %d)" % (what, msg, status))
+
+
+def call(name, anchor, *args, stream=None, tolerate=0):
+    """Call entry point ``name`` for the GPU tensor ``anchor`` and return its value.  A launching entry point (last parameter
+    ``stream``) runs with the anchor's device current -- a context is entered only when it is not already -- on ``stream`` (a
+    raw handle; default: torch's current stream of that device), appended to ``args``; a non-zero status raises RuntimeError,
+    except ``tolerate`` (a status on which the caller itself falls back).  An entry point without a stream parameter is
+    called with ``args`` as they are."""
+    fn = getattr(lib, name)
+    if not HAS_STREAM[name]:
+        return fn(*args)
+    device = anchor.device
+    if stream is None:
+        stream = torch.cuda.current_stream(device).cuda_stream
+    if device.index != torch.cuda.current_device():
+        with torch.cuda.device(device):
+            status = fn(*args, stream)
+    else:
+        status = fn(*args, stream)
+    if status != 0 and status != tolerate:
+        check(status, name)
+    return status

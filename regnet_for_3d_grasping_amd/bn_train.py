@@ -15,7 +15,7 @@ import torch
 from . import _lib, determinism
 
 ENABLED = True
-_check = _lib.check
+_call = _lib.call
 _L = _lib.lib
 
 
@@ -49,27 +49,23 @@ class _BnReluTrain(torch.autograd.Function):
         B, C = x.shape[0], x.shape[1]
         L = x.numel() // (B * C)
         dev = x.device
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            det = sums is None and determinism.enabled()
-            ws = sums if sums is not None else _workspace(B, C, L, dev, det)
-            mean = torch.empty((C,), dtype=torch.float32, device=dev)
-            invstd = torch.empty((C,), dtype=torch.float32, device=dev)
-            if pool_group:
-                y = torch.empty(x.shape[:-1], dtype=torch.float32, device=dev)
-                index = torch.empty(x.shape[:-1], dtype=torch.int32, device=dev)
-            else:
-                y, index = torch.empty_like(x), None
-            gamma, beta = gamma.contiguous(), beta.contiguous()
-            # sums: the convolution that produced x left the statistics (conv1x1_train FUSE_STATS): no pass over x for them
-            fwd = _L.regnet_bn_relu_train_fwd_f32 if sums is None else _L.regnet_bn_relu_train_fwd_from_sums_f32
-            if det:
-                fwd = _L.regnet_bn_relu_train_fwd_det_f32
-            _check(fwd(x.data_ptr(), B, C, L, gamma.data_ptr(), beta.data_ptr(), float(eps),
-                       float(momentum), running_mean.data_ptr(), running_var.data_ptr(),
-                       int(relu), int(pool_group), y.data_ptr(),
-                       index.data_ptr() if index is not None else None, mean.data_ptr(),
-                       invstd.data_ptr(), ws.data_ptr(), stream), "bn_relu_train_fwd")
+        det = sums is None and determinism.enabled()
+        ws = sums if sums is not None else _workspace(B, C, L, dev, det)
+        mean = torch.empty((C,), dtype=torch.float32, device=dev)
+        invstd = torch.empty((C,), dtype=torch.float32, device=dev)
+        if pool_group:
+            y = torch.empty(x.shape[:-1], dtype=torch.float32, device=dev)
+            index = torch.empty(x.shape[:-1], dtype=torch.int32, device=dev)
+        else:
+            y, index = torch.empty_like(x), None
+        gamma, beta = gamma.contiguous(), beta.contiguous()
+        # sums: the convolution that produced x left the statistics (conv1x1_train FUSE_STATS): no pass over x for them
+        fwd = "regnet_bn_relu_train_fwd_f32" if sums is None else "regnet_bn_relu_train_fwd_from_sums_f32"
+        if det:
+            fwd = "regnet_bn_relu_train_fwd_det_f32"
+        _call(fwd, x, x.data_ptr(), B, C, L, gamma.data_ptr(), beta.data_ptr(), float(eps), float(momentum),
+              running_mean.data_ptr(), running_var.data_ptr(), int(relu), int(pool_group), y.data_ptr(),
+              index.data_ptr() if index is not None else None, mean.data_ptr(), invstd.data_ptr(), ws.data_ptr())
         ctx.save_for_backward(x, gamma, beta, mean, invstd, *((y, index) if pool_group else ()))
         ctx.relu, ctx.pool_group = int(relu), int(pool_group)
         return y
@@ -83,19 +79,15 @@ class _BnReluTrain(torch.autograd.Function):
         L = x.numel() // (B * C)
         dev = x.device
         dy = _aligned(dy)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            det = determinism.enabled()
-            ws = _workspace(B, C, L, dev, det)
-            dx = torch.empty_like(x)
-            dgamma = torch.empty((C,), dtype=torch.float32, device=dev)
-            dbeta = torch.empty((C,), dtype=torch.float32, device=dev)
-            bwd = _L.regnet_bn_relu_train_bwd_det_f32 if det else _L.regnet_bn_relu_train_bwd_f32
-            _check(bwd(x.data_ptr(), y.data_ptr() if y is not None else None, dy.data_ptr(),
-                       index.data_ptr() if index is not None else None, B, C, L,
-                       gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                       ctx.relu, ctx.pool_group, dx.data_ptr(), dgamma.data_ptr(),
-                       dbeta.data_ptr(), ws.data_ptr(), stream), "bn_relu_train_bwd")
+        det = determinism.enabled()
+        ws = _workspace(B, C, L, dev, det)
+        dx = torch.empty_like(x)
+        dgamma = torch.empty((C,), dtype=torch.float32, device=dev)
+        dbeta = torch.empty((C,), dtype=torch.float32, device=dev)
+        _call("regnet_bn_relu_train_bwd_det_f32" if det else "regnet_bn_relu_train_bwd_f32", x, x.data_ptr(),
+              y.data_ptr() if y is not None else None, dy.data_ptr(), index.data_ptr() if index is not None else None, B, C, L,
+              gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(), invstd.data_ptr(), ctx.relu, ctx.pool_group, dx.data_ptr(),
+              dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr())
         return dx, dgamma, dbeta, None, None, None, None, None, None, None
 
 
@@ -127,24 +119,20 @@ def bn_stats(bn, x, relu=True):
     L = xc.numel() // (B * C)
     dev = xc.device
     p = Pending()
-    with torch.cuda.device(dev):
-        out = torch.empty((4, C), dtype=torch.float32, device=dev)
-        p.mean, p.invstd, p.scale, p.shift = out[0], out[1], out[2], out[3]
-        p.gamma, p.beta = bn.weight, bn.bias
-        g, b = bn.weight.detach().contiguous(), bn.bias.detach().contiguous()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        if sums is not None:      # left by the convolution that produced x (conv1x1_train FUSE_STATS): x is not read
-            _check(_L.regnet_bn_train_stats_from_sums_f32(B, C, L, g.data_ptr(), b.data_ptr(), float(bn.eps), float(bn.momentum),
-                                                          bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
-                                                          p.mean.data_ptr(), p.invstd.data_ptr(), p.scale.data_ptr(),
-                                                          p.shift.data_ptr(), sums.data_ptr(), stream), "bn_train_stats_from_sums")
-        else:
-            det = determinism.enabled()
-            ws = _workspace(B, C, L, dev, det)
-            stats = _L.regnet_bn_train_stats_det_f32 if det else _L.regnet_bn_train_stats_f32
-            _check(stats(xc.data_ptr(), B, C, L, g.data_ptr(), b.data_ptr(), float(bn.eps), float(bn.momentum),
-                         bn.running_mean.data_ptr(), bn.running_var.data_ptr(), p.mean.data_ptr(), p.invstd.data_ptr(),
-                         p.scale.data_ptr(), p.shift.data_ptr(), ws.data_ptr(), stream), "bn_train_stats")
+    out = torch.empty((4, C), dtype=torch.float32, device=dev)
+    p.mean, p.invstd, p.scale, p.shift = out[0], out[1], out[2], out[3]
+    p.gamma, p.beta = bn.weight, bn.bias
+    g, b = bn.weight.detach().contiguous(), bn.bias.detach().contiguous()
+    if sums is not None:      # left by the convolution that produced x (conv1x1_train FUSE_STATS): x is not read
+        _call("regnet_bn_train_stats_from_sums_f32", xc, B, C, L, g.data_ptr(), b.data_ptr(), float(bn.eps), float(bn.momentum),
+              bn.running_mean.data_ptr(), bn.running_var.data_ptr(), p.mean.data_ptr(), p.invstd.data_ptr(),
+              p.scale.data_ptr(), p.shift.data_ptr(), sums.data_ptr())
+    else:
+        det = determinism.enabled()
+        ws = _workspace(B, C, L, dev, det)
+        _call("regnet_bn_train_stats_det_f32" if det else "regnet_bn_train_stats_f32", xc, xc.data_ptr(), B, C, L, g.data_ptr(),
+              b.data_ptr(), float(bn.eps), float(bn.momentum), bn.running_mean.data_ptr(), bn.running_var.data_ptr(),
+              p.mean.data_ptr(), p.invstd.data_ptr(), p.scale.data_ptr(), p.shift.data_ptr(), ws.data_ptr())
     p.x, p.relu = xc, int(relu)
     return p
 
@@ -156,16 +144,14 @@ def bn_backward(x, dz, gamma, beta, mean, invstd, relu):
     dev = x.device
     dz = _aligned(dz)
     gamma, beta = gamma.detach().contiguous(), beta.detach().contiguous()
-    with torch.cuda.device(dev):
-        det = determinism.enabled()
-        ws = _workspace(B, C, L, dev, det)
-        dx = torch.empty_like(x)
-        dgamma = torch.empty((C,), dtype=torch.float32, device=dev)
-        dbeta = torch.empty((C,), dtype=torch.float32, device=dev)
-        bwd = _L.regnet_bn_relu_train_bwd_det_f32 if det else _L.regnet_bn_relu_train_bwd_f32
-        _check(bwd(x.data_ptr(), None, dz.data_ptr(), None, B, C, L, gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(),
-                   invstd.data_ptr(), int(relu), 0, dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(),
-                   torch.cuda.current_stream(dev).cuda_stream), "bn_relu_train_bwd")
+    det = determinism.enabled()
+    ws = _workspace(B, C, L, dev, det)
+    dx = torch.empty_like(x)
+    dgamma = torch.empty((C,), dtype=torch.float32, device=dev)
+    dbeta = torch.empty((C,), dtype=torch.float32, device=dev)
+    _call("regnet_bn_relu_train_bwd_det_f32" if det else "regnet_bn_relu_train_bwd_f32", x, x.data_ptr(), None, dz.data_ptr(),
+          None, B, C, L, gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(), invstd.data_ptr(), int(relu), 0, dx.data_ptr(),
+          dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr())
     return dx, dgamma, dbeta
 
 

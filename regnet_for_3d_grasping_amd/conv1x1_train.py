@@ -49,11 +49,9 @@ def _split(transposed, w, x, B, Co, Ci, L, scale=None, shift=None, relu=0):
     from . import _lib
     out = torch.empty((B, Ci if transposed else Co, L), dtype=torch.float32, device=x.device)
     ws = torch.empty((_lib.lib.regnet_conv1x1_split_workspace_bytes(Co, Ci, transposed),), dtype=torch.uint8, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib.regnet_conv1x1_split_f32(transposed, w.data_ptr(), x.data_ptr(), out.data_ptr(), B, Co, Ci, L,
-                                                     scale.data_ptr() if scale is not None else None,
-                                                     shift.data_ptr() if shift is not None else None, int(relu), ws.data_ptr(),
-                                                     _stream(x)), "conv1x1_split")
+    _lib.call("regnet_conv1x1_split_f32", x, transposed, w.data_ptr(), x.data_ptr(), out.data_ptr(), B, Co, Ci, L,
+              scale.data_ptr() if scale is not None else None, shift.data_ptr() if shift is not None else None, int(relu),
+              ws.data_ptr())
     return out
 
 
@@ -67,10 +65,6 @@ def _native_ok(B, Co, Ci, L, wgrad=False):
         return False
     from . import _lib
     return bool(_lib.lib.regnet_conv1x1_train_supported(Co, Ci, L)) and (not wgrad or L % 16 == 0)
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 def supported(conv, x):
@@ -111,20 +105,16 @@ def native_fwd(x, w, sums=None):
     if sums is None and _split_ok(Co, Ci, L):
         return _split(0, w, x, B, Co, Ci, L)
     y = torch.empty((B, Co, L), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        if sums is not None:
-            from . import fused
-            _lib.check(_lib.lib.regnet_conv1x1_fwd_stats_stream_f32(w.data_ptr(), x.data_ptr(), y.data_ptr(), B, Co, Ci, L, None,
-                                                                    None, 0, fused._tickets(x.device).data_ptr(),
-                                                                    sums.data_ptr(), _stream(x)), "conv1x1_fwd_stats")
-        elif STREAM:
-            from . import fused
-            _lib.check(_lib.lib.regnet_conv1x1_fwd_stream_f32(w.data_ptr(), x.data_ptr(), y.data_ptr(), B, Co, Ci, L,
-                                                              fused._tickets(x.device).data_ptr(), _stream(x)),
-                       "conv1x1_fwd_stream")
-        else:
-            _lib.check(_lib.lib.regnet_conv1x1_fwd_f32(w.data_ptr(), x.data_ptr(), y.data_ptr(), B, Co, Ci, L, _stream(x)),
-                       "conv1x1_fwd")
+    if sums is not None:
+        from . import fused
+        _lib.call("regnet_conv1x1_fwd_stats_stream_f32", x, w.data_ptr(), x.data_ptr(), y.data_ptr(), B, Co, Ci, L, None, None,
+                  0, fused._tickets(x.device).data_ptr(), sums.data_ptr())
+    elif STREAM:
+        from . import fused
+        _lib.call("regnet_conv1x1_fwd_stream_f32", x, w.data_ptr(), x.data_ptr(), y.data_ptr(), B, Co, Ci, L,
+                  fused._tickets(x.device).data_ptr())
+    else:
+        _lib.call("regnet_conv1x1_fwd_f32", x, w.data_ptr(), x.data_ptr(), y.data_ptr(), B, Co, Ci, L)
     return y
 
 
@@ -136,15 +126,12 @@ def native_dgrad(w, dy):
     if _split_ok(Co, Ci, L):
         return _split(1, w, dy, B, Co, Ci, L)
     dx = torch.empty((B, Ci, L), dtype=torch.float32, device=dy.device)
-    with torch.cuda.device(dy.device):
-        if STREAM:
-            from . import fused
-            _lib.check(_lib.lib.regnet_conv1x1_dgrad_stream_f32(w.data_ptr(), dy.data_ptr(), dx.data_ptr(), B, Co, Ci, L,
-                                                                fused._tickets(dy.device).data_ptr(), _stream(dy)),
-                       "conv1x1_dgrad_stream")
-        else:
-            _lib.check(_lib.lib.regnet_conv1x1_dgrad_f32(w.data_ptr(), dy.data_ptr(), dx.data_ptr(), B, Co, Ci, L,
-                                                         _stream(dy)), "conv1x1_dgrad")
+    if STREAM:
+        from . import fused
+        _lib.call("regnet_conv1x1_dgrad_stream_f32", dy, w.data_ptr(), dy.data_ptr(), dx.data_ptr(), B, Co, Ci, L,
+                  fused._tickets(dy.device).data_ptr())
+    else:
+        _lib.call("regnet_conv1x1_dgrad_f32", dy, w.data_ptr(), dy.data_ptr(), dx.data_ptr(), B, Co, Ci, L)
     return dx
 
 
@@ -157,9 +144,8 @@ def native_wgrad(dy, x):
     dw = torch.empty((Co, Ci), dtype=torch.float32, device=x.device)
     ws_bytes = L_.regnet_conv1x1_wgrad_workspace_bytes(B, Co, Ci, L)
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=x.device) if ws_bytes else None
-    with torch.cuda.device(x.device):
-        _lib.check(L_.regnet_conv1x1_wgrad_f32(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), B, Co, Ci, L,
-                                               ws.data_ptr() if ws is not None else None, _stream(x)), "conv1x1_wgrad")
+    _lib.call("regnet_conv1x1_wgrad_f32", x, dy.data_ptr(), x.data_ptr(), dw.data_ptr(), B, Co, Ci, L,
+              ws.data_ptr() if ws is not None else None)
     return dw
 
 
@@ -172,17 +158,12 @@ def native_fwd_bnrelu(x, w, scale, shift, relu, sums=None):
     if sums is None and _split_ok(Co, Ci, L, affine=True):
         return _split(0, w, x, B, Co, Ci, L, scale, shift, relu)
     y = torch.empty((B, Co, L), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        if sums is not None:
-            _lib.check(_lib.lib.regnet_conv1x1_fwd_stats_stream_f32(w.data_ptr(), x.data_ptr(), y.data_ptr(), B, Co, Ci, L,
-                                                                    scale.data_ptr(), shift.data_ptr(), relu,
-                                                                    fused._tickets(x.device).data_ptr(), sums.data_ptr(),
-                                                                    _stream(x)), "conv1x1_fwd_bnrelu_stats")
-            return y
-        _lib.check(_lib.lib.regnet_conv1x1_fwd_bnrelu_stream_f32(w.data_ptr(), x.data_ptr(), y.data_ptr(), B, Co, Ci, L,
-                                                                 scale.data_ptr(), shift.data_ptr(), relu,
-                                                                 fused._tickets(x.device).data_ptr(), _stream(x)),
-                   "conv1x1_fwd_bnrelu")
+    if sums is not None:
+        _lib.call("regnet_conv1x1_fwd_stats_stream_f32", x, w.data_ptr(), x.data_ptr(), y.data_ptr(), B, Co, Ci, L,
+                  scale.data_ptr(), shift.data_ptr(), relu, fused._tickets(x.device).data_ptr(), sums.data_ptr())
+        return y
+    _lib.call("regnet_conv1x1_fwd_bnrelu_stream_f32", x, w.data_ptr(), x.data_ptr(), y.data_ptr(), B, Co, Ci, L,
+              scale.data_ptr(), shift.data_ptr(), relu, fused._tickets(x.device).data_ptr())
     return y
 
 
@@ -195,11 +176,8 @@ def native_wgrad_bnrelu(dy, x, scale, shift, relu):
     dw = torch.empty((Co, Ci), dtype=torch.float32, device=x.device)
     ws_bytes = L_.regnet_conv1x1_wgrad_workspace_bytes(B, Co, Ci, L)
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=x.device) if ws_bytes else None
-    with torch.cuda.device(x.device):
-        _lib.check(L_.regnet_conv1x1_wgrad_bnrelu_f32(dy.data_ptr(), x.data_ptr(), dw.data_ptr(), B, Co, Ci, L,
-                                                      scale.data_ptr(), shift.data_ptr(), relu,
-                                                      ws.data_ptr() if ws is not None else None, _stream(x)),
-                   "conv1x1_wgrad_bnrelu")
+    _lib.call("regnet_conv1x1_wgrad_bnrelu_f32", x, dy.data_ptr(), x.data_ptr(), dw.data_ptr(), B, Co, Ci, L, scale.data_ptr(),
+              shift.data_ptr(), relu, ws.data_ptr() if ws is not None else None)
     return dw
 
 
@@ -238,16 +216,13 @@ def native_fwd_smallci(x, w, sums=None):
     B, Ci, L = x.shape
     Co = w.shape[0]
     y = torch.empty((B, Co, L), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        if sums is not None:
-            ws = torch.empty((_lib.lib.regnet_conv1x1_smallci_stats_workspace_bytes(B, Ci, L) // 8,), dtype=torch.float64,
-                             device=x.device)
-            _lib.check(_lib.lib.regnet_conv1x1_fwd_smallci_stats_f32(w.data_ptr(), x.data_ptr(), y.data_ptr(), B, Co, Ci, L,
-                                                                     ws.data_ptr(), sums.data_ptr(), _stream(x)),
-                       "conv1x1_fwd_smallci_stats")
-            return y
-        _lib.check(_lib.lib.regnet_conv1x1_fwd_smallci_f32(w.data_ptr(), x.data_ptr(), y.data_ptr(), B, Co, Ci, L, _stream(x)),
-                   "conv1x1_fwd_smallci")
+    if sums is not None:
+        ws = torch.empty((_lib.lib.regnet_conv1x1_smallci_stats_workspace_bytes(B, Ci, L) // 8,), dtype=torch.float64,
+                         device=x.device)
+        _lib.call("regnet_conv1x1_fwd_smallci_stats_f32", x, w.data_ptr(), x.data_ptr(), y.data_ptr(), B, Co, Ci, L,
+                  ws.data_ptr(), sums.data_ptr())
+        return y
+    _lib.call("regnet_conv1x1_fwd_smallci_f32", x, w.data_ptr(), x.data_ptr(), y.data_ptr(), B, Co, Ci, L)
     return y
 
 
@@ -260,9 +235,7 @@ def native_wgrad_smallci(dy, x):
     Ci = x.shape[1]
     n = int(L_.regnet_conv1x1_wgrad_smallci_partials(B, Co, L))
     part = torch.empty((n, Co, Ci), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(L_.regnet_conv1x1_wgrad_smallci_f32(dy.data_ptr(), x.data_ptr(), part.data_ptr(), B, Co, Ci, L, _stream(x)),
-                   "conv1x1_wgrad_smallci")
+    _lib.call("regnet_conv1x1_wgrad_smallci_f32", x, dy.data_ptr(), x.data_ptr(), part.data_ptr(), B, Co, Ci, L)
     return part.sum(0) if n > 1 else part.view(Co, Ci)
 
 
@@ -277,9 +250,8 @@ class _ConvSmallCo(torch.autograd.Function):
         Co = w.shape[0]
         w = w.contiguous()
         y = torch.empty((B, Co, L), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib.regnet_conv1x1_smallco_f32(0, w.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                                           x.data_ptr(), y.data_ptr(), B, Co, Ci, L, _stream(x)), "conv1x1_smallco")
+        _lib.call("regnet_conv1x1_smallco_f32", x, 0, w.data_ptr(), bias.data_ptr() if bias is not None else None, x.data_ptr(),
+                  y.data_ptr(), B, Co, Ci, L)
         ctx.save_for_backward(x, w)
         ctx.has_bias = bias is not None
         return y
@@ -294,9 +266,7 @@ class _ConvSmallCo(torch.autograd.Function):
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
-            with torch.cuda.device(x.device):
-                _lib.check(_lib.lib.regnet_conv1x1_smallco_f32(1, w.data_ptr(), None, dy.data_ptr(), dx.data_ptr(), B, Co, Ci, L,
-                                                               _stream(x)), "conv1x1_smallco")
+            _lib.call("regnet_conv1x1_smallco_f32", x, 1, w.data_ptr(), None, dy.data_ptr(), dx.data_ptr(), B, Co, Ci, L)
         if ctx.needs_input_grad[1]:
             dw = native_wgrad_smallci(x, dy).t().contiguous()       # (Ci, Co) partial sums with the roles swapped -> (Co, Ci)
         if ctx.has_bias and ctx.needs_input_grad[2]:

@@ -124,7 +124,8 @@ class GraspDetector:
         self.score_net.eval()
         self.region_net.eval()
         try:
-            # (the stages' progress prints stay off stdout: detect_file's three count lines are all a caller sees)
+            # (the stages' progress prints stay off stdout: detect_file's three count lines are all a caller sees; the device
+            # context covers the whole frame -- both networks' torch layers and every launch -- so none of them switches)
             with np_random.deferred(), torch.no_grad(), torch.cuda.device(self.device), \
                     contextlib.redirect_stdout(io.StringIO()):
                 self.table = None

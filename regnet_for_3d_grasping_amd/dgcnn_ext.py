@@ -6,9 +6,9 @@ completeness on top of the group_points kernels.  float32 or float64 (see pn2_ex
 import torch
 
 from . import _lib
-from .pn2_ext import _entry, _eq, _need_float, _need_i64, _scatter_backward, _stream
+from .pn2_ext import _entry, _eq, _need_float, _need_i64, _scatter_backward
 
-_check = _lib.check
+_call = _lib.call
 
 
 def gather_knn_forward(input, index):
@@ -20,11 +20,10 @@ def gather_knn_forward(input, index):
     _eq(index.size(0), input.size(0), "index.size(0) does not equal to batch_size")
     B, C, N = input.shape
     _, NI, K = index.shape
-    with torch.cuda.device(input.device):
-        idx = index.contiguous()
-        out = torch.empty((B, C, NI, K), dtype=input.dtype, device=input.device)
-        _check(_entry("gather_knn_fwd", input)(input.data_ptr(), *input.stride(), idx.data_ptr(), B, C, N, NI, K,
-                                               out.data_ptr(), _stream(input)), "gather_knn_forward")
+    idx = index.contiguous()
+    out = torch.empty((B, C, NI, K), dtype=input.dtype, device=input.device)
+    _call(_entry("gather_knn_fwd", input), input, input.data_ptr(), *input.stride(), idx.data_ptr(), B, C, N, NI, K,
+          out.data_ptr())
     return out
 
 
@@ -39,11 +38,10 @@ def gather_knn_backward(grad_output, index):
     _eq(index.size(0), B, "index.size(0) does not equal to batch_size")
     _eq(index.size(2), K, "index.size(2) does not equal to k")
     NI = index.size(1)
-    with torch.cuda.device(grad_output.device):
-        idx = index.contiguous()
-        # grad_output rows follow the index rows (NI); the reference sizes grad_input by N
-        return _scatter_backward(
-            "gather_knn_backward", grad_output, idx, None, B, C, N, NI * K, K, None,
-            lambda grad_in, *ws: _entry("gather_knn_bwd", grad_output)(
-                grad_output.data_ptr(), *grad_output.stride(), idx.data_ptr(), B, C, N, NI, K, grad_in.data_ptr(), *ws,
-                _stream(grad_output)))
+    idx = index.contiguous()
+    # grad_output rows follow the index rows (NI); the reference sizes grad_input by N
+    return _scatter_backward(
+        "gather_knn_backward", grad_output, idx, None, B, C, N, NI * K, K, None,
+        lambda grad_in, *ws: _call(
+            _entry("gather_knn_bwd", grad_output), grad_output, grad_output.data_ptr(), *grad_output.stride(),
+            idx.data_ptr(), B, C, N, NI, K, grad_in.data_ptr(), *ws))

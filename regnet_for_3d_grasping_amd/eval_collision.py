@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 
-_check = _lib.check
+_call = _lib.call
 _L = _lib.lib
 
 # dataset_utils/eval_score/configs/config.py:9,25-28,36-40
@@ -104,13 +104,10 @@ def collision_counts(points, T, depth, width):
     _points_ok(points)
     T = T.to(points.device, torch.float32).contiguous()
     B, N = T.shape[0], points.shape[0]
-    with torch.cuda.device(points.device):
-        counts = torch.zeros((B, 4), dtype=torch.int32, device=points.device)
-        box, keep = _box_args(depth, width, B, points.device)
-        _check(_L.regnet_grasp_collision_counts_f32(points.data_ptr(), points.stride(0), points.stride(1), N, T.data_ptr(),
-                                                    B, *box, counts.data_ptr(),
-                                                    torch.cuda.current_stream(points.device).cuda_stream),
-               "grasp_collision_counts")
+    counts = torch.zeros((B, 4), dtype=torch.int32, device=points.device)
+    box, keep = _box_args(depth, width, B, points.device)
+    _call("regnet_grasp_collision_counts_f32", points, points.data_ptr(), points.stride(0), points.stride(1), N, T.data_ptr(),
+          B, *box, counts.data_ptr())
     return counts
 
 
@@ -121,15 +118,11 @@ def antipodal_scores(points, normals, T, depth, width):
     _points_ok(normals, "normals")
     T = T.to(points.device, torch.float32).contiguous()
     B, N = T.shape[0], points.shape[0]
-    with torch.cuda.device(points.device):
-        stats = torch.zeros((B, 4), dtype=torch.float32, device=points.device)
-        sides = torch.zeros((B, 2), dtype=torch.int32, device=points.device)
-        box, keep = _box_args(depth, width, B, points.device)
-        _check(_L.regnet_grasp_antipodal_stats_f32(points.data_ptr(), points.stride(0), points.stride(1), normals.data_ptr(),
-                                                   normals.stride(0), normals.stride(1), N, T.data_ptr(), B, *box,
-                                                   NEIGHBOR_DEPTH, stats.data_ptr(), sides.data_ptr(),
-                                                   torch.cuda.current_stream(points.device).cuda_stream),
-               "grasp_antipodal_stats")
+    stats = torch.zeros((B, 4), dtype=torch.float32, device=points.device)
+    sides = torch.zeros((B, 2), dtype=torch.int32, device=points.device)
+    box, keep = _box_args(depth, width, B, points.device)
+    _call("regnet_grasp_antipodal_stats_f32", points, points.data_ptr(), points.stride(0), points.stride(1), normals.data_ptr(),
+          normals.stride(0), normals.stride(1), N, T.data_ptr(), B, *box, NEIGHBOR_DEPTH, stats.data_ptr(), sides.data_ptr())
     return (stats[:, 2] / sides[:, 0]) * (stats[:, 3] / sides[:, 1])
 
 
@@ -174,13 +167,11 @@ def estimate_normals(points, camera_pos=(0.0, 0.0, 0.0), radius=NORMAL_RADIUS, m
         raise ValueError("estimate_normals: points must be (N,3)")
     N = pts.shape[0]
     cam = [float(c) for c in camera_pos]
-    with torch.cuda.device(pts.device):
-        normals = torch.empty((N, 3), dtype=torch.float32, device=pts.device)
-        count = torch.empty((N,), dtype=torch.int32, device=pts.device)
-        ws = torch.empty((max(int(_L.regnet_normals_workspace_bytes(N)), 16),), dtype=torch.uint8, device=pts.device)
-        _check(_L.regnet_estimate_normals_f32(pts.data_ptr(), N, float(radius), int(max_nn), cam[0], cam[1], cam[2],
-                                              normals.data_ptr(), count.data_ptr(), ws.data_ptr(),
-                                              torch.cuda.current_stream(pts.device).cuda_stream), "estimate_normals")
+    normals = torch.empty((N, 3), dtype=torch.float32, device=pts.device)
+    count = torch.empty((N,), dtype=torch.int32, device=pts.device)
+    ws = torch.empty((max(int(_L.regnet_normals_workspace_bytes(N)), 16),), dtype=torch.uint8, device=pts.device)
+    _call("regnet_estimate_normals_f32", pts, pts.data_ptr(), N, float(radius), int(max_nn), cam[0], cam[1], cam[2],
+          normals.data_ptr(), count.data_ptr(), ws.data_ptr())
     return (normals, count) if return_count else normals
 
 

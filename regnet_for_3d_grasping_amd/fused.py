@@ -22,7 +22,7 @@ SPLITK_MAX_ROWS = 1024   # at most this many rows: the GEMM is "skinny" and is s
 PREMUL = True   # evaluate the first layer of wide set-abstraction blocks per source point (see sa_features)
 PREMUL_CENTRE = True   # ... on mean-centred coordinates (a module switch like the others: bench.py --set fused.PREMUL_CENTRE=0)
 
-_check = _lib.check
+_call = _lib.call
 _L = _lib.lib
 
 
@@ -48,29 +48,6 @@ def supports_sa(module, feature):
 def supports_fp(module, sparse_feature):
     return (sparse_feature.dtype == torch.float32 and _f32_weights(module)
             and getattr(module.interpolator, "num_neighbors", 0) == 3)
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-def _on_tensor_device(fn):
-    """Run a kernel wrapper with the HIP device of its first GPU tensor argument current (hipLaunchKernel on a stream
-    of another device fails with an invalid-resource-handle error): a model living on cuda:k must work whatever
-    ``torch.cuda.current_device()`` is, like pn2_ext / region_ops / bn_train.  Free when the device is already
-    current (the common case: one process per GPU)."""
-    import functools
-
-    @functools.wraps(fn)
-    def wrapped(*args, **kwargs):
-        for a in args:
-            if isinstance(a, torch.Tensor) and a.is_cuda:
-                if a.device.index != torch.cuda.current_device():
-                    with torch.cuda.device(a.device):
-                        return fn(*args, **kwargs)
-                break
-        return fn(*args, **kwargs)
-    return wrapped
 
 
 def _round_up(x, m):
@@ -188,7 +165,6 @@ def _packed_stack(owner, stack, first_col_order=None):
 
 
 # ---- thin kernel wrappers (module-level names so bench.py can bracket them with events) ------
-@_on_tensor_device
 def mlp_layer(A, Ka, layer, P, pool_group=0):
     """A: channels-last (P, lda) float32 buffer whose first Ka columns are valid."""
     rows = P // pool_group if pool_group else P
@@ -201,14 +177,12 @@ def mlp_layer(A, Ka, layer, P, pool_group=0):
         if ksplit > 1:
             ws = torch.empty((_L.regnet_mlp_splitk_workspace_bytes(P, layer.N, ksplit),), dtype=torch.uint8,
                              device=A.device)
-            _check(_L.regnet_mlp_layer_splitk_f32(A.data_ptr(), A.stride(0), Ka, layer.W.data_ptr(), layer.Kpad,
-                                                  layer.scale.data_ptr(), layer.shift.data_ptr(), out.data_ptr(),
-                                                  out.stride(0), P, layer.N, layer.relu, ksplit, ws.data_ptr(),
-                                                  _stream(A)), "mlp_layer_splitk")
+            _call("regnet_mlp_layer_splitk_f32", A, A.data_ptr(), A.stride(0), Ka, layer.W.data_ptr(), layer.Kpad,
+                  layer.scale.data_ptr(), layer.shift.data_ptr(), out.data_ptr(), out.stride(0), P, layer.N, layer.relu,
+                  ksplit, ws.data_ptr())
             return out
-    _check(_L.regnet_mlp_layer_f32(A.data_ptr(), A.stride(0), Ka, layer.W.data_ptr(), layer.Kpad,
-                                   layer.scale.data_ptr(), layer.shift.data_ptr(), out.data_ptr(), out.stride(0), P,
-                                   layer.N, layer.relu, pool_group, _stream(A)), "mlp_layer")
+    _call("regnet_mlp_layer_f32", A, A.data_ptr(), A.stride(0), Ka, layer.W.data_ptr(), layer.Kpad, layer.scale.data_ptr(),
+          layer.shift.data_ptr(), out.data_ptr(), out.stride(0), P, layer.N, layer.relu, pool_group)
     return out
 
 
@@ -217,30 +191,26 @@ def _strided3(t):
     return (None, 0, 0, 0, 0) if t is None else (t.data_ptr(),) + tuple(t.stride()) + (t.size(1),)
 
 
-@_on_tensor_device
 def sa_layer1(feature, xyz, nbr, ctr, layer, B, M, group):
     """Gather-fused first SA layer.  feature (B,Cf,N) any strides or None; xyz (B,3,N) any strides."""
     out = torch.empty((B * M * group, layer.N), dtype=torch.float32, device=xyz.device)
     fptr, fb, fc, fn, Cf = _strided3(feature)
-    _check(_L.regnet_sa_layer1_f32(fptr, fb, fn, fc, Cf, xyz.data_ptr(), *xyz.stride(), nbr.data_ptr(), ctr.data_ptr(),
-                                   B, M, group, layer.W.data_ptr(), layer.Kpad, layer.scale.data_ptr(),
-                                   layer.shift.data_ptr(), out.data_ptr(), out.stride(0), layer.N, layer.relu,
-                                   _stream(xyz)), "sa_layer1")
+    _call("regnet_sa_layer1_f32", xyz, fptr, fb, fn, fc, Cf, xyz.data_ptr(), *xyz.stride(), nbr.data_ptr(), ctr.data_ptr(),
+          B, M, group, layer.W.data_ptr(), layer.Kpad, layer.scale.data_ptr(), layer.shift.data_ptr(), out.data_ptr(),
+          out.stride(0), layer.N, layer.relu)
     return out
 
 
-@_on_tensor_device
 def sa_layer12(feature, xyz, nbr, ctr, first, layer, B, M, group, pool_group=0):
     """Gather + layer 1 (VALU, inside the operand load) + layer 2 (MFMA) of a narrow-input SA block."""
     P = B * M * group
     rows = P // pool_group if pool_group else P
     out = torch.empty((rows, layer.N), dtype=torch.float32, device=xyz.device)
     fptr, fb, fc, fn, Cf = _strided3(feature)
-    _check(_L.regnet_sa_layer12_f32(fptr, fb, fn, fc, Cf, xyz.data_ptr(), *xyz.stride(), nbr.data_ptr(),
-                                    ctr.data_ptr(), B, M, group, first.W8.data_ptr(), first.scale.data_ptr(),
-                                    first.shift.data_ptr(), first.N, layer.W.data_ptr(), layer.Kpad,
-                                    layer.scale.data_ptr(), layer.shift.data_ptr(), out.data_ptr(), out.stride(0),
-                                    layer.N, layer.relu, pool_group, _stream(xyz)), "sa_layer12")
+    _call("regnet_sa_layer12_f32", xyz, fptr, fb, fn, fc, Cf, xyz.data_ptr(), *xyz.stride(), nbr.data_ptr(),
+          ctr.data_ptr(), B, M, group, first.W8.data_ptr(), first.scale.data_ptr(), first.shift.data_ptr(), first.N,
+          layer.W.data_ptr(), layer.Kpad, layer.scale.data_ptr(), layer.shift.data_ptr(), out.data_ptr(), out.stride(0),
+          layer.N, layer.relu, pool_group)
     return out
 
 
@@ -257,7 +227,6 @@ def _premul_layers(first, Cf):
     return _derived(first, "premul", build)
 
 
-@_on_tensor_device
 def pack_rows(feature, xyz, width, mu=None):
     """Channels-last rows [feature | xyz - mu | 0] of every point: feature (B,Cf,N) or None, xyz (B,3,N), mu (B,3,1) or None
     -> (B*N, width)."""
@@ -267,22 +236,19 @@ def pack_rows(feature, xyz, width, mu=None):
     if mu is not None:
         mu = mu.reshape(B, 3)
         mu = mu if mu.is_contiguous() else mu.contiguous()
-    _check(_L.regnet_pack_rows_centred_f32(fptr, fb, fc, fn, Cf, xyz.data_ptr(), *xyz.stride(),
-                                           None if mu is None else mu.data_ptr(), B, N, width, out.data_ptr(),
-                                           _stream(xyz)), "pack_rows")
+    _call("regnet_pack_rows_centred_f32", xyz, fptr, fb, fc, fn, Cf, xyz.data_ptr(), *xyz.stride(),
+          None if mu is None else mu.data_ptr(), B, N, width, out.data_ptr())
     return out
 
 
-@_on_tensor_device
 def sa_premul_layer(U, V, nbr, layer, B, Nsrc, M, group, pool_group=0):
     """Layer 2 of a set-abstraction block over pre-multiplied layer-1 rows: relu(U[nbr] - V[centre]) . W."""
     P = B * M * group
     rows = P // pool_group if pool_group else P
     out = torch.empty((rows, layer.N), dtype=torch.float32, device=U.device)
-    _check(_L.regnet_sa_premul_layer_f32(U.data_ptr(), U.stride(0), V.data_ptr(), V.stride(0), U.size(1),
-                                         nbr.data_ptr(), B, Nsrc, M, group, layer.W.data_ptr(), layer.Kpad,
-                                         layer.scale.data_ptr(), layer.shift.data_ptr(), out.data_ptr(),
-                                         out.stride(0), layer.N, layer.relu, pool_group, _stream(U)), "sa_premul_layer")
+    _call("regnet_sa_premul_layer_f32", U, U.data_ptr(), U.stride(0), V.data_ptr(), V.stride(0), U.size(1),
+          nbr.data_ptr(), B, Nsrc, M, group, layer.W.data_ptr(), layer.Kpad, layer.scale.data_ptr(),
+          layer.shift.data_ptr(), out.data_ptr(), out.stride(0), layer.N, layer.relu, pool_group)
     return out
 
 
@@ -378,7 +344,6 @@ def chain3_pair_order(count):
 SPLIT_PRODUCTS = False
 
 
-@_on_tensor_device
 def sa_chain3_split(feature, xyz, nbr, ctr, l1, l2, l3, B, M, group, count=None, order=None):
     """``sa_chain3`` by ``regnet_sa_chain3_split_f32``; the weights' bf16 pieces are built by the kernel's first launch on
     a layer pack (both layers are of the same stack pack: the planes are kept on ``l3``)."""
@@ -389,16 +354,14 @@ def sa_chain3_split(feature, xyz, nbr, ctr, l1, l2, l3, B, M, group, count=None,
     if build:
         planes = l3.derived["split_planes"] = torch.empty((_L.regnet_sa_chain3_split_plane_bytes(l3.N),), dtype=torch.uint8,
                                                           device=xyz.device)
-    _check(_L.regnet_sa_chain3_split_f32(fptr, fb, fn, fc, Cf, xyz.data_ptr(), *xyz.stride(), nbr.data_ptr(), ctr.data_ptr(),
-                                         None if count is None else count.data_ptr(), None if order is None else order.data_ptr(), B, M,
-                                         group, l1.W8.data_ptr(), l1.scale.data_ptr(), l1.shift.data_ptr(), l2.W.data_ptr(), l2.Kpad,
-                                         l2.scale.data_ptr(), l2.shift.data_ptr(), l3.W.data_ptr(), l3.Kpad, l3.scale.data_ptr(),
-                                         l3.shift.data_ptr(), l3.N, l3.relu, planes.data_ptr(), int(build), out.data_ptr(),
-                                         out.stride(0), _tickets(xyz.device).data_ptr(), _stream(xyz)), "sa_chain3_split")
+    _call("regnet_sa_chain3_split_f32", xyz, fptr, fb, fn, fc, Cf, xyz.data_ptr(), *xyz.stride(), nbr.data_ptr(), ctr.data_ptr(),
+          None if count is None else count.data_ptr(), None if order is None else order.data_ptr(), B, M, group,
+          l1.W8.data_ptr(), l1.scale.data_ptr(), l1.shift.data_ptr(), l2.W.data_ptr(), l2.Kpad, l2.scale.data_ptr(),
+          l2.shift.data_ptr(), l3.W.data_ptr(), l3.Kpad, l3.scale.data_ptr(), l3.shift.data_ptr(), l3.N, l3.relu,
+          planes.data_ptr(), int(build), out.data_ptr(), out.stride(0), _tickets(xyz.device).data_ptr())
     return out
 
 
-@_on_tensor_device
 def sa_chain3(feature, xyz, nbr, ctr, l1, l2, l3, B, M, group, count=None, order=None):
     """Whole narrow-input SA block (gather, three layers, max over the neighbours) in one kernel; -> (B*M, C3).
     ``count`` (B,M) int64: members per neighbourhood (half the work for those with <= 32); ``order`` (B*M,) int64:
@@ -408,16 +371,14 @@ def sa_chain3(feature, xyz, nbr, ctr, l1, l2, l3, B, M, group, count=None, order
         return sa_chain3_split(feature, xyz, nbr, ctr, l1, l2, l3, B, M, group, count, order)
     out = torch.empty((B * M, l3.N), dtype=torch.float32, device=xyz.device)
     fptr, fb, fc, fn, Cf = _strided3(feature)
-    _check(_L.regnet_sa_chain3_f32(fptr, fb, fn, fc, Cf, xyz.data_ptr(), *xyz.stride(), nbr.data_ptr(), ctr.data_ptr(),
-                                   None if count is None else count.data_ptr(),
-                                   None if order is None else order.data_ptr(), B, M, group, l1.W8.data_ptr(), l1.scale.data_ptr(), l1.shift.data_ptr(), l1.N,
-                                   l2.W.data_ptr(), l2.Kpad, l2.scale.data_ptr(), l2.shift.data_ptr(), l2.N,
-                                   l3.W.data_ptr(), l3.Kpad, l3.scale.data_ptr(), l3.shift.data_ptr(), l3.N, l3.relu,
-                                   out.data_ptr(), out.stride(0), _stream(xyz)), "sa_chain3")
+    _call("regnet_sa_chain3_f32", xyz, fptr, fb, fn, fc, Cf, xyz.data_ptr(), *xyz.stride(), nbr.data_ptr(), ctr.data_ptr(),
+          None if count is None else count.data_ptr(), None if order is None else order.data_ptr(), B, M, group,
+          l1.W8.data_ptr(), l1.scale.data_ptr(), l1.shift.data_ptr(), l1.N,
+          l2.W.data_ptr(), l2.Kpad, l2.scale.data_ptr(), l2.shift.data_ptr(), l2.N,
+          l3.W.data_ptr(), l3.Kpad, l3.scale.data_ptr(), l3.shift.data_ptr(), l3.N, l3.relu, out.data_ptr(), out.stride(0))
     return out
 
 
-@_on_tensor_device
 def interp_concat(sparse_cl, idx, dist2, eps, dense_feature, B, Nd):
     """sparse_cl: (B,Ns,Cs) channels-last contiguous; dense_feature (B,Cd,Nd) any strides or None.
     Returns the (B*Nd, round_up(Cs+Cd,4)) channels-last operand of the first FP layer and its valid width."""
@@ -426,9 +387,8 @@ def interp_concat(sparse_cl, idx, dist2, eps, dense_feature, B, Nd):
     width = _round_up(Cs + Cd, 4)
     out = torch.empty((B * Nd, width), dtype=torch.float32, device=sparse_cl.device)
     dptr, db, dc, dn, _ = _strided3(dense_feature)
-    _check(_L.regnet_interp_concat_f32(sparse_cl.data_ptr(), sparse_cl.stride(0), sparse_cl.stride(1), Cs,
-                                       idx.data_ptr(), dist2.data_ptr(), float(eps), dptr, db, dn, dc, Cd, B, Nd,
-                                       out.data_ptr(), out.stride(0), width, _stream(sparse_cl)), "interp_concat")
+    _call("regnet_interp_concat_f32", sparse_cl, sparse_cl.data_ptr(), sparse_cl.stride(0), sparse_cl.stride(1), Cs,
+          idx.data_ptr(), dist2.data_ptr(), float(eps), dptr, db, dn, dc, Cd, B, Nd, out.data_ptr(), out.stride(0), width)
     return out, width
 
 
@@ -461,7 +421,6 @@ def _interp_tables(first, wd4):
     return _derived(first, "interp_tables", build)
 
 
-@_on_tensor_device
 def interp_affine(Ys, idx, dist2, eps, Yd, dense_small, wd4, layer, B, Ns, Nd):
     """relu(scale * (sum_k w_k Ys[idx_k] + Yd + Wd4 . dense_small) + shift): the 3-NN interpolation of
     pre-multiplied sparse rows.  ``dense_small``: (B,Cd<=4,Nd) any strides, or None."""
@@ -469,11 +428,9 @@ def interp_affine(Ys, idx, dist2, eps, Yd, dense_small, wd4, layer, B, Ns, Nd):
     out = torch.empty((B * Nd, C), dtype=torch.float32, device=Ys.device)
     dptr, db, dc, dn, Cd = _strided3(dense_small)
     wptr = None if dense_small is None else wd4.data_ptr()
-    _check(_L.regnet_interp_affine_f32(Ys.data_ptr(), Ns * Ys.stride(0), Ys.stride(0), idx.data_ptr(),
-                                       dist2.data_ptr(), float(eps), None if Yd is None else Yd.data_ptr(),
-                                       0 if Yd is None else Yd.stride(0), dptr, db, dn, dc, Cd, wptr,
-                                       layer.scale.data_ptr(), layer.shift.data_ptr(), layer.relu, B, Nd, C,
-                                       out.data_ptr(), out.stride(0), _stream(Ys)), "interp_affine")
+    _call("regnet_interp_affine_f32", Ys, Ys.data_ptr(), Ns * Ys.stride(0), Ys.stride(0), idx.data_ptr(), dist2.data_ptr(),
+          float(eps), None if Yd is None else Yd.data_ptr(), 0 if Yd is None else Yd.stride(0), dptr, db, dn, dc, Cd, wptr,
+          layer.scale.data_ptr(), layer.shift.data_ptr(), layer.relu, B, Nd, C, out.data_ptr(), out.stride(0))
     return out
 
 
@@ -490,12 +447,11 @@ def _packed_head(seg):
     return _cached(seg, "score_head", _signature(seg.conv_score) + _signature(seg.bn_score), build)
 
 
-@_on_tensor_device
 def score_head(x, seg, P):
     w, bias, bn_scale, bn_shift = _packed_head(seg)
     score = torch.empty((P,), dtype=torch.float32, device=x.device)
-    _check(_L.regnet_score_head_f32(x.data_ptr(), x.stride(0), w.numel(), w.data_ptr(), bias, bn_scale, bn_shift,
-                                    score.data_ptr(), P, _stream(x)), "score_head")
+    _call("regnet_score_head_f32", x, x.data_ptr(), x.stride(0), w.numel(), w.data_ptr(), bias, bn_scale, bn_shift,
+          score.data_ptr(), P)
     return score
 
 
@@ -749,13 +705,11 @@ def _packed_premul_chain(module, layers, C):
 
 def _premul_chain(C, U, V, nbr, module, layers, B, Nsrc, M):
     stream, affine = _packed_premul_chain(module, layers, C)
-    entry, name = ((_L.regnet_sa_premul_chain_f32, "sa_premul_chain") if C == 256 else
-                   (_L.regnet_sa3_premul_chain_f32, "sa3_premul_chain"))
     out = torch.empty((B * M, 2 * C), dtype=torch.float32, device=U.device)
     ticket = _tickets(U.device)
-    _check(entry(U.data_ptr(), U.stride(0), V.data_ptr(), V.stride(0), nbr.data_ptr(), B, Nsrc, M, stream.data_ptr(),
-                 stream.numel() // 8192, affine.data_ptr(), affine.numel(), layers[2].relu, out.data_ptr(), out.stride(0),
-                 ticket.data_ptr(), _stream(U)), name)
+    _call("regnet_sa_premul_chain_f32" if C == 256 else "regnet_sa3_premul_chain_f32", U, U.data_ptr(), U.stride(0),
+          V.data_ptr(), V.stride(0), nbr.data_ptr(), B, Nsrc, M, stream.data_ptr(), stream.numel() // 8192, affine.data_ptr(),
+          affine.numel(), layers[2].relu, out.data_ptr(), out.stride(0), ticket.data_ptr())
     return out
 
 
@@ -777,13 +731,11 @@ def supports_sa3_chain(layers):
             and layers[1].relu and layers[2].K == 512 and layers[2].N == 1024)
 
 
-@_on_tensor_device
 def sa_premul_chain(U, V, nbr, module, layers, B, Nsrc, M):
     """relu(U[nbr] - V[centre]) -> 256 -> 512 -> max over the 64 neighbours, one launch; -> (B*M, 512)."""
     return _premul_chain(256, U, V, nbr, module, layers, B, Nsrc, M)
 
 
-@_on_tensor_device
 def sa3_premul_chain(U, V, nbr, module, layers, B, Nsrc, M):
     """relu(U[nbr] - V[centre]) -> 512 -> 1024 -> max over the 64 neighbours, one launch; -> (B*M, 1024)."""
     return _premul_chain(512, U, V, nbr, module, layers, B, Nsrc, M)
@@ -845,7 +797,6 @@ def supports_rowchain(seg, fp_module):
     return widths == [256, 256, 256, 512, 256, 256, 128] and all(relus) and seg.mlp[0].conv.in_channels == 256
 
 
-@_on_tensor_device
 def fp_head_chain(h1, seg, fp_layers, P):
     """h1 (P, 256) -> (F (P, 256), score (P,)): FP layers 2-3 and the segmentation head in one launch."""
     stream, affine = _packed_rowchain(seg, fp_layers)
@@ -853,10 +804,9 @@ def fp_head_chain(h1, seg, fp_layers, P):
     F = torch.empty((P, 256), dtype=torch.float32, device=h1.device)
     score = torch.empty((P,), dtype=torch.float32, device=h1.device)
     ticket = _tickets(h1.device)   # work-queue head, zeroed on this stream
-    _check(_L.regnet_fp_head_chain_f32(h1.data_ptr(), h1.stride(0), stream.data_ptr(), 60, affine.data_ptr(),
-                                       affine.numel(), w.data_ptr(), bias, bn_scale, bn_shift, F.data_ptr(),
-                                       F.stride(0), score.data_ptr(), P, ticket.data_ptr(), 0, -1, _stream(h1)),
-           "fp_head_chain")
+    _call("regnet_fp_head_chain_f32", h1, h1.data_ptr(), h1.stride(0), stream.data_ptr(), 60, affine.data_ptr(),
+          affine.numel(), w.data_ptr(), bias, bn_scale, bn_shift, F.data_ptr(), F.stride(0), score.data_ptr(), P,
+          ticket.data_ptr(), 0, -1)
     return F, score
 
 
@@ -874,7 +824,6 @@ def _tail_stream(device):
     return _tail_streams[key]
 
 
-@_on_tensor_device
 def fp_head_chain_interp(Ys, idx, dist2, eps, dense_small, wd4, first, seg, fp_layers, B, Ns, Nd):
     """(Ys (B*Ns, 256) pre-multiplied sparse rows, 3-NN indices / squared distances, rgb-like skip input) -> (F, score):
     the whole last feature-propagation block + the segmentation head in one launch; h1 is never written."""
@@ -887,12 +836,11 @@ def fp_head_chain_interp(Ys, idx, dist2, eps, dense_small, wd4, first, seg, fp_l
     tickets = _tickets(Ys.device, 2)
     dptr, db, dc, dn, Cd = _strided3(dense_small)
 
-    def launch(first, count, ticket, stream_handle):
-        _check(_L.regnet_fp_head_chain_interp_f32(Ys.data_ptr(), Ns * Ys.stride(0), Ys.stride(0), idx.data_ptr(),
-                                                  dist2.data_ptr(), float(eps), dptr, db, dn, dc, Cd, tables.data_ptr(), B,
-                                                  Nd, stream.data_ptr(), 60, affine.data_ptr(), affine.numel(), w.data_ptr(),
-                                                  bias, bn_scale, bn_shift, F.data_ptr(), F.stride(0), score.data_ptr(),
-                                                  ticket.data_ptr(), first, count, stream_handle), "fp_head_chain_interp")
+    def launch(first, count, ticket, stream_handle=None):
+        _call("regnet_fp_head_chain_interp_f32", Ys, Ys.data_ptr(), Ns * Ys.stride(0), Ys.stride(0), idx.data_ptr(),
+              dist2.data_ptr(), float(eps), dptr, db, dn, dc, Cd, tables.data_ptr(), B, Nd, stream.data_ptr(), 60,
+              affine.data_ptr(), affine.numel(), w.data_ptr(), bias, bn_scale, bn_shift, F.data_ptr(), F.stride(0),
+              score.data_ptr(), ticket.data_ptr(), first, count, stream=stream_handle)
 
     # The last round of 128-row blocks is partial (8 x 25 600 rows: 1600 blocks = 6 x 256 + 64): run alone it keeps 64 CUs
     # busy for a whole pass while 192 idle (a pass costs the same however few blocks it holds).  A caller that can run
@@ -901,6 +849,8 @@ def fp_head_chain_interp(Ys, idx, dist2, eps, dense_small, wd4, first, seg, fp_l
     blocks = _L.regnet_fp_head_chain_blocks(P)
     tail = blocks % _CUS
     if TAIL_SINK is not None and blocks > _CUS and 0 < tail <= _CUS // 2:
+        # (no device context: an event binds to the device of the stream that first records it, the side stream is created
+        # for Ys.device by name)
         cur = torch.cuda.current_stream(Ys.device)
         side = _tail_stream(Ys.device)
         ready = torch.cuda.Event()
@@ -914,7 +864,7 @@ def fp_head_chain_interp(Ys, idx, dist2, eps, dense_small, wd4, first, seg, fp_l
         TAIL_SINK.append(done)
         launch(0, blocks - tail, tickets[:1], cur.cuda_stream)
     else:
-        launch(0, -1, tickets[:1], _stream(Ys))
+        launch(0, -1, tickets[:1])
     return F, score
 
 
@@ -1037,9 +987,8 @@ def _heads_chain(x, L, plan, n_a, n_b):
     arr = (ctypes.c_int64 * len(descr))(*descr)
     out_a = torch.empty((n, n_a), dtype=torch.float32, device=x.device)
     out_b = torch.empty((n, n_b), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _check(_L.regnet_heads_chain_f32(x.data_ptr(), x.stride(0), x.shape[1], n, ctypes.addressof(arr), len(plan),
-                                         out_a.data_ptr(), n_a, out_b.data_ptr(), n_b, _stream(x)), "heads_chain")
+    _call("regnet_heads_chain_f32", x, x.data_ptr(), x.stride(0), x.shape[1], n, ctypes.addressof(arr), len(plan),
+          out_a.data_ptr(), n_a, out_b.data_ptr(), n_b)
     return out_a, out_b
 
 
@@ -1063,9 +1012,8 @@ def _heads_tree(x, L, tree, tails, n_a, n_b):
     arr = (ctypes.c_int64 * len(descr))(*descr)
     out_a = torch.empty((n, n_a), dtype=torch.float32, device=x.device)
     out_b = torch.empty((n, n_b), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _check(_L.regnet_heads_tree_f32(x.data_ptr(), x.stride(0), x.shape[1], n, ctypes.addressof(arr), len(tails),
-                                        out_a.data_ptr(), n_a, out_b.data_ptr(), n_b, _stream(x)), "heads_tree")
+    _call("regnet_heads_tree_f32", x, x.data_ptr(), x.stride(0), x.shape[1], n, ctypes.addressof(arr), len(tails),
+          out_a.data_ptr(), n_a, out_b.data_ptr(), n_b)
     return out_a, out_b
 
 

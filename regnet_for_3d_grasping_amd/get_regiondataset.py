@@ -147,11 +147,9 @@ def _get_center_grasp(center_pc_index, center_pc, data_paths, depth, use_theta=T
             out = torch.empty((B, Nc, 10), dtype=torch.float32, device=dev)
             wide_row = torch.empty((B * Nc,), dtype=torch.int32, device=dev)
             xyz = center_pc if center_pc.dtype == torch.float32 and center_pc.stride(2) == 1 else center_pc.float().contiguous()
-            with torch.cuda.device(dev):
-                _lib.check(_lib.lib.regnet_label_match_f32(
-                    packed.data_ptr(), packed.data_ptr() + 4 * B * Gmax * 19, Gmax, xyz.data_ptr(), xyz.stride(0), xyz.stride(1),
-                    B, Nc, float(np.float32(depth)), float(NO_GRASP_SQ_DISTANCE), out.data_ptr(), wide_row.data_ptr(),
-                    torch.cuda.current_stream(dev).cuda_stream), "label_match")
+            _lib.call("regnet_label_match_f32", xyz, packed.data_ptr(), packed.data_ptr() + 4 * B * Gmax * 19, Gmax, xyz.data_ptr(),
+                      xyz.stride(0), xyz.stride(1), B, Nc, float(np.float32(depth)), float(NO_GRASP_SQ_DISTANCE), out.data_ptr(),
+                      wide_row.data_ptr())
             def finish():
                 return out if bool(wide_row.cpu().numpy().any()) else out[:, :, :8].contiguous()
 

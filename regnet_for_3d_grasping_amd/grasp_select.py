@@ -93,26 +93,24 @@ def nms_ranked(center, frame, order, translation_thresh=0.03, rotation_thresh_de
     dev = center.device
     T2, C = thresholds(translation_thresh, rotation_thresh_deg)
     k = 0 if top_k is None else int(top_k)
-    with torch.cuda.device(dev):
-        if keep is None:
-            keep = torch.empty((n,), dtype=torch.int64, device=dev)
-        if count is None:
-            count = torch.empty((1,), dtype=torch.int32, device=dev)
-        if n == 0:
-            count.zero_()
-            return keep, count
-        need = workspace_bytes(n)
-        if need < 0:
-            _check(-3, "grasp_nms (at most %d grasps)" % MAX_GRASPS)
-        if workspace is None:
-            workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
-        if keep.dtype != torch.int64 or keep.numel() != n or not keep.is_contiguous() or count.dtype != torch.int32 \
-                or count.numel() != 1 or workspace.dtype != torch.uint8 or workspace.numel() < need \
-                or not workspace.is_contiguous():
-            raise RuntimeError("nms_ranked: keep (n) int64, count (1) int32, workspace (>= %d) uint8 expected" % need)
-        _check(_L.regnet_grasp_nms_f32(center.data_ptr(), frame.data_ptr(), order.data_ptr(), n, T2, C, 1 if symmetric else 0,
-                                       k, keep.data_ptr(), count.data_ptr(), workspace.data_ptr(),
-                                       torch.cuda.current_stream(dev).cuda_stream), "grasp_nms")
+    if keep is None:
+        keep = torch.empty((n,), dtype=torch.int64, device=dev)
+    if count is None:
+        count = torch.empty((1,), dtype=torch.int32, device=dev)
+    if n == 0:
+        count.zero_()
+        return keep, count
+    need = workspace_bytes(n)
+    if need < 0:
+        _check(-3, "grasp_nms (at most %d grasps)" % MAX_GRASPS)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    if keep.dtype != torch.int64 or keep.numel() != n or not keep.is_contiguous() or count.dtype != torch.int32 \
+            or count.numel() != 1 or workspace.dtype != torch.uint8 or workspace.numel() < need \
+            or not workspace.is_contiguous():
+        raise RuntimeError("nms_ranked: keep (n) int64, count (1) int32, workspace (>= %d) uint8 expected" % need)
+    _lib.call("regnet_grasp_nms_f32", center, center.data_ptr(), frame.data_ptr(), order.data_ptr(), n, T2, C,
+              1 if symmetric else 0, k, keep.data_ptr(), count.data_ptr(), workspace.data_ptr())
     return keep, count
 
 
@@ -122,11 +120,10 @@ def pose_nms_device(grasp, translation_thresh=0.03, rotation_thresh_deg=30.0, to
     rank order followed by -1, count (1) int32, both on the device.  No host read: callable inside a captured graph."""
     _grasp_ok(grasp)
     g8 = grasp[:, :8].contiguous()
-    with torch.cuda.device(grasp.device):
-        frame, center = grasp_frames(g8)
-        order = rank_order(g8[:, 7])
-        return nms_ranked(center, frame, order, translation_thresh, rotation_thresh_deg, top_k, symmetric, keep, count,
-                          workspace)
+    frame, center = grasp_frames(g8)
+    order = rank_order(g8[:, 7])
+    return nms_ranked(center, frame, order, translation_thresh, rotation_thresh_deg, top_k, symmetric, keep, count,
+                      workspace)
 
 
 def pose_nms(grasp, translation_thresh=0.03, rotation_thresh_deg=30.0, top_k=None, symmetric=True, return_index=False):

@@ -19,10 +19,6 @@ ENABLED = True     # module switch (bench.py --set heads_train.ENABLED=0 / tests
 CALLS = {"forward": 0, "backward": 0}
 
 
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def _layers_twostage(m):
     """(conv, bn, parent, relu) in execution order; parent -1 = the head's input."""
     return [(m.conv, m.bn, -1, True),
@@ -68,7 +64,6 @@ class _HeadTree(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, meta, *params):
         from . import _lib
-        L = _lib.lib
         tree, buffers = meta
         nl = len(tree)
         R, K0 = x.shape
@@ -92,24 +87,23 @@ class _HeadTree(torch.autograd.Function):
         ws = torch.empty((off,), dtype=torch.float32, device=x.device)
         base = ws.data_ptr()
         leaves, y_ptr = [], []
-        stream = _stream(x)
-        with torch.cuda.device(x.device):
-            for l, (K, N) in enumerate(dims):
-                parent, relu = tree[l]
-                W, b, gamma, beta = params[4 * l: 4 * l + 4]
-                rm, rv, nbt, momentum, eps = buffers[l]
-                if is_parent[l]:
-                    yp = base + 4 * y_off[l]
-                else:
-                    out = torch.empty((R, N), dtype=torch.float32, device=x.device)
-                    leaves.append(out)
-                    yp = out.data_ptr()
-                y_ptr.append(yp)
-                src = x.data_ptr() if parent < 0 else y_ptr[parent]
-                _lib.check(L.regnet_head_layer_train_fwd_f32(
-                    src, K, W.data_ptr(), b.data_ptr() if b is not None else None, gamma.data_ptr(), beta.data_ptr(),
-                    rm.data_ptr(), rv.data_ptr(), nbt.data_ptr() if nbt is not None else None, momentum, eps, R, K, N,
-                    1 if relu else 0, base + 4 * xh_off[l], yp, base + 4 * inv_off[l], stream), "head_layer_train_fwd")
+        stream = torch.cuda.current_stream(x.device).cuda_stream      # looked up once for all the layers' launches
+        for l, (K, N) in enumerate(dims):
+            parent, relu = tree[l]
+            W, b, gamma, beta = params[4 * l: 4 * l + 4]
+            rm, rv, nbt, momentum, eps = buffers[l]
+            if is_parent[l]:
+                yp = base + 4 * y_off[l]
+            else:
+                out = torch.empty((R, N), dtype=torch.float32, device=x.device)
+                leaves.append(out)
+                yp = out.data_ptr()
+            y_ptr.append(yp)
+            src = x.data_ptr() if parent < 0 else y_ptr[parent]
+            _lib.call("regnet_head_layer_train_fwd_f32", x,
+                      src, K, W.data_ptr(), b.data_ptr() if b is not None else None, gamma.data_ptr(), beta.data_ptr(),
+                      rm.data_ptr(), rv.data_ptr(), nbt.data_ptr() if nbt is not None else None, momentum, eps, R, K, N,
+                      1 if relu else 0, base + 4 * xh_off[l], yp, base + 4 * inv_off[l], stream=stream)
         ctx.save_for_backward(x, ws, *params)
         ctx.layout = (tree, dims, is_parent, xh_off, y_off, inv_off)
         CALLS["forward"] += 1
@@ -118,7 +112,6 @@ class _HeadTree(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *grads):
         from . import _lib
-        L = _lib.lib
         x, ws = ctx.saved_tensors[:2]
         params = ctx.saved_tensors[2:]
         tree, dims, is_parent, xh_off, y_off, inv_off = ctx.layout
@@ -143,32 +136,31 @@ class _HeadTree(torch.autograd.Function):
                 leaf_grads[l] = g.contiguous() if g is not None else torch.zeros((R, dims[l][1]), dtype=torch.float32, device=dev)
         pgrads = [None] * (4 * nl)
         written = set()               # inner layers (and -1 = x) whose gradient buffer already holds a branch's contribution
-        stream = _stream(x)
-        with torch.cuda.device(dev):
-            for l in range(nl - 1, -1, -1):
-                K, N = dims[l]
-                parent, relu = tree[l]
-                W, b, gamma, beta = params[4 * l: 4 * l + 4]
-                dW = torch.empty_like(W)
-                db = torch.empty((N,), dtype=torch.float32, device=dev) if b is not None else None
-                dgamma = torch.empty((N,), dtype=torch.float32, device=dev)
-                dbeta = torch.empty((N,), dtype=torch.float32, device=dev)
-                if is_parent[l]:
-                    dyp, yp = gbase + 4 * dy_off[l], base + 4 * y_off[l]
-                else:
-                    dyp, yp = leaf_grads[l].data_ptr(), None          # leaves have no ReLU: Y is not read
-                    if relu:
-                        raise RuntimeError("heads_train: a leaf layer with ReLU needs its output saved")
-                if parent >= 0:
-                    dxp, srcp = gbase + 4 * dy_off[parent], base + 4 * y_off[parent]
-                else:
-                    dxp, srcp = (dx.data_ptr() if dx is not None else None), x.data_ptr()
-                _lib.check(L.regnet_head_layer_train_bwd_f32(
-                    dyp, N, yp, base + 4 * xh_off[l], gamma.data_ptr(), base + 4 * inv_off[l], srcp, K, W.data_ptr(), R, K, N,
-                    1 if relu else 0, gbase, dW.data_ptr(), db.data_ptr() if db is not None else None, dgamma.data_ptr(),
-                    dbeta.data_ptr(), dxp, K, 1 if parent in written else 0, stream), "head_layer_train_bwd")
-                written.add(parent)
-                pgrads[4 * l: 4 * l + 4] = [dW, db, dgamma, dbeta]
+        stream = torch.cuda.current_stream(x.device).cuda_stream      # looked up once for all the layers' launches
+        for l in range(nl - 1, -1, -1):
+            K, N = dims[l]
+            parent, relu = tree[l]
+            W, b, gamma, beta = params[4 * l: 4 * l + 4]
+            dW = torch.empty_like(W)
+            db = torch.empty((N,), dtype=torch.float32, device=dev) if b is not None else None
+            dgamma = torch.empty((N,), dtype=torch.float32, device=dev)
+            dbeta = torch.empty((N,), dtype=torch.float32, device=dev)
+            if is_parent[l]:
+                dyp, yp = gbase + 4 * dy_off[l], base + 4 * y_off[l]
+            else:
+                dyp, yp = leaf_grads[l].data_ptr(), None          # leaves have no ReLU: Y is not read
+                if relu:
+                    raise RuntimeError("heads_train: a leaf layer with ReLU needs its output saved")
+            if parent >= 0:
+                dxp, srcp = gbase + 4 * dy_off[parent], base + 4 * y_off[parent]
+            else:
+                dxp, srcp = (dx.data_ptr() if dx is not None else None), x.data_ptr()
+            _lib.call("regnet_head_layer_train_bwd_f32", x,
+                      dyp, N, yp, base + 4 * xh_off[l], gamma.data_ptr(), base + 4 * inv_off[l], srcp, K, W.data_ptr(), R, K, N,
+                      1 if relu else 0, gbase, dW.data_ptr(), db.data_ptr() if db is not None else None, dgamma.data_ptr(),
+                      dbeta.data_ptr(), dxp, K, 1 if parent in written else 0, stream=stream)
+            written.add(parent)
+            pgrads[4 * l: 4 * l + 4] = [dW, db, dgamma, dbeta]
         CALLS["backward"] += 1
         return (dx, None) + tuple(pgrads)
 

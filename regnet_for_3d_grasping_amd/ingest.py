@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _lib
 
-_check = _lib.check
+_call = _lib.call
 _L = _lib.lib
 
 NUM_POINTS = 25600                                   # test.py:61
@@ -230,17 +230,15 @@ def crop_frame(xyz, rgb, transform, bounds=DEFAULT_BOUNDS, drop_nonfinite=True, 
     M, dev = int(xyz.shape[0]), xyz.device
     if M > MAX_FRAME_POINTS:
         raise ValueError("frames of more than 2^21 points are not supported")
-    with torch.cuda.device(dev):
-        kept64 = torch.empty((M, 3), dtype=torch.float64, device=dev)
-        kept32 = torch.empty((M, 3), dtype=torch.float32, device=dev)
-        kept_rgb = torch.empty((M, 3), dtype=torch.float64, device=dev)
-        source = torch.empty((M,), dtype=torch.int32, device=dev) if with_source else None
-        count = torch.empty((1,), dtype=torch.int32, device=dev)
-        ws = torch.empty((max(int(_L.regnet_ingest_crop_workspace_bytes(M)), 8),), dtype=torch.uint8, device=dev)
-        crop = _L.regnet_ingest_crop_f64 if xyz.dtype == torch.float64 else _L.regnet_ingest_crop_f32
-        _check(crop(xyz.data_ptr(), rgb.data_ptr(), M, T.ctypes.data, b.ctypes.data, 1 if drop_nonfinite else 0,
-                    kept64.data_ptr(), kept32.data_ptr(), kept_rgb.data_ptr(), source.data_ptr() if with_source else None,
-                    count.data_ptr(), ws.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "ingest_crop")
+    kept64 = torch.empty((M, 3), dtype=torch.float64, device=dev)
+    kept32 = torch.empty((M, 3), dtype=torch.float32, device=dev)
+    kept_rgb = torch.empty((M, 3), dtype=torch.float64, device=dev)
+    source = torch.empty((M,), dtype=torch.int32, device=dev) if with_source else None
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+    ws = torch.empty((max(int(_L.regnet_ingest_crop_workspace_bytes(M)), 8),), dtype=torch.uint8, device=dev)
+    _call("regnet_ingest_crop_f64" if xyz.dtype == torch.float64 else "regnet_ingest_crop_f32", xyz, xyz.data_ptr(),
+          rgb.data_ptr(), M, T.ctypes.data, b.ctypes.data, 1 if drop_nonfinite else 0, kept64.data_ptr(), kept32.data_ptr(),
+          kept_rgb.data_ptr(), source.data_ptr() if with_source else None, count.data_ptr(), ws.data_ptr())
     return kept64, kept32, kept_rgb, count, source
 
 
@@ -249,14 +247,12 @@ def _resample(xyz32, rgb, count, num_points):
     import torch
     from . import np_random
     M, N, dev = int(xyz32.shape[0]), int(num_points), xyz32.device
-    with torch.cuda.device(dev):
-        bad = torch.zeros((1,), dtype=torch.int32, device=dev)
-        rand3 = np_random.rand_device(3, dev)                                    # utils.noise_color draws first
-        pick = np_random.choice_rows_device(count, N, 0, max(M, 1))[0].view(N)
-        pc = torch.empty((N, 6), dtype=torch.float32, device=dev)
-        _check(_L.regnet_ingest_resample_f32(xyz32.data_ptr(), rgb.data_ptr(), 1 if rgb.dtype == torch.float64 else 0,
-                                             count.data_ptr(), M, pick.data_ptr(), N, rand3.data_ptr(), pc.data_ptr(),
-                                             bad.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "ingest_resample")
+    bad = torch.zeros((1,), dtype=torch.int32, device=dev)
+    rand3 = np_random.rand_device(3, dev)                                    # utils.noise_color draws first
+    pick = np_random.choice_rows_device(count, N, 0, max(M, 1))[0].view(N)
+    pc = torch.empty((N, 6), dtype=torch.float32, device=dev)
+    _call("regnet_ingest_resample_f32", xyz32, xyz32.data_ptr(), rgb.data_ptr(), 1 if rgb.dtype == torch.float64 else 0,
+          count.data_ptr(), M, pick.data_ptr(), N, rand3.data_ptr(), pc.data_ptr(), bad.data_ptr())
     return pc.view(1, N, 6), bad
 
 
@@ -295,7 +291,6 @@ def ingest_record(path_or_dict, num_points=NUM_POINTS, device="cuda:0"):
     color = _to_device(np.asarray(data["view_cloud_color"]).astype(np.float32), dev)
     if cloud.dim() != 2 or cloud.shape[1] != 3 or tuple(color.shape) != tuple(cloud.shape):
         raise ValueError("view_cloud and view_cloud_color must both be (M, 3)")
-    with torch.cuda.device(cloud.device):
-        count = torch.full((1,), int(cloud.shape[0]), dtype=torch.int32, device=cloud.device)
+    count = torch.full((1,), int(cloud.shape[0]), dtype=torch.int32, device=cloud.device)
     pc, bad = _resample(cloud, color, count, num_points)
     return Frame(pc, cloud, color, cloud, count, bad)

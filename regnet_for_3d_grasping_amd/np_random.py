@@ -109,12 +109,11 @@ class _DeviceStream:
             self.ahead = False
             self.status = []
             return
-        with torch.cuda.device(self.device):
-            if self.last_event is not None:
-                torch.cuda.current_stream(self.device).wait_event(self.last_event)
-            key = self.key.cpu().numpy().view(np.uint32).copy()      # synchronising copies
-            pos = int(self.pos.cpu())
-            bad = [w for w in self.status if int(w[-1].cpu()) != 0]
+        if self.last_event is not None:
+            torch.cuda.current_stream(self.device).wait_event(self.last_event)
+        key = self.key.cpu().numpy().view(np.uint32).copy()      # synchronising copies
+        pos = int(self.pos.cpu())
+        bad = [w for w in self.status if int(w[-1].cpu()) != 0]
         self.status = []
         if bad:
             raise RuntimeError("device numpy draws: a candidate count exceeded the max_count the workspace was sized for")
@@ -147,20 +146,18 @@ def choice_rows_device(counts, size, mode, max_count):
     counts = counts.contiguous()
     rows = counts.numel()
     st = _stream_for(counts.device)
-    with torch.cuda.device(counts.device):
-        out = torch.empty((rows, int(size)), dtype=torch.int64, device=counts.device)
-        valid = torch.empty((rows,), dtype=torch.uint8, device=counts.device)
-        if rows:
-            ws = torch.empty((_L.regnet_np_choice_rows_dev_workspace_ints(rows, int(max_count)),), dtype=torch.int32,
-                             device=counts.device)
-            cur = st.acquire()
-            _check(_L.regnet_np_choice_rows_dev(st.key.data_ptr(), st.pos.data_ptr(), counts.data_ptr(), rows, int(size),
-                                                int(max_count), int(mode), out.data_ptr(), valid.data_ptr(),
-                                                ws.data_ptr(), cur.cuda_stream), "np_choice_rows_dev")
-            st.release(cur)
-            st.status.append(ws)
-            if len(st.status) > 64:      # bound what an unflushed (deferred) run keeps alive
-                st.status = st.status[-64:]
+    out = torch.empty((rows, int(size)), dtype=torch.int64, device=counts.device)
+    valid = torch.empty((rows,), dtype=torch.uint8, device=counts.device)
+    if rows:
+        ws = torch.empty((_L.regnet_np_choice_rows_dev_workspace_ints(rows, int(max_count)),), dtype=torch.int32,
+                         device=counts.device)
+        cur = st.acquire()
+        _lib.call("regnet_np_choice_rows_dev", counts, st.key.data_ptr(), st.pos.data_ptr(), counts.data_ptr(), rows, int(size),
+                  int(max_count), int(mode), out.data_ptr(), valid.data_ptr(), ws.data_ptr(), stream=cur.cuda_stream)
+        st.release(cur)
+        st.status.append(ws)
+        if len(st.status) > 64:      # bound what an unflushed (deferred) run keeps alive
+            st.status = st.status[-64:]
     return out.view(tuple(counts.shape) + (int(size),)), valid.bool().view(counts.shape)
 
 
@@ -168,13 +165,12 @@ def rand_device(count, device):
     """``np.random.rand(count)`` drawn from the device-resident generator -> float64 GPU tensor (no synchronisation)."""
     import torch
     st = _stream_for(device)
-    with torch.cuda.device(st.device):
-        out = torch.empty((int(count),), dtype=torch.float64, device=st.device)
-        if count:
-            cur = st.acquire()
-            _check(_L.regnet_np_rand_doubles_dev(st.key.data_ptr(), st.pos.data_ptr(), int(count), out.data_ptr(),
-                                                 cur.cuda_stream), "np_rand_doubles_dev")
-            st.release(cur)
+    out = torch.empty((int(count),), dtype=torch.float64, device=st.device)
+    if count:
+        cur = st.acquire()
+        _lib.call("regnet_np_rand_doubles_dev", out, st.key.data_ptr(), st.pos.data_ptr(), int(count), out.data_ptr(),
+                  stream=cur.cuda_stream)
+        st.release(cur)
     return out
 
 

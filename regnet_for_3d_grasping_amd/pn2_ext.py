@@ -19,17 +19,13 @@ import torch
 
 from . import _lib, determinism
 
-_check = _lib.check
+_call = _lib.call
 _L = _lib.lib
 
 # Source clouds with at least this many points are binned into a uniform grid first (csrc/grid.hip);
 # smaller ones are cheaper to scan exhaustively from LDS.  Results are identical either way.
 GRID_MIN_POINTS = 2048        # 3-NN keys
 GRID_MIN_POINTS_BALL = 8192   # ball-query cloud (measured break-even between 5 120 and 25 600 points)
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 def _need_gpu(t, name):
@@ -57,8 +53,8 @@ def _need_float(t, name, like=None):
 
 
 def _entry(name, x):
-    """The entry point ``regnet_<name>_f64`` or ``_f32``, by the dtype of ``x``."""
-    return getattr(_L, "regnet_%s_%s" % (name, "f64" if x.dtype == torch.float64 else "f32"))
+    """The name of the entry point ``regnet_<name>_f64`` or ``_f32``, by the dtype of ``x``."""
+    return "regnet_%s_%s" % (name, "f64" if x.dtype == torch.float64 else "f32")
 
 
 def _need_i64(t, name):
@@ -97,32 +93,29 @@ def farthest_point_sample(points, num_centroids, chain=None):
         raise RuntimeError("num_points is less than num_centroids")
     if f64 and chain is not None:
         raise RuntimeError("FpsChain is a float32 mechanism; float64 points take no chain")
-    with torch.cuda.device(points.device):
-        index = torch.empty((B, M), dtype=torch.int64, device=points.device)
-        ws_bytes = (_L.regnet_fps_f64_workspace_bytes if f64 else _L.regnet_fps_workspace_bytes)(B, N, M)
-        ws = torch.empty((ws_bytes // points.element_size(),), dtype=points.dtype, device=points.device) \
-            if ws_bytes else None
-        sb, sc, sn = points.stride()
-        if chain is None:
-            _check(_entry("fps", points)(points.data_ptr(), sb, sc, sn, B, N, M, index.data_ptr(),
-                                         ws.data_ptr() if ws is not None else None, _stream(points)),
-                   "farthest_point_sample")
-        else:
-            prefix = chain.prefix_ok
-            if prefix is not None and (prefix.dtype != torch.int32 or prefix.numel() != B or not prefix.is_cuda):
-                raise RuntimeError("FpsChain.prefix_ok must be a (B,) int32 GPU tensor")
-            prefix = prefix.contiguous() if prefix is not None else None   # held across the call
-            chain.first_tie = torch.empty((B,), dtype=torch.int32, device=points.device)
-            _check(_L.regnet_fps_chain_f32(points.data_ptr(), sb, sc, sn, B, N, M, index.data_ptr(),
-                                           ws.data_ptr() if ws is not None else None,
-                                           prefix.data_ptr() if prefix is not None else None,
-                                           chain.first_tie.data_ptr(), _stream(points)), "farthest_point_sample")
-        status_at = -1 if f64 else _L.regnet_fps_status_offset_bytes(B, N, M)
-        if status_at >= 0:
-            # cooperative sampling (N > 25 600): accumulate the launch's status word into the device's flag -- one tiny
-            # launch on the same stream, no synchronisation; raise_if_fps_failed() reads it where the caller synchronises
-            flag = _fps_flag(points.device)
-            torch.bitwise_or(flag, ws[status_at // 4: status_at // 4 + 1].view(torch.int32), out=flag)
+    index = torch.empty((B, M), dtype=torch.int64, device=points.device)
+    ws_bytes = (_L.regnet_fps_f64_workspace_bytes if f64 else _L.regnet_fps_workspace_bytes)(B, N, M)
+    ws = torch.empty((ws_bytes // points.element_size(),), dtype=points.dtype, device=points.device) \
+        if ws_bytes else None
+    sb, sc, sn = points.stride()
+    if chain is None:
+        _call(_entry("fps", points), points, points.data_ptr(), sb, sc, sn, B, N, M, index.data_ptr(),
+              ws.data_ptr() if ws is not None else None)
+    else:
+        prefix = chain.prefix_ok
+        if prefix is not None and (prefix.dtype != torch.int32 or prefix.numel() != B or not prefix.is_cuda):
+            raise RuntimeError("FpsChain.prefix_ok must be a (B,) int32 GPU tensor")
+        prefix = prefix.contiguous() if prefix is not None else None   # held across the call
+        chain.first_tie = torch.empty((B,), dtype=torch.int32, device=points.device)
+        _call("regnet_fps_chain_f32", points, points.data_ptr(), sb, sc, sn, B, N, M, index.data_ptr(),
+              ws.data_ptr() if ws is not None else None, prefix.data_ptr() if prefix is not None else None,
+              chain.first_tie.data_ptr())
+    status_at = -1 if f64 else _L.regnet_fps_status_offset_bytes(B, N, M)
+    if status_at >= 0:
+        # cooperative sampling (N > 25 600): accumulate the launch's status word into the device's flag -- one tiny
+        # launch on the same stream, no synchronisation; raise_if_fps_failed() reads it where the caller synchronises
+        flag = _fps_flag(points.device)
+        torch.bitwise_or(flag, ws[status_at // 4: status_at // 4 + 1].view(torch.int32), out=flag)
     return index
 
 
@@ -138,16 +131,14 @@ def gather_points(points, index, channels_last=False):
     _eq(points.size(0), index.size(0), "points and index differ in batch size")
     B, C, N = points.shape
     M = index.size(1)
-    with torch.cuda.device(points.device):
-        if channels_last:
-            out = torch.empty((B, M, C), dtype=torch.float32, device=points.device)
-            ob, om, oc = out.stride()
-        else:
-            out = torch.empty((B, C, M), dtype=torch.float32, device=points.device)
-            ob, oc, om = out.stride()
-        _check(_L.regnet_gather_points_f32(points.data_ptr(), *points.stride(), B, C, N, index.data_ptr(), *index.stride(), M,
-                                           out.data_ptr(), ob, oc, om, _fps_flag(points.device).data_ptr(),
-                                           _stream(points)), "gather_points")
+    if channels_last:
+        out = torch.empty((B, M, C), dtype=torch.float32, device=points.device)
+        ob, om, oc = out.stride()
+    else:
+        out = torch.empty((B, C, M), dtype=torch.float32, device=points.device)
+        ob, oc, om = out.stride()
+    _call("regnet_gather_points_f32", points, points.data_ptr(), *points.stride(), B, C, N, index.data_ptr(), *index.stride(),
+          M, out.data_ptr(), ob, oc, om, _fps_flag(points.device).data_ptr())
     return out
 
 
@@ -157,9 +148,8 @@ def class_order(count):
     _need_i64(count, "count")
     flat = count.reshape(-1)
     flat = flat if flat.is_contiguous() else flat.contiguous()
-    with torch.cuda.device(count.device):
-        order = torch.empty((flat.numel(),), dtype=torch.int64, device=count.device)
-        _check(_L.regnet_class_order_i64(flat.data_ptr(), flat.numel(), order.data_ptr(), _stream(count)), "class_order")
+    order = torch.empty((flat.numel(),), dtype=torch.int64, device=count.device)
+    _call("regnet_class_order_i64", count, flat.data_ptr(), flat.numel(), order.data_ptr())
     return order
 
 
@@ -170,11 +160,9 @@ def pair_order(count):
     _need_i64(count, "count")
     flat = count.reshape(-1)
     flat = flat if flat.is_contiguous() else flat.contiguous()
-    with torch.cuda.device(count.device):
-        order = torch.empty((flat.numel(),), dtype=torch.int64, device=count.device)
-        work = torch.empty((flat.numel(),), dtype=torch.int32, device=count.device)
-        _check(_L.regnet_pair_order_i64(flat.data_ptr(), flat.numel(), order.data_ptr(), work.data_ptr(), _stream(count)),
-               "pair_order")
+    order = torch.empty((flat.numel(),), dtype=torch.int64, device=count.device)
+    work = torch.empty((flat.numel(),), dtype=torch.int32, device=count.device)
+    _call("regnet_pair_order_i64", count, flat.data_ptr(), flat.numel(), order.data_ptr(), work.data_ptr())
     return order
 
 
@@ -212,19 +200,15 @@ def ball_query(points, centroids, radius, num_neighbours):
     B, _, N1 = points.shape
     N2 = centroids.size(2)
     K = int(num_neighbours)
-    with torch.cuda.device(points.device):
-        index = torch.empty((B, N2, K), dtype=torch.int64, device=points.device)
-        count = torch.empty((B, N2), dtype=torch.int64, device=points.device)
-        if not f64 and N1 >= GRID_MIN_POINTS_BALL and K <= 64 and B > 0 and float(radius) > 0:
-            ws = torch.empty((_L.regnet_grid_workspace_bytes(B, N1),), dtype=torch.uint8, device=points.device)
-            _check(_L.regnet_ball_query_grid_f32(points.data_ptr(), *points.stride(), centroids.data_ptr(),
-                                                 *centroids.stride(), B, N1, N2, float(radius), K,
-                                                 index.data_ptr(), count.data_ptr(), ws.data_ptr(),
-                                                 _stream(points)), "ball_query")
-        else:
-            _check(_entry("ball_query", points)(points.data_ptr(), *points.stride(), centroids.data_ptr(),
-                                                *centroids.stride(), B, N1, N2, float(radius), K, index.data_ptr(),
-                                                count.data_ptr(), _stream(points)), "ball_query")
+    index = torch.empty((B, N2, K), dtype=torch.int64, device=points.device)
+    count = torch.empty((B, N2), dtype=torch.int64, device=points.device)
+    if not f64 and N1 >= GRID_MIN_POINTS_BALL and K <= 64 and B > 0 and float(radius) > 0:
+        ws = torch.empty((_L.regnet_grid_workspace_bytes(B, N1),), dtype=torch.uint8, device=points.device)
+        _call("regnet_ball_query_grid_f32", points, points.data_ptr(), *points.stride(), centroids.data_ptr(),
+              *centroids.stride(), B, N1, N2, float(radius), K, index.data_ptr(), count.data_ptr(), ws.data_ptr())
+    else:
+        _call(_entry("ball_query", points), points, points.data_ptr(), *points.stride(), centroids.data_ptr(),
+              *centroids.stride(), B, N1, N2, float(radius), K, index.data_ptr(), count.data_ptr())
     return [index, count]
 
 
@@ -237,11 +221,10 @@ def group_points_forward(input, index):
     _eq(index.size(0), input.size(0), "index.size(0) does not equal to batch_size")
     B, C, N1 = input.shape
     _, N2, K = index.shape
-    with torch.cuda.device(input.device):
-        idx = index.contiguous()
-        out = torch.empty((B, C, N2, K), dtype=input.dtype, device=input.device)
-        _check(_entry("group_points_fwd", input)(input.data_ptr(), *input.stride(), idx.data_ptr(), B, C, N1, N2, K,
-                                                 out.data_ptr(), _stream(input)), "group_points_forward")
+    idx = index.contiguous()
+    out = torch.empty((B, C, N2, K), dtype=input.dtype, device=input.device)
+    _call(_entry("group_points_fwd", input), input, input.data_ptr(), *input.stride(), idx.data_ptr(), B, C, N1, N2, K,
+          out.data_ptr())
     return out
 
 
@@ -258,13 +241,12 @@ def group_points_backward(grad_output, index, num_points, plan=None):
     _eq(index.size(1), N2, "index.size(1) does not equal to num_select")
     _eq(index.size(2), K, "index.size(2) does not equal to k")
     N1 = int(num_points)
-    with torch.cuda.device(grad_output.device):
-        idx = index.contiguous()
-        return _scatter_backward(
-            "group_points_backward", grad_output, idx, None, B, C, N1, N2 * K, K, plan,
-            lambda grad_in, *ws: _entry("group_points_bwd", grad_output)(
-                grad_output.data_ptr(), *grad_output.stride(), idx.data_ptr(), B, C, N1, N2, K, grad_in.data_ptr(), *ws,
-                _stream(grad_output)))
+    idx = index.contiguous()
+    return _scatter_backward(
+        "group_points_backward", grad_output, idx, None, B, C, N1, N2 * K, K, plan,
+        lambda grad_in, *ws: _call(
+            _entry("group_points_bwd", grad_output), grad_output, grad_output.data_ptr(), *grad_output.stride(),
+            idx.data_ptr(), B, C, N1, N2, K, grad_in.data_ptr(), *ws))
 
 
 def _plan_buffer(B, num_dest, num_src, device):
@@ -293,9 +275,8 @@ def scatter_plan(index, num_dest):
     idx = index.contiguous()
     L = idx.numel() // max(B, 1)
     R = int(num_dest)
-    with torch.cuda.device(index.device):
-        buf = _plan_buffer(B, R, L, index.device)
-        _check(_L.regnet_scatter_plan(idx.data_ptr(), B, R, L, buf.data_ptr(), _stream(index)), "scatter_plan")
+    buf = _plan_buffer(B, R, L, index.device)
+    _call("regnet_scatter_plan", index, idx.data_ptr(), B, R, L, buf.data_ptr())
     PLANS["built"] += 1
     p = ScatterPlan()
     p.index, p.num_dest, p.num_src, p.buffer = idx, R, L, buf
@@ -305,15 +286,15 @@ def scatter_plan(index, num_dest):
 def _scatter_backward(op, go, idx, weight, B, C, R, L, inner, plan, native):
     """The backward of ``op`` -> grad_in (B, C, R): ``go`` (B, C, rows[, inner]) scatter-added by the contiguous index
     ``idx`` (B, L = rows * inner), weighted by ``weight`` (B, L) for interpolate (inner = 3).  ``native(grad_in[, ws])``
-    calls the op's own entry point for the dtype of ``go`` and returns its status: float64 with the workspace pointer
-    ``ws``, float32 (the atomics kernel) without.  float64, and float32 in deterministic mode, sum each destination in
+    calls the op's own entry point for the dtype of ``go``: float64 with the workspace pointer ``ws``, float32 (the
+    atomics kernel) without.  float64, and float32 in deterministic mode, sum each destination in
     ascending source position (csrc/scatter.hip; float32 through ``plan``, ``scatter_plan(idx, R)`` when given, else
     built here).  In deterministic mode a shape with no deterministic kernel goes to determinism.unsupported, which
     raises or (warn_only) lets the default kernel run."""
     grad_in = torch.empty((B, C, R), dtype=go.dtype, device=go.device)
     if go.dtype == torch.float64:
         ws = _plan_buffer(B, R, L, go.device)      # held until the call has enqueued every kernel that uses it
-        _check(native(grad_in, ws.data_ptr()), op)
+        native(grad_in, ws.data_ptr())
         return grad_in
     if determinism.enabled():
         if plan is not None and (plan.index is not idx or plan.num_dest != R or plan.num_src != L):
@@ -325,14 +306,13 @@ def _scatter_backward(op, go, idx, weight, B, C, R, L, inner, plan, native):
             determinism.unsupported(op, "%d destinations / %d sources per scene" % (R, L))
         else:
             sb, sc, s_hi, s_lo = (go.stride() + (0,))[:4]
-            st = _L.regnet_scatter_segsum_f32(go.data_ptr(), sb, sc, s_hi, s_lo, inner,
-                                              weight.data_ptr() if weight is not None else None, B, C, R, L,
-                                              plan.buffer.data_ptr(), grad_in.data_ptr(), _stream(go))
+            st = _call("regnet_scatter_segsum_f32", go, go.data_ptr(), sb, sc, s_hi, s_lo, inner,
+                       weight.data_ptr() if weight is not None else None, B, C, R, L, plan.buffer.data_ptr(),
+                       grad_in.data_ptr(), tolerate=determinism.REGNET_ERR_UNSUPPORTED)
             if st != determinism.REGNET_ERR_UNSUPPORTED:
-                _check(st, op)
                 return grad_in
             determinism.unsupported(op, "%d channels" % C)
-    _check(native(grad_in), op)
+    native(grad_in)
     return grad_in
 
 
@@ -349,18 +329,15 @@ def point_search(query_xyz, key_xyz, num_neighbours):
     _eq(int(num_neighbours), 3, "num_neighbours does not equal to K")
     if not N2 >= 3:
         raise RuntimeError("num_key is less than num_neighbours")
-    with torch.cuda.device(query_xyz.device):
-        index = torch.empty((B, N1, 3), dtype=torch.int64, device=query_xyz.device)
-        dist = torch.empty((B, N1, 3), dtype=query_xyz.dtype, device=query_xyz.device)
-        if not f64 and N2 >= GRID_MIN_POINTS and B > 0:
-            ws = torch.empty((_L.regnet_grid_workspace_bytes(B, N2),), dtype=torch.uint8, device=query_xyz.device)
-            _check(_L.regnet_three_nn_grid_f32(query_xyz.data_ptr(), *query_xyz.stride(), key_xyz.data_ptr(),
-                                               *key_xyz.stride(), B, N1, N2, index.data_ptr(), dist.data_ptr(),
-                                               ws.data_ptr(), _stream(query_xyz)), "point_search")
-        else:
-            _check(_entry("three_nn", query_xyz)(query_xyz.data_ptr(), *query_xyz.stride(), key_xyz.data_ptr(),
-                                                 *key_xyz.stride(), B, N1, N2, index.data_ptr(), dist.data_ptr(),
-                                                 _stream(query_xyz)), "point_search")
+    index = torch.empty((B, N1, 3), dtype=torch.int64, device=query_xyz.device)
+    dist = torch.empty((B, N1, 3), dtype=query_xyz.dtype, device=query_xyz.device)
+    if not f64 and N2 >= GRID_MIN_POINTS and B > 0:
+        ws = torch.empty((_L.regnet_grid_workspace_bytes(B, N2),), dtype=torch.uint8, device=query_xyz.device)
+        _call("regnet_three_nn_grid_f32", query_xyz, query_xyz.data_ptr(), *query_xyz.stride(), key_xyz.data_ptr(),
+              *key_xyz.stride(), B, N1, N2, index.data_ptr(), dist.data_ptr(), ws.data_ptr())
+    else:
+        _call(_entry("three_nn", query_xyz), query_xyz, query_xyz.data_ptr(), *query_xyz.stride(), key_xyz.data_ptr(),
+              *key_xyz.stride(), B, N1, N2, index.data_ptr(), dist.data_ptr())
     return [index, dist]
 
 
@@ -380,11 +357,10 @@ def interpolate_forward(input, index, weight):
     B, C, M = input.shape
     N = index.size(1)
     _check_interp(input, index, weight, B, N)
-    with torch.cuda.device(input.device):
-        idx, w = index.contiguous(), weight.contiguous()
-        out = torch.empty((B, C, N), dtype=input.dtype, device=input.device)
-        _check(_entry("interpolate_fwd", input)(input.data_ptr(), *input.stride(), idx.data_ptr(), w.data_ptr(), B, C,
-                                                M, N, out.data_ptr(), _stream(input)), "interpolate_forward")
+    idx, w = index.contiguous(), weight.contiguous()
+    out = torch.empty((B, C, N), dtype=input.dtype, device=input.device)
+    _call(_entry("interpolate_fwd", input), input, input.data_ptr(), *input.stride(), idx.data_ptr(), w.data_ptr(), B, C,
+          M, N, out.data_ptr())
     return out
 
 
@@ -396,10 +372,9 @@ def interpolate_backward(grad_output, index, weight, num_inst):
     B, C, N = grad_output.shape
     _check_interp(grad_output, index, weight, B, N)
     M = int(num_inst)
-    with torch.cuda.device(grad_output.device):
-        idx, w = index.contiguous(), weight.contiguous()
-        return _scatter_backward(
-            "interpolate_backward", grad_output, idx, w, B, C, M, N * 3, 3, None,
-            lambda grad_in, *ws: _entry("interpolate_bwd", grad_output)(
-                grad_output.data_ptr(), *grad_output.stride(), idx.data_ptr(), w.data_ptr(), B, C, M, N,
-                grad_in.data_ptr(), *ws, _stream(grad_output)))
+    idx, w = index.contiguous(), weight.contiguous()
+    return _scatter_backward(
+        "interpolate_backward", grad_output, idx, w, B, C, M, N * 3, 3, None,
+        lambda grad_in, *ws: _call(
+            _entry("interpolate_bwd", grad_output), grad_output, grad_output.data_ptr(), *grad_output.stride(),
+            idx.data_ptr(), w.data_ptr(), B, C, M, N, grad_in.data_ptr(), *ws))

@@ -15,12 +15,7 @@ import torch
 from . import _lib, host_io, np_random
 
 FUSED = True
-_L = _lib.lib
-_check = _lib.check
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
+_call = _lib.call
 
 
 def usable(*tensors):
@@ -60,7 +55,7 @@ class _Stage2Loss(torch.autograd.Function):
         x_reg, x_cls, labels = x_reg.contiguous(), x_cls.contiguous(), labels.contiguous()
         centres = centres if centres.stride(1) == 1 else centres.contiguous()
         weights = (ctypes.c_float * 4)(10.0 / (3 * m), 5.0 / (3 * m), 1.0 / m, 1.0 / (3 * m))
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev):     # two launches around a host read, a pinned upload and the tensor reduction of the terms
             next_grasp = torch.empty((m, C), dtype=torch.float32, device=dev)
             pick = torch.empty((m,), dtype=torch.int32, device=dev)
             g8 = torch.empty((m,), dtype=torch.int32, device=dev)
@@ -68,11 +63,10 @@ class _Stage2Loss(torch.autograd.Function):
             terms = torch.empty((m, 12), dtype=torch.float32, device=dev)
             dreg = torch.zeros((n, A, C), dtype=torch.float32, device=dev)
             dcls = torch.zeros((n, A), dtype=torch.float32, device=dev)
-            _check(_L.regnet_stage2_loss_rows_f32(x_cls.data_ptr(), x_reg.data_ptr(), A, C, centres.data_ptr(),
-                                                  centres.stride(0), templates.data_ptr(), labels.data_ptr(),
-                                                  labels.stride(0), float(radius), ctypes.addressof(weights), rows.data_ptr(),
-                                                  m, next_grasp.data_ptr(), pick.data_ptr(), g8.data_ptr(), a_gt.data_ptr(),
-                                                  terms.data_ptr(), dreg.data_ptr(), _stream(x_reg)), "stage2_loss_rows")
+            _call("regnet_stage2_loss_rows_f32", x_reg, x_cls.data_ptr(), x_reg.data_ptr(), A, C, centres.data_ptr(),
+                  centres.stride(0), templates.data_ptr(), labels.data_ptr(), labels.stride(0), float(radius),
+                  ctypes.addressof(weights), rows.data_ptr(), m, next_grasp.data_ptr(), pick.data_ptr(), g8.data_ptr(),
+                  a_gt.data_ptr(), terms.data_ptr(), dreg.data_ptr())
             # class-balanced subset: the same number of centres per (non-empty) anchor class, drawn from numpy's global stream
             # in class order (gripper_region_network.py:108-130) -- one device->host read of the <= B*64 class ids
             classes = g8.cpu().numpy()
@@ -88,8 +82,8 @@ class _Stage2Loss(torch.autograd.Function):
                 np.array([10.0, 5.0, 1.0, 1.0, 0, 0, 0, 0, 0, 0, 1.0, 0], dtype=np.float32)), dev)
             nb = int(idx.numel())
             ce_rows = torch.empty((nb,), dtype=torch.float32, device=dev)
-            _check(_L.regnet_ce_rows_f32(x_cls.data_ptr(), A, g8.data_ptr(), idx.data_ptr(), rows.data_ptr(), nb, 1.0 / nb,
-                                         ce_rows.data_ptr(), dcls.data_ptr(), _stream(x_reg)), "ce_rows")
+            _call("regnet_ce_rows_f32", x_reg, x_cls.data_ptr(), A, g8.data_ptr(), idx.data_ptr(), rows.data_ptr(), nb,
+                  1.0 / nb, ce_rows.data_ptr(), dcls.data_ptr())
             sums = terms.sum(0)
             ce = ce_rows.sum()
             values = sums * scale
@@ -128,16 +122,15 @@ class _RefineLoss(torch.autograd.Function):
         next_x_reg, next_x_cls = next_x_reg.contiguous(), next_x_cls.contiguous()
         grasp = next_grasp if next_grasp.stride(1) == 1 else next_grasp.contiguous()
         gt = next_gt if next_gt.stride(1) == 1 else next_gt.contiguous()
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev):     # as in _Stage2Loss: launches, a host read, a pinned upload and tensor glue
             final = torch.empty((m, C), dtype=torch.float32, device=dev)
             flags8 = torch.empty((3, m), dtype=torch.uint8, device=dev)
             terms = torch.empty((m, 20), dtype=torch.float32, device=dev)
             dreg = torch.empty((m, C), dtype=torch.float32, device=dev)
             dcls = torch.zeros((m, 2), dtype=torch.float32, device=dev)
-            _check(_L.regnet_refine_loss_rows_f32(grasp.data_ptr(), grasp.stride(0), next_x_cls.data_ptr(),
-                                                  next_x_reg.data_ptr(), gt.data_ptr(), gt.stride(0), C, float(radius),
-                                                  float(score_thre), m, final.data_ptr(), flags8.data_ptr(), terms.data_ptr(),
-                                                  dreg.data_ptr(), _stream(next_x_reg)), "refine_loss_rows")
+            _call("regnet_refine_loss_rows_f32", next_x_reg, grasp.data_ptr(), grasp.stride(0), next_x_cls.data_ptr(),
+                  next_x_reg.data_ptr(), gt.data_ptr(), gt.stride(0), C, float(radius), float(score_thre), m, final.data_ptr(),
+                  flags8.data_ptr(), terms.data_ptr(), dreg.data_ptr())
             flags = flags8.cpu().numpy().astype(bool)                  # the one read: class / score / label-positive flags
             class_np, score_np = np.nonzero(flags[0])[0], np.nonzero(flags[1])[0]
             pos_np, neg_np = np.nonzero(flags[2])[0], np.nonzero(~flags[2])[0]
@@ -171,8 +164,8 @@ class _RefineLoss(torch.autograd.Function):
                 nb = int(idx.numel())
                 target = flags8[2].to(torch.int32)
                 ce_rows = torch.empty((nb,), dtype=torch.float32, device=dev)
-                _check(_L.regnet_ce_rows_f32(next_x_cls.data_ptr(), 2, target.data_ptr(), idx.data_ptr(), None, nb, 1.0 / nb,
-                                             ce_rows.data_ptr(), dcls.data_ptr(), _stream(next_x_reg)), "ce_rows")
+                _call("regnet_ce_rows_f32", next_x_reg, next_x_cls.data_ptr(), 2, target.data_ptr(), idx.data_ptr(), None, nb,
+                      1.0 / nb, ce_rows.data_ptr(), dcls.data_ptr())
                 ce = ce_rows.sum() / nb
                 dreg = dreg * col
                 loss = ce + values[:4].sum()

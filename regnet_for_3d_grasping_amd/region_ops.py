@@ -4,10 +4,9 @@ import numpy as np
 import torch
 
 from . import _lib, determinism
-from .pn2_ext import _need_f32, _need_i64, _stream
+from .pn2_ext import _need_f32, _need_i64
 
-_check = _lib.check
-_L = _lib.lib
+_call = _lib.call
 
 
 def sqrt_le_threshold(radius):
@@ -37,13 +36,10 @@ def radius_candidates(pc, centres, radius):
         pc, centres = pc.contiguous(), centres.contiguous()
     B, N, _ = pc.shape
     Nc = centres.shape[1]
-    with torch.cuda.device(pc.device):
-        cand = torch.empty((B, Nc, max(N, 1)), dtype=torch.int32, device=pc.device)
-        count = torch.empty((B, Nc), dtype=torch.int32, device=pc.device)
-        _check(_L.regnet_radius_group_f32(pc.data_ptr(), pc.stride(0), pc.stride(1), centres.data_ptr(),
-                                          centres.stride(0), centres.stride(1), B, N, Nc,
-                                          sqrt_le_threshold(radius), cand.size(2), cand.data_ptr(), count.data_ptr(),
-                                          _stream(pc)), "radius_group")
+    cand = torch.empty((B, Nc, max(N, 1)), dtype=torch.int32, device=pc.device)
+    count = torch.empty((B, Nc), dtype=torch.int32, device=pc.device)
+    _call("regnet_radius_group_f32", pc, pc.data_ptr(), pc.stride(0), pc.stride(1), centres.data_ptr(), centres.stride(0),
+          centres.stride(1), B, N, Nc, sqrt_le_threshold(radius), cand.size(2), cand.data_ptr(), count.data_ptr())
     return cand, count
 
 
@@ -58,13 +54,11 @@ def select_positive(pc, score, threshold):
     if score.stride(1) != 1:
         score = score.contiguous()
     B, N, _ = pc.shape
-    with torch.cuda.device(pc.device):
-        index = torch.empty((B, max(N, 1)), dtype=torch.int64, device=pc.device)
-        xyz = torch.empty((B, 3, max(N, 1)), dtype=torch.float32, device=pc.device)
-        count = torch.empty((B,), dtype=torch.int32, device=pc.device)
-        _check(_L.regnet_select_positive_f32(pc.data_ptr(), pc.stride(0), pc.stride(1), score.data_ptr(),
-                                             score.stride(0), B, N, float(threshold), index.data_ptr(),
-                                             xyz.data_ptr(), count.data_ptr(), _stream(pc)), "select_positive")
+    index = torch.empty((B, max(N, 1)), dtype=torch.int64, device=pc.device)
+    xyz = torch.empty((B, 3, max(N, 1)), dtype=torch.float32, device=pc.device)
+    count = torch.empty((B,), dtype=torch.int32, device=pc.device)
+    _call("regnet_select_positive_f32", pc, pc.data_ptr(), pc.stride(0), pc.stride(1), score.data_ptr(), score.stride(0), B,
+          N, float(threshold), index.data_ptr(), xyz.data_ptr(), count.data_ptr())
     return index, xyz, count
 
 
@@ -80,40 +74,34 @@ def resample_groups(pc, cand, pos):
     cand, pos = cand.contiguous(), pos.contiguous()
     B, Nc, G = pos.shape
     C = pc.shape[2]
-    with torch.cuda.device(pc.device):
-        index = torch.empty((B, Nc, G), dtype=torch.int64, device=pc.device)
-        points = torch.empty((B, Nc, G, C), dtype=torch.float32, device=pc.device)
-        flag = _range_flag(pc.device)
-        _check(_L.regnet_resample_groups_f32(pc.data_ptr(), pc.stride(0), pc.stride(1), C, cand.data_ptr(), cand.size(2),
-                                             pos.data_ptr(), B, Nc, G, pc.shape[1], flag.data_ptr(), index.data_ptr(),
-                                             points.data_ptr(), _stream(pc)), "resample_groups")
+    index = torch.empty((B, Nc, G), dtype=torch.int64, device=pc.device)
+    points = torch.empty((B, Nc, G, C), dtype=torch.float32, device=pc.device)
+    flag = _range_flag(pc.device)
+    _call("regnet_resample_groups_f32", pc, pc.data_ptr(), pc.stride(0), pc.stride(1), C, cand.data_ptr(), cand.size(2),
+          pos.data_ptr(), B, Nc, G, pc.shape[1], flag.data_ptr(), index.data_ptr(), points.data_ptr())
     return index, points
 
 
 def _gather_max_arg(feature_rows, rows):
     R, G = rows.shape
     F = feature_rows.shape[1]
-    with torch.cuda.device(feature_rows.device):
-        out = torch.empty((R, F), dtype=torch.float32, device=feature_rows.device)
-        arg = torch.empty((R, F), dtype=torch.int64, device=feature_rows.device)
-        _check(_L.regnet_gather_max_arg_f32(feature_rows.data_ptr(), feature_rows.shape[0], F, rows.data_ptr(), R, G,
-                                            out.data_ptr(), arg.data_ptr(), _stream(feature_rows)), "gather_max_arg")
+    out = torch.empty((R, F), dtype=torch.float32, device=feature_rows.device)
+    arg = torch.empty((R, F), dtype=torch.int64, device=feature_rows.device)
+    _call("regnet_gather_max_arg_f32", feature_rows, feature_rows.data_ptr(), feature_rows.shape[0], F, rows.data_ptr(), R,
+          G, out.data_ptr(), arg.data_ptr())
     return out, arg
 
 
 def _scatter_max_grad(dy, arg, grad, scene_rows, batch_stride, row_stride, ch_stride):
     dy = dy.contiguous()
-    with torch.cuda.device(dy.device):
-        if determinism.enabled():     # ascending r per destination (csrc/det.hip)
-            st = _L.regnet_scatter_max_grad_det_f32(dy.data_ptr(), arg.data_ptr(), arg.shape[0], arg.shape[1], scene_rows,
-                                                    batch_stride, row_stride, ch_stride, grad.data_ptr(), _stream(dy))
-            if st != determinism.REGNET_ERR_UNSUPPORTED:
-                _check(st, "scatter_max_grad")
-                return
-            determinism.unsupported("scatter_max_grad", "%d rows (at most 8192)" % arg.shape[0])
-        _check(_L.regnet_scatter_max_grad_f32(dy.data_ptr(), arg.data_ptr(), arg.shape[0], arg.shape[1], scene_rows,
-                                              batch_stride, row_stride, ch_stride, grad.data_ptr(), _stream(dy)),
-               "scatter_max_grad")
+    if determinism.enabled():     # ascending r per destination (csrc/det.hip)
+        st = _call("regnet_scatter_max_grad_det_f32", dy, dy.data_ptr(), arg.data_ptr(), arg.shape[0], arg.shape[1], scene_rows,
+                   batch_stride, row_stride, ch_stride, grad.data_ptr(), tolerate=determinism.REGNET_ERR_UNSUPPORTED)
+        if st != determinism.REGNET_ERR_UNSUPPORTED:
+            return
+        determinism.unsupported("scatter_max_grad", "%d rows (at most 8192)" % arg.shape[0])
+    _call("regnet_scatter_max_grad_f32", dy, dy.data_ptr(), arg.data_ptr(), arg.shape[0], arg.shape[1], scene_rows,
+          batch_stride, row_stride, ch_stride, grad.data_ptr())
 
 
 class _GatherMaxFn(torch.autograd.Function):
@@ -196,9 +184,8 @@ def rowsum_neg(x, K):
     _need_f32(x, "x")
     x = x.contiguous()
     rows = x.numel() // K
-    with torch.cuda.device(x.device):
-        out = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
-        _check(_L.regnet_rowsum_neg_f32(x.data_ptr(), rows, K, out.data_ptr(), _stream(x)), "rowsum_neg")
+    out = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device)
+    _call("regnet_rowsum_neg_f32", x, x.data_ptr(), rows, K, out.data_ptr())
     return out
 
 
@@ -232,12 +219,10 @@ def box_candidates(group_points, centre, rot, xlim, ylim, zlim):
     gp = group_points if group_points.stride(2) == 1 else group_points.contiguous()
     centre, rot = centre.contiguous().float(), rot.contiguous().float()
     xlim, ylim = xlim.contiguous().float(), ylim.contiguous().float()
-    with torch.cuda.device(gp.device):
-        cand = torch.empty((n, max(G, 1)), dtype=torch.int32, device=gp.device)
-        count = torch.empty((n,), dtype=torch.int32, device=gp.device)
-        _check(_L.regnet_box_crop_f32(gp.data_ptr(), gp.stride(0), gp.stride(1), centre.data_ptr(), rot.data_ptr(),
-                                      xlim.data_ptr(), ylim.data_ptr(), float(zlim), n, G, cand.data_ptr(),
-                                      count.data_ptr(), _stream(gp)), "box_crop")
+    cand = torch.empty((n, max(G, 1)), dtype=torch.int32, device=gp.device)
+    count = torch.empty((n,), dtype=torch.int32, device=gp.device)
+    _call("regnet_box_crop_f32", gp, gp.data_ptr(), gp.stride(0), gp.stride(1), centre.data_ptr(), rot.data_ptr(),
+          xlim.data_ptr(), ylim.data_ptr(), float(zlim), n, G, cand.data_ptr(), count.data_ptr())
     return cand, count
 
 
@@ -246,11 +231,9 @@ def gripper_frame(grasp):
     _need_f32(grasp, "grasp")
     g = grasp if grasp.stride(1) == 1 else grasp.contiguous()
     n = g.shape[0]
-    with torch.cuda.device(g.device):
-        centre = torch.empty((n, 3), dtype=torch.float32, device=g.device)
-        rot = torch.empty((n, 3, 3), dtype=torch.float32, device=g.device)
-        _check(_L.regnet_gripper_frame_f32(g.data_ptr(), g.stride(0) if n else 7, n, centre.data_ptr(), rot.data_ptr(),
-                                           _stream(g)), "gripper_frame")
+    centre = torch.empty((n, 3), dtype=torch.float32, device=g.device)
+    rot = torch.empty((n, 3, 3), dtype=torch.float32, device=g.device)
+    _call("regnet_gripper_frame_f32", g, g.data_ptr(), g.stride(0) if n else 7, n, centre.data_ptr(), rot.data_ptr())
     return centre, rot
 
 
@@ -262,11 +245,9 @@ def stage2_decode(x_cls, x_reg, centres, templates, radius, sigmoid_tail):
     n, A, C = x_reg.shape
     x_cls, x_reg, templates = x_cls.contiguous(), x_reg.contiguous(), templates.contiguous()
     c = centres if centres.stride(1) == 1 else centres.contiguous()
-    with torch.cuda.device(x_reg.device):
-        out = torch.empty((n, C), dtype=torch.float32, device=x_reg.device)
-        _check(_L.regnet_stage2_decode_f32(x_cls.data_ptr(), x_reg.data_ptr(), A, C, c.data_ptr(), c.stride(0) if n else 3,
-                                           templates.data_ptr(), float(radius), int(bool(sigmoid_tail)), n, out.data_ptr(),
-                                           _stream(x_reg)), "stage2_decode")
+    out = torch.empty((n, C), dtype=torch.float32, device=x_reg.device)
+    _call("regnet_stage2_decode_f32", x_reg, x_cls.data_ptr(), x_reg.data_ptr(), A, C, c.data_ptr(),
+          c.stride(0) if n else 3, templates.data_ptr(), float(radius), int(bool(sigmoid_tail)), n, out.data_ptr())
     return out
 
 
@@ -277,12 +258,10 @@ def refine_decode(grasp, x_cls, x_reg, radius, score_thre):
     m, C = x_reg.shape
     g = grasp if grasp.stride(1) == 1 else grasp.contiguous()
     x_cls, x_reg = x_cls.contiguous(), x_reg.contiguous()
-    with torch.cuda.device(g.device):
-        final = torch.empty((m, C), dtype=torch.float32, device=g.device)
-        flags = torch.empty((2, m), dtype=torch.uint8, device=g.device)
-        _check(_L.regnet_refine_decode_f32(g.data_ptr(), g.stride(0) if m else C, x_cls.data_ptr(), x_reg.data_ptr(), C,
-                                           float(radius), float(score_thre), m, final.data_ptr(), flags.data_ptr(),
-                                           _stream(g)), "refine_decode")
+    final = torch.empty((m, C), dtype=torch.float32, device=g.device)
+    flags = torch.empty((2, m), dtype=torch.uint8, device=g.device)
+    _call("regnet_refine_decode_f32", g, g.data_ptr(), g.stride(0) if m else C, x_cls.data_ptr(), x_reg.data_ptr(), C,
+          float(radius), float(score_thre), m, final.data_ptr(), flags.data_ptr())
     return final, flags
 
 
@@ -294,11 +273,10 @@ def crop_pick(cand, pos, valid, group_index):
     valid8 = valid.contiguous().view(torch.uint8)
     gi = group_index if group_index.stride(1) == 1 else group_index.contiguous()
     _need_i64(gi, "group_index")
-    with torch.cuda.device(cand.device):
-        index = torch.empty((n, R), dtype=torch.int64, device=cand.device)
-        index_inall = torch.empty((n, R), dtype=torch.int64, device=cand.device)
-        _check(_L.regnet_crop_pick(cand.data_ptr(), G, pos.data_ptr(), R, valid8.data_ptr(), gi.data_ptr(),
-                                   gi.stride(0) if n else G, n, index.data_ptr(), index_inall.data_ptr(), _stream(cand)), "crop_pick")
+    index = torch.empty((n, R), dtype=torch.int64, device=cand.device)
+    index_inall = torch.empty((n, R), dtype=torch.int64, device=cand.device)
+    _call("regnet_crop_pick", cand, cand.data_ptr(), G, pos.data_ptr(), R, valid8.data_ptr(), gi.data_ptr(),
+          gi.stride(0) if n else G, n, index.data_ptr(), index_inall.data_ptr())
     return index, index_inall
 
 
@@ -315,11 +293,9 @@ def gather_max_scene(feature_rows, index, row_ids, per_scene, scene_stride):
         _need_i64(row_ids, "row_ids")
         row_ids = row_ids.contiguous()
     R = index.shape[0] if row_ids is None else row_ids.numel()
-    with torch.cuda.device(feature_rows.device):
-        out = torch.empty((R, F), dtype=torch.float32, device=feature_rows.device)
-        _check(_L.regnet_gather_max_scene_f32(feature_rows.data_ptr(), feature_rows.shape[0], F, index.data_ptr(),
-                                              None if row_ids is None else row_ids.data_ptr(), R, G, int(per_scene),
-                                              int(scene_stride), out.data_ptr(), _stream(feature_rows)), "gather_max_scene")
+    out = torch.empty((R, F), dtype=torch.float32, device=feature_rows.device)
+    _call("regnet_gather_max_scene_f32", feature_rows, feature_rows.data_ptr(), feature_rows.shape[0], F, index.data_ptr(),
+          None if row_ids is None else row_ids.data_ptr(), R, G, int(per_scene), int(scene_stride), out.data_ptr())
     return out
 
 
@@ -330,8 +306,7 @@ def gather_max(feature_rows, rows):
     feature_rows, rows = feature_rows.contiguous(), rows.contiguous()
     R, G = rows.shape
     F = feature_rows.shape[1]
-    with torch.cuda.device(feature_rows.device):
-        out = torch.empty((R, F), dtype=torch.float32, device=feature_rows.device)
-        _check(_L.regnet_gather_max_f32(feature_rows.data_ptr(), feature_rows.shape[0], F, rows.data_ptr(), R, G,
-                                        out.data_ptr(), _stream(feature_rows)), "gather_max")
+    out = torch.empty((R, F), dtype=torch.float32, device=feature_rows.device)
+    _call("regnet_gather_max_f32", feature_rows, feature_rows.data_ptr(), feature_rows.shape[0], F, rows.data_ptr(), R, G,
+          out.data_ptr())
     return out

@@ -87,14 +87,12 @@ class ScoreDataset(torch.utils.data.Dataset):
         # mode 0 = "without replacement when the list has at least `size` entries, else with" = scoredataset.py:68-72
         pick = np_random.choice_rows_device(counts, N, 0, M)[0].view(N)
         rand6 = np_random.rand_device(6, dev)
-        with torch.cuda.device(dev):
-            pc = torch.empty((N, 6), dtype=torch.float32, device=dev)
-            score_out = torch.empty((N,), dtype=torch.float32, device=dev)
-            label_out = torch.empty((N,), dtype=torch.float32, device=dev)
-            _lib.check(_lib.lib.regnet_dataset_resample_f32(
-                cloud.data_ptr(), color.data_ptr(), score.data_ptr(), label.data_ptr(), M, pick.data_ptr(), N,
-                rand6.data_ptr(), pc.data_ptr(), score_out.data_ptr(), label_out.data_ptr(),
-                region_ops._range_flag(dev).data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "dataset_resample")
+        pc = torch.empty((N, 6), dtype=torch.float32, device=dev)
+        score_out = torch.empty((N,), dtype=torch.float32, device=dev)
+        label_out = torch.empty((N,), dtype=torch.float32, device=dev)
+        _lib.call("regnet_dataset_resample_f32", cloud, cloud.data_ptr(), color.data_ptr(), score.data_ptr(), label.data_ptr(), M,
+                  pick.data_ptr(), N, rand6.data_ptr(), pc.data_ptr(), score_out.data_ptr(), label_out.data_ptr(),
+                  region_ops._range_flag(dev).data_ptr())
         return pc, score_out, label_out, data_path, self.width
 
     def gpu_batch(self, indices, device):

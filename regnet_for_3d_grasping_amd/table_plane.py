@@ -16,7 +16,6 @@ import numpy as np
 
 from . import _lib
 
-_check = _lib.check
 _L = _lib.lib
 
 MAX_FRAME_POINTS = 1 << 21          # regnet_plane_estimate_*'s documented limits
@@ -75,20 +74,19 @@ def estimate_device(xyz, threshold=DEFAULT_THRESHOLD, hypotheses=DEFAULT_HYPOTHE
             raise ValueError("up_hint must be (3,)")
         c2 = cos2_tilt(max_tilt_deg)
     xyz = xyz.contiguous()
-    with torch.cuda.device(dev):
-        if out is None:
-            result = torch.empty((96,), dtype=torch.uint8, device=dev)
-            details = PlaneDetails(torch.empty((H,), dtype=torch.int32, device=dev),
-                                   torch.empty((H, 8), dtype=torch.float32, device=dev),
-                                   torch.empty((M,), dtype=torch.uint8, device=dev), result[:80].view(torch.float64))
-            ws = torch.empty((workspace_bytes(M, H),), dtype=torch.uint8, device=dev)
-        else:
-            result, details, ws = out
-        fn = _L.regnet_plane_estimate_f64 if xyz.dtype == torch.float64 else _L.regnet_plane_estimate_f32
-        _check(fn(xyz.data_ptr() if M else None, M, H, seed, float(threshold), lo, hi,
-                  hint.ctypes.data if hint is not None else None, c2, details.hypotheses.data_ptr(), details.counts.data_ptr(),
-                  details.inlier_mask.data_ptr() if M else None, result.data_ptr(), result.data_ptr() + 80, ws.data_ptr(),
-                  int(stages), torch.cuda.current_stream(dev).cuda_stream), "plane_estimate")
+    if out is None:
+        result = torch.empty((96,), dtype=torch.uint8, device=dev)
+        details = PlaneDetails(torch.empty((H,), dtype=torch.int32, device=dev),
+                               torch.empty((H, 8), dtype=torch.float32, device=dev),
+                               torch.empty((M,), dtype=torch.uint8, device=dev), result[:80].view(torch.float64))
+        ws = torch.empty((workspace_bytes(M, H),), dtype=torch.uint8, device=dev)
+    else:
+        result, details, ws = out
+    _lib.call("regnet_plane_estimate_f64" if xyz.dtype == torch.float64 else "regnet_plane_estimate_f32", xyz,
+              xyz.data_ptr() if M else None, M, H, seed, float(threshold), lo, hi,
+              hint.ctypes.data if hint is not None else None, c2, details.hypotheses.data_ptr(), details.counts.data_ptr(),
+              details.inlier_mask.data_ptr() if M else None, result.data_ptr(), result.data_ptr() + 80, ws.data_ptr(),
+              int(stages))
     return result, details, ws
 
 

@@ -69,10 +69,10 @@ def child(kind):
                 e3 = event()
                 pc = torch.empty((25600, 6), dtype=torch.float32, device=dev)
                 bad = torch.zeros((1,), dtype=torch.int32, device=dev)
-                ingest._check(ingest._L.regnet_ingest_resample_f32(k32.data_ptr(), krgb.data_ptr(), 1, count.data_ptr(), len(xyz),
-                                                                   pick.data_ptr(), 25600, rand3.data_ptr(), pc.data_ptr(),
-                                                                   bad.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                              "ingest_resample")
+                ingest._lib.check(ingest._L.regnet_ingest_resample_f32(k32.data_ptr(), krgb.data_ptr(), 1, count.data_ptr(), len(xyz),
+                                                                       pick.data_ptr(), 25600, rand3.data_ptr(), pc.data_ptr(),
+                                                                       bad.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+                                  "ingest_resample")
                 e4 = event()
                 torch.cuda.synchronize()
                 if it >= WARMUP:

@@ -1,0 +1,132 @@
+"""The ctypes binding is derived from include/regnet_hip.h (regnet_for_3d_grasping_amd/_lib.py: parse_header): every declared
+symbol is bound with the prototype's own types, the parser refuses what it does not know, and the launching entry points --
+the ones ``_lib.call`` appends a stream to -- are exactly those whose last parameter is ``stream``.  No GPU."""
+import ctypes
+import os
+import re
+
+import pytest
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+_vp, _i64, _u64, _int, _f32, _f64 = (ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int, ctypes.c_float,
+                                     ctypes.c_double)
+
+
+def header_prototypes():
+    """[(name, [parameter texts])] of the header, read independently of the binding's parser: comments out, statements split at
+    ';', the parameter list split at ','."""
+    text = open(os.path.join(REPO, "include", "regnet_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    out = []
+    for stmt in text.split(";"):
+        m = re.search(r"\b(regnet_\w+)\s*\((.*)\)\s*$", stmt, flags=re.S)
+        if m:
+            params = [" ".join(p.split()) for p in m.group(2).split(",")]
+            out.append((m.group(1), [] if params == ["void"] else params))
+    return out
+
+
+def test_every_declared_symbol_is_bound_with_its_parameter_count():
+    from regnet_for_3d_grasping_amd import _lib
+    protos = header_prototypes()
+    assert len(protos) >= 100 and len({n for n, _ in protos}) == len(protos)
+    assert sorted(_lib.SIGNATURES) == sorted(n for n, _ in protos) == sorted(_lib.PARAMS)
+    for name, params in protos:
+        restype, argtypes = _lib.SIGNATURES[name]
+        assert len(argtypes) == len(params) == len(_lib.PARAMS[name]), name
+        assert _lib.PARAMS[name] == [re.search(r"(\w+)$", p).group(1) for p in params], name
+        fn = getattr(_lib.lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+
+
+SPOT = {
+    "regnet_fps_chain_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    # the float radius sits in the middle
+    "regnet_ball_query_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _i64, _vp, _vp, _vp]),
+    # the seed is a uint64_t
+    "regnet_plane_estimate_f32": (_int, [_vp, _i64, _i64, _u64, _f32, _f32, _f32, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _int,
+                                         _vp]),
+    # one float (depth) and one double (max_sq)
+    "regnet_label_match_f32": (_int, [_vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _f32, _f64, _vp, _vp, _vp]),
+    "regnet_build_info": (ctypes.c_char_p, []),
+    "regnet_strerror": (ctypes.c_char_p, [_int]),
+    "regnet_fps_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(SPOT))
+def test_exact_signature(name):
+    from regnet_for_3d_grasping_amd import _lib
+    restype, argtypes = _lib.SIGNATURES[name]
+    assert restype is SPOT[name][0]
+    assert list(argtypes) == SPOT[name][1]
+
+
+def test_parser_on_strings():
+    from regnet_for_3d_grasping_amd._lib import parse_header
+    sig, par = parse_header("""
+        #include <stdint.h>
+        #define REGNET_X (-1)   /* int regnet_in_a_define(int a); */
+        extern "C" {
+        /* int regnet_commented_out(int a);
+           spans lines */
+        int regnet_none(void);
+        // int regnet_line_comment(int a);
+        const char* regnet_text(int code);
+        int64_t regnet_split(const float* x, int64_t n,
+                             double   scale,
+                             uint8_t* flags, uint64_t seed, float eps,
+                             void* stream);
+        }
+    """)
+    assert sorted(sig) == ["regnet_none", "regnet_split", "regnet_text"]
+    assert sig["regnet_none"] == (_int, []) and par["regnet_none"] == []
+    assert sig["regnet_text"] == (ctypes.c_char_p, [_int])
+    assert sig["regnet_split"] == (_i64, [_vp, _i64, _f64, _vp, _u64, _f32, _vp])
+    assert par["regnet_split"] == ["x", "n", "scale", "flags", "seed", "eps", "stream"]
+
+
+@pytest.mark.parametrize("text, names", [
+    ("int regnet_bad(long double x);", ("regnet_bad", "long double x")),           # a parameter type outside the map
+    ("int regnet_bad(int64_t n, size_t m, void* stream);", ("regnet_bad", "size_t m")),
+    ("int regnet_bad(int64_t);", ("regnet_bad", "int64_t")),                       # no parameter name: not guessed
+    ("unsigned regnet_bad(int a);", ("regnet_bad", "unsigned")),                   # a return type outside the map
+    ("char* regnet_bad(void);", ("regnet_bad", "char*")),                          # only `const char*` is a string return
+    ("int regnet_ok(int a);\nint regnet_bad(int (*cb)(int));", ("regnet_",)),      # a declaration the pattern cannot read
+    ("/* int regnet_only_in_a_comment(void); */\nint other(void);", ("no regnet_",)),
+    ("", ("no regnet_",)),
+])
+def test_parser_refuses_what_it_does_not_know(text, names):
+    from regnet_for_3d_grasping_amd._lib import parse_header
+    with pytest.raises(ImportError) as err:
+        parse_header(text)
+    for n in names:
+        assert n in str(err.value)
+
+
+def test_stream_flag_is_the_last_parameter_named_stream():
+    from regnet_for_3d_grasping_amd import _lib
+    protos = header_prototypes()
+    want = set()
+    for name, params in protos:
+        named = [i for i, p in enumerate(params) if re.search(r"\bstream$", p)]
+        assert named in ([], [len(params) - 1]), "%s: a `stream` parameter that is not the last one" % name
+        if named:
+            assert params[-1] == "void* stream", name
+            want.add(name)
+    assert 0 < len(want) < len(protos)
+    assert {n for n, flag in _lib.HAS_STREAM.items() if flag} == want
+    assert set(_lib.HAS_STREAM) == {n for n, _ in protos}
+
+
+def test_call_passes_queries_through_and_raises_with_the_entry_point_name():
+    """``_lib.call`` without a GPU: an entry point without a stream parameter gets its arguments as they are and its value comes
+    back (the anchor is not looked at); ``check`` names the entry point."""
+    from regnet_for_3d_grasping_amd import _lib
+    assert _lib.call("regnet_fps_workspace_bytes", None, 4, 5120, 1024) == 4 * 5120 * 4
+    assert _lib.call("regnet_abi_version", None) == _lib.lib.regnet_abi_version()
+    with pytest.raises(RuntimeError, match="regnet_fps_f32 failed: shape"):
+        _lib.check(-1, "regnet_fps_f32")
+    with pytest.raises(AttributeError):
+        _lib.call("regnet_no_such_entry", None)

@@ -91,7 +91,8 @@ def test_radius_group_capacity_below_the_count(ops, cap):
     buf = torch.full((B * Nc * cap + 64,), SENTINEL, dtype=torch.int32, device=DEV)
     count = torch.full((B, Nc), SENTINEL, dtype=torch.int32, device=DEV)
     status = _lib.lib.regnet_radius_group_f32(p.data_ptr(), N * 6, 6, c.data_ptr(), Nc * 6, 6, B, N, Nc, T, cap,
-                                              buf.data_ptr() if cap else None, count.data_ptr(), ops._stream(p))
+                                              buf.data_ptr() if cap else None, count.data_ptr(),
+                                              torch.cuda.current_stream(p.device).cuda_stream)
     assert status == 0
     assert np.array_equal(count.cpu().numpy(), want_count)
     buf = buf.cpu().numpy()
