@@ -241,6 +241,17 @@ int regnet_mlp_layer_splitk_f32(const float* A, int64_t lda, int64_t Ka, const f
                                 const float* scale, const float* shift, float* C, int64_t ldc, int64_t P,
                                 int64_t N, int relu, int64_t ksplit, void* workspace, void* stream);
 
+/* regnet_mlp_layer_plan: HOST code, no device and no stream -- which kernel and grid regnet_mlp_layer_f32 takes for these
+ * sizes (the launcher calls the same function, environment switches included).  plan (8 int64, host memory):
+ *   [0] tile rows, [1] tile columns, [2] waves per workgroup, [3] workgroups per CU -- all 0 for the two-buffer kernel of
+ *       mlp.hip (mlp_gemm_kernel, taken when Kpad == 16: fewer than the two k-tiles the LDS-DMA ring starts with);
+ *   [4] k-tiles (of 16 columns) per accumulation slab, 0 = one chain over all of K;
+ *   [5] workgroups that compute one full tile each, [6] tiles of the last partial round that are cut into row slices
+ *       (tail split), [7] slices per such tile (2), 0 when [6] is 0.  The grid is [5] + [6] * [7] workgroups.
+ * Returns what regnet_mlp_layer_f32 returns for these sizes (REGNET_ERR_SHAPE / REGNET_ERR_UNSUPPORTED, plan zeroed);
+ * P == 0: success, plan zeroed; plan == NULL -> REGNET_ERR_NULL.                                                        */
+int regnet_mlp_layer_plan(int64_t P, int64_t N, int64_t Kpad, int pool_group, int64_t* plan);
+
 /* regnet_sa_layer1_f32: first SharedMLP layer of a set-abstraction block with the grouping fused
  * into the operand load (no (B,C,M,K) tensor is materialised; reference: QueryGrouper.forward,
  * modules.py:39-56).  Row p = (b, m, k): A[p] = [feat[b, nbr[p], 0:Cf] | xyz[b,:,nbr[p]] -

@@ -484,14 +484,32 @@ static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 #endif
 #define G2_CUS 256
 
+// The plain-layer tiles: TBM, TBN, WM, WN, STAGES, workgroups per CU.  G2Plan::tile holds the REGNET_G2_TILE number.
+#define G2_TILE_256 256, 128, 4, 2, 3, 2     // 0: 256 x 128, 8 waves
+#define G2_TILE_128 128, 128, 2, 2, 3, 3     // 1: 128 x 128, 4 waves, 3 per CU
+#define G2_TILE_64 64, 128, 1, 4, 3, 4       // 2: 64 x 128, 4 waves: slabs fit
+#define G2_TILE_128W8 128, 128, 4, 2, 3, 2   // 3: 8 waves of 32 x 64: slabs fit (A/B measurements only)
+#define G2_TILE_128S 128, 128, 2, 2, 3, 2    // 8: 4 waves of 64 x 64 at 2 workgroups per CU: slabs fit
+
+// What one plain-layer launch will do: the tile and its grid.  Computed by plan_gemm2 (host arithmetic only), used by
+// launch_gemm2 and reported by regnet_mlp_layer_plan.
+struct G2Plan {
+  int tile;                                   // REGNET_G2_TILE number of the instantiation
+  int tbm, tbn, waves, wg_per_cu, slab_kt;
+  int tiles_m, tiles_n;
+  int main_blocks, tail_tiles, tail_split;    // G2Args
+};
+
 // Tile choice (measured on the ScoreNet shapes, scripts/ablate/g2_bench.cpp): 256 x 128 x 8 waves (2 workgroups per CU)
 // when that grid still fills the chip, 128 x 128 x 4 waves (3 per CU) for few rows or N <= 128.  The last partial
 // round of tiles is cut into half-height slices (tail split) when it would occupy at most half the workgroup slots.
 template <int TBM, int TBN, int WM, int WN, int STAGES, int OCC>
-static int launch_gemm2_tile(G2Args g, bool pool, hipStream_t st) {
-  g.tiles_m = (int)((g.P + TBM - 1) / TBM);
-  g.tiles_n = (g.N + TBN - 1) / TBN;
-  const long long tiles = (long long)g.tiles_m * g.tiles_n;
+static int plan_gemm2_tile(int tile, long long P, int N, bool pool, G2Plan& pl) {
+  pl.tile = tile; pl.tbm = TBM; pl.tbn = TBN; pl.waves = WM * WN; pl.wg_per_cu = OCC;
+  pl.slab_kt = G2Slab<TBM, TBN, WM, WN, OCC>::kt;
+  pl.tiles_m = (int)((P + TBM - 1) / TBM);
+  pl.tiles_n = (N + TBN - 1) / TBN;
+  const long long tiles = (long long)pl.tiles_m * pl.tiles_n;
   if (tiles >= (1ll << 30)) return REGNET_ERR_UNSUPPORTED;
   const long long slots = (long long)G2_CUS * OCC;
   long long main_blocks = tiles, tail_tiles = 0;
@@ -500,8 +518,45 @@ static int launch_gemm2_tile(G2Args g, bool pool, hipStream_t st) {
     const long long rem = tiles % slots;
     if (rem > 0 && rem * 2 <= slots) { main_blocks = tiles - rem; tail_tiles = rem; }
   }
-  g.main_blocks = (int)main_blocks; g.tail_tiles = (int)tail_tiles; g.tail_split = 2;
-  const dim3 grid((unsigned)(main_blocks + 2 * tail_tiles)), block(WM * WN * 64);
+  pl.main_blocks = (int)main_blocks; pl.tail_tiles = (int)tail_tiles; pl.tail_split = 2;
+  if (pool && TBM / WM != 64) return REGNET_ERR_UNSUPPORTED;   // pooling: a wave's 64 rows are one neighbourhood
+  return REGNET_OK;
+}
+
+static int plan_gemm2(long long P, int N, int Kpad, bool pool, G2Plan& pl) {
+  // Tile choice, measured on the step's layer shapes BESIDE a level-1 sampling launch (one CU of every XCD held, the
+  // condition these launches run in: scripts/bench_gemm2_layers.py with SIDE_BLOCKS=8, REGNET_G2_TILE=0/1/2): the hardware's
+  // in-order workgroup rotation then loses a round to every tile that does not fit the first one, so a launch wants either
+  // several rounds of its tile (>= 4 x the CUs) or the smallest tile.  (Alone on the chip the big tile wins from one round
+  // up -- 149 vs 177 us at P = 8192, K = N = 1024 -- but beside the sampling it takes 277 vs 205 us.)
+  static const int force_tile = getenv("REGNET_G2_TILE") ? atoi(getenv("REGNET_G2_TILE")) : -1;   // A/B measurements only
+  if (force_tile == 0) return plan_gemm2_tile<G2_TILE_256>(0, P, N, pool, pl);
+  if (force_tile == 1) return plan_gemm2_tile<G2_TILE_128>(1, P, N, pool, pl);
+  if (force_tile == 2) return plan_gemm2_tile<G2_TILE_64>(2, P, N, pool, pl);
+  if (force_tile == 3 && !pool) return plan_gemm2_tile<G2_TILE_128W8>(3, P, N, pool, pl);
+  if (force_tile == 8 && !pool) return plan_gemm2_tile<G2_TILE_128S>(8, P, N, pool, pl);
+  const long long nt = (N + 127) / 128;
+  const long long t256 = ((P + 255) / 256) * nt, t128 = ((P + 127) / 128) * nt;
+  if (N > 128 && t256 >= 4 * G2_CUS) return plan_gemm2_tile<G2_TILE_256>(0, P, N, pool, pl);
+  // two or more slabs of K and at least one 128 x 128 tile per CU: four waves of 64 x 64 at two workgroups per CU -- at two waves
+  // per SIMD a wave has 256 registers, which hold the slab sums next to the 64 accumulator registers (180 VGPRs, no spill),
+  // and a 64 x 64 wave tile reads half the LDS bytes per MFMA of the 64 x 32 one.  Same order of additions as the 64 x 128
+  // tile: bit-identical (tests/test_gpu_gemm2_tiles.py).  Stand-alone on the step's shapes 4-7 % faster
+  // (profiles/r05_plain_layer_tiles.txt).
+  static const bool t8 = !(getenv("REGNET_G2_T8") && getenv("REGNET_G2_T8")[0] == '0');                 // A/B measurements only
+  if (t8 && !pool && G2_SLAB_KT > 0 && Kpad >= 2 * G2_SLAB_KT * G2_BK && t128 >= G2_CUS)
+    return plan_gemm2_tile<G2_TILE_128S>(8, P, N, pool, pl);
+  // (only the 64 x 128 tile has the registers for slab accumulation -- gemm2.h: G2Slab -- so a layer with two or more
+  // slabs of K takes it even where the 128 x 128 tile would be ~6 % faster: P = 40 960, N = 512, K = 256 / 512 of the
+  // ScoreNet forward, +18 us per step for 0.55e-5 of parity margin, profiles/r04_error_budget.txt)
+  if (t128 >= 4 * G2_CUS && (G2_SLAB_KT == 0 || Kpad < 2 * G2_SLAB_KT * G2_BK || pool))
+    return plan_gemm2_tile<G2_TILE_128>(1, P, N, pool, pl);
+  return plan_gemm2_tile<G2_TILE_64>(2, P, N, pool, pl);
+}
+
+template <int TBM, int TBN, int WM, int WN, int STAGES, int OCC>
+static int launch_gemm2_tile(const G2Args& g, bool pool, hipStream_t st) {
+  const dim3 grid((unsigned)(g.main_blocks + g.tail_split * g.tail_tiles)), block(WM * WN * 64);
   if (pool) {
     if constexpr (TBM / WM == 64) hipLaunchKernelGGL((gemm2_kernel<TBM, TBN, WM, WN, STAGES, OCC, true>), grid, block, 0, st, g);
     else return REGNET_ERR_UNSUPPORTED;
@@ -512,34 +567,50 @@ static int launch_gemm2_tile(G2Args g, bool pool, hipStream_t st) {
   return REGNET_OK;
 }
 
-static int launch_gemm2(const G2Args& g, bool pool, hipStream_t st) {
-  // Tile choice, measured on the step's layer shapes BESIDE a level-1 sampling launch (one CU of every XCD held, the
-  // condition these launches run in: scripts/bench_gemm2_layers.py with SIDE_BLOCKS=8, REGNET_G2_TILE=0/1/2): the hardware's
-  // in-order workgroup rotation then loses a round to every tile that does not fit the first one, so a launch wants either
-  // several rounds of its tile (>= 4 x the CUs) or the smallest tile.  (Alone on the chip the big tile wins from one round
-  // up -- 149 vs 177 us at P = 8192, K = N = 1024 -- but beside the sampling it takes 277 vs 205 us.)
-  static const int force_tile = getenv("REGNET_G2_TILE") ? atoi(getenv("REGNET_G2_TILE")) : -1;   // A/B measurements only
-  if (force_tile == 0) return launch_gemm2_tile<256, 128, 4, 2, 3, 2>(g, pool, st);
-  if (force_tile == 1) return launch_gemm2_tile<128, 128, 2, 2, 3, 3>(g, pool, st);
-  if (force_tile == 2) return launch_gemm2_tile<64, 128, 1, 4, 3, 4>(g, pool, st);
-  if (force_tile == 3 && !pool) return launch_gemm2_tile<128, 128, 4, 2, 3, 2>(g, pool, st);   // 8 waves of 32 x 64: slabs fit
-  if (force_tile == 8 && !pool) return launch_gemm2_tile<128, 128, 2, 2, 3, 2>(g, pool, st);   // 4 waves of 64 x 64 at 2 workgroups per CU: slabs fit
-  const long long nt = (g.N + 127) / 128;
-  const long long t256 = ((g.P + 255) / 256) * nt, t128 = ((g.P + 127) / 128) * nt;
-  if (g.N > 128 && t256 >= 4 * G2_CUS) return launch_gemm2_tile<256, 128, 4, 2, 3, 2>(g, pool, st);
-  // two or more slabs of K and at least one 128 x 128 tile per CU: four waves of 64 x 64 at two workgroups per CU -- at two waves
-  // per SIMD a wave has 256 registers, which hold the slab sums next to the 64 accumulator registers (180 VGPRs, no spill),
-  // and a 64 x 64 wave tile reads half the LDS bytes per MFMA of the 64 x 32 one.  Same order of additions as the 64 x 128
-  // tile: bit-identical.  Stand-alone on the step's shapes 4-7 % faster (profiles/r05_plain_layer_tiles.txt).
-  static const bool t8 = !(getenv("REGNET_G2_T8") && getenv("REGNET_G2_T8")[0] == '0');                 // A/B measurements only
-  if (t8 && !pool && G2_SLAB_KT > 0 && g.Kpad >= 2 * G2_SLAB_KT * G2_BK && t128 >= G2_CUS)
-    return launch_gemm2_tile<128, 128, 2, 2, 3, 2>(g, pool, st);
-  // (only the 64 x 128 tile has the registers for slab accumulation -- gemm2.h: G2Slab -- so a layer with two or more
-  // slabs of K takes it even where the 128 x 128 tile would be ~6 % faster: P = 40 960, N = 512, K = 256 / 512 of the
-  // ScoreNet forward, +18 us per step for 0.55e-5 of parity margin, profiles/r04_error_budget.txt)
-  if (t128 >= 4 * G2_CUS && (G2_SLAB_KT == 0 || g.Kpad < 2 * G2_SLAB_KT * G2_BK || pool))
-    return launch_gemm2_tile<128, 128, 2, 2, 3, 3>(g, pool, st);
-  return launch_gemm2_tile<64, 128, 1, 4, 3, 4>(g, pool, st);
+static int launch_gemm2(G2Args g, const G2Plan& pl, bool pool, hipStream_t st) {
+  g.tiles_m = pl.tiles_m; g.tiles_n = pl.tiles_n;
+  g.main_blocks = pl.main_blocks; g.tail_tiles = pl.tail_tiles; g.tail_split = pl.tail_split;
+  switch (pl.tile) {
+    case 0: return launch_gemm2_tile<G2_TILE_256>(g, pool, st);
+    case 1: return launch_gemm2_tile<G2_TILE_128>(g, pool, st);
+    case 2: return launch_gemm2_tile<G2_TILE_64>(g, pool, st);
+    case 3: return launch_gemm2_tile<G2_TILE_128W8>(g, pool, st);
+    case 8: return launch_gemm2_tile<G2_TILE_128S>(g, pool, st);
+  }
+  return REGNET_ERR_UNSUPPORTED;
+}
+
+// Which kernel a plain layer of these sizes takes and with which grid: the size checks of regnet_mlp_layer_f32 and the
+// choice its launch uses.  gemm2 == false: mlp_gemm_kernel<0, pool> (128 x 128 tiles, one block each).
+struct MlpLayerPlan { bool gemm2; G2Plan g2; long long blocks; };
+static int plan_mlp_layer(long long P, long long N, long long Kpad, int pool_group, MlpLayerPlan& pl) {
+  pl = MlpLayerPlan{};
+  if (P < 0 || N <= 0 || Kpad <= 0 || Kpad % BK) return REGNET_ERR_SHAPE;
+  if (pool_group != 0 && (pool_group != 64 || P % 64)) return REGNET_ERR_UNSUPPORTED;
+  if (P == 0) return REGNET_OK;
+  static const bool use_gemm2 = MLP_USE_GEMM2 && !(getenv("REGNET_GEMM2") && getenv("REGNET_GEMM2")[0] == '0');   // debugging switch
+  if (use_gemm2 && Kpad >= 2 * G2_BK) {   // LDS-DMA ring kernel (gemm2.h); needs two k-tiles for its prologue
+    pl.gemm2 = true;
+    return plan_gemm2(P, (int)N, (int)Kpad, pool_group != 0, pl.g2);
+  }
+  pl.blocks = ((P + BM - 1) / BM) * ((N + BN - 1) / BN);
+  return pl.blocks >= (1ll << 31) ? REGNET_ERR_UNSUPPORTED : REGNET_OK;
+}
+
+extern "C" int regnet_mlp_layer_plan(int64_t P, int64_t N, int64_t Kpad, int pool_group, int64_t* plan) {
+  if (!plan) return REGNET_ERR_NULL;
+  for (int i = 0; i < 8; ++i) plan[i] = 0;
+  MlpLayerPlan pl;
+  const int rc = plan_mlp_layer(P, N, Kpad, pool_group, pl);
+  if (rc != REGNET_OK || P == 0) return rc;
+  if (pl.gemm2) {
+    const G2Plan& g = pl.g2;
+    plan[0] = g.tbm; plan[1] = g.tbn; plan[2] = g.waves; plan[3] = g.wg_per_cu; plan[4] = g.slab_kt;
+    plan[5] = g.main_blocks; plan[6] = g.tail_tiles; plan[7] = g.tail_tiles ? g.tail_split : 0;
+  } else {
+    plan[5] = pl.blocks;
+  }
+  return REGNET_OK;
 }
 
 extern "C" int regnet_mlp_layer_f32(const float* A, int64_t lda, int64_t Ka, const float* W, int64_t Kpad,
@@ -550,12 +621,14 @@ extern "C" int regnet_mlp_layer_f32(const float* A, int64_t lda, int64_t Ka, con
   if (P == 0) return REGNET_OK;
   if (!A || !W || !scale || !shift || !C) return REGNET_ERR_NULL;
   if (!aligned16(A) || !aligned16(W)) return REGNET_ERR_SHAPE;
-  static const bool use_gemm2 = MLP_USE_GEMM2 && !(getenv("REGNET_GEMM2") && getenv("REGNET_GEMM2")[0] == '0');   // debugging switch
-  if (use_gemm2 && Kpad >= 2 * G2_BK) {   // LDS-DMA ring kernel (gemm2.h); needs two k-tiles for its prologue
+  MlpLayerPlan pl;
+  const int rc = plan_mlp_layer(P, N, Kpad, pool_group, pl);
+  if (rc != REGNET_OK) return rc;
+  if (pl.gemm2) {
     G2Args g = {};
     g.A = A; g.lda = lda; g.Ka = (int)Ka; g.W = W; g.Kpad = (int)Kpad; g.scale = scale; g.shift = shift;
     g.C = C; g.ldc = ldc; g.P = P; g.N = (int)N; g.relu = relu;
-    return launch_gemm2(g, pool_group != 0, as_stream(stream));
+    return launch_gemm2(g, pl.g2, pool_group != 0, as_stream(stream));
   }
   MlpArgs a = {};
   a.A = A; a.lda = lda; a.Ka = (int)Ka;

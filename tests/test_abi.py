@@ -56,6 +56,46 @@ def test_argument_checks_without_gpu():
         _lib.check(-1, "x")
 
 
+def test_mlp_layer_argument_checks_without_gpu():
+    """regnet_mlp_layer_f32 / regnet_mlp_layer_splitk_f32 return before any launch for every argument they reject (and for an
+    empty layer), so invented addresses are never read: 0x1000 stands for a 16-byte aligned buffer."""
+    from regnet_for_3d_grasping_amd import _lib
+    L = _lib.lib
+    SHAPE, NULL, UNSUPPORTED = -1, -2, -3
+    p = 0x1000
+
+    def layer(A=p, lda=64, Ka=64, W=p, Kpad=64, scale=p, shift=p, C=p, ldc=128, P=128, N=128, relu=1, pool=0):
+        return L.regnet_mlp_layer_f32(A, lda, Ka, W, Kpad, scale, shift, C, ldc, P, N, relu, pool, None)
+
+    assert layer(Ka=62) == SHAPE and layer(Ka=2, lda=4) == SHAPE            # Ka % 4
+    assert layer(lda=66) == SHAPE                                            # lda % 4
+    assert layer(Kpad=72, Ka=64) == SHAPE and layer(Kpad=8, Ka=8) == SHAPE   # Kpad % 16
+    assert layer(Ka=68, lda=68) == SHAPE                                     # Ka > Kpad
+    assert layer(P=-1) == SHAPE and layer(N=0) == SHAPE and layer(Kpad=0, Ka=0) == SHAPE and layer(Ka=-4) == SHAPE
+    assert layer(A=p + 4) == SHAPE and layer(A=p + 8) == SHAPE and layer(W=p + 4) == SHAPE   # 16-byte alignment of A / W
+    for pool in (1, 32, 63, 65, 128, -64):
+        assert layer(pool=pool) == UNSUPPORTED
+    assert layer(P=100, pool=64) == UNSUPPORTED and layer(P=64 * 3 + 1, pool=64) == UNSUPPORTED
+    assert layer(P=0) == 0 and layer(P=0, pool=64) == 0 and layer(P=0, A=None, W=None, scale=None, shift=None, C=None) == 0
+    for name in ("A", "W", "scale", "shift", "C"):
+        assert layer(**{name: None}) == NULL, name
+    # order: shape before pooling support before the empty layer before the pointers
+    assert layer(Ka=62, pool=32) == SHAPE and layer(P=0, pool=32) == UNSUPPORTED and layer(A=None, W=p + 4) == NULL
+
+    def splitk(A=p, lda=64, Ka=64, W=p, Kpad=64, scale=p, shift=p, C=p, ldc=128, P=128, N=128, relu=1, ksplit=2, ws=p):
+        return L.regnet_mlp_layer_splitk_f32(A, lda, Ka, W, Kpad, scale, shift, C, ldc, P, N, relu, ksplit, ws, None)
+
+    assert splitk(Ka=62) == SHAPE and splitk(lda=66) == SHAPE and splitk(Kpad=72) == SHAPE and splitk(Ka=68, lda=68) == SHAPE
+    assert splitk(ksplit=0) == SHAPE and splitk(ksplit=5) == UNSUPPORTED     # at most Kpad / 16 slices
+    assert splitk(P=0) == 0
+    for name in ("A", "W", "scale", "shift", "C", "ws"):
+        assert splitk(**{name: None}) == NULL, name
+    assert splitk(ksplit=1, ws=None, A=p + 4) == SHAPE                       # one slice needs no workspace
+    assert splitk(A=p + 4) == SHAPE and splitk(W=p + 8) == SHAPE and splitk(ws=p + 4) == SHAPE
+    assert L.regnet_mlp_splitk_workspace_bytes(70, 130, 33) == 33 * 70 * 132 * 4
+    assert L.regnet_mlp_splitk_workspace_bytes(70, 130, 1) == 0
+
+
 def test_binding_rejects_cpu_tensors_like_check_cuda():
     from regnet_for_3d_grasping_amd import dgcnn_ext, pn2_ext, region_ops
     x = torch.zeros(1, 3, 8)

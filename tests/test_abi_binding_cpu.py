@@ -52,6 +52,8 @@ SPOT = {
     "regnet_build_info": (ctypes.c_char_p, []),
     "regnet_strerror": (ctypes.c_char_p, [_int]),
     "regnet_fps_workspace_bytes": (_i64, [_i64, _i64, _i64]),
+    # host-only query: sizes, an int, a host pointer, no stream
+    "regnet_mlp_layer_plan": (_int, [_i64, _i64, _i64, _int, _vp]),
 }
 
 
