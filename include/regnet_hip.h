@@ -45,12 +45,8 @@ const char* regnet_strerror(int code);
  * Errors: M<=0 or N<M -> REGNET_ERR_SHAPE (CHECK_GT/CHECK_GE :136-137).                        */
 int regnet_fps_f32(const float* xyz, int64_t sb, int64_t sc, int64_t sn, int64_t B, int64_t N,
                    int64_t M, int64_t* index, float* workspace, void* stream);
-/* Scratch bytes regnet_fps_f32 needs for (B,N,M): 0 for N <= 4096 and for short runs (register-resident kernels);
- * B*N*4 for long runs (M >= 512 over 4096 < N <= 8192 points, 1024 <= M <= 8192 over 8192 < N <= 25600 points:
- * fps_cluster_kernel keeps the permutation of its in-kernel Morton sort there); beyond 25600 points B*N*4 (rounded
- * up to 16 bytes: the permutation, or the reference's `temp` tensor, sampling_kernel.cu:142) + 16640 bytes per scene
- * through which the 2-4 cooperating workgroups of a scene exchange their candidate records + 256 bytes (status word).  The callee
- * initialises it; `workspace` may be NULL when this returns 0.                                   */
+/* Scratch bytes regnet_fps_f32 needs for (B,N,M) -- regnet_fps_plan's [6], which says what they hold.  The callee
+ * initialises them; `workspace` may be NULL when this returns 0.                                */
 int64_t regnet_fps_workspace_bytes(int64_t B, int64_t N, int64_t M);
 /* regnet_fps_f32 for a cloud that is itself a furthest-point-sampling sequence -- what PointNet++ does at levels 2 and 3:
  * FarthestPointSampler over the previous level's centroids in their pick order (pointnet2.py:40-42, modules.py:23-26).
@@ -73,6 +69,23 @@ int regnet_fps_chain_f32(const float* xyz, int64_t sb, int64_t sc, int64_t sn, i
  * then incomplete.  The callee zeroes the word; the caller reads it once the stream has passed the launch (the Python
  * binding accumulates it into a per-device flag and raises lazily: pn2_ext.raise_if_fps_failed).                      */
 int64_t regnet_fps_status_offset_bytes(int64_t B, int64_t N, int64_t M);
+/* regnet_fps_plan: HOST code, no device and no stream -- which kernel, grid and workspace regnet_fps_f32 and
+ * regnet_fps_chain_f32 take for these sizes (the launcher and the two queries above call the same function; the only input
+ * besides the sizes is the device's compute-unit count, 256 where there is no device).  plan (9 int64, host memory):
+ *   [0] kernel family: 1 fps_resident_kernel (points in registers, one pick per round), 2 fps_cluster_kernel (Morton-sorted,
+ *       pruning per 64-point cluster, several picks per round), 3 fps_sorted_kernel (sorted, pruning per wave), 4
+ *       fps_cluster_kernel on cooperating workgroups, 5 fps_multi_kernel (cooperating workgroups, one pick per round),
+ *       6 fps_streaming_kernel (running distances in the workspace); 0: nothing is launched (B == 0);
+ *   [1] threads per workgroup, [2] points per thread (0 for family 6);
+ *   [3] workgroups per scene G, [4] scenes padded to a multiple of 8 when G > 1 (else B), [5] grid = [3] * [4] workgroups;
+ *   [6] workspace bytes: B*N*4 for family 2 (the sort's permutation); families 4-6 are all sized B*N*4 (the permutation /
+ *       the running distances; family 5 leaves these words unused), rounded up to 16, + 16640 bytes of exchange area per
+ *       scene + 256 bytes for the status word;
+ *   [7] byte offset of the exchange area in the workspace (family 5 keeps its 64 bytes per scene at offset 0), -1: none;
+ *   [8] byte offset of the status word = regnet_fps_status_offset_bytes, -1: none (every family but 4).
+ * Returns what regnet_fps_f32 returns for these sizes before it looks at a pointer (REGNET_ERR_SHAPE, or REGNET_ERR_UNSUPPORTED
+ * for N >= 2^30: plan zeroed); B == 0: success, [0]-[6] zero, [7] = [8] = -1; plan == NULL -> REGNET_ERR_NULL.                 */
+int regnet_fps_plan(int64_t B, int64_t N, int64_t M, int64_t* plan);
 
 /* ---- pn2_ext.ball_query  (csrc/ball_query.h:7-11, ball_query_kernel.cu:87-131) ---------------
  * xyz (B,3,N1) strided, centroids (B,3,N2) strided -> index (B,N2,K) int64, count (B,N2) int64.

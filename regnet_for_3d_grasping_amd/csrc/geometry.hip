@@ -7,6 +7,9 @@
 //   FPS        csrc/sampling_kernel.cu:47-117
 //   ball query csrc/ball_query_kernel.cu:31-74
 //   3-NN       csrc/interpolate_kernel.cu:28-77
+#include <type_traits>
+#include <utility>
+
 #include "common.h"
 
 
@@ -1261,7 +1264,6 @@ static int ref_block_log2(int64_t n) {  // csrc/sampling_kernel.cu:32-40 + the >
 }
 
 #define FPS_RESIDENT_MAX 25600
-
 #define FPS_MULTI_MAX (4 * FPS_RESIDENT_MAX)
 
 static int fps_num_cus() {
@@ -1276,6 +1278,7 @@ static int fps_num_cus() {
   return n;
 }
 
+// Measurement switches: inputs of fps_plan and of nothing else.
 #ifndef FPS_CLUSTERS
 #define FPS_CLUSTERS 1   // 1: fps_cluster_kernel (pruning per 64-point cluster); 0: fps_sorted_kernel (per wave)
 #endif
@@ -1286,7 +1289,7 @@ static int fps_num_cus() {
 #define FPS_COOP_MIN_N FPS_RESIDENT_MAX   // scenes with MORE points sample on cooperating workgroups ...
 #endif
 #ifndef FPS_COOP_SLICE
-#define FPS_COOP_SLICE FPS_RESIDENT_MAX   // ... ceil(N / this) of them (measurement builds lower both: scripts/fps_coop_probe.sh)
+#define FPS_COOP_SLICE FPS_RESIDENT_MAX   // ... ceil(N / this) of them (measurement builds lower both: scripts/fps_coop_probe.py)
 #endif
 #ifndef FPS_CLUSTER_MIN_PICKS_SMALL
 #define FPS_CLUSTER_MIN_PICKS_SMALL 512   // 4096 < N <= 8192: runs at least this long take the cluster kernel too
@@ -1295,64 +1298,135 @@ static int fps_num_cus() {
 #define FPS_CLUSTER_PICKS 8
 #endif
 
-// 8 192 < N <= 25 600 with M >= 1024 (fps_cluster_kernel): N words per scene for the sort's permutation.
-// N > 25 600: 64 bytes of exchange slots per scene for the multi-workgroup kernel, or (scenes that do not fit it) a (B,N)
-// float array of running distances for the streaming kernel.  The callee initialises the workspace.
-static const bool fps_coop_enabled = FPS_CLUSTERS != 0 && FPS_COOP != 0;
-static int64_t fps_xchg_offset_floats(int64_t B, int64_t N) { return (B * N + 3) / 4 * 4; }   // 16-byte aligned behind B x N words
+// The points-per-thread ladder: a scene (or a cooperating workgroup's slice of one) of up to `n` points is held by `threads`
+// threads with `ppt` points each.  The in-thread scan keeps the first strict maximum in slot order; that equals the reference's
+// order only if all points of a thread share one reference lane (j mod RB), i.e. T % RB == 0 or one point per thread.  Hence
+// T = RB (PPT 1) up to 512 points and T in {512, 1024} above.
+struct FpsTile { int n, threads, ppt; };
+static constexpr FpsTile fps_tiles[] = {{64, 64, 1},      {128, 128, 1},    {256, 256, 1},    {512, 512, 1},   {1024, 512, 2},
+                                        {2048, 512, 4},   {4096, 512, 8},   {6144, 1024, 6},  {8192, 1024, 8}, {12288, 1024, 12},
+                                        {16384, 1024, 16}, {20480, 1024, 20}, {FPS_RESIDENT_MAX, 1024, 25}};
+enum { FPS_TILES = sizeof(fps_tiles) / sizeof(fps_tiles[0]) };
+static_assert(FPS_COOP_SLICE <= FPS_RESIDENT_MAX, "a slice is held by one workgroup");
 
-static bool fps_takes_coop_cluster_kernel(int64_t B, int64_t N, int64_t M);
-extern "C" int64_t regnet_fps_workspace_bytes(int64_t B, int64_t N, int64_t M) {
-  (void)M;
-  if (N <= FPS_RESIDENT_MAX && fps_takes_coop_cluster_kernel(B, N, M))   // (measurement builds only: FPS_COOP_MIN_N < FPS_RESIDENT_MAX)
-    return fps_xchg_offset_floats(B, N) * (int64_t)sizeof(float) + B * (int64_t)FPS_XCHG_BYTES + FPS_STATUS_BYTES;
-#if FPS_CLUSTERS
-  if (N > 8192 && N <= FPS_RESIDENT_MAX && M >= 1024 && M <= FPS_CLUSTER_MAX_PICKS)
-    return B * N * (int64_t)sizeof(unsigned);   // fps_cluster_kernel: the sort's permutation
-  if (N > 4096 && N <= 8192 && M >= FPS_CLUSTER_MIN_PICKS_SMALL) return B * N * (int64_t)sizeof(unsigned);
-#endif
-  if (N <= FPS_RESIDENT_MAX) return 0;
-  // beyond one CU: the streaming kernel's running distances / the cooperative cluster kernel's permutation (B x N words
-  // either way) followed by the cooperative kernels' exchange area
-  return fps_xchg_offset_floats(B, N) * (int64_t)sizeof(float) + B * (int64_t)FPS_XCHG_BYTES + FPS_STATUS_BYTES;
+// The one place a run-time row of fps_tiles becomes template arguments: f(std::integral_constant<int, tile>), false if f
+// launched nothing.
+template <class F, int... I>
+static bool fps_with_tile(int tile, F f, std::integer_sequence<int, I...>) {
+  return ((tile == I && f(std::integral_constant<int, I>{})) || ...);
 }
 
-// scenes beyond one CU's registers whose sampling runs on 2..4 cooperating workgroups (fps_cluster_kernel<.., true>)
-static bool fps_takes_coop_cluster_kernel(int64_t B, int64_t N, int64_t M) {
-  return fps_coop_enabled && N > FPS_COOP_MIN_N && N <= FPS_MULTI_MAX && M >= 1024 && M <= FPS_CLUSTER_MAX_PICKS &&
-         ((N + FPS_COOP_SLICE - 1) / FPS_COOP_SLICE) <= 4 && ((N + FPS_COOP_SLICE - 1) / FPS_COOP_SLICE) * B <= fps_num_cus();
+// kernel families, regnet_fps_plan's [0]: from FPS_FAM_COOP up a launch wants the exchange area's bytes
+enum { FPS_FAM_NONE = 0, FPS_FAM_RESIDENT, FPS_FAM_CLUSTER, FPS_FAM_SORTED, FPS_FAM_COOP, FPS_FAM_MULTI, FPS_FAM_STREAMING };
+// by family: the first row of fps_tiles its kernel is instantiated for (the plan takes no smaller one, the launch compiles no other)
+static constexpr int fps_first_tile[] = {0, 0, 7, 9, 9, FPS_TILES - 1, FPS_TILES - 1};
+
+// What (B, N, M) takes, regnet_fps_plan's words (include/regnet_hip.h) with the row of fps_tiles in place of [1] and [2].
+struct FpsPlan {
+  int family, tile, G, Bpad;
+  int64_t grid, ws_bytes, xchg_off, status_off;
+};
+
+// The only place that knows the thresholds; no device pointer, no stream.  Returns what fps_launch returns for these sizes
+// before it looks at a pointer.
+static int fps_plan(int64_t B, int64_t N, int64_t M, FpsPlan& p) {
+  p = FpsPlan{};
+  p.xchg_off = p.status_off = -1;
+  if (M <= 0 || N < M || B < 0) return REGNET_ERR_SHAPE;
+  if (N >= (int64_t)1 << 30) return REGNET_ERR_UNSUPPORTED;
+  if (B == 0) return REGNET_OK;
+  const int64_t Gc = (N + FPS_COOP_SLICE - 1) / FPS_COOP_SLICE, Gm = (N + FPS_RESIDENT_MAX - 1) / FPS_RESIDENT_MAX;
+  // the counting-sort prologue of the sorting kernels costs ~0.7 ms: only worth it for long runs (4096 < N <= 8192 is level 2
+  // of the network: 1024 picks of 5120 points)
+  const bool long_run = N > 8192 ? M >= 1024 : N > 4096 && FPS_CLUSTERS && M >= FPS_CLUSTER_MIN_PICKS_SMALL;
+  const bool fits_lds = M <= FPS_CLUSTER_MAX_PICKS;   // fps_cluster_kernel keeps the picks of one launch in LDS
+  p.G = 1;
+  if (FPS_CLUSTERS && FPS_COOP && N > FPS_COOP_MIN_N && N <= FPS_MULTI_MAX && M >= 1024 && fits_lds && Gc <= 4 &&
+      Gc * B <= fps_num_cus()) {
+    // several exact picks per round on 2..4 cooperating workgroups per scene (fps_cluster_kernel<.., true>)
+    p.family = FPS_FAM_COOP; p.G = (int)Gc;
+  } else if (N <= FPS_RESIDENT_MAX) {
+    p.family = !long_run ? FPS_FAM_RESIDENT : FPS_CLUSTERS && fits_lds ? FPS_FAM_CLUSTER : FPS_FAM_SORTED;
+  } else if (N <= FPS_MULTI_MAX && M < 32768 /* 15-bit round tag */ && Gm * B <= fps_num_cus()) {
+    p.family = FPS_FAM_MULTI; p.G = (int)Gm;   // 2..4 workgroups (whole CUs) per scene
+  } else {
+    p.family = FPS_FAM_STREAMING;              // running distances in the workspace, any N
+  }
+  // the points one workgroup holds in registers (the multi-workgroup and streaming kernels: always the last row)
+  for (p.tile = fps_first_tile[p.family]; p.tile < FPS_TILES - 1 && fps_tiles[p.tile].n < (N + p.G - 1) / p.G; ++p.tile) {}
+  p.Bpad = p.G > 1 ? (int)((B + 7) / 8 * 8) : (int)B;
+  p.grid = (int64_t)p.Bpad * p.G;
+  const int64_t words = B * N * (int64_t)sizeof(float);
+  if (p.family == FPS_FAM_CLUSTER) p.ws_bytes = words;
+  if (p.family >= FPS_FAM_COOP) {   // beyond one CU: the exchange area, 16-byte aligned behind the B x N words, and the status word
+    const int64_t behind = (words + 15) / 16 * 16;
+    p.ws_bytes = behind + B * (int64_t)FPS_XCHG_BYTES + FPS_STATUS_BYTES;
+    if (p.family == FPS_FAM_COOP) { p.xchg_off = behind; p.status_off = behind + B * (int64_t)FPS_XCHG_BYTES; }
+    if (p.family == FPS_FAM_MULTI) p.xchg_off = 0;   // 64 bytes per scene at the front: it keeps no B x N words
+  }
+  return REGNET_OK;
 }
 
-extern "C" int64_t regnet_fps_status_offset_bytes(int64_t B, int64_t N, int64_t M) {
-  if (!fps_takes_coop_cluster_kernel(B, N, M)) return -1;
-  return fps_xchg_offset_floats(B, N) * (int64_t)sizeof(float) + B * (int64_t)FPS_XCHG_BYTES;
+extern "C" int regnet_fps_plan(int64_t B, int64_t N, int64_t M, int64_t* plan) {
+  if (!plan) return REGNET_ERR_NULL;
+  FpsPlan p;
+  const int rc = fps_plan(B, N, M, p);
+  const FpsTile t = p.family == FPS_FAM_NONE ? FpsTile{} : fps_tiles[p.tile];
+  const int64_t out[9] = {p.family, t.threads, p.family == FPS_FAM_STREAMING ? 0 : t.ppt, p.G, p.Bpad, p.grid, p.ws_bytes,
+                          p.xchg_off, p.status_off};
+  for (int i = 0; i < 9; ++i) plan[i] = rc == REGNET_OK ? out[i] : 0;
+  return rc;
 }
 
-#define FPS_CASE(T, PPT)                                                                                  \
-  hipLaunchKernelGGL((fps_resident_kernel<T, PPT>), dim3((unsigned)B), dim3(T), 0, st, xyz, sb, sc, sn, \
-                     (int)N, (int)M, rbl, index, prefix_ok, first_tie)
-
-#define FPS_WAVE_CASE(PPT)                                                                                       \
-  hipLaunchKernelGGL((fps_sorted_kernel<PPT, FPS_PICKS>), dim3((unsigned)B), dim3(1024), 0, st, xyz, sb, sc, sn, \
-                     (int)N, (int)M, rbl, index, prefix_ok, first_tie)
-#if FPS_CLUSTERS
-#define FPS_CLUSTER_LIMIT FPS_CLUSTER_MAX_PICKS
-#define FPS_SORTED_CASE(PPT)                                                                                          \
-  hipLaunchKernelGGL((fps_cluster_kernel<PPT, FPS_CLUSTER_PICKS, false>), dim3((unsigned)B), dim3(1024), 0, st, xyz, \
-                     sb, sc, sn, (int)N, (int)M, rbl, reinterpret_cast<unsigned*>(workspace), index, 1, (int)B, (int)B,    \
-                     (float*)nullptr, prefix_ok, first_tie)
-// G cooperating workgroups per scene; the exchange area sits behind the B x N permutation words of the workspace
-#define FPS_COOP_CASE(PPT)                                                                                                \
-  hipLaunchKernelGGL((fps_cluster_kernel<PPT, FPS_CLUSTER_PICKS, true>), dim3((unsigned)(Bpad * G)), dim3(1024), 0, st,   \
-                     xyz, sb, sc, sn, (int)N, (int)M, rbl, reinterpret_cast<unsigned*>(workspace), index, G, (int)B, Bpad, \
-                     workspace + fps_xchg_offset_floats(B, N), prefix_ok, first_tie)
-#else
-#define FPS_CLUSTER_LIMIT (1 << 30)
-#define FPS_SORTED_CASE(PPT) FPS_WAVE_CASE(PPT)
-#endif
+static FpsPlan fps_plan_of(int64_t B, int64_t N, int64_t M) { FpsPlan p; fps_plan(B, N, M, p); return p; }
+extern "C" int64_t regnet_fps_workspace_bytes(int64_t B, int64_t N, int64_t M) { return fps_plan_of(B, N, M).ws_bytes; }
+extern "C" int64_t regnet_fps_status_offset_bytes(int64_t B, int64_t N, int64_t M) { return fps_plan_of(B, N, M).status_off; }
 
 static int fps_launch(const float* xyz, int64_t sb, int64_t sc, int64_t sn, int64_t B, int64_t N, int64_t M, int64_t* index,
-                      float* workspace, const int* prefix_ok, int* first_tie, void* stream);
+                      float* workspace, const int* prefix_ok, int* first_tie, void* stream) {
+  FpsPlan p;
+  const int rc = fps_plan(B, N, M, p);
+  if (rc != REGNET_OK || B == 0) return rc;
+  if (!xyz || !index || (p.ws_bytes > 0 && !workspace)) return REGNET_ERR_NULL;
+  hipStream_t st = as_stream(stream);
+  hipError_t e = hipSuccess;
+  if (p.family == FPS_FAM_COOP)    // tags 0 = nothing published, status 0 = no poll gave up
+    e = hipMemsetAsync(workspace + p.xchg_off / 4, 0, (size_t)B * FPS_XCHG_BYTES + FPS_STATUS_BYTES, st);
+  if (p.family == FPS_FAM_MULTI) e = hipMemsetAsync(workspace, 0, (size_t)B * 64, st);   // round tag 0 = "nothing published"
+  if (e != hipSuccess) return (int)e;
+  if (first_tie && p.family >= FPS_FAM_MULTI &&   // (no tie tracking, no shortcut: "unknown")
+      (e = hipMemsetAsync(first_tie, 0, (size_t)B * sizeof(int), st)) != hipSuccess)
+    return (int)e;
+  const int rbl = ref_block_log2(N), n = (int)N, m = (int)M, b = (int)B;
+  const dim3 grid((unsigned)p.grid), block((unsigned)fps_tiles[p.tile].threads);
+  unsigned* const perm = reinterpret_cast<unsigned*>(workspace);                        // the sort's permutation: B x N words
+  float* const xchg = p.family == FPS_FAM_COOP ? workspace + p.xchg_off / 4 : nullptr;
+  // every launch starts with the same arguments; a family's kernel exists from fps_first_tile up
+#define FPS_LAUNCH(FAMILY, KERNEL, ...)                                                                              \
+  case FAMILY:                                                                                                       \
+    if constexpr (tile < fps_first_tile[FAMILY]) return false;                                                       \
+    else { hipLaunchKernelGGL(KERNEL, grid, block, 0, st, xyz, sb, sc, sn, n, m, rbl, __VA_ARGS__); return true; }
+  const bool launched = fps_with_tile(p.tile, [&](auto I) {
+    constexpr int tile = decltype(I)::value;
+    constexpr FpsTile t = fps_tiles[tile];
+    switch (p.family) {
+      FPS_LAUNCH(FPS_FAM_RESIDENT, (fps_resident_kernel<t.threads, t.ppt>), index, prefix_ok, first_tie)
+      FPS_LAUNCH(FPS_FAM_SORTED, (fps_sorted_kernel<t.ppt, FPS_PICKS>), index, prefix_ok, first_tie)
+#if FPS_CLUSTERS
+      FPS_LAUNCH(FPS_FAM_CLUSTER, (fps_cluster_kernel<t.ppt, FPS_CLUSTER_PICKS, false>), perm, index, p.G, b, p.Bpad, xchg,
+                 prefix_ok, first_tie)
+      FPS_LAUNCH(FPS_FAM_COOP, (fps_cluster_kernel<t.ppt, FPS_CLUSTER_PICKS, true>), perm, index, p.G, b, p.Bpad, xchg,
+                 prefix_ok, first_tie)
+#endif
+      FPS_LAUNCH(FPS_FAM_MULTI, (fps_multi_kernel<t.ppt>), p.G, b, p.Bpad, (unsigned long long*)workspace, index)
+      FPS_LAUNCH(FPS_FAM_STREAMING, (fps_streaming_kernel<t.threads>), workspace, index)
+    }
+    return false;
+  }, std::make_integer_sequence<int, FPS_TILES>{});
+  if (!launched) return REGNET_ERR_UNSUPPORTED;   // a (family, tile) no kernel is compiled for: never OK with index unwritten
+  REGNET_LAUNCH_CHECK();
+  return REGNET_OK;
+}
 
 extern "C" int regnet_fps_f32(const float* xyz, int64_t sb, int64_t sc, int64_t sn, int64_t B, int64_t N, int64_t M,
                               int64_t* index, float* workspace, void* stream) {
@@ -1363,80 +1437,6 @@ extern "C" int regnet_fps_chain_f32(const float* xyz, int64_t sb, int64_t sc, in
                                     int64_t* index, float* workspace, const int32_t* prefix_ok, int32_t* first_tie,
                                     void* stream) {
   return fps_launch(xyz, sb, sc, sn, B, N, M, index, workspace, prefix_ok, first_tie, stream);
-}
-
-static int fps_launch(const float* xyz, int64_t sb, int64_t sc, int64_t sn, int64_t B, int64_t N, int64_t M, int64_t* index,
-                      float* workspace, const int* prefix_ok, int* first_tie, void* stream) {
-  if (M <= 0 || N < M || B < 0) return REGNET_ERR_SHAPE;
-  if (N >= (int64_t)1 << 30) return REGNET_ERR_UNSUPPORTED;
-  if (B == 0) return REGNET_OK;
-  if (!xyz || !index) return REGNET_ERR_NULL;
-  hipStream_t st = as_stream(stream);
-  const int rbl = ref_block_log2(N);
-  // The in-thread scan keeps the first strict maximum in slot order; that equals the reference's
-  // order only if all points of a thread share one reference lane (j mod RB), i.e. T % RB == 0 or
-  // one point per thread.  Hence T = RB (PPT 1) up to 512 points and T in {512, 1024} above.
-  if (regnet_fps_workspace_bytes(B, N, M) > 0 && !workspace) return REGNET_ERR_NULL;
-  const bool coop = fps_takes_coop_cluster_kernel(B, N, M);
-  if (coop) {
-    // several exact picks per round on 2..4 cooperating workgroups per scene (fps_cluster_kernel<.., true>)
-    if (!workspace) return REGNET_ERR_NULL;
-    const int G = (int)((N + FPS_COOP_SLICE - 1) / FPS_COOP_SLICE);
-    const int Bpad = (int)((B + 7) / 8 * 8);                                       // a scene's workgroups on one XCD
-    const int64_t Nh = (N + G - 1) / G;
-    hipError_t e = hipMemsetAsync(workspace + fps_xchg_offset_floats(B, N), 0, (size_t)B * FPS_XCHG_BYTES + FPS_STATUS_BYTES,
-                                  st);   // tags 0 = nothing published, status 0 = no poll gave up
-    if (e != hipSuccess) return (int)e;
-    if (Nh <= 12288) FPS_COOP_CASE(12);
-    else if (Nh <= 16384) FPS_COOP_CASE(16);
-    else if (Nh <= 20480) FPS_COOP_CASE(20);
-    else FPS_COOP_CASE(25);
-  }
-  else if (N <= 64) FPS_CASE(64, 1);
-  else if (N <= 128) FPS_CASE(128, 1);
-  else if (N <= 256) FPS_CASE(256, 1);
-  else if (N <= 512) FPS_CASE(512, 1);
-  else if (N <= 1024) FPS_CASE(512, 2);
-  else if (N <= 2048) FPS_CASE(512, 4);
-  else if (N <= 4096) FPS_CASE(512, 8);
-  else if (N <= 6144 && (M < FPS_CLUSTER_MIN_PICKS_SMALL || !FPS_CLUSTERS)) FPS_CASE(1024, 6);
-  else if (N <= 8192 && (M < FPS_CLUSTER_MIN_PICKS_SMALL || !FPS_CLUSTERS)) FPS_CASE(1024, 8);
-  else if (N <= 6144) FPS_SORTED_CASE(6);      // level 2 of the network: 1024 picks of 5120 points
-  else if (N <= 8192) FPS_SORTED_CASE(8);
-  // the counting-sort prologue of the sorted kernel costs ~0.7 ms: only worth it for long runs
-  else if (M < 1024 && N <= 12288) FPS_CASE(1024, 12);
-  else if (M < 1024 && N <= 16384) FPS_CASE(1024, 16);
-  else if (M < 1024 && N <= 20480) FPS_CASE(1024, 20);
-  else if (M < 1024 && N <= FPS_RESIDENT_MAX) FPS_CASE(1024, 25);
-  else if (N <= 12288 && M <= FPS_CLUSTER_LIMIT) FPS_SORTED_CASE(12);
-  else if (N <= 16384 && M <= FPS_CLUSTER_LIMIT) FPS_SORTED_CASE(16);
-  else if (N <= 20480 && M <= FPS_CLUSTER_LIMIT) FPS_SORTED_CASE(20);
-  else if (N <= FPS_RESIDENT_MAX && M <= FPS_CLUSTER_LIMIT) FPS_SORTED_CASE(25);
-  else if (N <= 12288) FPS_WAVE_CASE(12);
-  else if (N <= 16384) FPS_WAVE_CASE(16);
-  else if (N <= 20480) FPS_WAVE_CASE(20);
-  else if (N <= FPS_RESIDENT_MAX) FPS_WAVE_CASE(25);
-  else if (N <= FPS_MULTI_MAX && M < 32768 /* 15-bit round tag */ &&
-           ((N + FPS_RESIDENT_MAX - 1) / FPS_RESIDENT_MAX) * B <= fps_num_cus()) {
-    if (!workspace) return REGNET_ERR_NULL;
-    const int G = (int)((N + FPS_RESIDENT_MAX - 1) / FPS_RESIDENT_MAX);          // 2..4 workgroups (whole CUs) per scene
-    const int Bpad = (int)((B + 7) / 8 * 8);                                       // a scene's workgroups on one XCD
-    hipError_t e = hipMemsetAsync(workspace, 0, (size_t)B * 64, st);               // round tag 0 = "nothing published"
-    if (e != hipSuccess) return (int)e;
-    if (first_tie && (e = hipMemsetAsync(first_tie, 0, (size_t)B * sizeof(int), st)) != hipSuccess) return (int)e;   // "unknown"
-    hipLaunchKernelGGL((fps_multi_kernel<25>), dim3((unsigned)(Bpad * G)), dim3(1024), 0, st, xyz, sb, sc, sn, (int)N,
-                       (int)M, rbl, G, (int)B, Bpad, (unsigned long long*)workspace, index);
-  } else {
-    if (!workspace) return REGNET_ERR_NULL;
-    if (first_tie) {
-      hipError_t e = hipMemsetAsync(first_tie, 0, (size_t)B * sizeof(int), st);    // (no tie tracking, no shortcut: "unknown")
-      if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL((fps_streaming_kernel<1024>), dim3((unsigned)B), dim3(1024), 0, st, xyz, sb, sc, sn, (int)N,
-                       (int)M, rbl, workspace, index);
-  }
-  REGNET_LAUNCH_CHECK();
-  return REGNET_OK;
 }
 
 // =====================================================================================

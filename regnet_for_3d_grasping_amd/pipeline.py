@@ -65,7 +65,8 @@ NUM_CUS = 256              # MI355X
 
 def sampling_workgroups_per_scene(num_points):
     """Workgroups (= whole CUs) one scene's level-1 sampling holds: 1 up to 25 600 points, else 2-4 COOPERATING workgroups
-    (fps_multi_kernel) that exchange a word per round and therefore must all be resident at the same time."""
+    (fps_cluster_kernel<.., true>; fps_multi_kernel for runs of fewer than 1024 or more than 8192 picks) that exchange records
+    per round and therefore must all be resident at the same time."""
     return max(1, -(-int(num_points) // SINGLE_CU_POINTS))
 
 
@@ -539,7 +540,7 @@ class ForwardPipeline:
                             break
                         if first_want <= 0:
                             # scenes one launch may hold.  A scene beyond 25 600 points samples on G = 2-4 COOPERATING
-                            # workgroups (csrc/geometry.hip: fps_multi_kernel) that spin on each other's words: every
+                            # workgroups (csrc/geometry.hip: fps_cluster_kernel<.., true>) that spin on each other's words: every
                             # workgroup of every such launch IN FLIGHT must be resident, or two half-resident launches
                             # wait for each other's CUs for ever.  So with G > 1: one sampling stream (launches are
                             # serialised by stream order) and a launch leaves room for the only other cooperative

@@ -54,6 +54,7 @@ SPOT = {
     "regnet_fps_workspace_bytes": (_i64, [_i64, _i64, _i64]),
     # host-only query: sizes, an int, a host pointer, no stream
     "regnet_mlp_layer_plan": (_int, [_i64, _i64, _i64, _int, _vp]),
+    "regnet_fps_plan": (_int, [_i64, _i64, _i64, _vp]),
 }
 
 
