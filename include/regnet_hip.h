@@ -908,6 +908,58 @@ int regnet_plane_estimate_f64(const double* xyz, int64_t M, int64_t H, uint64_t 
                               float range_hi, const float* up_hint, float cos2_tilt, float* hypotheses, int32_t* counts,
                               uint8_t* inlier, double* moments, int32_t* winner, void* workspace, int stages, void* stream);
 
+/* regnet_plane_moments_det_f32 / _f64: the ten moments of the rows whose `inlier` byte is non-zero (and whose float32 coordinates
+ * are finite), summed in ONE fixed order -- per 2048-point tile in the moments kernel's own order, the tiles' partial rows in
+ * ascending order by one workgroup --, so two estimates of the same cloud give the same bits (the atomics of
+ * regnet_plane_estimate_* do not).  moments (10) float64 DEVICE, written whole; workspace
+ * regnet_plane_moments_det_workspace_bytes(M) = 80 max(1, ceil(M / 2048)) bytes, 8-byte aligned (-1 for M < 0 or M > 2^21).
+ * Two launches, no atomics, no host read.  M == 0: zeros.  Errors as regnet_plane_estimate_*.                              */
+int64_t regnet_plane_moments_det_workspace_bytes(int64_t M);
+int regnet_plane_moments_det_f32(const float* xyz, int64_t M, const uint8_t* inlier, double* moments, void* workspace, void* stream);
+int regnet_plane_moments_det_f64(const double* xyz, int64_t M, const uint8_t* inlier, double* moments, void* workspace, void* stream);
+
+/* ---- depth frames (csrc/depth.hip): a depth image and an optional colour image -> the organised cloud, on the device ----------
+ * regnet_depth_to_cloud_u16 / _f32: depth (H, W) contiguous, uint16 raw units or float32 metres; pixel (u, v) = column u, row v,
+ * output row v W + u.  Pinhole intrinsics, no distortion model.  Canonical fp32 arithmetic: individually rounded binary32
+ * operations in the written order (-ffp-contract=off); constants are evaluated in float64 by the caller and rounded once.
+ *   params      (25) float32 HOST memory: rfx = float32(1 / fx), rfy, cx, cy, s (depth scale), lo, hi, t (edge threshold),
+ *               margin, fxc, fyc, cxc, cyc, R (9, row-major), tr (3).  Entries a mode does not use are ignored.
+ *   depth       uint16 d: z = float32(d) * s, d == 0: no depth.  float32: z = d; not finite or z <= 0: no depth.
+ *               valid0 = has depth and lo <= z <= hi (inclusive), else status 0 / 1.
+ *   edge filter use_edge != 0: a valid0 pixel is removed (status 2) when for one of its 8 neighbours q inside the image and valid0
+ *               fabsf(z - zq) > t * fminf(z, zq) (strict).  Decided on valid0 alone, one pass: both sides of a jump lose a pixel.
+ *               min_neighbours k in 0..8: fewer than k valid0 8-neighbours inside the image -> removed (status 3).
+ *   deproject   x = ((float32(u) - cx) * z) * rfx, y = ((float32(v) - cy) * z) * rfy, z.  No division.
+ *   colour      mode 0 (none): rgb = 0.  mode 1 (aligned): colour (H, W, 3) uint8 (Wc = W, Hc = H), rgb[k] = LUT[c[k]],
+ *               LUT[i] = float32(i / 255.0) (regnet_depth_colour_lut writes the 256 entries to HOST memory).
+ *               mode 2 (registered): colour (Hc, Wc, 3) uint8, Wc Hc <= 2^23.  p' = R p + tr with x' = ((r00 x + r01 y) + r02 z)
+ *               + t0 and likewise y', z'; outside (status 4) when z' is not finite or z' <= 0; uc = (x' / z') * fxc + cxc with
+ *               the correctly rounded division, fu = floorf(uc + 0.5f), inside when fu >= 0 && fu < Wc in float; likewise fv.
+ *               Visibility: a uint32 z-buffer over the colour grid starts at the bits of +inf; every point that survived the
+ *               filter and is inside does an unsigned atomicMin with the bits of z' into every pixel of the (2 splat + 1)^2
+ *               footprint around (fu, fv) that lies in the image (splat 0..2); a point is visible when
+ *               z' - zmin(fu, fv) <= margin (inclusive), else status 5.  A visible point takes LUT[colour(fv, fu)].
+ *               keep_uncoloured != 0: status 4 / 5 rows keep their coordinates (rgb = 0); otherwise they are dropped.
+ * Outputs, all DEVICE memory, written whole (no host read, no synchronisation, no allocation: capturable):
+ *   xyz (H W, 3), rgb (H W, 3) float32; status (H W) uint8: 0 no depth, 1 out of range, 2 edge jump, 3 too few neighbours,
+ *   4 outside the colour image, 5 occluded, 6 kept (the first that applies); counts (8) int32: the histogram of status.
+ *   A row that is not kept holds the quiet NaN 0x7FC00000 in its three coordinates and rgb = 0.
+ *   workspace   regnet_depth_workspace_bytes(W, H, Wc, Hc, mode): the z-buffer, 4 Wc Hc rounded up to 16, 16-byte aligned, in
+ *               mode 2; 16 (not touched, may be NULL) otherwise; -1 for unsupported sizes.
+ * Modes 0 / 1: a one-workgroup fill of counts and ONE launch (32 x 8 pixel tiles, depths + halo staged in LDS).  Mode 2: z-buffer
+ * fill, points + atomicMin, colour -- three launches ordered by the stream; no workgroup waits for another.  Errors, all before
+ * any launch: W < 1, H < 1, mode outside 0..2, (Wc, Hc) != (W, H) in mode 1 or < 1 in mode 2, min_neighbours outside 0..8,
+ * splat outside 0..2 -> REGNET_ERR_SHAPE; W H > 2^21 or Wc Hc > 2^23 -> REGNET_ERR_UNSUPPORTED; a NULL pointer for a required
+ * array -> REGNET_ERR_NULL.                                                                                                */
+int64_t regnet_depth_workspace_bytes(int64_t W, int64_t H, int64_t Wc, int64_t Hc, int mode);
+int regnet_depth_colour_lut(float* lut);
+int regnet_depth_to_cloud_u16(const uint16_t* depth, int64_t W, int64_t H, const float* params, const uint8_t* colour, int64_t Wc,
+                              int64_t Hc, int mode, int use_edge, int min_neighbours, int splat, int keep_uncoloured, float* xyz,
+                              float* rgb, uint8_t* status, int32_t* counts, void* workspace, void* stream);
+int regnet_depth_to_cloud_f32(const float* depth, int64_t W, int64_t H, const float* params, const uint8_t* colour, int64_t Wc,
+                              int64_t Hc, int mode, int use_edge, int min_neighbours, int splat, int keep_uncoloured, float* xyz,
+                              float* rgb, uint8_t* status, int32_t* counts, void* workspace, void* stream);
+
 /* ---- deterministic mode (csrc/scatter.hip, csrc/det.hip, csrc/bn_train.hip) ------------------------------------------
  * The float32 kernels behind torch.use_deterministic_algorithms(True): every sum of the training backward is formed in one
  * fixed order, so runs agree bit for bit.  The default entry points above are unchanged.

@@ -40,6 +40,7 @@ SOURCES = [
     ("nms.hip", ["-ffp-contract=off"]),   # pose NMS: "the same grasp" is decided on individually rounded fp32 products and sums
     ("plane.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),   # table plane: inliers and the winner are decided on individually
                                                                # rounded fp32 arithmetic; SLP packs the tests into v_pk ops + moves
+    ("depth.hip", ["-ffp-contract=off"]),   # depth frames: coordinates, filter and visibility are compared bit for bit with numpy
 ]
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc"]
@@ -72,7 +73,7 @@ NO_VGPR_SPILL = {"mlp.o": ["mlp_gemm_kernelILi0E", "gemm2_kernel"], "sa_chain.o"
                  "rowchain.o": ["sa_premul_chain_kernel", "sa3_premul_chain_kernel", "fp_head_chain_kernelILb0E"],
                  "heads.o": ["heads_chain_kernel", "heads_tree_kernel"], "ops_f64.o": ["_f64_kernel"],
                  "scatter.o": ["scatter_", "segsum_"], "det.o": ["det_"],
-                 "ingest.o": ["ingest_"], "nms.o": ["nms_"], "plane.o": ["plane_"]}
+                 "ingest.o": ["ingest_"], "nms.o": ["nms_"], "plane.o": ["plane_"], "depth.o": ["depth_"]}
 
 
 def check_no_vgpr_spill(obj_path, fragments):

@@ -17,6 +17,8 @@
 //     the moments.
 //   * plane_moments_kernel: re-tests every point against the winner, writes the (M) uint8 inlier mask and reduces the ten
 //     float64 moments per workgroup -> one float64 atomic per sum and workgroup (tgemm.hip's statistics pattern).
+//   * plane_moments_partial_kernel + plane_moments_sum_kernel (regnet_plane_moments_det_*): the ten moments over a given mask in
+//     one fixed order, without atomics -- what estimate_plane refits from, so that one cloud gives one plane bit for bit.
 // No workgroup waits for another: the four launches are ordered by the stream.  Integer atomics only for everything that is
 // compared exactly; every other result is written by plain vector stores.
 #include "common.h"
@@ -245,6 +247,77 @@ __global__ __launch_bounds__(PL_BLOCK) void plane_moments_kernel(const T* __rest
   }
 }
 
+// The ten moments once more, in ONE fixed order (regnet_plane_moments_det_*): a workgroup reduces its 2048 points over the given
+// mask exactly as plane_moments_kernel does (per-lane order, shuffle tree, waves in order) but leaves its partial row in the
+// workspace instead of adding it atomically; plane_moments_sum_kernel, one workgroup, adds the rows in a fixed order.
+template <typename T>
+__global__ __launch_bounds__(PL_BLOCK) void plane_moments_partial_kernel(const T* __restrict__ xyz, long long M,
+                                                                         const uint8_t* __restrict__ inlier,
+                                                                         double* __restrict__ partial) {
+  __shared__ double s_part[PL_BLOCK / 64][10];
+  const int tid = threadIdx.x;
+  double acc[10];
+#pragma unroll
+  for (int k = 0; k < 10; ++k) acc[k] = 0.0;
+  const long long base = (long long)blockIdx.x * PL_TILE + tid;
+#pragma unroll 2
+  for (int j = 0; j < PL_PPL; ++j) {
+    const long long i = base + (long long)j * PL_BLOCK;
+    if (i < M && inlier[i] != 0) {
+      float fx, fy, fz;
+      if (load_row(xyz, i, fx, fy, fz)) {
+        const double x = (double)fx, y = (double)fy, z = (double)fz;
+        acc[0] += 1.0; acc[1] += x; acc[2] += y; acc[3] += z;
+        acc[4] += x * x; acc[5] += x * y; acc[6] += x * z; acc[7] += y * y; acc[8] += y * z; acc[9] += z * z;
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 10; ++k) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) acc[k] += __shfl_xor(acc[k], d, 64);
+  }
+  if (lane_id() == 0) {
+#pragma unroll
+    for (int k = 0; k < 10; ++k) s_part[tid >> 6][k] = acc[k];
+  }
+  __syncthreads();
+  if (tid < 10) {
+    double v = 0.0;
+#pragma unroll
+    for (int wv = 0; wv < PL_BLOCK / 64; ++wv) v += s_part[wv][tid];
+    partial[(long long)blockIdx.x * 10 + tid] = v;
+  }
+}
+
+__global__ __launch_bounds__(64) void plane_moments_sum_kernel(const double* __restrict__ partial, int rows,
+                                                               double* __restrict__ moments) {
+  const int tid = threadIdx.x;
+  if (tid < 10) {
+    double v = 0.0;
+    for (int r = 0; r < rows; ++r) v += partial[(long long)r * 10 + tid];      // ascending tile order
+    moments[tid] = v;
+  }
+}
+
+template <typename T>
+int plane_moments_det_launch(const T* xyz, int64_t M, const uint8_t* inlier, double* moments, void* workspace, void* stream) {
+  if (M < 0) return REGNET_ERR_SHAPE;
+  if (M > PL_MAX_POINTS) return REGNET_ERR_UNSUPPORTED;
+  if (!moments || !workspace) return REGNET_ERR_NULL;
+  if (M > 0 && (!xyz || !inlier)) return REGNET_ERR_NULL;
+  hipStream_t s = as_stream(stream);
+  const int tiles = (int)((M + PL_TILE - 1) / PL_TILE);
+  if (tiles > 0) {
+    hipLaunchKernelGGL(plane_moments_partial_kernel<T>, dim3((unsigned)tiles), dim3(PL_BLOCK), 0, s, xyz, (long long)M, inlier,
+                       (double*)workspace);
+    REGNET_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(plane_moments_sum_kernel, dim3(1), dim3(64), 0, s, (const double*)workspace, tiles, moments);
+  REGNET_LAUNCH_CHECK();
+  return REGNET_OK;
+}
+
 template <typename T>
 int plane_launch(const T* xyz, int64_t M, int64_t H, uint64_t seed, float threshold, float range_lo, float range_hi,
                  const float* up_hint, float cos2_tilt, float* hypotheses, int32_t* counts, uint8_t* inlier, double* moments,
@@ -318,4 +391,20 @@ extern "C" int regnet_plane_estimate_f64(const double* xyz, int64_t M, int64_t H
                                          int stages, void* stream) {
   return plane_launch<double>(xyz, M, H, seed, threshold, range_lo, range_hi, up_hint, cos2_tilt, hypotheses, counts, inlier,
                               moments, winner, workspace, stages, stream);
+}
+
+extern "C" int64_t regnet_plane_moments_det_workspace_bytes(int64_t M) {
+  if (M < 0 || M > PL_MAX_POINTS) return -1;
+  const int64_t tiles = (M + PL_TILE - 1) / PL_TILE;
+  return (tiles > 0 ? tiles : 1) * 10 * (int64_t)sizeof(double);
+}
+
+extern "C" int regnet_plane_moments_det_f32(const float* xyz, int64_t M, const uint8_t* inlier, double* moments, void* workspace,
+                                            void* stream) {
+  return plane_moments_det_launch<float>(xyz, M, inlier, moments, workspace, stream);
+}
+
+extern "C" int regnet_plane_moments_det_f64(const double* xyz, int64_t M, const uint8_t* inlier, double* moments, void* workspace,
+                                            void* stream) {
+  return plane_moments_det_launch<double>(xyz, M, inlier, moments, workspace, stream);
 }

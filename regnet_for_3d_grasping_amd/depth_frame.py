@@ -1,0 +1,275 @@
+"""What a depth camera delivers -- a 16-bit depth image, an 8-bit colour image, pinhole intrinsics -- turned into the organised
+cloud ``ingest.crop_frame`` and ``table_plane.estimate_plane`` take, on the device (csrc/depth.hip): the step the reference did
+with open3d before ``test.py`` ever saw a ``.pcd``.
+
+``to_cloud`` uploads the images as they are (2 + 3 bytes per pixel, not 48), and one launch (three when the colour sensor has its
+own pose) deprojects, removes flying pixels at depth discontinuities (``edge_threshold``, ``min_neighbours``) and colours the
+points -- through a z-buffer of the colour camera when the sensors are not aligned, so that a foreground colour is not painted
+on a background point the colour sensor cannot see.  Removed points are NaN rows, which every consumer treats as absent.
+Everything that decides is canonical fp32 arithmetic (DESIGN.md par. 5, include/regnet_hip.h): ``tests/depth_reference.py``
+restates it in numpy and the two agree bit for bit.  No host synchronisation, no host read.  GPU only: there is no CPU path.
+"""
+import math
+from dataclasses import dataclass
+from typing import Any, Optional, Tuple
+
+import numpy as np
+
+from . import _lib
+
+_L = _lib.lib
+
+MAX_DEPTH_PIXELS = 1 << 21          # regnet_depth_to_cloud_*'s documented limits; = ingest.MAX_FRAME_POINTS
+MAX_COLOR_PIXELS = 1 << 23
+MODE_NONE, MODE_ALIGNED, MODE_REGISTERED = 0, 1, 2
+STATUS = ("no depth", "out of range", "edge jump", "too few neighbours", "outside the colour image", "occluded", "kept")
+KEPT = 6
+NUM_PARAMS = 25
+
+
+@dataclass(frozen=True)
+class Intrinsics:
+    """Pinhole intrinsics in pixels; no distortion model."""
+    fx: float
+    fy: float
+    cx: float
+    cy: float
+
+    @classmethod
+    def coerce(cls, value):
+        if value is None or isinstance(value, cls):
+            return value
+        v = np.asarray(value, dtype=np.float64).reshape(-1)
+        if v.shape != (4,):
+            raise ValueError("intrinsics must be (fx, fy, cx, cy)")
+        return cls(*(float(x) for x in v))
+
+    def astuple(self):
+        return (self.fx, self.fy, self.cx, self.cy)
+
+
+@dataclass
+class DepthFrame:
+    """One frame of a depth camera.  ``depth`` (H, W): uint16 raw units (``z = depth * depth_scale`` metres, 0 = no depth) or
+    float32 metres; ``color`` (H, W, 3) uint8 on the depth grid, or (Hc, Wc, 3) uint8 with ``color_intrinsics`` and the row-major
+    4x4 ``depth_to_color`` transform of a colour sensor with its own pose.  Arrays may be numpy arrays or device tensors."""
+    depth: Any
+    intrinsics: Any
+    color: Any = None
+    color_intrinsics: Any = None
+    depth_to_color: Any = None
+    depth_scale: float = 0.001
+
+    def __post_init__(self):
+        self.intrinsics = Intrinsics.coerce(self.intrinsics)
+        self.color_intrinsics = Intrinsics.coerce(self.color_intrinsics)
+        if self.intrinsics is None:
+            raise ValueError("DepthFrame: the depth intrinsics are required")
+
+    def mode(self):
+        """0 none / 1 aligned / 2 registered; a half-given colour camera is a ValueError."""
+        has_k, has_t = self.color_intrinsics is not None, self.depth_to_color is not None
+        if self.color is None:
+            if has_k or has_t:
+                raise ValueError("DepthFrame: color_intrinsics / depth_to_color without a colour image")
+            return MODE_NONE
+        if not has_k and not has_t:
+            return MODE_ALIGNED
+        if has_k and has_t:
+            return MODE_REGISTERED
+        raise ValueError("DepthFrame: a colour camera of its own needs both color_intrinsics and depth_to_color")
+
+
+@dataclass(frozen=True)
+class DepthParams:
+    """``depth_range = (lo, hi)`` [m], inclusive; ``edge_threshold`` t (None: off): a pixel is removed when an 8-neighbour's
+    depth differs by more than t times the smaller of the two; ``min_neighbours`` k (0..8): a pixel with fewer valid 8-neighbours
+    is removed; ``occlusion_margin`` [m] and ``splat`` (0..2, the z-buffer footprint's radius in colour pixels) govern the
+    visibility test of a colour sensor with its own pose; ``keep_uncoloured``: points that sensor does not see keep their
+    coordinates with rgb = 0 instead of being dropped."""
+    depth_range: Tuple[float, float] = (0.0, math.inf)
+    edge_threshold: Optional[float] = None
+    min_neighbours: int = 0
+    occlusion_margin: float = 0.01
+    splat: int = 1
+    keep_uncoloured: bool = False
+
+    def __post_init__(self):
+        lo, hi = (float(v) for v in self.depth_range)
+        if not (0.0 <= lo <= hi):
+            raise ValueError("depth: depth_range must be 0 <= lo <= hi")
+        if self.edge_threshold is not None and not (float(self.edge_threshold) >= 0.0):
+            raise ValueError("depth: edge_threshold must be None or >= 0")
+        if int(self.min_neighbours) != self.min_neighbours or not 0 <= self.min_neighbours <= 8:
+            raise ValueError("depth: min_neighbours must be in 0..8")
+        if int(self.splat) != self.splat or not 0 <= self.splat <= 2:
+            raise ValueError("depth: splat must be 0, 1 or 2")
+        if not (float(self.occlusion_margin) >= 0.0):
+            raise ValueError("depth: occlusion_margin must be >= 0")
+
+    @classmethod
+    def coerce(cls, value):
+        """None -> the defaults, a DepthParams -> itself, a dict -> DepthParams(**dict)."""
+        if value is None:
+            return cls()
+        if isinstance(value, cls):
+            return value
+        if isinstance(value, dict):
+            value = dict(value)
+            if "depth_range" in value:
+                value["depth_range"] = tuple(float(v) for v in value["depth_range"])
+            return cls(**value)
+        raise TypeError("depth must be None, a dict or a DepthParams")
+
+
+def colour_lut():
+    """The 256 entries float32(i / 255.0) the kernels hold in constant memory (the library's host copy)."""
+    lut = np.empty((256,), dtype=np.float32)
+    _L.regnet_depth_colour_lut(lut.ctypes.data)
+    return lut
+
+
+def workspace_bytes(width, height, color_width=0, color_height=0, mode=MODE_NONE):
+    """Bytes of scratch ``regnet_depth_to_cloud_*`` needs: the z-buffer (4 Wc Hc rounded up to 16) in registered mode, 16
+    otherwise; -1 for unsupported sizes."""
+    return int(_L.regnet_depth_workspace_bytes(int(width), int(height), int(color_width), int(color_height), int(mode)))
+
+
+def pack_params(frame, params, mode):
+    """The 25 float32 constants of the C call: evaluated in float64, rounded once."""
+    k = frame.intrinsics
+    if not (k.fx != 0.0 and k.fy != 0.0):
+        raise ValueError("depth: fx and fy must not be zero")
+    p = np.zeros((NUM_PARAMS,), dtype=np.float64)
+    p[0:5] = (1.0 / float(k.fx), 1.0 / float(k.fy), k.cx, k.cy, float(frame.depth_scale))
+    p[5:7] = params.depth_range
+    p[7] = 0.0 if params.edge_threshold is None else float(params.edge_threshold)
+    p[8] = params.occlusion_margin
+    if mode == MODE_REGISTERED:
+        T = np.asarray(frame.depth_to_color.detach().cpu().numpy() if hasattr(frame.depth_to_color, "detach")
+                       else frame.depth_to_color, dtype=np.float64)
+        if T.shape != (4, 4):
+            raise ValueError("depth_to_color must be 4x4")
+        p[9:13] = frame.color_intrinsics.astuple()
+        p[13:22] = T[:3, :3].reshape(9)
+        p[22:25] = T[:3, 3]
+    with np.errstate(over="ignore"):
+        return np.ascontiguousarray(p.astype(np.float32))
+
+
+def _image(a, device, what, dtypes):
+    """A host array or tensor -> a contiguous device tensor of one of ``dtypes`` (host arrays go up once, as they are)."""
+    import torch
+    from . import host_io
+    if isinstance(a, torch.Tensor):
+        t = a if a.is_cuda else host_io.upload(a.contiguous(), device)
+    else:
+        a = np.ascontiguousarray(a)
+        if a.dtype == np.float64 and torch.float32 in dtypes:
+            a = a.astype(np.float32)
+        t = host_io.upload(a, device)
+    if t.dtype == torch.int16 and torch.uint16 in dtypes:
+        t = t.view(torch.uint16)
+    if t.dtype not in dtypes:
+        raise TypeError("%s must be %s" % (what, " or ".join(str(d).replace("torch.", "") for d in dtypes)))
+    return t.contiguous()
+
+
+def to_cloud(frame, params=None, device="cuda:0", stream=None, return_status=False, out=None):
+    """``frame`` (a ``DepthFrame``) -> ``(xyz, rgb)``: (H W, 3) float32 device tensors, row ``v W + u`` for pixel (u, v); a row
+    that was removed holds NaN coordinates and rgb = 0.  With ``return_status`` also ``status`` (H W) uint8 (``STATUS``'s codes)
+    and ``counts`` (8) int32, its histogram, both on the device.  ``params``: a ``DepthParams``, a dict of its fields or None.
+    Host images go up once through ``host_io`` as uint16 / float32 and uint8; device tensors are used where they are (then the
+    call is on their device).  ``stream``: a ``torch.cuda.Stream`` (default: the current one).  ``out``: a previous call's
+    ``(xyz, rgb, status, counts, workspace)`` to run without an allocation.  No host synchronisation."""
+    import torch
+    if not isinstance(frame, DepthFrame):
+        raise TypeError("to_cloud takes a DepthFrame")
+    params = DepthParams.coerce(params)
+    mode = frame.mode()
+    dev = frame.depth.device if isinstance(frame.depth, torch.Tensor) and frame.depth.is_cuda else torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("to_cloud: the device must be a GPU (no CPU path)")
+    scale = float(frame.depth_scale)
+    if not (scale > 0.0 and math.isfinite(scale)):
+        raise ValueError("depth_scale must be positive and finite")
+    consts = pack_params(frame, params, mode)
+    with torch.cuda.stream(stream) if stream is not None else _null():
+        depth = _image(frame.depth, dev, "depth", (torch.uint16, torch.float32))
+        if depth.dim() != 2 or depth.shape[0] < 1 or depth.shape[1] < 1:
+            raise ValueError("depth must be (H, W) with at least one pixel")
+        H, W = int(depth.shape[0]), int(depth.shape[1])
+        if W * H > MAX_DEPTH_PIXELS:
+            raise ValueError("depth images of more than 2^21 pixels are not supported")
+        color, Wc, Hc = None, 0, 0
+        if mode != MODE_NONE:
+            color = _image(frame.color, dev, "color", (torch.uint8,))
+            if color.dim() != 3 or color.shape[2] != 3 or color.shape[0] < 1 or color.shape[1] < 1:
+                raise ValueError("color must be (H, W, 3) uint8")
+            Hc, Wc = int(color.shape[0]), int(color.shape[1])
+            if mode == MODE_ALIGNED and (Hc, Wc) != (H, W):
+                raise ValueError("a colour image without intrinsics of its own must have the depth image's shape")
+            if Wc * Hc > MAX_COLOR_PIXELS:
+                raise ValueError("colour images of more than 2^23 pixels are not supported")
+        if out is None:
+            xyz = torch.empty((H * W, 3), dtype=torch.float32, device=dev)
+            rgb = torch.empty((H * W, 3), dtype=torch.float32, device=dev)
+            status = torch.empty((H * W,), dtype=torch.uint8, device=dev)
+            counts = torch.empty((8,), dtype=torch.int32, device=dev)
+            ws = torch.empty((workspace_bytes(W, H, Wc, Hc, mode),), dtype=torch.uint8, device=dev)
+        else:
+            xyz, rgb, status, counts, ws = out
+        _lib.call("regnet_depth_to_cloud_u16" if depth.dtype == torch.uint16 else "regnet_depth_to_cloud_f32", depth,
+                  depth.data_ptr(), W, H, consts.ctypes.data, color.data_ptr() if color is not None else None, Wc, Hc, mode,
+                  0 if params.edge_threshold is None else 1, int(params.min_neighbours), int(params.splat),
+                  1 if params.keep_uncoloured else 0, xyz.data_ptr(), rgb.data_ptr(), status.data_ptr(), counts.data_ptr(),
+                  ws.data_ptr())
+        if stream is not None:              # the inputs are read on `stream`: keep them alive for it
+            for t in (depth, color):
+                if t is not None:
+                    t.record_stream(stream)
+    return (xyz, rgb, status, counts) if return_status else (xyz, rgb)
+
+
+class _null:
+    def __enter__(self):
+        return None
+
+    def __exit__(self, *exc):
+        return False
+
+
+_NPZ_KEYS = ("depth", "intrinsics", "color", "color_intrinsics", "depth_to_color", "depth_scale")
+
+
+def save_npz(path, frame):
+    """Write ``frame`` as a ``.npz``: ``depth``, ``intrinsics`` (4) and, where given, ``color``, ``color_intrinsics`` (4),
+    ``depth_to_color`` (4,4), ``depth_scale``."""
+    def host(a):
+        return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+    items = {"depth": host(frame.depth), "intrinsics": np.array(frame.intrinsics.astuple(), dtype=np.float64),
+             "depth_scale": np.float64(frame.depth_scale)}
+    if frame.color is not None:
+        items["color"] = host(frame.color)
+    if frame.color_intrinsics is not None:
+        items["color_intrinsics"] = np.array(frame.color_intrinsics.astuple(), dtype=np.float64)
+    if frame.depth_to_color is not None:
+        items["depth_to_color"] = host(frame.depth_to_color).astype(np.float64)
+    with open(path, "wb") as f:
+        np.savez(f, **items)
+
+
+def load_npz(path):
+    """Read a ``.npz`` written by ``save_npz`` (or by anything that uses its keys) -> ``DepthFrame``."""
+    with np.load(path, allow_pickle=False) as data:
+        unknown = sorted(set(data.files) - set(_NPZ_KEYS))
+        if unknown:
+            raise ValueError("depth frame %s: unknown entries %s" % (path, ", ".join(unknown)))
+        for key in ("depth", "intrinsics"):
+            if key not in data.files:
+                raise ValueError("depth frame %s: no %r entry" % (path, key))
+        get = lambda key: data[key] if key in data.files else None      # noqa: E731
+        scale = get("depth_scale")
+        return DepthFrame(depth=data["depth"], intrinsics=data["intrinsics"], color=get("color"),
+                          color_intrinsics=get("color_intrinsics"), depth_to_color=get("depth_to_color"),
+                          depth_scale=0.001 if scale is None else float(scale))

@@ -17,6 +17,10 @@ With ``transform="auto"`` (``--auto-table``, ``--table-range LO HI``, ``--plane-
 the reference lab's hard-coded camera pose but is estimated on every camera frame: the dominant plane found on the device
 (``table_plane.estimate_plane``) becomes the table at ``eval_params[2]``, and the record additionally carries ``TABLE_KEYS``.
 ``GraspDetector.calibrate(frame)`` does it once and keeps the transform.  Dataset records are never transformed.
+
+A camera frame may also be a ``depth_frame.DepthFrame`` (a ``.npz`` file: depth image, optional colour image, intrinsics): it
+becomes the ``(xyz, rgb)`` pair on the device (``depth_frame.to_cloud``; ``depth`` / ``--depth-range``, ``--edge-threshold``,
+``--min-neighbours``, ``--occlusion-margin``, ``--keep-uncoloured`` set its filter) and takes the camera-frame path from there.
 """
 import argparse
 import contextlib
@@ -44,8 +48,11 @@ TABLE_KEYS = ("table_transform", "table_plane")                # added when the 
 
 
 def save_path_for(pc_path, real_data):
-    """test.py:143-145: ``_data`` -> ``_data_predict`` anywhere in the path; camera frames also ``.pcd`` -> ``.p``."""
+    """test.py:143-145: ``_data`` -> ``_data_predict`` anywhere in the path; camera frames also ``.pcd`` -> ``.p``, and a depth
+    frame's trailing ``.npz`` -> ``.p``."""
     path = pc_path.replace("_data", "_data_predict")
+    if real_data and path.endswith(".npz"):
+        return path[:-len(".npz")] + ".p"
     return path.replace(".pcd", ".p") if real_data else path
 
 
@@ -59,12 +66,14 @@ class GraspDetector:
     that set.  ``transform``: a 4x4 (default ``ingest.table_frame_transform()``), or ``"auto"`` / a dict of
     ``table_plane.estimate_plane`` keywords: the table plane is then estimated on every camera frame and placed at
     ``eval_params[2]``, and the record also carries ``table_transform`` (4,4) float64 and ``table_plane`` (5,) float64 =
-    normal, offset, rms."""
+    normal, offset, rms.  ``depth``: None, or a ``depth_frame.DepthParams`` / a dict of its fields: how a ``DepthFrame`` handed
+    to ``ingest`` / ``detect`` becomes a cloud (range, edge filter, occlusion test); other frames never see it."""
 
     def __init__(self, score_net, region_net, params=TEST_PARAMS, gripper_params=GRIPPER_PARAMS, eval_params=EVAL_PARAMS,
-                 transform=None, bounds=None, num_points=ALL_POINTS_NUM, use_theta=USE_THETA, select=None):
-        from . import grasp_select, ingest
+                 transform=None, bounds=None, num_points=ALL_POINTS_NUM, use_theta=USE_THETA, select=None, depth=None):
+        from . import depth_frame, grasp_select, ingest
         self.select = grasp_select.SelectParams.coerce(select)
+        self.depth = depth_frame.DepthParams.coerce(depth)
         self.score_net, self.region_net = score_net, region_net
         self.params, self.gripper_params, self.eval_params = list(params), list(gripper_params), list(eval_params)
         self.auto_table = None                    # estimate_plane's keywords when the transform is estimated per frame
@@ -83,12 +92,15 @@ class GraspDetector:
             raise RuntimeError("GraspDetector: the networks must be on a GPU (no CPU path)")
 
     def ingest(self, frame):
-        """``frame``: an ``ingest.Frame``, an ``(xyz, rgb)`` pair of a camera frame, or a record dict -> ``ingest.Frame``."""
-        from . import ingest
+        """``frame``: an ``ingest.Frame``, an ``(xyz, rgb)`` pair of a camera frame, a ``depth_frame.DepthFrame`` or a record
+        dict -> ``ingest.Frame``."""
+        from . import depth_frame, ingest
         if isinstance(frame, ingest.Frame):
             return frame
         if isinstance(frame, dict):
             return ingest.ingest_record(frame, self.num_points, self.device)
+        if isinstance(frame, depth_frame.DepthFrame):      # on the device, no host read; draws nothing from numpy's stream
+            frame = depth_frame.to_cloud(frame, self.depth, device=self.device)
         xyz, rgb = frame
         transform = self.transform
         if self.auto_table is not None:           # draws nothing from numpy's stream; one 96-byte read
@@ -168,14 +180,18 @@ class GraspDetector:
         return {key: out[key] for key in keys}
 
     def detect_file(self, path, save_path=None, real_data=None):
-        """``test_one_file`` (test.py:94-148): ``.pcd`` -> camera frame, anything else -> dataset record, unless ``real_data``
-        says so.  The dict is pickled to ``save_path`` (default: the rule of :143-145; no file when that rule leaves the path
+        """``test_one_file`` (test.py:94-148): ``.pcd`` -> camera frame, ``.npz`` -> depth frame, anything else -> dataset
+        record, unless ``real_data`` says so.  The dict is pickled to ``save_path`` (default: the rule of :143-145; no file when that rule leaves the path
         unchanged, which would overwrite the input).  Prints the reference's three count lines, and the selected count when
         the detector has ``select``.  -> (dict, save path or None)."""
-        from . import ingest
+        from . import depth_frame, ingest
+        is_depth = path.endswith(".npz")
         if real_data is None:
-            real_data = path.lower().endswith(".pcd")
-        if real_data:
+            real_data = is_depth or path.lower().endswith(".pcd")
+        if is_depth:
+            real_data = True
+            out = self.detect(depth_frame.load_npz(path))
+        elif real_data:
             xyz, rgb, _ = ingest.read_pcd(path)
             out = self.detect((xyz, rgb))
         else:
@@ -216,6 +232,18 @@ def transform_from_args(args):
     return given if given else "auto"
 
 
+def depth_from_args(args):
+    """The CLI's five depth-frame flags -> a ``depth`` dict, or None when none of them was given."""
+    given = {"edge_threshold": args.edge_threshold, "min_neighbours": args.min_neighbours,
+             "occlusion_margin": args.occlusion_margin}
+    given = {key: value for key, value in given.items() if value is not None}
+    if args.depth_range is not None:
+        given["depth_range"] = (float(args.depth_range[0]), float(args.depth_range[1]))
+    if args.keep_uncoloured:
+        given["keep_uncoloured"] = True
+    return given if given else None
+
+
 def main(argv=None):
     """``main()`` of test.py:150-164."""
     from . import checkpoint
@@ -235,6 +263,16 @@ def main(argv=None):
     parser.add_argument("--table-range", type=float, nargs=2, metavar=("LO", "HI"), default=None,
                         help="the table plane lies between LO and HI metres from the camera")
     parser.add_argument("--plane-threshold", type=float, default=None, help="inlier distance of the table plane [m] (0.005)")
+    # depth frames (*.npz: depth_frame.to_cloud): the range, the flying-pixel filter and the occlusion test of the colour sensor
+    parser.add_argument("--depth-range", type=float, nargs=2, metavar=("LO", "HI"), default=None,
+                        help="keep depths between LO and HI metres, inclusive (0 inf)")
+    parser.add_argument("--edge-threshold", type=float, default=None,
+                        help="remove pixels whose depth jumps by more than this share of the nearer depth to a neighbour (off)")
+    parser.add_argument("--min-neighbours", type=int, default=None, help="remove pixels with fewer valid 8-neighbours (0)")
+    parser.add_argument("--occlusion-margin", type=float, default=None,
+                        help="a point this far behind the colour camera's nearest surface is still seen by it [m] (0.01)")
+    parser.add_argument("--keep-uncoloured", action="store_true",
+                        help="keep points the colour camera does not see, with black colour, instead of dropping them")
     args = parser.parse_args(argv)
     select = select_from_args(args)
     obj_class_num, group_num, gripper_num, score_thre, depth, reg_channel = MODEL_PARAMS
@@ -245,12 +283,14 @@ def main(argv=None):
                                                   args.load_region_path, args.gpu)
     eval_params = [DEPTH, WIDTH, TABLE_HEIGHT, args.gpu, CENTER_NUM]
     detector = GraspDetector(score_net.to(dev), region_net.to(dev), eval_params=eval_params, select=select,
-                             transform=transform_from_args(args))
+                             transform=transform_from_args(args), depth=depth_from_args(args))
     real_data = "real_data" in args.folder
     if args.file:
         paths = [os.path.join(args.folder, args.file)]
     else:
         paths = glob.glob(args.folder + ("/*.pcd" if real_data else "/*.p"), recursive=True)
+        if real_data:
+            paths += sorted(glob.glob(args.folder + "/*.npz"))
     for path in paths:
         detector.detect_file(path, real_data=real_data)
 

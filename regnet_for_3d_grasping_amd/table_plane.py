@@ -3,7 +3,7 @@
 
 ``estimate_plane`` runs a seeded RANSAC over the frame (``hypotheses`` planes through three drawn points against every point,
 inclusive threshold, optional gates on the plane's distance from the camera and on its tilt), then refits the winner's
-inliers from ten float64 moments -- the only host read of the whole estimate, together with the winner's index and count
+inliers from ten float64 moments (summed once more in a fixed order, so the same cloud gives the same plane bit for bit) -- the only host read of the whole estimate, together with the winner's index and count
 (96 bytes).  Everything that decides is canonical fp32 arithmetic (DESIGN.md par. 5, include/regnet_hip.h):
 ``tests/plane_reference.py`` restates it in numpy and the two agree exactly.  The draws come from a counter-based generator
 of their own: numpy's global stream is not touched.  ``table_frame`` turns a plane into the 4x4 of
@@ -90,6 +90,20 @@ def estimate_device(xyz, threshold=DEFAULT_THRESHOLD, hypotheses=DEFAULT_HYPOTHE
     return result, details, ws
 
 
+def moments_fixed_order(xyz, inlier_mask, out=None):
+    """regnet_plane_moments_det_*: the ten float64 moments of the rows of ``xyz`` (M,3) that ``inlier_mask`` (M) uint8 marks,
+    summed in one fixed order, so that two estimates of one cloud agree bit for bit (the moments ``estimate_device`` leaves are
+    added with float64 atomics in no fixed order).  -> (10,) float64 on the device (``out`` when given); no host read."""
+    import torch
+    M, dev = int(xyz.shape[0]), xyz.device
+    if out is None:
+        out = torch.empty((10,), dtype=torch.float64, device=dev)
+    ws = torch.empty((int(_L.regnet_plane_moments_det_workspace_bytes(M)),), dtype=torch.uint8, device=dev)
+    _lib.call("regnet_plane_moments_det_f64" if xyz.dtype == torch.float64 else "regnet_plane_moments_det_f32", xyz,
+              xyz.data_ptr() if M else None, M, inlier_mask.data_ptr() if M else None, out.data_ptr(), ws.data_ptr())
+    return out
+
+
 def plane_from_moments(moments, hypothesis, inliers):
     """The refit on the host: ten float64 moments -> ``Plane``.  ``np.linalg.eigh`` of the covariance; the normal is the
     eigenvector of the smallest eigenvalue, signed so that the camera origin is on its positive side; rms = sqrt(eigenvalue)."""
@@ -120,7 +134,9 @@ def estimate_plane(xyz, threshold=DEFAULT_THRESHOLD, hypotheses=DEFAULT_HYPOTHES
     from . import ingest
     if not (isinstance(xyz, torch.Tensor) and xyz.is_cuda):
         xyz = ingest._to_device(xyz, torch.device(device))
+    xyz = xyz.contiguous()
     result, details, _ = estimate_device(xyz, threshold, hypotheses, seed, range, up_hint, max_tilt_deg)
+    moments_fixed_order(xyz, details.inlier_mask, out=details.moments)      # the refit's input, reproducible to the last bit
     host = result.cpu().numpy()                                    # the one blocking read: 96 bytes
     moments, (winner, count) = host[:80].view(np.float64), host[80:88].view(np.int32)
     if winner < 0:
