@@ -960,6 +960,52 @@ int regnet_depth_to_cloud_f32(const float* depth, int64_t W, int64_t H, const fl
                               int64_t Hc, int mode, int use_edge, int min_neighbours, int splat, int keep_uncoloured, float* xyz,
                               float* rgb, uint8_t* status, int32_t* counts, void* workspace, void* stream);
 
+/* ---- object segmentation (csrc/cluster.hip): Euclidean cluster extraction over one cloud, on the device --------------------
+ * regnet_cluster_points_f32: xyz (N,3) float32 contiguous; mask (N) uint8 or NULL.  Canonical fp32 arithmetic: individually
+ * rounded binary32 operations in the written order (-ffp-contract=off).
+ *   graph rows  row i is in the graph iff (mask == NULL or mask[i] != 0) and its three coordinates are finite.  The other rows
+ *               are compacted away before the uniform grid (csrc/grid.h) is built; they never reach it.
+ *   edges       i ~ j iff d2 <= T2 (inclusive), d2 = ((dx dx) + (dy dy)) + (dz dz) with dx = x_i - x_j, T2 = tolerance * tolerance
+ *               (one float32 product).  Symmetric by construction.  The grid visits the cells overlapping the ball; it only
+ *               decides which pairs are evaluated.
+ *   root        (N) int32: the smallest row of i's connected component, -1 for a row outside the graph -- independent of the
+ *               order in which the atomics land.
+ *   key         (N) int32: key[r] = the size of the component whose root is r when that size is >= min_points (the component
+ *               is KEPT), 0 for every other row.
+ *   ranking     kept components by descending size, equal sizes by smaller root; rank r < max_objects is object r.  The caller
+ *               ranks between the two stages: order = the indices of a STABLE DESCENDING sort of key (its index is the root),
+ *               of which the first min(N, max_objects) entries are read.  Entries outside [0, N) or with key 0 are no object.
+ *   label       (N) int32: the object id, -1 for rows outside the graph, in dropped components or ranked >= max_objects.
+ *   num         (2) int32 DEVICE: num[0] = min(kept, max_objects), num[1] = kept.
+ *   object_size / object_first (max_objects) int32, object_bbox (max_objects,6) float32: size, root and (min x, y, z, max x, y,
+ *               z) of the member coordinates for ids < num[0]; -1 / -1 / the quiet NaN 0x7FC00000 beyond.  min / max are exact,
+ *               under the total order in which -0.0 < +0.0.
+ *   stages      1: init + compaction, grid build, union, flatten + sizes, keys -> root, key.  2: tables, labels + boxes, box
+ *               decode -> label, num, object_*; reads root, key, order and the workspace stage 1 left.  3: both, with `order`
+ *               already in place (a re-run).  Outputs of a stage that does not run may be NULL.
+ *   workspace   regnet_cluster_workspace_bytes(N, max_objects), 16-byte aligned: counters, the compacted rows and their source
+ *               rows, the parent array, root -> object id, the grid slab; -1 for unsupported sizes.
+ * Union: a thread per graph row unites with every in-tolerance row of higher index -- lock-free union-find on an int32 parent
+ * array, the larger root hooked under the smaller by atomicCAS, paths halved by atomicMin.  Parent pointers only ever decrease,
+ * every loop ends on its own and no thread waits for another workgroup.  No host read, no synchronisation, no allocation.
+ * N == 0: success; stage 2 writes num = (0, 0) and the empty tables.  Errors, all before any launch: N < 0, min_points < 1,
+ * max_objects < 1 or stages outside 1..3 -> REGNET_ERR_SHAPE; tolerance not finite or <= 0, N >= 2^31 or max_objects > 2^28 ->
+ * REGNET_ERR_UNSUPPORTED (regnet_cluster_workspace_bytes: -1 for the same sizes); a NULL pointer for a required array ->
+ * REGNET_ERR_NULL.  A failed launch or fill returns the positive hipError_t, as every launching entry point does.
+ *
+ * regnet_cluster_assign_f32: query (Q,3), xyz (N,3) float32 contiguous, label (N) int32.  point[q] = the row with label >= 0
+ * and d2 <= R2 (inclusive; the same d2 with x_i the query; R2 = radius * radius, one float32 product) that is smallest by
+ * (d2, row); object[q] = label[point[q]]; both -1 when there is none or the query has a non-finite coordinate.  A wave per
+ * query over all N rows, one launch.  Q == 0: success.  Errors: Q < 0 or N < 0 -> REGNET_ERR_SHAPE; radius < 0 or NaN, Q or
+ * N >= 2^31 -> REGNET_ERR_UNSUPPORTED; NULL -> REGNET_ERR_NULL.                                                            */
+int64_t regnet_cluster_workspace_bytes(int64_t N, int64_t max_objects);
+int regnet_cluster_points_f32(const float* xyz, const uint8_t* mask, int64_t N, float tolerance, int64_t min_points,
+                              int64_t max_objects, int32_t* root, int32_t* key, const int64_t* order, int32_t* label,
+                              int32_t* num, int32_t* object_size, int32_t* object_first, float* object_bbox, void* workspace,
+                              int stages, void* stream);
+int regnet_cluster_assign_f32(const float* query, int64_t Q, const float* xyz, const int32_t* label, int64_t N, float radius,
+                              int32_t* object, int32_t* point, void* stream);
+
 /* ---- deterministic mode (csrc/scatter.hip, csrc/det.hip, csrc/bn_train.hip) ------------------------------------------
  * The float32 kernels behind torch.use_deterministic_algorithms(True): every sum of the training backward is formed in one
  * fixed order, so runs agree bit for bit.  The default entry points above are unchanged.

@@ -41,6 +41,7 @@ SOURCES = [
     ("plane.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),   # table plane: inliers and the winner are decided on individually
                                                                # rounded fp32 arithmetic; SLP packs the tests into v_pk ops + moves
     ("depth.hip", ["-ffp-contract=off"]),   # depth frames: coordinates, filter and visibility are compared bit for bit with numpy
+    ("cluster.hip", ["-ffp-contract=off"]),   # object segmentation: every edge is decided on individually rounded fp32 distances
 ]
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc"]

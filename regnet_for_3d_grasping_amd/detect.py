@@ -21,6 +21,10 @@ the reference lab's hard-coded camera pose but is estimated on every camera fram
 A camera frame may also be a ``depth_frame.DepthFrame`` (a ``.npz`` file: depth image, optional colour image, intrinsics): it
 becomes the ``(xyz, rgb)`` pair on the device (``depth_frame.to_cloud``; ``depth`` / ``--depth-range``, ``--edge-threshold``,
 ``--min-neighbours``, ``--occlusion-margin``, ``--keep-uncoloured`` set its filter) and takes the camera-frame path from there.
+
+With ``segment`` (``--segment``, ``--cluster-tolerance``, ``--min-object-points``, ``--max-objects``, ``--top-k-per-object``) the
+points above the table are clustered into objects on the device (``segment.cluster_points``), every grasp of one set is given
+the object it belongs to, and the selection may be per object; the record additionally carries ``SEGMENT_KEYS``.
 """
 import argparse
 import contextlib
@@ -45,6 +49,8 @@ USE_THETA = True
 RESULT_KEYS = ("points", "colors", "scores", "grasp_stage2", "grasp_stage3_stage2", "grasp_stage3", "grasp_stage3_score")
 SELECT_KEYS = ("grasp_selected", "grasp_selected_index")       # added to the record when the detector has ``select``
 TABLE_KEYS = ("table_transform", "table_plane")                # added when the transform is estimated per frame ("auto")
+SEGMENT_KEYS = ("point_object", "object_size", "object_bbox", "grasp_object")    # added when the detector has ``segment``
+SEGMENT_SELECT_KEYS = SELECT_KEYS + ("grasp_selected_object",)                  # ... with ``top_k_per_object``
 
 
 def save_path_for(pc_path, real_data):
@@ -67,11 +73,19 @@ class GraspDetector:
     ``table_plane.estimate_plane`` keywords: the table plane is then estimated on every camera frame and placed at
     ``eval_params[2]``, and the record also carries ``table_transform`` (4,4) float64 and ``table_plane`` (5,) float64 =
     normal, offset, rms.  ``depth``: None, or a ``depth_frame.DepthParams`` / a dict of its fields: how a ``DepthFrame`` handed
-    to ``ingest`` / ``detect`` becomes a cloud (range, edge filter, occlusion test); other frames never see it."""
+    to ``ingest`` / ``detect`` becomes a cloud (range, edge filter, occlusion test); other frames never see it.
+    ``segment``: None, or a ``segment.SegmentParams`` / a dict of its fields: the record's points above the table are clustered
+    into objects and the record also carries ``point_object`` (count,) int32, ``object_size`` (K,) int32, ``object_bbox`` (K,6)
+    float32 and ``grasp_object`` (k_source,) int32, the object of every grasp of the source set (-1: none); with
+    ``top_k_per_object`` the selection is the best distinct grasps of every object and ``grasp_selected_object`` (k,) int32
+    names each one's object; it replaces the per-frame selection: ``select``'s source and thresholds apply, its ``top_k`` does
+    not."""
 
     def __init__(self, score_net, region_net, params=TEST_PARAMS, gripper_params=GRIPPER_PARAMS, eval_params=EVAL_PARAMS,
-                 transform=None, bounds=None, num_points=ALL_POINTS_NUM, use_theta=USE_THETA, select=None, depth=None):
+                 transform=None, bounds=None, num_points=ALL_POINTS_NUM, use_theta=USE_THETA, select=None, depth=None, segment=None):
         from . import depth_frame, grasp_select, ingest
+        from . import segment as segment_mod
+        self.segment = segment_mod.SegmentParams.coerce(segment)
         self.select = grasp_select.SelectParams.coerce(select)
         self.depth = depth_frame.DepthParams.coerce(depth)
         self.score_net, self.region_net = score_net, region_net
@@ -126,9 +140,10 @@ class GraspDetector:
     def detect(self, frame):
         """test.py:97-148 for one frame -> ``eval_notruth``'s dict of numpy arrays: ``points`` / ``colors`` (the cropped,
         un-jittered cloud: float64 for a camera frame, float32 for a record), ``scores`` (N,1) float32 and the four
-        collision-filtered grasp sets (k,8) float32; with ``select`` also ``SELECT_KEYS``."""
+        collision-filtered grasp sets (k,8) float32; with ``select`` also ``SELECT_KEYS``, with ``segment`` ``SEGMENT_KEYS``."""
         import torch
         from . import eval_collision, grasp_select, np_random
+        from . import segment as segment_mod
         from .get_regiondataset import get_grasp_allobj
         depth, width, table_height, _, _ = self.eval_params
         gpu = self.device.index if self.device.index is not None else torch.cuda.current_device()
@@ -160,18 +175,40 @@ class GraspDetector:
                     if grasp.shape[0] >= 1:
                         grasp = eval_collision.eval_test(points32, grasp[:, :8], None, table_height, depth, width, gpu)
                     sets[key] = grasp
-                sel = self.select
-                if sel is not None:         # on the device, before the download; draws nothing from numpy's stream
+                sel, seg = self.select, self.segment
+                # on the device, before the download; draws nothing from numpy's stream (a per-object selection replaces it)
+                if sel is not None and (seg is None or seg.top_k_per_object is None):
                     sets["grasp_selected"], sets["grasp_selected_index"] = grasp_select.pose_nms(
                         sets[sel.source], sel.translation_thresh, sel.rotation_thresh_deg, sel.top_k, sel.symmetric,
                         return_index=True)
+                segmented = None
+                if seg is not None:        # on the device, before the download; draws nothing from numpy's stream
+                    source = seg.source or (sel.source if sel is not None else "grasp_stage3")
+                    above = segment_mod.above_table_mask(points32, table_height, seg.table_clearance)
+                    segmented = segment_mod.cluster_points(points32, above, seg.tolerance, seg.min_points, seg.max_objects)
+                    grasp_object, _ = segment_mod.assign_grasps(sets[source], points32, segmented.label, seg.assign_radius)
+                    if seg.top_k_per_object is not None:
+                        nms = {} if sel is None else {"translation_thresh": sel.translation_thresh,
+                                                      "rotation_thresh_deg": sel.rotation_thresh_deg,
+                                                      "symmetric": sel.symmetric}
+                        sets["grasp_selected"], sets["grasp_selected_index"], sets["grasp_selected_object"] = \
+                            segment_mod.select_per_object(sets[source], grasp_object, seg.max_objects,
+                                                          seg.top_k_per_object, **nms)
                 points, colors = fr.download(kept)
                 out = {"points": points, "colors": colors, "scores": output_score.view(-1, 1).cpu().numpy()}
                 out.update({key: grasp.cpu().numpy() for key, grasp in sets.items()})
+                if segmented is not None:
+                    _, _, out["object_size"], _, out["object_bbox"] = segmented.objects()
+                    out["point_object"] = segmented.label.cpu().numpy()
+                    out["grasp_object"] = grasp_object.cpu().numpy()
         finally:
             self.score_net.train(was_training[0])
             self.region_net.train(was_training[1])
         keys = RESULT_KEYS if self.select is None else RESULT_KEYS + SELECT_KEYS
+        if self.segment is not None:
+            if self.segment.top_k_per_object is not None:
+                keys = RESULT_KEYS + SEGMENT_SELECT_KEYS
+            keys = keys + SEGMENT_KEYS
         if self.table is not None:
             transform, plane = self.table
             out["table_transform"] = np.array(transform, dtype=np.float64)
@@ -183,7 +220,7 @@ class GraspDetector:
         """``test_one_file`` (test.py:94-148): ``.pcd`` -> camera frame, ``.npz`` -> depth frame, anything else -> dataset
         record, unless ``real_data`` says so.  The dict is pickled to ``save_path`` (default: the rule of :143-145; no file when that rule leaves the path
         unchanged, which would overwrite the input).  Prints the reference's three count lines, and the selected count when
-        the detector has ``select``.  -> (dict, save path or None)."""
+        the detector has ``select``, and the object count when it has ``segment``.  -> (dict, save path or None)."""
         from . import depth_frame, ingest
         is_depth = path.endswith(".npz")
         if real_data is None:
@@ -202,6 +239,8 @@ class GraspDetector:
         print("stage3 grasp num (with scorethre):", len(out["grasp_stage3_score"]))
         if self.select is not None:
             print("selected grasp num (%s):" % self.select.source, len(out["grasp_selected"]))
+        if self.segment is not None:
+            print("object num:", len(out["object_size"]))
         if save_path is None:
             save_path = save_path_for(path, real_data)
             if save_path == path:
@@ -218,6 +257,14 @@ def select_from_args(args):
              "source": args.select_from}
     given = {key: value for key, value in given.items() if value is not None}
     return given if given else None
+
+
+def segment_from_args(args):
+    """The CLI's five segmentation flags -> a ``segment`` dict, or None when none of them was given."""
+    given = {"tolerance": args.cluster_tolerance, "min_points": args.min_object_points, "max_objects": args.max_objects,
+             "top_k_per_object": args.top_k_per_object}
+    given = {key: value for key, value in given.items() if value is not None}
+    return given if (given or args.segment) else None
 
 
 def transform_from_args(args):
@@ -273,6 +320,12 @@ def main(argv=None):
                         help="a point this far behind the colour camera's nearest surface is still seen by it [m] (0.01)")
     parser.add_argument("--keep-uncoloured", action="store_true",
                         help="keep points the colour camera does not see, with black colour, instead of dropping them")
+    # object segmentation (segment.cluster_points): --segment or any of the four turns it on
+    parser.add_argument("--segment", action="store_true", help="cluster the points above the table into objects")
+    parser.add_argument("--cluster-tolerance", type=float, default=None, help="points this close belong to one object [m] (0.01)")
+    parser.add_argument("--min-object-points", type=int, default=None, help="drop clusters of fewer points (50)")
+    parser.add_argument("--max-objects", type=int, default=None, help="keep the largest so many objects (64)")
+    parser.add_argument("--top-k-per-object", type=int, default=None, help="select the K best distinct grasps of every object")
     args = parser.parse_args(argv)
     select = select_from_args(args)
     obj_class_num, group_num, gripper_num, score_thre, depth, reg_channel = MODEL_PARAMS
@@ -283,7 +336,8 @@ def main(argv=None):
                                                   args.load_region_path, args.gpu)
     eval_params = [DEPTH, WIDTH, TABLE_HEIGHT, args.gpu, CENTER_NUM]
     detector = GraspDetector(score_net.to(dev), region_net.to(dev), eval_params=eval_params, select=select,
-                             transform=transform_from_args(args), depth=depth_from_args(args))
+                             transform=transform_from_args(args), depth=depth_from_args(args),
+                             segment=segment_from_args(args))
     real_data = "real_data" in args.folder
     if args.file:
         paths = [os.path.join(args.folder, args.file)]
