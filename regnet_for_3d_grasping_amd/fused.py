@@ -6,21 +6,94 @@ tensors in and out -- but internally activations are channels-last buffers drive
 fp32-MFMA shared-MLP kernels of csrc/mlp.hip, and the tensors handed back are transposed *views*
 of those buffers (so the next fused block reads them without a copy).
 
-Per block (reference pn2_utils/modules.py:210-246 and :500-509, pointnet2.py:116-119):
-  SA  : FPS -> ball query -> [gather(feat | xyz - centre) . W1] -> [. W2] -> [. W3 + max over K]
-  FP  : 3-NN -> interpolate+concat (channels-last) -> [. W1] -> [. W2] (-> [. W3])
-  head: [. W]*4 -> conv_score + bn_score + sigmoid
+Per block (reference pn2_utils/modules.py:210-246 and :500-509, pointnet2.py:116-119) ``sa_route`` / ``fp_route`` choose one of
+these ([...]: one kernel), and the geometry stage, the feature stage and ``prepack`` all follow that choice:
+  SA  chain3         FPS -> ball query + pairing -> [gather(feat | xyz - centre) . W1 . W2 . W3 + max over K]
+      layer12        FPS -> ball query -> [gather . W1 . W2 (+ max)] (-> [. W3 + max])
+      premul_chain*  ... + V = W1x . centre -> U = W1 . [feat | xyz] per SOURCE point -> [relu(U[nbr] - V) . W2 . W3 + max]
+      premul_layer   ... -> [relu(U[nbr] - V) . W2 (+ max)] (-> [. W3 + max])
+      layer1         FPS -> ball query -> [gather . W1] -> [. W2 (+ max)] (-> [. W3 + max])
+  FP  premul         3-NN -> Ys = W1s . sparse (, Yd = W1d . skip) -> [interpolate(Ys) + Yd, BN, ReLU] -> [. W2] (-> [. W3])
+      concat         3-NN -> interpolate+concat (channels-last) -> [. W1] -> [. W2] (-> [. W3])
+      head_chain     last block: as premul -> [. W2 . W3 . head] -- head_interp: the interpolation in that kernel's prologue
+  head: [. W]*4 -> conv_score + bn_score + sigmoid (behind a last block that took neither head route)
 Eval-mode BatchNorm is folded into a per-channel (scale, shift) applied in the GEMM epilogue.
 """
+import collections
+import ctypes
+
 import torch
 
 from . import _lib, pn2_ext
 
 ENABLED = True
-CHAIN3 = True   # level-1 set-abstraction block as one register-chained kernel (see sa_features)
+CHAIN3 = True   # level-1 set-abstraction block as one register-chained kernel (sa_route: chain3)
 SPLITK_MAX_ROWS = 1024   # at most this many rows: the GEMM is "skinny" and is split along K (see mlp_layer)
-PREMUL = True   # evaluate the first layer of wide set-abstraction blocks per source point (see sa_features)
+PREMUL = True   # evaluate the first layer of wide set-abstraction blocks per source point (sa_route: premul_*; fp_route likewise)
 PREMUL_CENTRE = True   # ... on mean-centred coordinates (a module switch like the others: bench.py --set fused.PREMUL_CENTRE=0)
+ROWCHAIN = True   # last FP block's layers 2-3 + the whole head in one register-chained kernel; level-2 SA block's layers 2-3 + pooling
+SA3_CHAIN = True  # level-3 set-abstraction block's layers 2-3 + pooling in one register-chained kernel
+FP_HEAD_INTERP = True   # ROWCHAIN's head kernel with the block's first layer (interpolation of the pre-multiplied sparse rows) in its prologue
+
+# The kernels of one set-abstraction block: ``features`` chain3 | layer12 | premul_chain512 | premul_chain256 | premul_layer |
+# layer1; ``tail``: plain layers (mlp_layer) behind that kernel, the last of them pooling -- 0: the kernel pools itself;
+# ``prepare``: what the geometry stage computes for it: pairs (count, order) | premul (mu, V, V_layer) | None.
+SaRoute = collections.namedtuple("SaRoute", "features tail prepare")
+
+
+def sa_route(module, has_feature=True):
+    """The one place that chooses a set-abstraction block's kernels, from the module's shapes and flags and the module
+    switches (the only statement of the shape limits); host only: no packed layer, no tensor.  ``has_feature``: the block is
+    given point features (the geometry stage sees coordinates only and assumes so).  None: a block the fused forward does not
+    cover (supports_sa).  ``prepare`` is premul for the eval-mode forward only: that term is a function of the weights."""
+    mlp, n = module.mlp, len(module.mlp)
+    if getattr(module.grouper, "num_neighbours", 0) != 64 or n < 2 or (has_feature and not module.use_xyz):
+        return None
+    width = [block.conv.out_channels for block in mlp]
+    relu = [block.relu is not None for block in mlp]
+    if mlp[0].conv.in_channels <= 8 and width[0] % 16 == 0 and relu[0]:
+        # narrow gathered input (level 1: rgb + xyz): layer 1 is recomputed on the VALU inside layer 2's operand load, its
+        # (P x C1) activation never exists in HBM -- or the whole block in one kernel, activations in registers (csrc/sa_chain.hip)
+        if CHAIN3 and n == 3 and width[0] == 128 and width[1] == 128 and relu[1] and width[2] % 32 == 0:
+            return SaRoute("chain3", 0, "pairs")
+        return SaRoute("layer12", n - 2, None)
+    if PREMUL and has_feature and relu[0] and width[0] % 4 == 0:
+        # wide gathered input (levels 2+; a narrow one of another first width too): layer 1 is linear in [f_j | x_j - x_c], so
+        # it is evaluated once per source point and once per centre (N + M rows instead of M * 64) and the gather, the subtraction
+        # and the ReLU happen inside layer 2's operand load -- or layers 2 and 3 + the pooling in one kernel (csrc/rowchain.hip)
+        prepare = None if module.training or torch.is_grad_enabled() else "premul"
+        if SA3_CHAIN and n == 3 and width == [512, 512, 1024] and relu[1]:
+            return SaRoute("premul_chain512", 0, prepare)
+        if ROWCHAIN and n == 3 and width == [256, 256, 512] and relu[1]:
+            return SaRoute("premul_chain256", 0, prepare)
+        return SaRoute("premul_layer", n - 2, prepare)
+    return SaRoute("layer1", n - 1, None)
+
+
+# The kernels of one feature-propagation block: ``features`` head_interp | head_chain (the last block and the segmentation
+# head as one kernel) | premul | concat; ``skip``: how the dense skip input enters a pre-multiplied first layer: table (at
+# most 4 channels: multiplied inside the interpolation) | gemm (a product of its own) | None (no skip input, or concat).
+FpRoute = collections.namedtuple("FpRoute", "features skip")
+
+
+def fp_route(module, Cs, Cd, Ns=None, Nd=None, *, seg=None, f32=True):
+    """The one place that chooses a feature-propagation block's kernels; host only, plain integers.  ``Cs`` / ``Cd``:
+    channels of the sparse and the dense (skip) input, ``Ns`` / ``Nd``: their points -- None: assume Ns < Nd (prepack knows
+    widths only); ``f32``: the skip input is float32.  ``seg``: the PointNet2Seg whose LAST block this is, when the caller
+    wants the block and the head as one kernel -- None where that does not apply (the caller runs the two separately)."""
+    first = module.mlp[0].conv
+    C1 = first.out_channels
+    # layer 1 is linear in [interpolated | skip]: multiply the SPARSE rows (and the skip rows by their own weight columns),
+    # interpolate the products.  (C1 / 4 lanes walk a row of the interpolation, a block holds a whole number of rows.)
+    premul = (PREMUL and f32 and C1 % 4 == 0 and 256 % (C1 // 4) == 0 and Cs % 4 == 0 and Cd >= 0 and (Cd % 4 == 0 or Cd <= 4)
+              and (Ns is None or Ns < Nd) and first.in_channels == Cs + Cd)
+    skip = None if not premul or Cd == 0 else "table" if Cd <= 4 else "gemm"
+    if seg is not None:
+        if not (premul and supports_rowchain(seg, module)):
+            return None
+        return FpRoute("head_interp" if FP_HEAD_INTERP and Cd <= 4 else "head_chain", skip)
+    return FpRoute("premul" if premul else "concat", skip)
+
 
 _call = _lib.call
 _L = _lib.lib
@@ -225,6 +298,26 @@ def _premul_layers(first, Cf):
         v = _Layer(W=Wx.contiguous(), scale=first.scale, shift=(-first.shift).contiguous(), N=first.N, K=3, Kpad=16, relu=0)
         return u, v
     return _derived(first, "premul", build)
+
+
+def _sa_packs(module, route, Cf, device):
+    """The packs ``route``'s kernels read (beside a chain's own weight stream, _packed_premul_chain): -> (layers, (u, v) of
+    _premul_layers or None).  The reference's channel order is [xyz(3) | feature] (modules.py:52); the kernels gather
+    [feature | xyz], so the first layer's weight columns are permuted accordingly."""
+    layers = _packed_stack(module, module.mlp, lambda: torch.cat([torch.arange(3, 3 + Cf), torch.arange(0, 3)]).to(device))
+    return layers, _premul_layers(layers[0], Cf) if route.features.startswith("premul") else None
+
+
+def _premul_centres(xyz, new_xyz, v_layer, known=()):
+    """What sa_route's ``prepare`` premul stands for: the scene mean ``mu`` (``known``: a plan that may hold it already) and
+    the per-centre term ``V`` = W_xyz . (centre - mu) with the first layer's BatchNorm folded in.  U[j] - V[c] = s W [f_j |
+    x_j - x_c] - t only up to fp32 rounding of the two big terms: both sides use the coordinates RELATIVE TO THE SCENE'S MEAN
+    (the difference is unchanged, the magnitudes -- table-top scenes sit ~0.75 m from the origin -- and with them the
+    cancellation error shrink; pack_rows subtracts).  V is a function of the WEIGHTS too, unlike the rest of a plan, so the
+    plan keeps the pack it was made with (``V_layer``) and sa_features recomputes V when the block's pack is another by then."""
+    mu = known["mu"] if "mu" in known else xyz.mean(dim=2, keepdim=True) if PREMUL_CENTRE else None
+    rows = new_xyz.shape[0] * new_xyz.shape[2]
+    return {"mu": mu, "V": mlp_layer(pack_rows(None, new_xyz, 4, mu), 4, v_layer, rows), "V_layer": v_layer}
 
 
 def pack_rows(feature, xyz, width, mu=None):
@@ -510,31 +603,18 @@ def sa_group(module, xyz, ctr, first_tie=None):
     geo = {"ctr": ctr, "new_xyz": new_xyz, "nbr": nbr}
     if first_tie is not None:
         geo["first_tie"] = first_tie
-    if (CHAIN3 and module.grouper.num_neighbours == 64 and len(module.mlp) == 3
-            and module.mlp[0].conv.in_channels <= 8):
-        # for the register-chained block (narrow gathered input, sa_features): partners whose remainders fit one point
-        # tile at waves w and w + 4 of a workgroup (csrc/sa_chain.hip), pairs of 1, 2, 3, 4 tiles in that order so that
-        # whole workgroups are of one kind; computed here, in the geometry stage, off the matrix cores' critical path
+    route = sa_route(module)
+    prepare = route.prepare if route is not None else None
+    if prepare == "pairs":
+        # partners whose remainders fit one point tile at waves w and w + 4 of a workgroup (csrc/sa_chain.hip), pairs of 1, 2,
+        # 3, 4 tiles in that order so that whole workgroups are of one kind; off the matrix cores' critical path
         geo["count"] = count
         geo["order"] = chain3_pair_order(count)
-    elif (PREMUL and not module.training and not torch.is_grad_enabled() and module.use_xyz
-          and module.mlp[0].conv.in_channels > 8 and len(module.mlp) >= 2):
-        # wide gathered input (levels 2+, see sa_features): everything of the pre-multiplied first layer that depends on the
-        # coordinates only -- the scene mean, the centred source coordinates, the per-centre term V -- is computed HERE, in
-        # the geometry stage, off the feature stage's stream (two reductions / subtractions, a pack and a tiny GEMM per level)
-        Cf = module.mlp[0].conv.in_channels - 3
-        layers = _packed_stack(module, module.mlp,
-                               lambda: torch.cat([torch.arange(3, 3 + Cf), torch.arange(0, 3)]).to(xyz.device))
-        first = layers[0]
-        if first.relu and first.N % 4 == 0 and layers[1].K == first.N:
-            _, v_layer = _premul_layers(first, Cf)
-            # (the subtraction of the scene mean happens inside the packs: pack_rows(..., mu))
-            geo["mu"] = xyz.mean(dim=2, keepdim=True) if PREMUL_CENTRE else None
-            geo["V"] = mlp_layer(pack_rows(None, new_xyz, 4, geo["mu"]), 4, v_layer, B * M)
-            # V = W_xyz . centre with the first layer's BatchNorm folded in: a function of the WEIGHTS too, unlike the rest
-            # of the plan.  The plan keeps the pack it was made with; sa_features recomputes V when the block's pack is
-            # another one by then (the weights changed: a plan reused across an optimizer step / load_state_dict)
-            geo["V_layer"] = v_layer
+    elif prepare == "premul":
+        # what the pre-multiplied first layer takes from the coordinates only, off the feature stage's stream (a reduction, a
+        # pack and a tiny GEMM per level)
+        _, (_, v_layer) = _sa_packs(module, route, module.mlp[0].conv.in_channels - 3, xyz.device)
+        geo.update(_premul_centres(xyz, new_xyz, v_layer))
     return geo
 
 
@@ -549,71 +629,37 @@ def sa_geometry(module, xyz, ctr=None, prefix_ok=None):
 
 def sa_features(module, xyz, feature, geo):
     """Grouping + SharedMLP + max over K of a PointNetSAModule (modules.py:44-56, :244-245)."""
-    B = xyz.shape[0]
+    B, N1 = xyz.shape[0], xyz.shape[2]
     M, K = module.num_centroids, module.grouper.num_neighbours
     Cf = 0 if feature is None else feature.size(1)
-    if K != 64 or len(module.mlp) < 2:
-        raise NotImplementedError("fused SA supports 64 neighbours and >= 2 MLP layers")
-    if feature is not None and not module.use_xyz:
-        raise NotImplementedError("fused SA without use_xyz")
-    # reference channel order is [xyz(3) | feature] (modules.py:52); the kernel gathers
-    # [feature | xyz], so permute the first layer's weight columns accordingly.
-    layers = _packed_stack(module, module.mlp,
-                           lambda: torch.cat([torch.arange(3, 3 + Cf), torch.arange(0, 3)]).to(xyz.device))
+    route = sa_route(module, feature is not None)
+    if route is None:
+        raise NotImplementedError("fused SA supports 64 neighbours, >= 2 MLP layers and features only with use_xyz")
+    layers, premul = _sa_packs(module, route, Cf, xyz.device)
     P = B * M * K
-    if layers[0].W8 is not None and layers[0].N % 16 == 0 and layers[0].relu:
-        # narrow gathered input (level 1: rgb + xyz): layer 1 is recomputed on the VALU inside layer 2's
-        # operand load, its (P x C1) activation never exists in HBM
-        if (CHAIN3 and len(layers) == 3 and layers[0].N == 128 and layers[1].N == 128 and layers[1].relu
-                and layers[2].N % 32 == 0):
-            # the whole block in one kernel, activations in registers (csrc/sa_chain.hip)
-            pooled = sa_chain3(feature, xyz, geo["nbr"], geo["ctr"], layers[0], layers[1], layers[2], B, M, K,
-                               geo.get("count"), geo.get("order"))
-            return geo["new_xyz"], pooled.view(B, M, -1).transpose(1, 2)
-        if len(layers) == 2:
-            pooled = sa_layer12(feature, xyz, geo["nbr"], geo["ctr"], layers[0], layers[1], B, M, K, pool_group=K)
-            return geo["new_xyz"], pooled.view(B, M, -1).transpose(1, 2)
-        h = sa_layer12(feature, xyz, geo["nbr"], geo["ctr"], layers[0], layers[1], B, M, K)
-        rest = layers[2:]
-    elif PREMUL and feature is not None and layers[0].relu and layers[0].N % 4 == 0 and layers[1].K == layers[0].N:
-        # wide gathered input (levels 2+): layer 1 is linear in [f_j | x_j - x_c], so it is evaluated once
-        # per source point and once per centre (N + M rows instead of M * 64) and the gather, the
-        # subtraction and the ReLU happen inside layer 2's operand load
-        first, N1 = layers[0], xyz.shape[2]
-        u_layer, v_layer = _premul_layers(first, Cf)
+    pool = 0 if route.tail else K       # no plain layer behind the route's kernel: it takes the max over the neighbours itself
+    nbr, ctr = geo["nbr"], geo["ctr"]
+    if premul is not None:
+        u_layer, v_layer = premul
+        if geo.get("V_layer") is not v_layer:    # stale: the weights moved after the plan was made (or it was made for another route)
+            geo = dict(geo, **_premul_centres(xyz, geo["new_xyz"], v_layer, geo))
         width = _round_up(Cf + 3, 4)
-        # U[j] - V[c] = s W [f_j | x_j - x_c] - t only up to fp32 rounding of the two big terms: both sides use the
-        # coordinates RELATIVE TO THE SCENE'S MEAN (the difference is unchanged, the magnitudes -- table-top scenes sit
-        # ~0.75 m from the origin -- and with them the cancellation error of the subtraction shrink)
-        if "V" in geo and geo.get("V_layer") is v_layer:
-            mu, V = geo["mu"], geo["V"]                  # already done by the geometry stage (sa_group), same weights
-        elif "V" in geo:                                 # stale: the weights moved after the plan was made
-            mu = geo["mu"]
-            V = mlp_layer(pack_rows(None, geo["new_xyz"], 4, mu), 4, v_layer, B * M)
-        else:
-            mu = xyz.mean(dim=2, keepdim=True) if PREMUL_CENTRE else None
-            V = mlp_layer(pack_rows(None, geo["new_xyz"], 4, mu), 4, v_layer, B * M)
-        U = mlp_layer(pack_rows(feature, xyz, width, mu), width, u_layer, B * N1)
-        if supports_sa3_chain(layers) and U.size(1) == 512:
-            # level 3: the same with 512-wide activations (layer 2 as two K-halves, csrc/rowchain.hip)
-            pooled = sa3_premul_chain(U, V, geo["nbr"], module, layers, B, N1, M)
-            return geo["new_xyz"], pooled.view(B, M, -1).transpose(1, 2)
-        if supports_sa_chain(layers) and U.size(1) == 256:
-            # layers 2 and 3 + the pooling in one kernel, layer-2 activation in registers (csrc/rowchain.hip)
-            pooled = sa_premul_chain(U, V, geo["nbr"], module, layers, B, N1, M)
-            return geo["new_xyz"], pooled.view(B, M, -1).transpose(1, 2)
-        if len(layers) == 2:
-            pooled = sa_premul_layer(U, V, geo["nbr"], layers[1], B, N1, M, K, pool_group=K)
-            return geo["new_xyz"], pooled.view(B, M, -1).transpose(1, 2)
-        h = sa_premul_layer(U, V, geo["nbr"], layers[1], B, N1, M, K)
-        rest = layers[2:]
+        U = mlp_layer(pack_rows(feature, xyz, width, geo["mu"]), width, u_layer, B * N1)
+    if route.features == "chain3":
+        h = sa_chain3(feature, xyz, nbr, ctr, layers[0], layers[1], layers[2], B, M, K, geo.get("count"), geo.get("order"))
+    elif route.features == "layer12":
+        h = sa_layer12(feature, xyz, nbr, ctr, layers[0], layers[1], B, M, K, pool_group=pool)
+    elif route.features == "premul_chain512":   # 512-wide activations (layer 2 as two K-halves)
+        h = sa3_premul_chain(U, geo["V"], nbr, module, layers, B, N1, M)
+    elif route.features == "premul_chain256":   # the layer-2 activation in registers
+        h = sa_premul_chain(U, geo["V"], nbr, module, layers, B, N1, M)
+    elif route.features == "premul_layer":
+        h = sa_premul_layer(U, geo["V"], nbr, layers[1], B, N1, M, K, pool_group=pool)
     else:
-        h = sa_layer1(feature, xyz, geo["nbr"], geo["ctr"], layers[0], B, M, K)
-        rest = layers[1:]
-    for layer in rest[:-1]:
-        h = mlp_layer(h, layer.K, layer, P)
-    pooled = mlp_layer(h, rest[-1].K, rest[-1], P, pool_group=K)              # (B*M, C_out)
-    return geo["new_xyz"], pooled.view(B, M, -1).transpose(1, 2)
+        h = sa_layer1(feature, xyz, nbr, ctr, layers[0], B, M, K)
+    for i, layer in enumerate(layers[len(layers) - route.tail:], 1):
+        h = mlp_layer(h, layer.K, layer, P, pool_group=K if i == route.tail else 0)
+    return geo["new_xyz"], h.view(B, M, -1).transpose(1, 2)              # (B*M, C_out) pooled rows
 
 
 def sa_forward(module, xyz, feature, geo=None):
@@ -627,33 +673,43 @@ def fp_geometry(module, dense_xyz, sparse_xyz):
     return {"idx": idx, "dist2": dist2}
 
 
-def _fp_first_layer(module, layers, dense_xyz, dense_feature, sparse_feature, geo):
-    """First layer of a feature-propagation block evaluated on the SPARSE rows (see fp_features); -> (B*Nd, C1)
-    channels-last activation after BN + ReLU, or None when the split does not apply."""
-    B, _, Nd = dense_xyz.shape
-    Cs, Ns = sparse_feature.size(1), sparse_feature.size(2)
-    Cd = 0 if dense_feature is None else dense_feature.size(1)
-    first = layers[0]
-    if not (PREMUL and first.N % 4 == 0 and 256 % (first.N // 4) == 0 and Cs % 4 == 0 and (Cd % 4 == 0 or Cd <= 4)
-            and Ns < Nd and first.K == Cs + Cd and (dense_feature is None or dense_feature.dtype == torch.float32)):
-        return None
-    # layer 1 is linear in [interpolated | skip]: multiply the SPARSE rows (and the skip rows by their own
-    # weight columns), interpolate the products
-    lay_s, lay_d, wd4 = _fp_split_layers(first, Cs)
+def _fp_route_of(module, dense_xyz, dense_feature, sparse_feature, seg=None):
+    return fp_route(module, sparse_feature.size(1), 0 if dense_feature is None else dense_feature.size(1),
+                    sparse_feature.size(2), dense_xyz.size(2), seg=seg,
+                    f32=dense_feature is None or dense_feature.dtype == torch.float32)
+
+
+def _fp_packs(module, route, Cs):
+    """The packs ``route``'s kernels read (beside the head chain's own, _head_chain_packs): -> (layers, _fp_split_layers or None)."""
+    layers = _packed_stack(module, module.mlp)
+    return layers, _fp_split_layers(layers[0], Cs) if route.features != "concat" else None
+
+
+def _fp_first_layer(module, route, layers, split, dense_feature, sparse_feature, geo, seg=None):
+    """First layer of a feature-propagation block evaluated on the SPARSE rows (fp_route: every route but concat); -> (B*Nd,
+    C1) channels-last activation after BN + ReLU -- route head_interp: -> (F, score) of the whole block and the head."""
+    B, Cs, Ns = sparse_feature.shape
+    Nd = geo["idx"].size(1)
+    lay_s, lay_d, wd4 = split
     Ys = mlp_layer(_as_channels_last(sparse_feature).view(B * Ns, Cs), Cs, lay_s, B * Ns)
+    dense_small = dense_feature if route.skip == "table" else None
+    if route.features == "head_interp":    # the interpolation inside the chain's prologue
+        return fp_head_chain_interp(Ys, geo["idx"], geo["dist2"], module.interpolator._eps, dense_small, wd4, layers[0], seg,
+                                    layers, B, Ns, Nd)
     Yd = None
-    if lay_d is not None:
+    if route.skip == "gemm":
+        Cd = dense_feature.size(1)
         Yd = mlp_layer(_as_channels_last(dense_feature).view(B * Nd, Cd), Cd, lay_d, B * Nd)
-    return interp_affine(Ys, geo["idx"], geo["dist2"], module.interpolator._eps, Yd,
-                         dense_feature if wd4 is not None else None, wd4, first, B, Ns, Nd)
+    return interp_affine(Ys, geo["idx"], geo["dist2"], module.interpolator._eps, Yd, dense_small, wd4, layers[0], B, Ns, Nd)
 
 
 def fp_features(module, dense_xyz, dense_feature, sparse_feature, geo):
     """Interpolate + concat + SharedMLP of a PointnetFPModule (modules.py:117-131, :507)."""
     B, _, Nd = dense_xyz.shape
-    layers = _packed_stack(module, module.mlp)
-    h = _fp_first_layer(module, layers, dense_xyz, dense_feature, sparse_feature, geo)
-    if h is not None:
+    route = _fp_route_of(module, dense_xyz, dense_feature, sparse_feature)
+    layers, split = _fp_packs(module, route, sparse_feature.size(1))
+    if route.features == "premul":
+        h = _fp_first_layer(module, route, layers, split, dense_feature, sparse_feature, geo)
         Ka, layers = layers[0].N, layers[1:]
     else:
         h, Ka = interp_concat(_as_channels_last(sparse_feature), geo["idx"], geo["dist2"], module.interpolator._eps,
@@ -686,10 +742,17 @@ def head_forward(seg, sparse_feature):
 
 
 # ---- level-2 / level-3 set-abstraction blocks: layers 2 + 3 + pooling as ONE kernel (csrc/rowchain.hip) ----------------
+_CHAIN_WIDTH = {"premul_chain256": 256, "premul_chain512": 512}    # sa_route -> C, the width of its chain's activations
+# C -> (cache slot, launching entry point, the query of its weight stream's size)
+_CHAINS = {256: ("sa_chain", "regnet_sa_premul_chain_f32", "regnet_sa_premul_chain_stream_floats"),
+           512: ("sa3_chain", "regnet_sa3_premul_chain_f32", "regnet_sa3_premul_chain_stream_floats")}
+
+
 def _packed_premul_chain(module, layers, C):
-    """Weight stream of [32 rows][256 k] stages + affine table of the SA chain with C-wide activations.  C = 256 (level 2,
-    cache slot "sa_chain"): 24 stages, layer 2 then layer 3.  C = 512 (level 3, "sa3_chain"): 96 stages, W2 as (K-half, 16 row
-    blocks), W3 as (32 row blocks, K-half)."""
+    """Weight stream of [32 rows][256 k] stages + affine table of the SA chain with C-wide activations.  Level 2: 24 stages,
+    layer 2 then layer 3.  Level 3: 96 stages, W2 as (K-half, 16 row blocks), W3 as (32 row blocks, K-half)."""
+    slot, _, stream_floats = _CHAINS[C]
+
     def build():
         l2, l3 = layers[1], layers[2]
         halves = range(C // 256)
@@ -697,38 +760,19 @@ def _packed_premul_chain(module, layers, C):
         stages += [_swizzle_stage(l3.W[32 * s:32 * s + 32, 256 * kh:256 * kh + 256]) for s in range(C // 16) for kh in halves]
         stream = torch.cat(stages).contiguous()
         affine = torch.cat([l2.scale[:C], l2.shift[:C], l3.scale[:2 * C], l3.shift[:2 * C]]).contiguous()
-        floats = _L.regnet_sa_premul_chain_stream_floats() if C == 256 else _L.regnet_sa3_premul_chain_stream_floats()
-        assert stream.numel() == floats and affine.numel() == 6 * C
+        assert stream.numel() == getattr(_L, stream_floats)() and affine.numel() == 6 * C
         return stream, affine
-    return _cached(module, "sa_chain" if C == 256 else "sa3_chain", _signature(module.mlp), build)
+    return _cached(module, slot, _signature(module.mlp), build)
 
 
 def _premul_chain(C, U, V, nbr, module, layers, B, Nsrc, M):
     stream, affine = _packed_premul_chain(module, layers, C)
     out = torch.empty((B * M, 2 * C), dtype=torch.float32, device=U.device)
     ticket = _tickets(U.device)
-    _call("regnet_sa_premul_chain_f32" if C == 256 else "regnet_sa3_premul_chain_f32", U, U.data_ptr(), U.stride(0),
-          V.data_ptr(), V.stride(0), nbr.data_ptr(), B, Nsrc, M, stream.data_ptr(), stream.numel() // 8192, affine.data_ptr(),
-          affine.numel(), layers[2].relu, out.data_ptr(), out.stride(0), ticket.data_ptr())
+    _call(_CHAINS[C][1], U, U.data_ptr(), U.stride(0), V.data_ptr(), V.stride(0), nbr.data_ptr(), B, Nsrc, M, stream.data_ptr(),
+          stream.numel() // 8192, affine.data_ptr(), affine.numel(), layers[2].relu, out.data_ptr(), out.stride(0),
+          ticket.data_ptr())
     return out
-
-
-def _packed_sa_chain(module, layers):
-    return _packed_premul_chain(module, layers, 256)
-
-
-def _packed_sa3_chain(module, layers):
-    return _packed_premul_chain(module, layers, 512)
-
-
-def supports_sa_chain(layers):
-    return (ROWCHAIN and len(layers) == 3 and layers[0].N == 256 and layers[1].K == 256 and layers[1].N == 256
-            and layers[1].relu and layers[2].K == 256 and layers[2].N == 512)
-
-
-def supports_sa3_chain(layers):
-    return (SA3_CHAIN and len(layers) == 3 and layers[0].N == 512 and layers[1].K == 512 and layers[1].N == 512
-            and layers[1].relu and layers[2].K == 512 and layers[2].N == 1024)
 
 
 def sa_premul_chain(U, V, nbr, module, layers, B, Nsrc, M):
@@ -742,10 +786,6 @@ def sa3_premul_chain(U, V, nbr, module, layers, B, Nsrc, M):
 
 
 # ---- FP3 tail + segmentation head as ONE kernel (csrc/rowchain.hip) --------------------------------------------------
-ROWCHAIN = True   # last FP block's layers 2-3 + the whole head in one register-chained kernel
-SA3_CHAIN = True  # level-3 set-abstraction block's layers 2-3 + pooling in one register-chained kernel
-
-
 def _swizzle_stage(block):
     """(R, KC) weight block -> the LDS image of a rowchain stage: 16-byte chunk c' of row r holds logical chunk
     c' ^ (r & 15) (XOR on the low 4 bits of the chunk index; see csrc/rowchain.hip:rc_frag_offsets)."""
@@ -797,10 +837,14 @@ def supports_rowchain(seg, fp_module):
     return widths == [256, 256, 256, 512, 256, 256, 128] and all(relus) and seg.mlp[0].conv.in_channels == 256
 
 
+def _head_chain_packs(seg, fp_layers, first=None, wd4=None):
+    """The head routes' own packs: -> (weight stream, affine table, score head, head_interp's tables -- given its ``first`` layer)."""
+    return (*_packed_rowchain(seg, fp_layers), _packed_head(seg), None if first is None else _interp_tables(first, wd4))
+
+
 def fp_head_chain(h1, seg, fp_layers, P):
     """h1 (P, 256) -> (F (P, 256), score (P,)): FP layers 2-3 and the segmentation head in one launch."""
-    stream, affine = _packed_rowchain(seg, fp_layers)
-    w, bias, bn_scale, bn_shift = _packed_head(seg)
+    stream, affine, (w, bias, bn_scale, bn_shift), _ = _head_chain_packs(seg, fp_layers)
     F = torch.empty((P, 256), dtype=torch.float32, device=h1.device)
     score = torch.empty((P,), dtype=torch.float32, device=h1.device)
     ticket = _tickets(h1.device)   # work-queue head, zeroed on this stream
@@ -810,8 +854,7 @@ def fp_head_chain(h1, seg, fp_layers, P):
     return F, score
 
 
-FP_HEAD_INTERP = True   # ... with the block's first layer (interpolation of the pre-multiplied sparse rows) in its prologue
-TAIL_SINK = None        # a list (set by ForwardPipeline around a feature stage): fp_head_chain_interp puts its partial last round
+TAIL_SINK = None       # a list (set by ForwardPipeline around a feature stage): fp_head_chain_interp puts its partial last round
                         # of blocks on a side stream and appends the event that marks its end; None: one launch, as always
 _CUS = 256
 _tail_streams = {}
@@ -827,9 +870,7 @@ def _tail_stream(device):
 def fp_head_chain_interp(Ys, idx, dist2, eps, dense_small, wd4, first, seg, fp_layers, B, Ns, Nd):
     """(Ys (B*Ns, 256) pre-multiplied sparse rows, 3-NN indices / squared distances, rgb-like skip input) -> (F, score):
     the whole last feature-propagation block + the segmentation head in one launch; h1 is never written."""
-    stream, affine = _packed_rowchain(seg, fp_layers)
-    w, bias, bn_scale, bn_shift = _packed_head(seg)
-    tables = _interp_tables(first, wd4)
+    stream, affine, (w, bias, bn_scale, bn_shift), tables = _head_chain_packs(seg, fp_layers, first, wd4)
     P = B * Nd
     F = torch.empty((P, 256), dtype=torch.float32, device=Ys.device)
     score = torch.empty((P,), dtype=torch.float32, device=Ys.device)
@@ -871,59 +912,41 @@ def fp_head_chain_interp(Ys, idx, dist2, eps, dense_small, wd4, first, seg, fp_l
 def fp_head_forward(seg, fp_module, dense_xyz, dense_feature, sparse_feature, geo):
     """Last feature-propagation block + segmentation head (pointnet2.py:64-84, :116-119) -> (feature (B,256,N) view,
     score (B,N)); None when the chained kernel does not apply (the caller then runs the two blocks separately)."""
-    if not supports_rowchain(seg, fp_module):
+    route = _fp_route_of(fp_module, dense_xyz, dense_feature, sparse_feature, seg)
+    if route is None:
         return None
     B, _, Nd = dense_xyz.shape
-    layers = _packed_stack(fp_module, fp_module.mlp)
-    Cs, Ns = sparse_feature.size(1), sparse_feature.size(2)
-    Cd = 0 if dense_feature is None else dense_feature.size(1)
-    first = layers[0]
-    if (FP_HEAD_INTERP and PREMUL and first.N == 256 and first.relu and Cs % 4 == 0 and Cd <= 4 and Ns < Nd
-            and first.K == Cs + Cd and sparse_feature.dtype == torch.float32
-            and (dense_feature is None or dense_feature.dtype == torch.float32)):
-        # the first layer on the SPARSE rows (fused._fp_first_layer), its interpolation inside the chain's prologue
-        lay_s, _, wd4 = _fp_split_layers(first, Cs)
-        Ys = mlp_layer(_as_channels_last(sparse_feature).view(B * Ns, Cs), Cs, lay_s, B * Ns)
-        F, score = fp_head_chain_interp(Ys, geo["idx"], geo["dist2"], fp_module.interpolator._eps,
-                                        dense_feature if wd4 is not None else None, wd4, first, seg, layers, B, Ns, Nd)
-        return F.view(B, Nd, 256).transpose(1, 2), score.view(B, Nd)
-    h1 = _fp_first_layer(fp_module, layers, dense_xyz, dense_feature, sparse_feature, geo)
-    if h1 is None:
-        return None
-    F, score = fp_head_chain(h1, seg, layers, B * Nd)
+    layers, split = _fp_packs(fp_module, route, sparse_feature.size(1))
+    out = _fp_first_layer(fp_module, route, layers, split, dense_feature, sparse_feature, geo, seg)
+    F, score = out if route.features == "head_interp" else fp_head_chain(out, seg, layers, B * Nd)
     return F.view(B, Nd, 256).transpose(1, 2), score.view(B, Nd)
 
 
 def prepack(score_net, region_net=None):
-    """Build every packed-weight cache of the fused forward NOW, on the current stream.  The caches are otherwise
-    filled lazily by whichever stream first runs a block; with several feature-stage streams
-    (``ForwardPipeline(mlp_streams=2)``) a second stream could then read a cache whose packing kernels, enqueued on
-    the first stream, have not finished.  ``ForwardPipeline.run`` calls this before its streams start."""
+    """Build every packed-weight cache of the fused forward NOW, on the current stream: the packs of the route each block will
+    take, through the helpers its kernels read them through.  The caches are otherwise filled lazily by whichever stream first
+    runs a block; with several feature-stage streams (``ForwardPipeline(mlp_streams=2)``) a second stream could then read a
+    cache whose packing kernels, enqueued on the first, have not finished.  ``ForwardPipeline.run`` calls this first."""
     forget(score_net, region_net)
     seg = getattr(score_net, "extrat_featurePN2", score_net)
     dev = next(seg.parameters()).device
     for sa in seg.sa_modules:
-        Cf = sa.in_channels
-        layers = _packed_stack(sa, sa.mlp, lambda Cf=Cf: torch.cat([torch.arange(3, 3 + Cf), torch.arange(0, 3)]).to(dev))
-        if layers[0].W8 is None and Cf > 0:
-            _premul_layers(layers[0], Cf)
-            if supports_sa_chain(layers):
-                _packed_sa_chain(sa, layers)
-            if supports_sa3_chain(layers):
-                _packed_sa3_chain(sa, layers)
-    sparse = seg.sa_modules[-1].out_channels
+        route = sa_route(sa, bool(sa.in_channels))
+        if route is not None:
+            layers, premul = _sa_packs(sa, route, sa.in_channels, dev)
+            if route.features in _CHAIN_WIDTH:
+                _packed_premul_chain(sa, layers, _CHAIN_WIDTH[route.features])
+    Cs = seg.sa_modules[-1].out_channels
     for fp in seg.fp_modules:
-        layers = _packed_stack(fp, fp.mlp)
-        Cs = sparse
-        if Cs <= layers[0].K:
-            split = _fp_split_layers(layers[0], Cs)
-            if fp is seg.fp_modules[-1] and layers[0].N == 256:
-                _interp_tables(layers[0], split[2])
-        sparse = fp.out_channels
+        last = fp is seg.fp_modules[-1]
+        Cd = fp.mlp[0].conv.in_channels - Cs
+        route = (fp_route(fp, Cs, Cd, seg=seg) if last else None) or fp_route(fp, Cs, Cd)
+        layers, split = _fp_packs(fp, route, Cs)
+        if route.features.startswith("head"):
+            _head_chain_packs(seg, layers, *((layers[0], split[2]) if route.features == "head_interp" else ()))
+        Cs = fp.out_channels
     _packed_stack(seg.mlp, seg.mlp)
     _packed_head(seg)
-    if supports_rowchain(seg, seg.fp_modules[-1]):
-        _packed_rowchain(seg, _packed_stack(seg.fp_modules[-1], seg.fp_modules[-1].mlp))
     if region_net is not None:
         _packed_named(region_net.extrat_feature_region, _TWOSTAGE, _TWOSTAGE_TREE)
         _packed_named(region_net.extrat_feature_refine, _REFINE, _REFINE_TREE)
@@ -973,23 +996,28 @@ HEADS_CHAIN = True   # the grasp heads as ONE launch each (csrc/heads.hip) inste
 HEADS_CHAIN_MAX_ROWS = 256
 
 
-def _heads_chain(x, L, plan, n_a, n_b):
-    """x (n, K) float32 rows; ``plan``: [(layer name, src buffer, dst buffer)] in execution order (buffers: 0 input, 1-3 LDS
-    scratch, 4 / 5 outputs a / b) -> (out_a (n, n_a), out_b (n, n_b)).  The int64 descriptor (device addresses of the packed
-    weights) is built per call: nine integers per layer."""
+def _heads_launch(entry, x, L, rows, count, n_a, n_b):
+    """One launch of a csrc/heads.hip entry point on x (n, K) float32 rows -> (out_a (n, n_a), out_b (n, n_b)).  ``rows``:
+    [(layer name, *where)] in execution order; the int64 descriptor (device addresses of the packed weights, the layer's
+    shape, then ``where``) is built per call."""
     n = x.shape[0]
     x = x if x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 else x.contiguous().clone()
     descr = []
-    for name, src, dst in plan:
+    for name, *where in rows:
         lay = L[name]
-        descr += [lay.W.data_ptr(), lay.scale.data_ptr(), lay.shift.data_ptr(), lay.K, lay.Kpad, lay.N, lay.relu, src, dst]
-    import ctypes
+        descr += [lay.W.data_ptr(), lay.scale.data_ptr(), lay.shift.data_ptr(), lay.K, lay.Kpad, lay.N, lay.relu, *where]
     arr = (ctypes.c_int64 * len(descr))(*descr)
     out_a = torch.empty((n, n_a), dtype=torch.float32, device=x.device)
     out_b = torch.empty((n, n_b), dtype=torch.float32, device=x.device)
-    _call("regnet_heads_chain_f32", x, x.data_ptr(), x.stride(0), x.shape[1], n, ctypes.addressof(arr), len(plan),
-          out_a.data_ptr(), n_a, out_b.data_ptr(), n_b)
+    _call(entry, x, x.data_ptr(), x.stride(0), x.shape[1], n, ctypes.addressof(arr), count, out_a.data_ptr(), n_a,
+          out_b.data_ptr(), n_b)
     return out_a, out_b
+
+
+def _heads_chain(x, L, plan, n_a, n_b):
+    """``plan``: [(layer name, src buffer, dst buffer)] in execution order (buffers: 0 input, 1-3 LDS scratch, 4 / 5 outputs
+    a / b): nine integers per layer."""
+    return _heads_launch("regnet_heads_chain_f32", x, L, plan, len(plan), n_a, n_b)
 
 
 HEADS_TREE = True    # more rows than HEADS_CHAIN_MAX_ROWS: ONE launch of csrc/heads.hip's heads_tree_kernel (32 rows per workgroup,
@@ -1000,21 +1028,8 @@ def _heads_tree(x, L, tree, tails, n_a, n_b):
     """x (n, K) rows -> (out_a (n, n_a), out_b (n, n_b)) by ``regnet_heads_tree_f32``.  ``tree``: (trunk layer name, the two
     branches' first layer names), whose joined layer ``_packed_named`` put in ``L``; ``tails``: [(layer, src, src_off, dst,
     dst_off)] in execution order."""
-    n = x.shape[0]
-    x = x if x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 else x.contiguous().clone()
     trunk, first = tree
-    descr = []
-    for name, src, src_off, dst, dst_off in [(trunk, 0, 0, 0, 0), (first, 0, 0, 0, 0)] + tails:
-        lay = L[name]
-        descr += [lay.W.data_ptr(), lay.scale.data_ptr(), lay.shift.data_ptr(), lay.K, lay.Kpad, lay.N, lay.relu, src, src_off,
-                  dst, dst_off]
-    import ctypes
-    arr = (ctypes.c_int64 * len(descr))(*descr)
-    out_a = torch.empty((n, n_a), dtype=torch.float32, device=x.device)
-    out_b = torch.empty((n, n_b), dtype=torch.float32, device=x.device)
-    _call("regnet_heads_tree_f32", x, x.data_ptr(), x.stride(0), x.shape[1], n, ctypes.addressof(arr), len(tails),
-          out_a.data_ptr(), n_a, out_b.data_ptr(), n_b)
-    return out_a, out_b
+    return _heads_launch("regnet_heads_tree_f32", x, L, [(trunk, 0, 0, 0, 0), (first, 0, 0, 0, 0)] + tails, len(tails), n_a, n_b)
 
 
 def _tree_ok(L, tree, x):

@@ -406,7 +406,7 @@ def test_sa_premul_chain_equals_layerwise_kernels(B, M):
     sa = score_net.extrat_featurePN2.sa_modules[1]
     Cf = sa.in_channels
     layers = fused._packed_stack(sa, sa.mlp, lambda: torch.cat([torch.arange(3, 3 + Cf), torch.arange(0, 3)]).to(DEV))
-    assert fused.supports_sa_chain(layers)
+    assert fused.sa_route(sa).features == "premul_chain256"
     Nsrc = 300
     U = torch.randn(B * Nsrc, 256, device=DEV)
     V = torch.randn(B * M, 256, device=DEV) * 0.5
@@ -440,7 +440,7 @@ def test_sa3_premul_chain_equals_layerwise_kernels(B, M):
     sa = score_net.extrat_featurePN2.sa_modules[2]
     Cf = sa.in_channels
     layers = fused._packed_stack(sa, sa.mlp, lambda: torch.cat([torch.arange(3, 3 + Cf), torch.arange(0, 3)]).to(DEV))
-    assert fused.supports_sa3_chain(layers)
+    assert fused.sa_route(sa).features == "premul_chain512"
     Nsrc = 300
     U = torch.randn(B * Nsrc, 512, device=DEV)
     V = torch.randn(B * M, 512, device=DEV) * 0.5
