@@ -1006,6 +1006,61 @@ int regnet_cluster_points_f32(const float* xyz, const uint8_t* mask, int64_t N, 
 int regnet_cluster_assign_f32(const float* query, int64_t Q, const float* xyz, const int32_t* label, int64_t N, float radius,
                               int32_t* object, int32_t* point, void* stream);
 
+/* ---- multi-view fusion (csrc/fuse.hip): a voxel-grid merge of up to 8 posed clouds into one cloud, on the device ------------
+ * One output point per occupied voxel: the centroid of the voxel's points and colours.  Canonical fp32 arithmetic: individually
+ * rounded binary32 operations in the written order (-ffp-contract=off); no float is ever summed, so the result is bitwise
+ * reproducible and independent of the order in which the atomics land.
+ *   rows        view v has n_v rows: xyz (n_v,3) float32 contiguous, rgb (n_v,3) float32 contiguous or NULL (colour 0).  The
+ *               global row of row r of view v is row_offset_v + r, row_offset_v = n_0 + ... + n_{v-1} (the caller's sum).  A row
+ *               whose three coordinates are not all finite is dropped and counted.
+ *   pose        pose12 (12 float32, HOST): rows 0..2 of the row-major 4x4 camera-to-common transform, each entry rounded once
+ *               from float64 by the caller.  x' = ((r00 x + r01 y) + r02 z) + t0 and likewise y', z'.
+ *   voxel       inv = float32(1.0 / voxel), the division in float64; origin3 (3 float32, HOST).  Per axis a = (x' - ox) * inv,
+ *               i = floorf(a), f = a - float32(i) (in [0, 1]; 1 only where a tiny negative a rounds up).  A row whose a is not
+ *               finite or whose i lies outside [-2^20, 2^20) on any axis is out of range: dropped and counted.
+ *   key         ((ix + 2^20) << 42) | ((iy + 2^20) << 21) | (iz + 2^20), uint64, below 2^63; all ones marks an empty slot.
+ *   table       regnet_fuse_table_slots(max_voxels) = 2 * next_pow2(max_voxels) slots, open addressing with linear probing; the
+ *               home slot is the top log2(slots) bits of key * 0x9E3779B97F4A7C15 (mod 2^64).  A row claims an empty slot with a
+ *               64-bit atomicCAS on the key word.  The probe loop is bounded by the slot count.  A row that finds no slot, or
+ *               that opens voxel number max_voxels + 1 or a later one, sets the overflow flag and is dropped.
+ *   per slot    count: int32 add; S_x, S_y, S_z: 64-bit adds of (int32)(f * 16777216.0f); C_r, C_g, C_b: 64-bit adds of
+ *               (int32)rintf(clamp(c, 0, 1) * 255.0f), a NaN colour counting as 0; first: atomicMin of the global row; views:
+ *               atomicOr of 1 << view.
+ *   output      voxels with count >= min_count, in ascending key order, K of them.  count == 1: the transformed point (x', y', z')
+ *               of row `first` and its colour as given, bit for bit.  Otherwise, in float64 with one rounding per operation:
+ *               a_mean = i + S / (count * 2^24), x = float32(ox + a_mean / (double)inv); colour = float32(C / (count * 255.0)).
+ *   xyz, rgb    (max_voxels,3) float32: rows >= K hold the quiet NaN 0x7FC00000 / 0.
+ *   count, views, first  (max_voxels) int32: -1 for rows >= K.
+ *   num         (4) int32 DEVICE: K, rows accumulated into a voxel, rows dropped (non-finite + out of range), overflow 0 / 1.
+ *               With overflow set the rows are a merge of a subset of the input and num[1] + num[2] is below the row count.
+ * The three stages of one merge share `workspace`: regnet_fuse_workspace_bytes(max_voxels) bytes, 16-byte aligned (64 bytes of
+ * counters, 92 bytes per slot, 4 bytes per voxel); -1 for max_voxels outside [1, 2^21], as regnet_fuse_table_slots.
+ *   regnet_fuse_accumulate_f32  stage 1 for ONE view, called once per view on the same workspace, view = 0..7.  reset != 0 first
+ *               empties the table and the counters (three fills); give it on the first call of a merge.  n == 0: success, and
+ *               with reset the table is still emptied.  One launch, a thread per row.
+ *   regnet_fuse_finalise_f32    stage 2: kept_keys (max_voxels) int64 DEVICE is written whole: the keys of the kept voxels in
+ *               its first K entries, in any order, 0x7FFFFFFFFFFFFFFF beyond.  Two launches.
+ *   (the caller)                order = the indices of an ascending sort of kept_keys (the keys are distinct).
+ *   regnet_fuse_emit_f32        stage 3: order (max_voxels) int64 DEVICE, of which the first K entries are read; writes the
+ *               outputs whole.  One launch.
+ * No host read, no synchronisation, no allocation; no thread waits for another and every loop ends on its own count.  Errors,
+ * all before any launch: n < 0, row_offset < 0, view < 0 or min_count < 1 -> REGNET_ERR_SHAPE; view >= 8, voxel not finite or
+ * <= 0, max_voxels outside [1, 2^21] or row_offset + n >= 2^31 -> REGNET_ERR_UNSUPPORTED; a NULL pointer for a required array ->
+ * REGNET_ERR_NULL.
+ *
+ * HOST code, no device: regnet_fuse_key_host evaluates pose, voxel and key of one point with the inline functions the kernel is
+ * compiled from -> 0 and *key; 1 (a non-finite coordinate) or 2 (out of range) and *key = all ones.  regnet_fuse_home_slot_host:
+ * the home slot of `key` in a table of `slots` slots (a power of two in [2, 2^22], else -1).                                  */
+int64_t regnet_fuse_table_slots(int64_t max_voxels);
+int64_t regnet_fuse_workspace_bytes(int64_t max_voxels);
+int regnet_fuse_key_host(float x, float y, float z, const float* pose12, const float* origin3, float inv, uint64_t* key);
+int64_t regnet_fuse_home_slot_host(uint64_t key, int64_t slots);
+int regnet_fuse_accumulate_f32(const float* xyz, const float* rgb, int64_t n, int view, int64_t row_offset, const float* pose12,
+                               const float* origin3, double voxel, int64_t max_voxels, int reset, void* workspace, void* stream);
+int regnet_fuse_finalise_f32(int64_t max_voxels, int64_t min_count, int64_t* kept_keys, void* workspace, void* stream);
+int regnet_fuse_emit_f32(const int64_t* order, const float* origin3, double voxel, int64_t max_voxels, float* xyz, float* rgb,
+                         int32_t* count, int32_t* views, int32_t* first, int32_t* num, void* workspace, void* stream);
+
 /* ---- deterministic mode (csrc/scatter.hip, csrc/det.hip, csrc/bn_train.hip) ------------------------------------------
  * The float32 kernels behind torch.use_deterministic_algorithms(True): every sum of the training backward is formed in one
  * fixed order, so runs agree bit for bit.  The default entry points above are unchanged.

@@ -42,6 +42,7 @@ SOURCES = [
                                                                # rounded fp32 arithmetic; SLP packs the tests into v_pk ops + moves
     ("depth.hip", ["-ffp-contract=off"]),   # depth frames: coordinates, filter and visibility are compared bit for bit with numpy
     ("cluster.hip", ["-ffp-contract=off"]),   # object segmentation: every edge is decided on individually rounded fp32 distances
+    ("fuse.hip", ["-ffp-contract=off"]),   # multi-view fusion: every voxel is decided on individually rounded fp32 arithmetic
 ]
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc"]
@@ -74,7 +75,8 @@ NO_VGPR_SPILL = {"mlp.o": ["mlp_gemm_kernelILi0E", "gemm2_kernel"], "sa_chain.o"
                  "rowchain.o": ["sa_premul_chain_kernel", "sa3_premul_chain_kernel", "fp_head_chain_kernelILb0E"],
                  "heads.o": ["heads_chain_kernel", "heads_tree_kernel"], "ops_f64.o": ["_f64_kernel"],
                  "scatter.o": ["scatter_", "segsum_"], "det.o": ["det_"],
-                 "ingest.o": ["ingest_"], "nms.o": ["nms_"], "plane.o": ["plane_"], "depth.o": ["depth_"]}
+                 "ingest.o": ["ingest_"], "nms.o": ["nms_"], "plane.o": ["plane_"], "depth.o": ["depth_"],
+                 "fuse.o": ["fuse_"]}
 
 
 def check_no_vgpr_spill(obj_path, fragments):

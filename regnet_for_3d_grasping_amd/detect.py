@@ -25,6 +25,11 @@ becomes the ``(xyz, rgb)`` pair on the device (``depth_frame.to_cloud``; ``depth
 With ``segment`` (``--segment``, ``--cluster-tolerance``, ``--min-object-points``, ``--max-objects``, ``--top-k-per-object``) the
 points above the table are clustered into objects on the device (``segment.cluster_points``), every grasp of one set is given
 the object it belongs to, and the selection may be per object; the record additionally carries ``SEGMENT_KEYS``.
+
+A camera frame may also be a ``fusion.MultiView`` (a ``.npz`` file with a ``views`` entry: the depth frames of up to 8 cameras
+and their poses): the views are merged into one evenly sampled cloud on the device (``fusion.voxel_merge``; ``fuse`` / ``--voxel``,
+``--max-voxels``, ``--min-voxel-points`` set the voxel grid) and take the camera-frame path from there, ``transform="auto"``
+included; the record additionally carries ``FUSE_KEYS``.
 """
 import argparse
 import contextlib
@@ -51,6 +56,7 @@ SELECT_KEYS = ("grasp_selected", "grasp_selected_index")       # added to the re
 TABLE_KEYS = ("table_transform", "table_plane")                # added when the transform is estimated per frame ("auto")
 SEGMENT_KEYS = ("point_object", "object_size", "object_bbox", "grasp_object")    # added when the detector has ``segment``
 SEGMENT_SELECT_KEYS = SELECT_KEYS + ("grasp_selected_object",)                  # ... with ``top_k_per_object``
+FUSE_KEYS = ("fuse_num", "fuse_views")                          # added when the frame was a ``fusion.MultiView``
 
 
 def save_path_for(pc_path, real_data):
@@ -79,12 +85,18 @@ class GraspDetector:
     float32 and ``grasp_object`` (k_source,) int32, the object of every grasp of the source set (-1: none); with
     ``top_k_per_object`` the selection is the best distinct grasps of every object and ``grasp_selected_object`` (k,) int32
     names each one's object; it replaces the per-frame selection: ``select``'s source and thresholds apply, its ``top_k`` does
-    not."""
+    not.  ``fuse``: None, or a ``fusion.FuseParams`` / a dict of its fields (``voxel``, ``origin``, ``max_voxels``, ``min_count``):
+    how a ``fusion.MultiView`` handed to ``ingest`` / ``detect`` is merged into one cloud; the record then also carries
+    ``fuse_num`` (4,) int32 = (merged points, rows merged, rows dropped, overflow) and ``fuse_views`` (views,) int64, the merged
+    points each view contributed to.  Other frames never see it."""
 
     def __init__(self, score_net, region_net, params=TEST_PARAMS, gripper_params=GRIPPER_PARAMS, eval_params=EVAL_PARAMS,
-                 transform=None, bounds=None, num_points=ALL_POINTS_NUM, use_theta=USE_THETA, select=None, depth=None, segment=None):
-        from . import depth_frame, grasp_select, ingest
+                 transform=None, bounds=None, num_points=ALL_POINTS_NUM, use_theta=USE_THETA, select=None, depth=None, segment=None,
+                 fuse=None):
+        from . import depth_frame, fusion, grasp_select, ingest
         from . import segment as segment_mod
+        self.fuse = fusion.FuseParams.coerce(fuse)
+        self.fused = None                         # the fusion.Fused of the last frame, when it was a MultiView
         self.segment = segment_mod.SegmentParams.coerce(segment)
         self.select = grasp_select.SelectParams.coerce(select)
         self.depth = depth_frame.DepthParams.coerce(depth)
@@ -106,14 +118,17 @@ class GraspDetector:
             raise RuntimeError("GraspDetector: the networks must be on a GPU (no CPU path)")
 
     def ingest(self, frame):
-        """``frame``: an ``ingest.Frame``, an ``(xyz, rgb)`` pair of a camera frame, a ``depth_frame.DepthFrame`` or a record
-        dict -> ``ingest.Frame``."""
-        from . import depth_frame, ingest
+        """``frame``: an ``ingest.Frame``, an ``(xyz, rgb)`` pair of a camera frame, a ``depth_frame.DepthFrame``, a
+        ``fusion.MultiView`` or a record dict -> ``ingest.Frame``."""
+        from . import depth_frame, fusion, ingest
         if isinstance(frame, ingest.Frame):
             return frame
         if isinstance(frame, dict):
             return ingest.ingest_record(frame, self.num_points, self.device)
-        if isinstance(frame, depth_frame.DepthFrame):      # on the device, no host read; draws nothing from numpy's stream
+        if isinstance(frame, fusion.MultiView):            # merged on the device, no host read; the rows beyond the merged
+            self.fused = fusion.fuse_frames(frame, self.depth, self.fuse, device=self.device)    # points are NaN rows
+            frame = self.fused.cloud()
+        elif isinstance(frame, depth_frame.DepthFrame):    # on the device, no host read; draws nothing from numpy's stream
             frame = depth_frame.to_cloud(frame, self.depth, device=self.device)
         xyz, rgb = frame
         transform = self.transform
@@ -156,7 +171,11 @@ class GraspDetector:
             with np_random.deferred(), torch.no_grad(), torch.cuda.device(self.device), \
                     contextlib.redirect_stdout(io.StringIO()):
                 self.table = None
+                self.fused = None
                 fr = self.ingest(frame)
+                fused = self.fused
+                if fused is not None:
+                    fused.check()          # one 16-byte read; ValueError naming max_voxels when the merge overflowed
                 pc = fr.pc
                 all_feature, output_score, _ = self.score_net(pc)
                 g = get_grasp_allobj(pc, output_score, self.params, [], self.use_theta)
@@ -201,6 +220,9 @@ class GraspDetector:
                     _, _, out["object_size"], _, out["object_bbox"] = segmented.objects()
                     out["point_object"] = segmented.label.cpu().numpy()
                     out["grasp_object"] = grasp_object.cpu().numpy()
+                if fused is not None:
+                    out["fuse_num"] = fused.num.cpu().numpy()
+                    out["fuse_views"] = fused.per_view().cpu().numpy()
         finally:
             self.score_net.train(was_training[0])
             self.region_net.train(was_training[1])
@@ -214,20 +236,22 @@ class GraspDetector:
             out["table_transform"] = np.array(transform, dtype=np.float64)
             out["table_plane"] = np.array(list(plane.normal) + [plane.offset, plane.rms], dtype=np.float64)
             keys = keys + TABLE_KEYS
+        if fused is not None:
+            keys = keys + FUSE_KEYS
         return {key: out[key] for key in keys}
 
     def detect_file(self, path, save_path=None, real_data=None):
-        """``test_one_file`` (test.py:94-148): ``.pcd`` -> camera frame, ``.npz`` -> depth frame, anything else -> dataset
-        record, unless ``real_data`` says so.  The dict is pickled to ``save_path`` (default: the rule of :143-145; no file when that rule leaves the path
+        """``test_one_file`` (test.py:94-148): ``.pcd`` -> camera frame, ``.npz`` -> depth frame (with a ``views`` entry: the depth frames of several
+        cameras, ``fusion.load_npz``), anything else -> dataset record, unless ``real_data`` says so.  The dict is pickled to ``save_path`` (default: the rule of :143-145; no file when that rule leaves the path
         unchanged, which would overwrite the input).  Prints the reference's three count lines, and the selected count when
         the detector has ``select``, and the object count when it has ``segment``.  -> (dict, save path or None)."""
-        from . import depth_frame, ingest
+        from . import depth_frame, fusion, ingest
         is_depth = path.endswith(".npz")
         if real_data is None:
             real_data = is_depth or path.lower().endswith(".pcd")
         if is_depth:
             real_data = True
-            out = self.detect(depth_frame.load_npz(path))
+            out = self.detect(fusion.load_npz(path) if fusion.is_multiview_npz(path) else depth_frame.load_npz(path))
         elif real_data:
             xyz, rgb, _ = ingest.read_pcd(path)
             out = self.detect((xyz, rgb))
@@ -291,6 +315,13 @@ def depth_from_args(args):
     return given if given else None
 
 
+def fuse_from_args(args):
+    """The CLI's three fusion flags -> a ``fuse`` dict, or None when none of them was given."""
+    given = {"voxel": args.voxel, "max_voxels": args.max_voxels, "min_count": args.min_voxel_points}
+    given = {key: value for key, value in given.items() if value is not None}
+    return given if given else None
+
+
 def main(argv=None):
     """``main()`` of test.py:150-164."""
     from . import checkpoint
@@ -326,6 +357,10 @@ def main(argv=None):
     parser.add_argument("--min-object-points", type=int, default=None, help="drop clusters of fewer points (50)")
     parser.add_argument("--max-objects", type=int, default=None, help="keep the largest so many objects (64)")
     parser.add_argument("--top-k-per-object", type=int, default=None, help="select the K best distinct grasps of every object")
+    # multi-view frames (*.npz with a `views` entry: fusion.voxel_merge): the voxel grid the views are merged on
+    parser.add_argument("--voxel", type=float, default=None, help="edge of the voxels the views are merged in [m] (0.002)")
+    parser.add_argument("--max-voxels", type=int, default=None, help="rows of the merged cloud, at most 2^21 (2^20)")
+    parser.add_argument("--min-voxel-points", type=int, default=None, help="drop voxels with fewer points (1)")
     args = parser.parse_args(argv)
     select = select_from_args(args)
     obj_class_num, group_num, gripper_num, score_thre, depth, reg_channel = MODEL_PARAMS
@@ -337,7 +372,7 @@ def main(argv=None):
     eval_params = [DEPTH, WIDTH, TABLE_HEIGHT, args.gpu, CENTER_NUM]
     detector = GraspDetector(score_net.to(dev), region_net.to(dev), eval_params=eval_params, select=select,
                              transform=transform_from_args(args), depth=depth_from_args(args),
-                             segment=segment_from_args(args))
+                             segment=segment_from_args(args), fuse=fuse_from_args(args))
     real_data = "real_data" in args.folder
     if args.file:
         paths = [os.path.join(args.folder, args.file)]

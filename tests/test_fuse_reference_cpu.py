@@ -1,0 +1,310 @@
+"""The multi-view fusion contract without a GPU: the numpy restatement (tests/fuse_reference.py) on hand-built cases with known
+answers and against a float64 ``np.unique`` + mean formulation; the library's host-side key, hash and size functions against the
+restatement; ``FuseParams``, the multi-view ``.npz`` format and the CLI flags."""
+import argparse
+import ctypes
+
+import numpy as np
+import pytest
+
+from . import fuse_reference as ref
+
+f32 = np.float32
+IDENTITY = ref.pose12(None)
+ZERO = np.zeros(3, dtype=np.float32)
+
+
+def _merge(points, colours=None, **params):
+    params.setdefault("max_voxels", 64)
+    return ref.merge([(np.asarray(points, dtype=np.float32), None if colours is None else np.asarray(colours, dtype=np.float32))],
+                     None, params)
+
+
+def test_two_points_in_one_voxel_give_the_midpoint():
+    # voxel 0.5: inv = 2 exactly; 0.25 and 0.375 lie in voxel 0 of x; fractions 0.5 and 0.75, all exact
+    out = _merge([[0.25, 0.0, 0.0], [0.375, 0.0, 0.0]], [[0.0, 1.0, 0.2], [1.0, 1.0, 0.4]], voxel=0.5)
+    assert out["num"].tolist() == [1, 2, 0, 0] and out["count"][0] == 2 and out["first"][0] == 0 and out["views"][0] == 1
+    assert out["xyz"][0].tolist() == [0.3125, 0.0, 0.0]
+    assert out["rgb"][0].tobytes() == np.array([0.5, 1.0, (51 + 102) / 510.0], dtype=np.float64).astype(np.float32).tobytes()
+    assert np.isnan(out["xyz"][1:]).all() and (out["rgb"][1:] == 0).all()
+    assert (out["count"][1:] == -1).all() and (out["views"][1:] == -1).all() and (out["first"][1:] == -1).all()
+    assert out["xyz"][1:].view(np.uint32).max() == out["xyz"][1:].view(np.uint32).min() == 0x7FC00000
+
+
+def test_negative_coordinates_floor_downwards_and_signed_zero():
+    inv = ref.inverse_voxel(0.5)
+    _, i, f, _, inside = ref.voxel_coords(np.array([[-0.25, -0.5, -0.0], [0.0, 0.5, -1e-30]], dtype=np.float32), IDENTITY, ZERO, inv)
+    assert inside.all() and i.tolist() == [[-1, -1, 0], [0, 1, -1]]
+    assert f[0].tolist() == [0.5, 0.0, 0.0] and f[1, 0] == 0.0 and f[1, 1] == 0.0
+    assert f[1, 2] == f32(1.0)                       # a tiny negative a: the fraction rounds up to 1, the mean lands at the face
+    out = _merge([[-0.25, 0.0, 0.0], [-0.125, 0.0, 0.0], [0.125, 0.0, 0.0]], voxel=0.5)
+    assert out["K"] == 2 and out["count"][:2].tolist() == [2, 1]                  # the negative voxel sorts first
+    assert out["xyz"][0].tolist() == [-0.1875, 0.0, 0.0] and out["xyz"][1].tolist() == [0.125, 0.0, 0.0]
+    out = _merge([[-0.0, 0.0, 0.0], [0.0, -0.0, 0.0]], voxel=0.5)                 # -0.0 is voxel 0, not voxel -1
+    assert out["K"] == 1 and out["count"][0] == 2 and out["xyz"][0].tolist() == [0.0, 0.0, 0.0]
+    tiny = _merge([[0.0, 0.0, -1e-30], [0.0, 0.0, -1e-30]], voxel=0.5)
+    assert tiny["K"] == 1 and tiny["xyz"][0, 2] == 0.0                            # i = -1, fraction 1: -1 + 1
+
+
+def test_a_voxel_of_one_point_is_that_point_bit_for_bit_and_poses_apply():
+    rng = np.random.RandomState(0)
+    pts = rng.uniform(-1, 1, (50, 3)).astype(np.float32)
+    col = rng.uniform(-0.2, 1.2, (50, 3)).astype(np.float32)                      # colours outside [0, 1] pass unchanged
+    pose = np.eye(4)
+    pose[:3, :3] = [[0, -1, 0], [1, 0, 0], [0, 0, 1]]
+    pose[:3, 3] = [0.5, -0.25, 2.0]
+    out = ref.merge([(pts, col)], [pose], {"voxel": 1e-5, "max_voxels": 64})
+    assert out["K"] == 50 and (out["count"][:50] == 1).all()
+    moved = np.stack([-pts[:, 1] + f32(0.5), pts[:, 0] - f32(0.25), pts[:, 2] + f32(2.0)], axis=1)
+    rows = out["first"][:50]
+    assert sorted(rows.tolist()) == list(range(50))
+    assert out["xyz"][:50].tobytes() == moved[rows].tobytes() and out["rgb"][:50].tobytes() == col[rows].tobytes()
+    keys = [ref.key(*pts[r], ref.pose12(pose), ZERO, ref.inverse_voxel(1e-5)) for r in rows]
+    assert keys == sorted(keys) and len(set(keys)) == 50
+
+
+def test_dropped_rows_min_count_views_and_overflow():
+    pts = np.array([[0.1, 0.1, 0.1], [np.nan, 0, 0], [0, np.inf, 0], [0.1, 0.1, 0.15], [3e5, 0, 0], [0.7, 0.1, 0.1]], dtype=np.float32)
+    out = ref.merge([(pts, None), (pts[:1], None)], None, {"voxel": 0.25, "max_voxels": 8})
+    assert out["num"].tolist() == [2, 4, 3, 0]       # 3e5 / 0.25 = 1.2e6 >= 2^20: out of range
+    assert out["count"][:2].tolist() == [3, 1] and out["views"][:2].tolist() == [3, 1] and out["first"][:2].tolist() == [0, 5]
+    out = ref.merge([(pts, None), (pts[:1], None)], None, {"voxel": 0.25, "max_voxels": 8, "min_count": 2})
+    assert out["num"].tolist() == [1, 4, 3, 0] and out["count"][0] == 3
+    line = np.arange(9, dtype=np.float32)[:, None] * np.array([[1.0, 0, 0]], dtype=np.float32)
+    assert ref.merge([(line[:8], None)], None, {"voxel": 1.0, "max_voxels": 8})["num"].tolist() == [8, 8, 0, 0]
+    assert ref.merge([(line, None)], None, {"voxel": 1.0, "max_voxels": 8})["num"][3] == 1
+
+
+def test_agreement_with_a_float64_unique_and_mean_formulation():
+    """Against the centroid, in float64, of the float32 transformed points of every voxel.  The bound, per axis, in metres with
+    h = 1 / inv: a = (x' - o) * inv carries two float32 roundings, |a - a_exact| <= |a| 2^-23 (1 + 2^-24) with |a| <= |i| + 1; the
+    24-bit fraction truncates by less than 2^-24 of a voxel and the fraction itself is off by at most 2^-24 where a tiny negative
+    a rounds it up to 1; the float64 operations add rounding errors of 2^-52 relative (covered by 1e-12); the result is rounded to
+    float32 once, half an ulp = 2^-24 |x|.  Colours: the 8-bit level is off by at most 0.5 / 255 plus the float32 rounding of
+    c * 255 (2^-24 after the division), the result by another 2^-24."""
+    rng = np.random.RandomState(3)
+    voxel = 0.05
+    clouds, poses = [], []
+    for v in range(3):
+        clouds.append((rng.uniform(-0.3, 0.3, (1500, 3)).astype(np.float32), rng.uniform(0, 1, (1500, 3)).astype(np.float32)))
+        pose = np.eye(4)
+        a = 0.4 * v
+        pose[:3, :3] = [[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]]
+        pose[:3, 3] = [0.05 * v, -0.02 * v, 0.5]
+        poses.append(pose)
+    origin = (0.013, -0.4, 0.0)
+    out = ref.merge(clouds, poses, {"voxel": voxel, "origin": origin, "max_voxels": 8192})
+    inv = ref.inverse_voxel(voxel)
+    o32 = np.asarray(origin, dtype=np.float64).astype(np.float32)
+    moved, index, colour = [], [], []
+    for (xyz, rgb), pose in zip(clouds, poses):
+        p, i, _, _, inside = ref.voxel_coords(xyz, ref.pose12(pose), o32, inv)
+        assert inside.all()
+        moved.append(p.astype(np.float64)); index.append(i); colour.append(rgb.astype(np.float64))
+    moved, index, colour = np.concatenate(moved), np.concatenate(index), np.concatenate(colour)
+    keys = np.array([ref.key_of(i) for i in index], dtype=np.int64)
+    uniq, inverse, counts = np.unique(keys, return_inverse=True, return_counts=True)
+    K = len(uniq)
+    assert out["K"] == K and (counts > 1).sum() > 200 and np.array_equal(out["count"][:K], counts)
+    mean, mean_colour, cell = np.zeros((K, 3)), np.zeros((K, 3)), np.zeros((K, 3))
+    np.add.at(mean, inverse, moved)
+    np.add.at(mean_colour, inverse, colour)
+    cell[inverse] = index
+    mean, mean_colour = mean / counts[:, None], mean_colour / counts[:, None]
+    h = 1.0 / float(inv)
+    bound = h * ((np.abs(cell) + 1) * 2.0 ** -23 * (1 + 2.0 ** -24) + 2.0 ** -23) + 2.0 ** -24 * np.abs(mean) + 1e-12
+    err = np.abs(out["xyz"][:K].astype(np.float64) - mean)
+    print("max err %.3e m, max err / bound %.3f" % (err.max(), (err / bound).max()))
+    assert (err <= bound).all() and bound.max() < 5e-7
+    assert (np.abs(out["rgb"][:K].astype(np.float64) - mean_colour) <= 0.5 / 255 + 2.0 ** -23).all()
+
+
+def _host_key(lib, point, pose, origin, inv):
+    key = ctypes.c_uint64(0)
+    status = lib.regnet_fuse_key_host(float(point[0]), float(point[1]), float(point[2]), pose.ctypes.data, origin.ctypes.data,
+                                      float(inv), ctypes.byref(key))
+    return status, key.value
+
+
+def test_host_key_and_home_slot_equal_the_restatement():
+    from regnet_for_3d_grasping_amd import _lib
+    lib = _lib.lib
+    rng = np.random.RandomState(7)
+    cases = 0
+    for voxel, origin, angle in ((0.002, (0, 0, 0), 0.0), (0.005, (0.1, -0.2, 0.3), 0.7), (1.0, (-3, 2, 0.5), -1.3), (1e-3, (0, 0, 0), 2.0)):
+        inv = ref.inverse_voxel(voxel)
+        o = np.asarray(origin, dtype=np.float64).astype(np.float32)
+        T = np.eye(4)
+        T[:3, :3] = [[np.cos(angle), 0, np.sin(angle)], [0, 1, 0], [-np.sin(angle), 0, np.cos(angle)]]
+        T[:3, 3] = rng.uniform(-1, 1, 3)
+        pose = ref.pose12(T)
+        pts = rng.uniform(-2, 2, (1000, 3)).astype(np.float32)
+        # boundaries: voxel faces and one ulp either side, zeros of both signs, the range limits, non-finite values
+        faces = (np.arange(-8, 9, dtype=np.float64) * voxel).astype(np.float32)
+        edge = np.concatenate([faces, np.nextafter(faces, f32(np.inf)), np.nextafter(faces, f32(-np.inf)),
+                               np.array([0.0, -0.0, 1e-30, -1e-30, np.nan, np.inf, -np.inf, 3e38, -3e38], dtype=np.float32),
+                               (np.array([-2.0 ** 20, 2.0 ** 20, 2.0 ** 20 - 1, -2.0 ** 20 - 1]) * voxel).astype(np.float32)])
+        special = np.zeros((len(edge) * 3, 3), dtype=np.float32)
+        for axis in range(3):
+            special[axis * len(edge):(axis + 1) * len(edge), axis] = edge
+        for use_pose, batch in ((pose, pts), (ref.pose12(None), special), (pose, special)):
+            _, i, _, finite, inside = ref.voxel_coords(batch, use_pose, o, inv)
+            for r, point in enumerate(batch):
+                status, got = _host_key(lib, point, use_pose, o, inv)
+                if inside[r]:
+                    assert status == 0 and got == ref.key_of(i[r]) == ref.key(*point, use_pose, o, inv), (voxel, point)
+                else:
+                    assert status == (2 if finite[r] else 1) and got == ref.EMPTY, (voxel, point, status)
+                cases += 1
+    assert cases > 4000
+    keys = [int(k) for k in rng.randint(0, 2 ** 62, 3000, dtype=np.int64)] + [0, 1, 2 ** 63 - 1, ref.key_of((-BIAS_, -BIAS_, -BIAS_)),
+                                                                             ref.key_of((BIAS_ - 1, BIAS_ - 1, BIAS_ - 1))]
+    for slots in (2, 4, 128, 1 << 11, 1 << 22):
+        homes = [lib.regnet_fuse_home_slot_host(k, slots) for k in keys]
+        assert homes == [ref.home_slot(k, slots) for k in keys] and 0 <= min(homes) and max(homes) < slots
+    assert len(set(lib.regnet_fuse_home_slot_host(ref.key_of((0, 0, z)), 128) for z in range(64))) > 32   # neighbours spread out
+    for bad in (0, 1, 3, 100, 1 << 23, -4):
+        assert lib.regnet_fuse_home_slot_host(5, bad) == -1
+    assert lib.regnet_fuse_key_host(0.0, 0.0, 0.0, None, o.ctypes.data, 1.0, None) == -2
+
+
+BIAS_ = ref.BIAS
+
+
+def test_table_slots_and_workspace_bytes_around_every_limit():
+    from regnet_for_3d_grasping_amd import _lib, fusion
+    lib = _lib.lib
+    for mv, slots in ((1, 2), (2, 4), (3, 8), (4, 8), (5, 16), (63, 128), (64, 128), (65, 256), (1 << 20, 1 << 21),
+                      ((1 << 20) + 1, 1 << 22), (1 << 21, 1 << 22)):
+        assert lib.regnet_fuse_table_slots(mv) == slots == ref.table_slots(mv) == fusion.table_slots(mv)
+        assert lib.regnet_fuse_workspace_bytes(mv) == ref.workspace_bytes(mv) == fusion.workspace_bytes(mv)
+        assert lib.regnet_fuse_workspace_bytes(mv) % 16 == 0
+    for bad in (0, -1, (1 << 21) + 1, 1 << 40):
+        assert lib.regnet_fuse_table_slots(bad) == -1 and lib.regnet_fuse_workspace_bytes(bad) == -1
+    from regnet_for_3d_grasping_amd import ingest
+    assert fusion.MAX_VOXELS == ingest.MAX_FRAME_POINTS == 1 << 21
+    # the launching entry points refuse what the header says they refuse, before they touch a device
+    pose, origin, ws = ref.pose12(None), np.zeros(3, dtype=np.float32), ctypes.create_string_buffer(64)
+    acc = lambda **kw: lib.regnet_fuse_accumulate_f32(None, None, kw.get("n", 0), kw.get("view", 0), kw.get("offset", 0),   # noqa: E731
+                                                      pose.ctypes.data, origin.ctypes.data, kw.get("voxel", 0.01),
+                                                      kw.get("mv", 16), 0, kw.get("ws", ctypes.addressof(ws)), None)
+    assert acc(view=8) == -3 and acc(voxel=0.0) == -3 and acc(voxel=-1.0) == -3 and acc(voxel=float("nan")) == -3
+    assert acc(voxel=float("inf")) == -3 and acc(mv=0) == -3 and acc(mv=(1 << 21) + 1) == -3 and acc(offset=1 << 31) == -3
+    assert acc(n=-1) == -1 and acc(view=-1) == -1 and acc(offset=-1) == -1
+    assert acc(ws=None) == -2 and acc(n=5) == -2
+    assert acc() == 0                                 # n = 0 without a reset: nothing to do
+    assert lib.regnet_fuse_finalise_f32(16, 0, ctypes.addressof(ws), ctypes.addressof(ws), None) == -1
+    assert lib.regnet_fuse_finalise_f32(0, 1, ctypes.addressof(ws), ctypes.addressof(ws), None) == -3
+    assert lib.regnet_fuse_finalise_f32(16, 1, None, ctypes.addressof(ws), None) == -2
+    assert lib.regnet_fuse_emit_f32(None, origin.ctypes.data, 0.01, 16, None, None, None, None, None, None, None, None) == -2
+    assert lib.regnet_fuse_emit_f32(None, origin.ctypes.data, 0.0, 16, None, None, None, None, None, None, None, None) == -3
+
+
+def test_fuse_params_validation():
+    from regnet_for_3d_grasping_amd import fusion
+    p = fusion.FuseParams()
+    assert (p.voxel, p.origin, p.max_voxels, p.min_count) == (0.002, (0.0, 0.0, 0.0), 1 << 20, 1)
+    assert fusion.FuseParams.coerce(None) == p and fusion.FuseParams.coerce(p) is p
+    q = fusion.FuseParams.coerce({"voxel": 0.005, "origin": [1, 2, 3], "max_voxels": 1 << 21, "min_count": 3})
+    assert q.origin == (1.0, 2.0, 3.0) and q.max_voxels == 1 << 21
+    with pytest.raises(TypeError):
+        fusion.FuseParams.coerce("yes")
+    for bad in ({"voxel": 0.0}, {"voxel": -1.0}, {"voxel": float("nan")}, {"voxel": float("inf")}, {"origin": (0, 0)},
+                {"origin": (0, 0, float("nan"))}, {"max_voxels": 0}, {"max_voxels": (1 << 21) + 1}, {"max_voxels": 2.5},
+                {"min_count": 0}, {"min_count": 1.5}):
+        with pytest.raises(ValueError):
+            fusion.FuseParams(**bad)
+    with pytest.raises(TypeError):
+        fusion.FuseParams(spacing=1)
+    assert fusion.pose12(None).tolist() == ref.pose12(None).tolist()
+    T = np.arange(16, dtype=np.float64).reshape(4, 4) / 7.0
+    assert fusion.pose12(T).tobytes() == ref.pose12(T).tobytes()
+    with pytest.raises(ValueError):
+        fusion.pose12(np.eye(3))
+
+
+def test_voxel_merge_refuses_cpu_tensors_and_bad_lists():
+    import torch
+    from regnet_for_3d_grasping_amd import fusion
+    cloud = (torch.zeros((4, 3)), torch.zeros((4, 3)))
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        fusion.voxel_merge([cloud])
+    with pytest.raises(ValueError):
+        fusion.voxel_merge([])
+    with pytest.raises(ValueError):
+        fusion.voxel_merge([cloud] * 9)
+    with pytest.raises(ValueError):
+        fusion.voxel_merge([cloud], poses=[None, None])
+    with pytest.raises(ValueError):
+        fusion.voxel_merge([cloud], poses=[np.eye(3)])
+
+
+def test_multiview_npz_round_trip(tmp_path):
+    from regnet_for_3d_grasping_amd import depth_frame, fusion
+    frames, poses = ref.two_view_scene(16, 12)
+    second = dict(frames[1], color_intrinsics=(20.0, 21.0, 8.0, 6.0), depth_to_color=np.eye(4), depth_scale=0.002)
+    first = {key: value for key, value in frames[0].items() if key != "color"}
+    mv = fusion.MultiView([depth_frame.DepthFrame(**first), depth_frame.DepthFrame(**second)], [None, poses[1]])
+    path = str(tmp_path / "two.npz")
+    fusion.save_npz(path, mv)
+    assert fusion.is_multiview_npz(path)
+    with np.load(path) as data:
+        assert int(data["views"]) == 2 and "view0_color" not in data.files and "view1_depth_to_color" in data.files
+        assert np.array_equal(data["view0_pose"], np.eye(4))
+        items = {key: data[key] for key in data.files}
+    back = fusion.load_npz(path)
+    assert len(back.frames) == 2 and np.array_equal(back.poses[0], np.eye(4)) and np.array_equal(back.poses[1], poses[1])
+    for got, want in zip(back.frames, mv.frames):
+        assert np.array_equal(got.depth, want.depth) and got.depth.dtype == np.uint16
+        assert got.intrinsics == want.intrinsics and got.depth_scale == want.depth_scale and got.mode() == want.mode()
+    assert np.array_equal(back.frames[1].color, second["color"]) and back.frames[1].color_intrinsics.astuple() == (20.0, 21.0, 8.0, 6.0)
+    for change in ({"extra": np.zeros(1)}, {"view2_depth": np.zeros((2, 2))}, {"views": np.int64(9)}, {"views": np.int64(0)}):
+        with open(path, "wb") as f:
+            np.savez(f, **dict(items, **change))
+        with pytest.raises(ValueError):
+            fusion.load_npz(path)
+    for missing in ("view1_pose", "view0_depth", "view0_intrinsics", "views"):
+        with open(path, "wb") as f:
+            np.savez(f, **{key: value for key, value in items.items() if key != missing})
+        with pytest.raises(ValueError):
+            fusion.load_npz(path)
+    single = str(tmp_path / "one.npz")
+    depth_frame.save_npz(single, mv.frames[0])
+    assert not fusion.is_multiview_npz(single)
+    assert isinstance(depth_frame.load_npz(single), depth_frame.DepthFrame)       # depth_frame's format is untouched
+    with pytest.raises(ValueError):
+        fusion.MultiView([], [])
+    with pytest.raises(ValueError):
+        fusion.MultiView(mv.frames, [None])
+    with pytest.raises(TypeError):
+        fusion.MultiView([(1, 2)], [None])
+    with pytest.raises(ValueError):
+        fusion.MultiView(mv.frames, [None, np.eye(3)])
+
+
+def test_cli_flags():
+    from regnet_for_3d_grasping_amd import detect
+    none = argparse.Namespace(voxel=None, max_voxels=None, min_voxel_points=None)
+    assert detect.fuse_from_args(none) is None
+    flags = argparse.Namespace(voxel=0.005, max_voxels=4096, min_voxel_points=2)
+    assert detect.fuse_from_args(flags) == {"voxel": 0.005, "max_voxels": 4096, "min_count": 2}
+    assert detect.fuse_from_args(argparse.Namespace(**dict(vars(none), voxel=0.003))) == {"voxel": 0.003}
+    assert detect.FUSE_KEYS == ("fuse_num", "fuse_views")
+    with pytest.raises(SystemExit):                   # the flags parse (the run then stops at the required paths)
+        detect.main(["--voxel", "0.004", "--max-voxels", "100", "--min-voxel-points", "2"])
+
+
+def test_two_view_scene_overlaps():
+    """The poses ``tests/test_gpu_fuse.py`` uses give an overlap: voxels both cameras contribute to."""
+    from . import depth_reference
+    frames, poses = ref.two_view_scene()
+    clouds = []
+    for kw in frames:
+        xyz, rgb, _, _ = depth_reference.to_cloud(**kw)
+        clouds.append((xyz, rgb))
+    out = ref.merge(clouds, poses, {"voxel": ref.TWO_VIEW_VOXEL, "max_voxels": 4096})
+    K = out["K"]
+    both = int((out["views"][:K] == 3).sum())
+    print("K = %d, seen by both = %d, rows merged %d, dropped %d" % (K, both, out["num"][1], out["num"][2]))
+    assert K == ref.TWO_VIEW_K and both > 50 and out["num"][3] == 0
+
