@@ -59,14 +59,8 @@ __global__ __launch_bounds__(256) void cl_init_kernel(const float* __restrict__ 
     objid[i] = -1;
     key[i] = 0;
   }
-  const uint64_t votes = __ballot(valid);
-  if (votes == 0ull) return;
-  const int leader = __builtin_ctzll(votes);
-  int base = 0;
-  if (lane_id() == leader) base = atomicAdd(&cnt[0], (int)__popcll(votes));
-  base = __shfl(base, leader, 64);
+  const int c = wave_append(valid, &cnt[0]);
   if (valid) {
-    const int c = base + mbcnt64(votes);
     src[c] = i;
     cxyz[(int64_t)c * 3] = x; cxyz[(int64_t)c * 3 + 1] = y; cxyz[(int64_t)c * 3 + 2] = z;
   }
@@ -157,8 +151,7 @@ __global__ __launch_bounds__(256) void cl_key_kernel(const int* __restrict__ roo
     kept = key[i] >= min_points;
     if (!kept) key[i] = 0;
   }
-  const uint64_t votes = __ballot(kept);
-  if (votes != 0ull && lane_id() == __builtin_ctzll(votes)) atomicAdd(&cnt[1], (int)__popcll(votes));
+  wave_append(kept, &cnt[1]);   // (only the count is wanted)
 }
 
 // order-preserving integer key of a float (-0.0 below +0.0) and back

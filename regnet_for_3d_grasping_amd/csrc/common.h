@@ -23,9 +23,28 @@ __device__ __forceinline__ float sqdist3(float ax, float ay, float az, float bx,
   return s + zz;
 }
 
+// Canonical dot product, under the same rule: ((ax*bx)+(ay*by))+(az*bz).
+__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
+  float xx = ax * bx, yy = ay * by, zz = az * bz;
+  float s = xx + yy;
+  return s + zz;
+}
+
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 
 // number of set bits of `mask` below this lane
 __device__ __forceinline__ int mbcnt64(uint64_t mask) {
   return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+// Wave-aggregated append: the lanes whose `flag` is set take consecutive slots behind `*counter`, in lane order, with one
+// atomicAdd per wave -> this lane's slot, -1 without the flag.  Every lane of the wave must make the call.
+__device__ __forceinline__ int wave_append(bool flag, int* counter) {
+  const uint64_t votes = __ballot(flag);
+  if (votes == 0ull) return -1;
+  const int leader = __builtin_ctzll(votes);
+  int base = 0;
+  if (lane_id() == leader) base = atomicAdd(counter, (int)__popcll(votes));
+  base = __shfl(base, leader, 64);
+  return flag ? base + mbcnt64(votes) : -1;
 }

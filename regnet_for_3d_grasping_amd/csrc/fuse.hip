@@ -168,14 +168,8 @@ __global__ __launch_bounds__(256) void fuse_compact_kernel(const unsigned long l
                                                            long long* __restrict__ kept_keys, int* __restrict__ slot_of) {
   const unsigned s = blockIdx.x * 256u + threadIdx.x;
   const bool kept = s < slots && keys[s] != FUSE_EMPTY && count[s] >= min_count;
-  const uint64_t votes = __ballot(kept);
-  if (votes == 0ull) return;
-  const int leader = __builtin_ctzll(votes);
-  int base = 0;
-  if (lane_id() == leader) base = atomicAdd(&hdr[4], (int)__popcll(votes));
-  base = __shfl(base, leader, 64);
+  const int pos = wave_append(kept, &hdr[4]);
   if (kept) {
-    const int pos = base + mbcnt64(votes);
     if (pos < max_voxels) {
       kept_keys[pos] = (long long)keys[s];
       slot_of[pos] = (int)s;

@@ -32,12 +32,6 @@ __host__ __device__ __forceinline__ long long nms_block_base(long long rb, long 
   return 64 * (rb * nb - rb * (rb - 1) / 2);
 }
 
-__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
-  float xx = ax * bx, yy = ay * by, zz = az * bz;
-  float s = xx + yy;
-  return s + zz;
-}
-
 // centre (3), approach (3), axis_y (3), minor normal (3) of input row `src`: frame is (n,3,3) with those vectors as COLUMNS
 __device__ __forceinline__ void load_pose(const float* __restrict__ center, const float* __restrict__ frame, long long src,
                                           float (&p)[12]) {

@@ -50,12 +50,6 @@ __device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
   return z ^ (z >> 31);
 }
 
-__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
-  float xx = ax * bx, yy = ay * by, zz = az * bz;
-  float s = xx + yy;
-  return s + zz;
-}
-
 // row i as float32; false (and NaN coordinates, which fail every inlier test) when one of them is not finite
 template <typename T>
 __device__ __forceinline__ bool load_row(const T* __restrict__ xyz, long long i, float& x, float& y, float& z) {

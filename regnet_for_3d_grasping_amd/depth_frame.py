@@ -16,10 +16,11 @@ from typing import Any, Optional, Tuple
 import numpy as np
 
 from . import _lib
+from ._frame_util import MAX_FRAME_POINTS, ParamsBase, matrix4, record_streams, stream_scope, to_device, to_host
 
 _L = _lib.lib
 
-MAX_DEPTH_PIXELS = 1 << 21          # regnet_depth_to_cloud_*'s documented limits; = ingest.MAX_FRAME_POINTS
+MAX_DEPTH_PIXELS = MAX_FRAME_POINTS         # regnet_depth_to_cloud_*'s documented limits
 MAX_COLOR_PIXELS = 1 << 23
 MODE_NONE, MODE_ALIGNED, MODE_REGISTERED = 0, 1, 2
 STATUS = ("no depth", "out of range", "edge jump", "too few neighbours", "outside the colour image", "occluded", "kept")
@@ -81,12 +82,13 @@ class DepthFrame:
 
 
 @dataclass(frozen=True)
-class DepthParams:
+class DepthParams(ParamsBase):
     """``depth_range = (lo, hi)`` [m], inclusive; ``edge_threshold`` t (None: off): a pixel is removed when an 8-neighbour's
     depth differs by more than t times the smaller of the two; ``min_neighbours`` k (0..8): a pixel with fewer valid 8-neighbours
     is removed; ``occlusion_margin`` [m] and ``splat`` (0..2, the z-buffer footprint's radius in colour pixels) govern the
     visibility test of a colour sensor with its own pose; ``keep_uncoloured``: points that sensor does not see keep their
     coordinates with rgb = 0 instead of being dropped."""
+    WORD, NONE_IS_DEFAULT = "depth", True
     depth_range: Tuple[float, float] = (0.0, math.inf)
     edge_threshold: Optional[float] = None
     min_neighbours: int = 0
@@ -98,6 +100,7 @@ class DepthParams:
         lo, hi = (float(v) for v in self.depth_range)
         if not (0.0 <= lo <= hi):
             raise ValueError("depth: depth_range must be 0 <= lo <= hi")
+        object.__setattr__(self, "depth_range", (lo, hi))
         if self.edge_threshold is not None and not (float(self.edge_threshold) >= 0.0):
             raise ValueError("depth: edge_threshold must be None or >= 0")
         if int(self.min_neighbours) != self.min_neighbours or not 0 <= self.min_neighbours <= 8:
@@ -106,20 +109,6 @@ class DepthParams:
             raise ValueError("depth: splat must be 0, 1 or 2")
         if not (float(self.occlusion_margin) >= 0.0):
             raise ValueError("depth: occlusion_margin must be >= 0")
-
-    @classmethod
-    def coerce(cls, value):
-        """None -> the defaults, a DepthParams -> itself, a dict -> DepthParams(**dict)."""
-        if value is None:
-            return cls()
-        if isinstance(value, cls):
-            return value
-        if isinstance(value, dict):
-            value = dict(value)
-            if "depth_range" in value:
-                value["depth_range"] = tuple(float(v) for v in value["depth_range"])
-            return cls(**value)
-        raise TypeError("depth must be None, a dict or a DepthParams")
 
 
 def colour_lut():
@@ -146,10 +135,7 @@ def pack_params(frame, params, mode):
     p[7] = 0.0 if params.edge_threshold is None else float(params.edge_threshold)
     p[8] = params.occlusion_margin
     if mode == MODE_REGISTERED:
-        T = np.asarray(frame.depth_to_color.detach().cpu().numpy() if hasattr(frame.depth_to_color, "detach")
-                       else frame.depth_to_color, dtype=np.float64)
-        if T.shape != (4, 4):
-            raise ValueError("depth_to_color must be 4x4")
+        T = matrix4(frame.depth_to_color, "depth_to_color must be 4x4")
         p[9:13] = frame.color_intrinsics.astuple()
         p[13:22] = T[:3, :3].reshape(9)
         p[22:25] = T[:3, 3]
@@ -160,19 +146,14 @@ def pack_params(frame, params, mode):
 def _image(a, device, what, dtypes):
     """A host array or tensor -> a contiguous device tensor of one of ``dtypes`` (host arrays go up once, as they are)."""
     import torch
-    from . import host_io
-    if isinstance(a, torch.Tensor):
-        t = a if a.is_cuda else host_io.upload(a.contiguous(), device)
-    else:
-        a = np.ascontiguousarray(a)
-        if a.dtype == np.float64 and torch.float32 in dtypes:
-            a = a.astype(np.float32)
-        t = host_io.upload(a, device)
+    if not isinstance(a, torch.Tensor) and np.asarray(a).dtype == np.float64 and torch.float32 in dtypes:
+        a = np.asarray(a, dtype=np.float32)
+    t = to_device(a, device)
     if t.dtype == torch.int16 and torch.uint16 in dtypes:
         t = t.view(torch.uint16)
     if t.dtype not in dtypes:
         raise TypeError("%s must be %s" % (what, " or ".join(str(d).replace("torch.", "") for d in dtypes)))
-    return t.contiguous()
+    return t
 
 
 def to_cloud(frame, params=None, device="cuda:0", stream=None, return_status=False, out=None):
@@ -194,7 +175,7 @@ def to_cloud(frame, params=None, device="cuda:0", stream=None, return_status=Fal
     if not (scale > 0.0 and math.isfinite(scale)):
         raise ValueError("depth_scale must be positive and finite")
     consts = pack_params(frame, params, mode)
-    with torch.cuda.stream(stream) if stream is not None else _null():
+    with stream_scope(stream):
         depth = _image(frame.depth, dev, "depth", (torch.uint16, torch.float32))
         if depth.dim() != 2 or depth.shape[0] < 1 or depth.shape[1] < 1:
             raise ValueError("depth must be (H, W) with at least one pixel")
@@ -224,52 +205,55 @@ def to_cloud(frame, params=None, device="cuda:0", stream=None, return_status=Fal
                   0 if params.edge_threshold is None else 1, int(params.min_neighbours), int(params.splat),
                   1 if params.keep_uncoloured else 0, xyz.data_ptr(), rgb.data_ptr(), status.data_ptr(), counts.data_ptr(),
                   ws.data_ptr())
-        if stream is not None:              # the inputs are read on `stream`: keep them alive for it
-            for t in (depth, color):
-                if t is not None:
-                    t.record_stream(stream)
+        record_streams(stream, depth, color)       # the inputs are read on `stream`: keep them alive for it
     return (xyz, rgb, status, counts) if return_status else (xyz, rgb)
-
-
-class _null:
-    def __enter__(self):
-        return None
-
-    def __exit__(self, *exc):
-        return False
 
 
 _NPZ_KEYS = ("depth", "intrinsics", "color", "color_intrinsics", "depth_to_color", "depth_scale")
 
 
-def save_npz(path, frame):
-    """Write ``frame`` as a ``.npz``: ``depth``, ``intrinsics`` (4) and, where given, ``color``, ``color_intrinsics`` (4),
-    ``depth_to_color`` (4,4), ``depth_scale``."""
-    def host(a):
-        return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
-    items = {"depth": host(frame.depth), "intrinsics": np.array(frame.intrinsics.astuple(), dtype=np.float64),
+def frame_items(frame, prefix=""):
+    """The ``.npz`` entries of one ``DepthFrame``, their names behind ``prefix``: ``depth``, ``intrinsics`` (4), ``depth_scale``
+    and, where given, ``color``, ``color_intrinsics`` (4), ``depth_to_color`` (4,4)."""
+    items = {"depth": to_host(frame.depth), "intrinsics": np.array(frame.intrinsics.astuple(), dtype=np.float64),
              "depth_scale": np.float64(frame.depth_scale)}
     if frame.color is not None:
-        items["color"] = host(frame.color)
+        items["color"] = to_host(frame.color)
     if frame.color_intrinsics is not None:
         items["color_intrinsics"] = np.array(frame.color_intrinsics.astuple(), dtype=np.float64)
     if frame.depth_to_color is not None:
-        items["depth_to_color"] = host(frame.depth_to_color).astype(np.float64)
+        items["depth_to_color"] = to_host(frame.depth_to_color).astype(np.float64)
+    return {prefix + key: value for key, value in items.items()}
+
+
+def frame_from_items(data, prefix, path, required=("depth", "intrinsics")):
+    """The ``DepthFrame`` of ``data``'s entries behind ``prefix`` (``path`` names the file in the error); a ``required`` entry
+    that is missing is a ValueError."""
+    for key in required:
+        if prefix + key not in data.files:
+            raise ValueError("%s: no %r entry" % (path, prefix + key))
+    get = lambda key: data[prefix + key] if prefix + key in data.files else None      # noqa: E731
+    scale = get("depth_scale")
+    return DepthFrame(depth=get("depth"), intrinsics=get("intrinsics"), color=get("color"),
+                      color_intrinsics=get("color_intrinsics"), depth_to_color=get("depth_to_color"),
+                      depth_scale=0.001 if scale is None else float(scale))
+
+
+def check_npz_entries(data, known, path):
+    """Entries of ``data`` outside ``known`` are a ValueError (``path`` names the file)."""
+    unknown = sorted(set(data.files) - set(known))
+    if unknown:
+        raise ValueError("%s: unknown entries %s" % (path, ", ".join(unknown)))
+
+
+def save_npz(path, frame):
+    """Write ``frame`` as a ``.npz``: ``frame_items``' entries."""
     with open(path, "wb") as f:
-        np.savez(f, **items)
+        np.savez(f, **frame_items(frame))
 
 
 def load_npz(path):
     """Read a ``.npz`` written by ``save_npz`` (or by anything that uses its keys) -> ``DepthFrame``."""
     with np.load(path, allow_pickle=False) as data:
-        unknown = sorted(set(data.files) - set(_NPZ_KEYS))
-        if unknown:
-            raise ValueError("depth frame %s: unknown entries %s" % (path, ", ".join(unknown)))
-        for key in ("depth", "intrinsics"):
-            if key not in data.files:
-                raise ValueError("depth frame %s: no %r entry" % (path, key))
-        get = lambda key: data[key] if key in data.files else None      # noqa: E731
-        scale = get("depth_scale")
-        return DepthFrame(depth=data["depth"], intrinsics=data["intrinsics"], color=get("color"),
-                          color_intrinsics=get("color_intrinsics"), depth_to_color=get("depth_to_color"),
-                          depth_scale=0.001 if scale is None else float(scale))
+        check_npz_entries(data, _NPZ_KEYS, "depth frame %s" % path)
+        return frame_from_items(data, "", "depth frame %s" % path)

@@ -119,25 +119,30 @@ class GraspDetector:
 
     def ingest(self, frame):
         """``frame``: an ``ingest.Frame``, an ``(xyz, rgb)`` pair of a camera frame, a ``depth_frame.DepthFrame``, a
-        ``fusion.MultiView`` or a record dict -> ``ingest.Frame``."""
+        ``fusion.MultiView`` or a record dict -> ``ingest.Frame``; what was found on the way rides on it: ``fused`` (the
+        ``fusion.Fused`` of a ``MultiView``) and ``table`` (the (transform, plane) estimated in the frame), else None."""
         from . import depth_frame, fusion, ingest
+        from ._frame_util import to_device
         if isinstance(frame, ingest.Frame):
             return frame
         if isinstance(frame, dict):
             return ingest.ingest_record(frame, self.num_points, self.device)
+        fused = table = None
         if isinstance(frame, fusion.MultiView):            # merged on the device, no host read; the rows beyond the merged
-            self.fused = fusion.fuse_frames(frame, self.depth, self.fuse, device=self.device)    # points are NaN rows
-            frame = self.fused.cloud()
+            fused = fusion.fuse_frames(frame, self.depth, self.fuse, device=self.device)         # points are NaN rows
+            frame = fused.cloud()
         elif isinstance(frame, depth_frame.DepthFrame):    # on the device, no host read; draws nothing from numpy's stream
             frame = depth_frame.to_cloud(frame, self.depth, device=self.device)
         xyz, rgb = frame
         transform = self.transform
         if self.auto_table is not None:           # draws nothing from numpy's stream; one 96-byte read
             from . import table_plane
-            xyz, rgb = ingest._to_device(xyz, self.device), ingest._to_device(rgb, self.device)
-            transform, plane = table_plane.calibrate(xyz, self.eval_params[2], **self.auto_table)
-            self.table = (transform, plane)
-        return ingest.ingest_frame(xyz, rgb, transform, self.bounds, self.num_points, self.device)
+            xyz, rgb = to_device(xyz, self.device), to_device(rgb, self.device)
+            table = table_plane.calibrate(xyz, self.eval_params[2], **self.auto_table)
+            transform = table[0]
+        fr = ingest.ingest_frame(xyz, rgb, transform, self.bounds, self.num_points, self.device)
+        fr.fused, fr.table = fused, table
+        return fr
 
     def calibrate(self, frame, **estimate_kwargs):
         """Estimate the table plane of ``frame`` (an ``(xyz, rgb)`` pair or just ``xyz``) once and keep the transform for every
@@ -152,16 +157,84 @@ class GraspDetector:
         self.auto_table = None
         return self.transform, plane
 
+    def _networks(self, fr):
+        """ScoreNet -> the grouping -> the region network -> (scores, the four grasp sets as the networks leave them)."""
+        from .get_regiondataset import get_grasp_allobj
+        pc = fr.pc
+        all_feature, output_score, _ = self.score_net(pc)
+        g = get_grasp_allobj(pc, output_score, self.params, [], self.use_theta)
+        res = self.region_net(g[3], g[5], g[2], g[4], g[0], g[1], pc, all_feature, self.gripper_params, None, [])
+        # eval_notruth(pc_back, color_back, grasp_stage2, select_grasp_class, select_grasp_score,
+        #              select_grasp_class_stage2, output_score, ...): test.py:147 -> utils.py:391
+        return output_score, {"grasp_stage2": res[0], "grasp_stage3_stage2": res[8], "grasp_stage3": res[6],
+                              "grasp_stage3_score": res[7]}
+
+    def _collision_filter(self, sets, points32):
+        """``eval_collision.eval_test`` on each set, in place; ``raw_counts``: their sizes before it."""
+        import torch
+        from . import eval_collision
+        depth, width, table_height, _, _ = self.eval_params
+        gpu = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self.raw_counts = {}
+        for key, grasp in sets.items():
+            if grasp is None:      # (the refine head saw no valid crop: an empty set)
+                grasp = torch.zeros((0, 8), dtype=torch.float32, device=self.device)
+            self.raw_counts[key] = int(grasp.shape[0])
+            if grasp.shape[0] >= 1:
+                grasp = eval_collision.eval_test(points32, grasp[:, :8], None, table_height, depth, width, gpu)
+            sets[key] = grasp
+
+    def _select_and_segment(self, sets, points32):
+        """The optional stages behind the filter, on the device, before the download; they draw nothing from numpy's stream.  A
+        selection joins ``sets``.  -> (the keys the stages add to the record, in its order; the device tensors of those that
+        are not in ``sets``; the ``Segmentation`` or None)."""
+        from . import grasp_select
+        from . import segment as segment_mod
+        sel, seg = self.select, self.segment
+        nms = {} if sel is None else sel.nms()
+        keys, extra, segmented = (), {}, None
+        if sel is not None and (seg is None or seg.top_k_per_object is None):      # (a per-object selection replaces it)
+            keys = SELECT_KEYS
+            sets.update(zip(keys, grasp_select.pose_nms(sets[sel.source], top_k=sel.top_k, return_index=True, **nms)))
+        if seg is not None:
+            source = seg.source or (sel.source if sel is not None else "grasp_stage3")
+            above = segment_mod.above_table_mask(points32, self.eval_params[2], seg.table_clearance)
+            segmented = segment_mod.cluster_points(points32, above, seg.tolerance, seg.min_points, seg.max_objects)
+            grasp_object, _ = segment_mod.assign_grasps(sets[source], points32, segmented.label, seg.assign_radius)
+            if seg.top_k_per_object is not None:
+                keys = SEGMENT_SELECT_KEYS
+                sets.update(zip(keys, segment_mod.select_per_object(sets[source], grasp_object, seg.max_objects,
+                                                                    seg.top_k_per_object, **nms)))
+            keys = keys + SEGMENT_KEYS
+            extra = {"point_object": segmented.label, "grasp_object": grasp_object}
+        return keys, extra, segmented
+
+    def _record(self, fr, kept, output_score, sets, keys, extra, segmented):
+        """The downloads, in the order they have always been made -> the record, its keys in the documented order."""
+        points, colors = fr.download(kept)
+        out = {"points": points, "colors": colors, "scores": output_score.view(-1, 1).cpu().numpy()}
+        out.update({key: grasp.cpu().numpy() for key, grasp in sets.items()})
+        if segmented is not None:
+            _, _, out["object_size"], _, out["object_bbox"] = segmented.objects()
+        out.update({key: value.cpu().numpy() for key, value in extra.items()})
+        keys = RESULT_KEYS + keys
+        if fr.table is not None:
+            transform, plane = fr.table
+            out["table_transform"] = np.array(transform, dtype=np.float64)
+            out["table_plane"] = np.array(list(plane.normal) + [plane.offset, plane.rms], dtype=np.float64)
+            keys = keys + TABLE_KEYS
+        if fr.fused is not None:
+            out["fuse_num"] = fr.fused.num.cpu().numpy()
+            out["fuse_views"] = fr.fused.per_view().cpu().numpy()
+            keys = keys + FUSE_KEYS
+        return {key: out[key] for key in keys}
+
     def detect(self, frame):
         """test.py:97-148 for one frame -> ``eval_notruth``'s dict of numpy arrays: ``points`` / ``colors`` (the cropped,
         un-jittered cloud: float64 for a camera frame, float32 for a record), ``scores`` (N,1) float32 and the four
         collision-filtered grasp sets (k,8) float32; with ``select`` also ``SELECT_KEYS``, with ``segment`` ``SEGMENT_KEYS``."""
         import torch
-        from . import eval_collision, grasp_select, np_random
-        from . import segment as segment_mod
-        from .get_regiondataset import get_grasp_allobj
-        depth, width, table_height, _, _ = self.eval_params
-        gpu = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        from . import np_random
         was_training = self.score_net.training, self.region_net.training
         self.score_net.eval()
         self.region_net.eval()
@@ -170,75 +243,20 @@ class GraspDetector:
             # context covers the whole frame -- both networks' torch layers and every launch -- so none of them switches)
             with np_random.deferred(), torch.no_grad(), torch.cuda.device(self.device), \
                     contextlib.redirect_stdout(io.StringIO()):
-                self.table = None
-                self.fused = None
+                self.table = self.fused = None
                 fr = self.ingest(frame)
-                fused = self.fused
-                if fused is not None:
-                    fused.check()          # one 16-byte read; ValueError naming max_voxels when the merge overflowed
-                pc = fr.pc
-                all_feature, output_score, _ = self.score_net(pc)
-                g = get_grasp_allobj(pc, output_score, self.params, [], self.use_theta)
-                res = self.region_net(g[3], g[5], g[2], g[4], g[0], g[1], pc, all_feature, self.gripper_params, None, [])
-                # eval_notruth(pc_back, color_back, grasp_stage2, select_grasp_class, select_grasp_score,
-                #              select_grasp_class_stage2, output_score, ...): test.py:147 -> utils.py:391
-                sets = {"grasp_stage2": res[0], "grasp_stage3_stage2": res[8], "grasp_stage3": res[6],
-                        "grasp_stage3_score": res[7]}
+                self.table, self.fused = fr.table, fr.fused
+                if fr.fused is not None:
+                    fr.fused.check()       # one 16-byte read; ValueError naming max_voxels when the merge overflowed
+                output_score, sets = self._networks(fr)
                 kept = fr.kept()
                 points32 = fr.points32[:kept]
-                self.raw_counts = {}
-                for key, grasp in sets.items():
-                    if grasp is None:      # (the refine head saw no valid crop: an empty set)
-                        grasp = torch.zeros((0, 8), dtype=torch.float32, device=self.device)
-                    self.raw_counts[key] = int(grasp.shape[0])
-                    if grasp.shape[0] >= 1:
-                        grasp = eval_collision.eval_test(points32, grasp[:, :8], None, table_height, depth, width, gpu)
-                    sets[key] = grasp
-                sel, seg = self.select, self.segment
-                # on the device, before the download; draws nothing from numpy's stream (a per-object selection replaces it)
-                if sel is not None and (seg is None or seg.top_k_per_object is None):
-                    sets["grasp_selected"], sets["grasp_selected_index"] = grasp_select.pose_nms(
-                        sets[sel.source], sel.translation_thresh, sel.rotation_thresh_deg, sel.top_k, sel.symmetric,
-                        return_index=True)
-                segmented = None
-                if seg is not None:        # on the device, before the download; draws nothing from numpy's stream
-                    source = seg.source or (sel.source if sel is not None else "grasp_stage3")
-                    above = segment_mod.above_table_mask(points32, table_height, seg.table_clearance)
-                    segmented = segment_mod.cluster_points(points32, above, seg.tolerance, seg.min_points, seg.max_objects)
-                    grasp_object, _ = segment_mod.assign_grasps(sets[source], points32, segmented.label, seg.assign_radius)
-                    if seg.top_k_per_object is not None:
-                        nms = {} if sel is None else {"translation_thresh": sel.translation_thresh,
-                                                      "rotation_thresh_deg": sel.rotation_thresh_deg,
-                                                      "symmetric": sel.symmetric}
-                        sets["grasp_selected"], sets["grasp_selected_index"], sets["grasp_selected_object"] = \
-                            segment_mod.select_per_object(sets[source], grasp_object, seg.max_objects,
-                                                          seg.top_k_per_object, **nms)
-                points, colors = fr.download(kept)
-                out = {"points": points, "colors": colors, "scores": output_score.view(-1, 1).cpu().numpy()}
-                out.update({key: grasp.cpu().numpy() for key, grasp in sets.items()})
-                if segmented is not None:
-                    _, _, out["object_size"], _, out["object_bbox"] = segmented.objects()
-                    out["point_object"] = segmented.label.cpu().numpy()
-                    out["grasp_object"] = grasp_object.cpu().numpy()
-                if fused is not None:
-                    out["fuse_num"] = fused.num.cpu().numpy()
-                    out["fuse_views"] = fused.per_view().cpu().numpy()
+                self._collision_filter(sets, points32)
+                keys, extra, segmented = self._select_and_segment(sets, points32)
+                return self._record(fr, kept, output_score, sets, keys, extra, segmented)
         finally:
             self.score_net.train(was_training[0])
             self.region_net.train(was_training[1])
-        keys = RESULT_KEYS if self.select is None else RESULT_KEYS + SELECT_KEYS
-        if self.segment is not None:
-            if self.segment.top_k_per_object is not None:
-                keys = RESULT_KEYS + SEGMENT_SELECT_KEYS
-            keys = keys + SEGMENT_KEYS
-        if self.table is not None:
-            transform, plane = self.table
-            out["table_transform"] = np.array(transform, dtype=np.float64)
-            out["table_plane"] = np.array(list(plane.normal) + [plane.offset, plane.rms], dtype=np.float64)
-            keys = keys + TABLE_KEYS
-        if fused is not None:
-            keys = keys + FUSE_KEYS
-        return {key: out[key] for key in keys}
 
     def detect_file(self, path, save_path=None, real_data=None):
         """``test_one_file`` (test.py:94-148): ``.pcd`` -> camera frame, ``.npz`` -> depth frame (with a ``views`` entry: the depth frames of several
@@ -275,92 +293,115 @@ class GraspDetector:
         return out, save_path
 
 
+# The regular flags of the CLI: (flag, group, field of the group's parameter class, type or the choices, help stem).  A flag that
+# is not given is None and stays out of the group's dict; a field's default other than None follows the stem in brackets, read
+# from the class.  ``--auto-table``, ``--segment``, ``--keep-uncoloured`` and the two LO HI ranges are written out in build_parser.
+_FLAGS = (
+    # pose NMS + top-K on one of the four sets (grasp_select.pose_nms); giving any of the four turns the selection on
+    ("--top-k", "select", "top_k", int, "keep the K best distinct grasps (default: every distinct one)"),
+    ("--nms-translation", "select", "translation_thresh", float, "centres this close are the same grasp [m]"),
+    ("--nms-rotation", "select", "rotation_thresh_deg", float, "frames this close are the same grasp [deg]"),
+    ("--select-from", "select", "source", RESULT_KEYS[3:], "the set to select from"),
+    # the table plane estimated on every camera frame (table_plane.estimate_plane); giving any of its three flags turns it on
+    ("--plane-threshold", "transform", "threshold", float, "inlier distance of the table plane [m]"),
+    # depth frames (*.npz: depth_frame.to_cloud): the flying-pixel filter and the occlusion test of the colour sensor
+    ("--edge-threshold", "depth", "edge_threshold", float,
+     "remove pixels whose depth jumps by more than this share of the nearer depth to a neighbour (off)"),
+    ("--min-neighbours", "depth", "min_neighbours", int, "remove pixels with fewer valid 8-neighbours"),
+    ("--occlusion-margin", "depth", "occlusion_margin", float,
+     "a point this far behind the colour camera's nearest surface is still seen by it [m]"),
+    # object segmentation (segment.cluster_points): --segment or any of the four turns it on
+    ("--cluster-tolerance", "segment", "tolerance", float, "points this close belong to one object [m]"),
+    ("--min-object-points", "segment", "min_points", int, "drop clusters of fewer points"),
+    ("--max-objects", "segment", "max_objects", int, "keep the largest so many objects"),
+    ("--top-k-per-object", "segment", "top_k_per_object", int, "select the K best distinct grasps of every object"),
+    # multi-view frames (*.npz with a `views` entry: fusion.voxel_merge): the voxel grid the views are merged on
+    ("--voxel", "fuse", "voxel", float, "edge of the voxels the views are merged in [m]"),
+    ("--max-voxels", "fuse", "max_voxels", int, "rows of the merged cloud, at most 2^21"),
+    ("--min-voxel-points", "fuse", "min_count", int, "drop voxels with fewer points"),
+)
+
+
+def _given(args, group):
+    """The fields of ``group`` whose flags were given -> a dict (empty when none was)."""
+    given = {field: getattr(args, flag[2:].replace("-", "_")) for flag, g, field, _, _ in _FLAGS if g == group}
+    return {field: value for field, value in given.items() if value is not None}
+
+
 def select_from_args(args):
     """The CLI's four selection flags -> a ``select`` dict, or None when none of them was given."""
-    given = {"top_k": args.top_k, "translation_thresh": args.nms_translation, "rotation_thresh_deg": args.nms_rotation,
-             "source": args.select_from}
-    given = {key: value for key, value in given.items() if value is not None}
-    return given if given else None
+    return _given(args, "select") or None
 
 
 def segment_from_args(args):
     """The CLI's five segmentation flags -> a ``segment`` dict, or None when none of them was given."""
-    given = {"tolerance": args.cluster_tolerance, "min_points": args.min_object_points, "max_objects": args.max_objects,
-             "top_k_per_object": args.top_k_per_object}
-    given = {key: value for key, value in given.items() if value is not None}
+    given = _given(args, "segment")
     return given if (given or args.segment) else None
 
 
 def transform_from_args(args):
     """The CLI's three table flags -> ``GraspDetector``'s ``transform``: None (the default transform) unless one was given."""
-    if not (args.auto_table or args.table_range is not None or args.plane_threshold is not None):
-        return None
-    given = {}
-    if args.table_range is not None:
-        given["range"] = (float(args.table_range[0]), float(args.table_range[1]))
-    if args.plane_threshold is not None:
-        given["threshold"] = float(args.plane_threshold)
-    return given if given else "auto"
+    given = {} if args.table_range is None else {"range": (float(args.table_range[0]), float(args.table_range[1]))}
+    given.update(_given(args, "transform"))
+    return given or ("auto" if args.auto_table else None)
 
 
 def depth_from_args(args):
     """The CLI's five depth-frame flags -> a ``depth`` dict, or None when none of them was given."""
-    given = {"edge_threshold": args.edge_threshold, "min_neighbours": args.min_neighbours,
-             "occlusion_margin": args.occlusion_margin}
-    given = {key: value for key, value in given.items() if value is not None}
+    given = _given(args, "depth")
     if args.depth_range is not None:
         given["depth_range"] = (float(args.depth_range[0]), float(args.depth_range[1]))
     if args.keep_uncoloured:
         given["keep_uncoloured"] = True
-    return given if given else None
+    return given or None
 
 
 def fuse_from_args(args):
     """The CLI's three fusion flags -> a ``fuse`` dict, or None when none of them was given."""
-    given = {"voxel": args.voxel, "max_voxels": args.max_voxels, "min_count": args.min_voxel_points}
-    given = {key: value for key, value in given.items() if value is not None}
-    return given if given else None
+    return _given(args, "fuse") or None
 
 
-def main(argv=None):
-    """``main()`` of test.py:150-164."""
-    from . import checkpoint
+def build_parser():
+    """The CLI of ``main``: test.py's arguments, ``_FLAGS`` and the irregular flags of each group."""
+    from . import depth_frame, fusion, grasp_select, table_plane
+    from . import segment as segment_mod
+    defaults = {"select": grasp_select.SelectParams(), "transform": argparse.Namespace(threshold=table_plane.DEFAULT_THRESHOLD),
+                "depth": depth_frame.DepthParams(), "segment": segment_mod.SegmentParams(), "fuse": fusion.FuseParams()}
     parser = argparse.ArgumentParser(description="REGNet single-file inference (the reference's test.py)")
     parser.add_argument("--folder", "--folder-name", dest="folder", required=True)
     parser.add_argument("--file", "--file-name", dest="file", default="")
     parser.add_argument("--load-score-path", required=True)
     parser.add_argument("--load-region-path", required=True)
     parser.add_argument("--gpu", type=int, default=0)
-    # pose NMS + top-K on one of the four sets (grasp_select.pose_nms); giving any of the four turns the selection on
-    parser.add_argument("--top-k", type=int, default=None, help="keep the K best distinct grasps (default: every distinct one)")
-    parser.add_argument("--nms-translation", type=float, default=None, help="centres this close are the same grasp [m] (0.03)")
-    parser.add_argument("--nms-rotation", type=float, default=None, help="frames this close are the same grasp [deg] (30)")
-    parser.add_argument("--select-from", choices=list(RESULT_KEYS[3:]), default=None, help="the set to select from (grasp_stage3)")
-    # the table plane estimated on every camera frame (table_plane.estimate_plane); giving any of the three turns it on
+
+    def regular(group):
+        for flag, g, field, kind, stem in _FLAGS:
+            if g == group:
+                default = getattr(defaults[group], field)
+                shown = "" if default is None else " (%s)" % ("%g" % default if isinstance(default, float) else default)
+                parser.add_argument(flag, default=None, help=stem + shown,
+                                    **({"choices": list(kind)} if isinstance(kind, tuple) else {"type": kind}))
+
+    regular("select")
     parser.add_argument("--auto-table", action="store_true", help="estimate the camera -> table transform on every frame")
     parser.add_argument("--table-range", type=float, nargs=2, metavar=("LO", "HI"), default=None,
                         help="the table plane lies between LO and HI metres from the camera")
-    parser.add_argument("--plane-threshold", type=float, default=None, help="inlier distance of the table plane [m] (0.005)")
-    # depth frames (*.npz: depth_frame.to_cloud): the range, the flying-pixel filter and the occlusion test of the colour sensor
+    regular("transform")
     parser.add_argument("--depth-range", type=float, nargs=2, metavar=("LO", "HI"), default=None,
-                        help="keep depths between LO and HI metres, inclusive (0 inf)")
-    parser.add_argument("--edge-threshold", type=float, default=None,
-                        help="remove pixels whose depth jumps by more than this share of the nearer depth to a neighbour (off)")
-    parser.add_argument("--min-neighbours", type=int, default=None, help="remove pixels with fewer valid 8-neighbours (0)")
-    parser.add_argument("--occlusion-margin", type=float, default=None,
-                        help="a point this far behind the colour camera's nearest surface is still seen by it [m] (0.01)")
+                        help="keep depths between LO and HI metres, inclusive (%g %g)" % defaults["depth"].depth_range)
+    regular("depth")
     parser.add_argument("--keep-uncoloured", action="store_true",
                         help="keep points the colour camera does not see, with black colour, instead of dropping them")
-    # object segmentation (segment.cluster_points): --segment or any of the four turns it on
     parser.add_argument("--segment", action="store_true", help="cluster the points above the table into objects")
-    parser.add_argument("--cluster-tolerance", type=float, default=None, help="points this close belong to one object [m] (0.01)")
-    parser.add_argument("--min-object-points", type=int, default=None, help="drop clusters of fewer points (50)")
-    parser.add_argument("--max-objects", type=int, default=None, help="keep the largest so many objects (64)")
-    parser.add_argument("--top-k-per-object", type=int, default=None, help="select the K best distinct grasps of every object")
-    # multi-view frames (*.npz with a `views` entry: fusion.voxel_merge): the voxel grid the views are merged on
-    parser.add_argument("--voxel", type=float, default=None, help="edge of the voxels the views are merged in [m] (0.002)")
-    parser.add_argument("--max-voxels", type=int, default=None, help="rows of the merged cloud, at most 2^21 (2^20)")
-    parser.add_argument("--min-voxel-points", type=int, default=None, help="drop voxels with fewer points (1)")
+    regular("segment")
+    regular("fuse")
+    return parser
+
+
+def main(argv=None):
+    """``main()`` of test.py:150-164."""
+    from . import checkpoint
+    parser = build_parser()
     args = parser.parse_args(argv)
     select = select_from_args(args)
     obj_class_num, group_num, gripper_num, score_thre, depth, reg_channel = MODEL_PARAMS

@@ -19,16 +19,17 @@ from typing import Any, List, Tuple
 import numpy as np
 
 from . import _lib, depth_frame
+from ._frame_util import MAX_FRAME_POINTS, ParamsBase, matrix4, record_streams, require_cuda, stream_scope
 
 _L = _lib.lib
 
 MAX_VIEWS = 8
-MAX_VOXELS = 1 << 21                # regnet_fuse_*'s documented limit; = ingest.MAX_FRAME_POINTS
+MAX_VOXELS = MAX_FRAME_POINTS       # regnet_fuse_*'s documented limit
 COORD_LIMIT = 1 << 20               # voxel coordinates lie in [-2^20, 2^20)
 
 
 @dataclass(frozen=True)
-class FuseParams:
+class FuseParams(ParamsBase):
     """``voxel``: the voxel edge [m]; ``origin``: a corner of voxel (0, 0, 0) in the common frame; ``max_voxels``: the rows of the
     result, at most 2^21 -- a merge that occupies more sets the overflow flag; ``min_count``: voxels with fewer points are dropped
     (2 and more remove isolated points, and points only one camera sees once where two overlap pixel for pixel).
@@ -36,6 +37,7 @@ class FuseParams:
     The 2 mm default is a choice -- about the spacing of the points of a 640 x 480 frame at 1 m -- and not a measurement on real
     cameras.  A voxel below the point spacing makes the merge a pure transform-and-sort: every voxel holds one point, which comes
     out as it went in."""
+    WORD, NONE_IS_DEFAULT = "fuse", True
     voxel: float = 0.002
     origin: Tuple[float, float, float] = (0.0, 0.0, 0.0)
     max_voxels: int = 1 << 20
@@ -52,17 +54,6 @@ class FuseParams:
             raise ValueError("fuse: max_voxels must be in 1..2^21")
         if int(self.min_count) != self.min_count or self.min_count < 1:
             raise ValueError("fuse: min_count must be at least 1")
-
-    @classmethod
-    def coerce(cls, value):
-        """None -> the defaults, a FuseParams -> itself, a dict -> FuseParams(**dict)."""
-        if value is None:
-            return cls()
-        if isinstance(value, cls):
-            return value
-        if isinstance(value, dict):
-            return cls(**value)
-        raise TypeError("fuse must be None, a dict or a FuseParams")
 
 
 class Fused:
@@ -109,16 +100,14 @@ def workspace_bytes(max_voxels):
 
 def pose12(pose):
     """A row-major 4x4 (None: identity) -> its first three rows as 12 float32, each entry rounded once from float64."""
-    T = np.eye(4) if pose is None else np.asarray(pose.detach().cpu().numpy() if hasattr(pose, "detach") else pose,
-                                                  dtype=np.float64)
-    if T.shape != (4, 4):
-        raise ValueError("a pose must be a 4x4 camera-to-common transform")
+    T = np.eye(4) if pose is None else matrix4(pose, "a pose must be a 4x4 camera-to-common transform")
     with np.errstate(over="ignore"):
         return np.ascontiguousarray(T[:3, :].reshape(12).astype(np.float32))
 
 
 def _cloud(v, pair, dev):
     import torch
+    what = "cloud %d: " % v
     if not isinstance(pair, (tuple, list)) or len(pair) != 2:
         raise TypeError("cloud %d must be an (xyz, rgb) pair" % v)
     out = []
@@ -126,10 +115,7 @@ def _cloud(v, pair, dev):
         if t is None and name == "rgb":
             out.append(None)
             continue
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise RuntimeError("cloud %d: %s must be a CUDA tensor (no CPU path)" % (v, name))
-        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3:
-            raise TypeError("cloud %d: %s must be float32 (n, 3)" % (v, name))
+        require_cuda(what + name, t, torch.float32, 3, error=TypeError)
         if dev is not None and t.device != dev:
             raise RuntimeError("cloud %d: %s is on %s, the first cloud on %s" % (v, name, t.device, dev))
         out.append(t.contiguous())
@@ -166,7 +152,7 @@ def voxel_merge(clouds, poses=None, params=None, stream=None, out=None):
     origin = np.ascontiguousarray(np.asarray(params.origin, dtype=np.float64).astype(np.float32))
     voxel = float(params.voxel)
     raw = None if stream is None else stream.cuda_stream
-    with torch.cuda.device(dev), (torch.cuda.stream(stream) if stream is not None else depth_frame._null()):
+    with torch.cuda.device(dev), stream_scope(stream):
         ws = torch.empty((workspace_bytes(mv),), dtype=torch.uint8, device=dev)
         kept_keys = torch.empty((mv,), dtype=torch.int64, device=dev)
         shapes = (((mv, 3), torch.float32), ((mv, 3), torch.float32), ((mv,), torch.int32), ((mv,), torch.int32),
@@ -189,10 +175,7 @@ def voxel_merge(clouds, poses=None, params=None, stream=None, out=None):
                   rgb_out.data_ptr(), count.data_ptr(), views.data_ptr(), first.data_ptr(), num.data_ptr(), ws.data_ptr(),
                   stream=raw)
         if stream is not None:                              # the inputs are read on `stream`: keep them alive for it
-            for xyz, rgb in pairs:
-                xyz.record_stream(stream)
-                if rgb is not None:
-                    rgb.record_stream(stream)
+            record_streams(stream, *(t for pair in pairs for t in pair))
     return Fused(xyz_out, rgb_out, count, views, first, num, params, len(pairs))
 
 
@@ -218,10 +201,7 @@ class MultiView:
 
 def pose_matrix(pose):
     """A pose as a (4, 4) float64 array; anything else is a ValueError."""
-    T = np.asarray(pose.detach().cpu().numpy() if hasattr(pose, "detach") else pose, dtype=np.float64)
-    if T.shape != (4, 4) or not np.isfinite(T).all():
-        raise ValueError("a pose must be a finite 4x4 camera-to-common transform")
-    return T
+    return matrix4(pose, "a pose must be a finite 4x4 camera-to-common transform", finite=True)
 
 
 def fuse_frames(multiview, depth_params=None, fuse_params=None, device="cuda:0", stream=None):
@@ -242,24 +222,12 @@ def is_multiview_npz(path):
 
 
 def save_npz(path, multiview):
-    """Write ``multiview`` as one ``.npz``: ``views`` (the count) and per view ``view{v}_depth``, ``view{v}_intrinsics`` (4),
-    ``view{v}_pose`` (4,4) and, where given, ``view{v}_color``, ``view{v}_color_intrinsics``, ``view{v}_depth_to_color``,
-    ``view{v}_depth_scale``."""
-    def host(a):
-        return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+    """Write ``multiview`` as one ``.npz``: ``views`` (the count) and per view ``view{v}_pose`` (4,4) and
+    ``depth_frame.frame_items``' entries behind ``view{v}_``."""
     items = {"views": np.int64(len(multiview.frames))}
     for v, (frame, pose) in enumerate(zip(multiview.frames, multiview.poses)):
-        pre = "view%d_" % v
-        items[pre + "depth"] = host(frame.depth)
-        items[pre + "intrinsics"] = np.array(frame.intrinsics.astuple(), dtype=np.float64)
-        items[pre + "pose"] = np.eye(4) if pose is None else pose_matrix(pose)
-        items[pre + "depth_scale"] = np.float64(frame.depth_scale)
-        if frame.color is not None:
-            items[pre + "color"] = host(frame.color)
-        if frame.color_intrinsics is not None:
-            items[pre + "color_intrinsics"] = np.array(frame.color_intrinsics.astuple(), dtype=np.float64)
-        if frame.depth_to_color is not None:
-            items[pre + "depth_to_color"] = host(frame.depth_to_color).astype(np.float64)
+        items.update(depth_frame.frame_items(frame, "view%d_" % v))
+        items["view%d_pose" % v] = np.eye(4) if pose is None else pose_matrix(pose)
     with open(path, "wb") as f:
         np.savez(f, **items)
 
@@ -267,27 +235,13 @@ def save_npz(path, multiview):
 def load_npz(path):
     """Read a ``.npz`` written by ``save_npz`` (or by anything that uses its entries) -> ``MultiView``.  Unknown entries, a
     missing depth image, intrinsics or pose are a ``ValueError``."""
+    what = "multi-view frame %s" % path
     with np.load(path, allow_pickle=False) as data:
         if "views" not in data.files:
-            raise ValueError("multi-view frame %s: no 'views' entry" % path)
+            raise ValueError("%s: no 'views' entry" % what)
         count = int(data["views"])
         if not 1 <= count <= MAX_VIEWS:
-            raise ValueError("multi-view frame %s: views must be 1..%d" % (path, MAX_VIEWS))
-        known = {"views"} | {"view%d_%s" % (v, key) for v in range(count) for key in _VIEW_KEYS}
-        unknown = sorted(set(data.files) - known)
-        if unknown:
-            raise ValueError("multi-view frame %s: unknown entries %s" % (path, ", ".join(unknown)))
-        frames, poses = [], []
-        for v in range(count):
-            pre = "view%d_" % v
-            for key in ("depth", "intrinsics", "pose"):
-                if pre + key not in data.files:
-                    raise ValueError("multi-view frame %s: no %r entry" % (path, pre + key))
-            get = lambda key: data[pre + key] if pre + key in data.files else None      # noqa: E731
-            scale = get("depth_scale")
-            frames.append(depth_frame.DepthFrame(depth=data[pre + "depth"], intrinsics=data[pre + "intrinsics"],
-                                                 color=get("color"), color_intrinsics=get("color_intrinsics"),
-                                                 depth_to_color=get("depth_to_color"),
-                                                 depth_scale=0.001 if scale is None else float(scale)))
-            poses.append(pose_matrix(data[pre + "pose"]))
-        return MultiView(frames, poses)
+            raise ValueError("%s: views must be 1..%d" % (what, MAX_VIEWS))
+        depth_frame.check_npz_entries(data, {"views"} | {"view%d_%s" % (v, key) for v in range(count) for key in _VIEW_KEYS}, what)
+        frames = [depth_frame.frame_from_items(data, "view%d_" % v, what, ("depth", "intrinsics", "pose")) for v in range(count)]
+        return MultiView(frames, [pose_matrix(data["view%d_pose" % v]) for v in range(count)])

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._frame_util import ParamsBase, require_cuda
 from .eval_collision import grasp_frames
 
 _check = _lib.check
@@ -29,9 +30,10 @@ SOURCES = ("grasp_stage2", "grasp_stage3_stage2", "grasp_stage3", "grasp_stage3_
 
 
 @dataclass
-class SelectParams:
+class SelectParams(ParamsBase):
     """What ``GraspDetector(select=...)`` takes (a dict with these keys works too): which of the four collision-filtered grasp
     sets to select from, how many to keep (``None`` / <= 0: every distinct one) and ``pose_nms``'s thresholds."""
+    WORD = "select"
     source: str = "grasp_stage3"
     top_k: Optional[int] = None
     translation_thresh: float = 0.03
@@ -42,14 +44,10 @@ class SelectParams:
         if self.source not in SOURCES:
             raise ValueError("select: source must be one of %s, not %r" % (", ".join(SOURCES), self.source))
 
-    @classmethod
-    def coerce(cls, value):
-        """None -> None, a SelectParams -> itself, a dict -> SelectParams(**dict)."""
-        if value is None or isinstance(value, cls):
-            return value
-        if isinstance(value, dict):
-            return cls(**value)
-        raise TypeError("select must be None, a dict or a SelectParams")
+    def nms(self):
+        """``pose_nms``'s keywords other than ``top_k``: what the per-frame and the per-object selection share."""
+        return {"translation_thresh": self.translation_thresh, "rotation_thresh_deg": self.rotation_thresh_deg,
+                "symmetric": self.symmetric}
 
 
 def thresholds(translation_thresh, rotation_thresh_deg):
@@ -65,10 +63,7 @@ def workspace_bytes(n):
 
 
 def _grasp_ok(grasp):
-    if not isinstance(grasp, torch.Tensor) or not grasp.is_cuda:
-        raise RuntimeError("grasp must be a CUDA tensor (no CPU path)")
-    if grasp.dtype != torch.float32 or grasp.dim() != 2 or grasp.shape[1] < 8:
-        raise RuntimeError("grasp must be float32 (n, >=8)")
+    require_cuda("grasp", grasp, torch.float32, 8, at_least=True, error=RuntimeError)
 
 
 def rank_order(score):

@@ -12,13 +12,13 @@ import pickle
 import numpy as np
 
 from . import _lib
+from ._frame_util import MAX_FRAME_POINTS, require_cuda, to_device      # noqa: F401  (the limit is this module's too)
 
 _call = _lib.call
 _L = _lib.lib
 
 NUM_POINTS = 25600                                   # test.py:61
 DEFAULT_BOUNDS = (0.26, -0.4, 1.0, 0.65, 0.2)        # test.py:114-118: x < 0.26, x > -0.4, z < 1, y < 0.65, y > 0.2
-MAX_FRAME_POINTS = 1 << 21                           # regnet_ingest_crop_*: larger frames are REGNET_ERR_UNSUPPORTED
 CENTER_CAMERA = (0.0, 0.0, 1.658)                    # test.py:103
 
 _PCD_KEYS = ("VERSION", "FIELDS", "SIZE", "TYPE", "COUNT", "WIDTH", "HEIGHT", "VIEWPOINT", "POINTS", "DATA")
@@ -180,6 +180,7 @@ class Frame:
     def __init__(self, pc, points_back, colors_back, points32, count, out_of_range, source=None):
         self.pc, self.points_back, self.colors_back, self.points32 = pc, points_back, colors_back, points32
         self.count, self.out_of_range, self.source = count, out_of_range, source
+        self.fused = self.table = None           # GraspDetector.ingest: the fusion.Fused / the (transform, plane) it found
 
     def kept(self):
         """The number of kept rows as a Python int (a 4-byte blocking read).  Raises ``ValueError`` when nothing was kept:
@@ -199,16 +200,6 @@ class Frame:
         return self.points_back[:n].cpu().numpy(), self.colors_back[:n].cpu().numpy()
 
 
-def _to_device(a, device):
-    import torch
-    from . import host_io
-    if isinstance(a, torch.Tensor):
-        t = a if a.is_cuda else host_io.upload(a, device)
-    else:
-        t = host_io.upload(np.ascontiguousarray(a), device)
-    return t.contiguous()
-
-
 def crop_frame(xyz, rgb, transform, bounds=DEFAULT_BOUNDS, drop_nonfinite=True, with_source=False):
     """regnet_ingest_crop_*: ``xyz`` / ``rgb`` (M,3) contiguous GPU tensors of one dtype (float32 or float64) ->
     ``(kept_xyz64 (M,3), kept_xyz32 (M,3), kept_rgb (M,3) float64, count (1,) int32, source (M,) int32 or None)``, all on
@@ -220,13 +211,10 @@ def crop_frame(xyz, rgb, transform, bounds=DEFAULT_BOUNDS, drop_nonfinite=True, 
     b = np.ascontiguousarray(bounds, dtype=np.float64)
     if b.shape != (5,):
         raise ValueError("bounds must be (x_hi, x_lo, z_hi, y_hi, y_lo)")
-    if not (xyz.is_cuda and rgb.is_cuda):
-        raise RuntimeError("crop_frame: xyz and rgb must be CUDA tensors (no CPU path)")
-    if xyz.dim() != 2 or xyz.shape[1] != 3 or tuple(rgb.shape) != tuple(xyz.shape):
+    xyz = require_cuda("crop_frame: xyz", xyz, (torch.float32, torch.float64), 3).contiguous()
+    rgb = require_cuda("crop_frame: rgb", rgb, xyz.dtype, 3).contiguous()
+    if rgb.shape[0] != xyz.shape[0]:
         raise ValueError("xyz and rgb must both be (M, 3)")
-    if xyz.dtype != rgb.dtype or xyz.dtype not in (torch.float32, torch.float64):
-        raise TypeError("xyz and rgb must both be float32 or both float64")
-    xyz, rgb = xyz.contiguous(), rgb.contiguous()
     M, dev = int(xyz.shape[0]), xyz.device
     if M > MAX_FRAME_POINTS:
         raise ValueError("frames of more than 2^21 points are not supported")
@@ -271,7 +259,7 @@ def ingest_frame(xyz, rgb, transform=None, bounds=DEFAULT_BOUNDS, num_points=NUM
     ``np.random`` on the host again."""
     import torch
     dev = torch.device(device)
-    xyz_d, rgb_d = _to_device(xyz, dev), _to_device(rgb, dev)
+    xyz_d, rgb_d = to_device(xyz, dev), to_device(rgb, dev)
     kept64, kept32, kept_rgb, count, source = crop_frame(xyz_d, rgb_d, table_frame_transform() if transform is None else transform,
                                                          bounds, drop_nonfinite, with_source)
     pc, bad = _resample(kept32, kept_rgb, count, num_points)
@@ -287,8 +275,8 @@ def ingest_record(path_or_dict, num_points=NUM_POINTS, device="cuda:0"):
         with open(path_or_dict, "rb") as f:
             data = pickle.load(f)
     dev = torch.device(device)
-    cloud = _to_device(np.asarray(data["view_cloud"]).astype(np.float32), dev)
-    color = _to_device(np.asarray(data["view_cloud_color"]).astype(np.float32), dev)
+    cloud = to_device(np.asarray(data["view_cloud"]).astype(np.float32), dev)
+    color = to_device(np.asarray(data["view_cloud_color"]).astype(np.float32), dev)
     if cloud.dim() != 2 or cloud.shape[1] != 3 or tuple(color.shape) != tuple(cloud.shape):
         raise ValueError("view_cloud and view_cloud_color must both be (M, 3)")
     count = torch.full((1,), int(cloud.shape[0]), dtype=torch.int32, device=cloud.device)

@@ -18,12 +18,13 @@ import numpy as np
 import torch
 
 from . import _lib, grasp_select
+from ._frame_util import ParamsBase, require_cuda
 
 _L = _lib.lib
 
 
 @dataclass
-class SegmentParams:
+class SegmentParams(ParamsBase):
     """What ``GraspDetector(segment=...)`` takes (a dict with these keys works too).  ``tolerance``: two points this close [m]
     belong to one object; ``min_points``: smaller clusters are dropped; ``max_objects``: the largest so many are kept;
     ``table_clearance``: points must lie this far above the table; ``assign_radius``: a grasp belongs to the object of the
@@ -34,6 +35,7 @@ class SegmentParams:
 
     The defaults are a choice made from the reference's gripper (8 cm opening, 6 cm fingers) and crop sizes.  Nobody has
     measured them on real frames."""
+    WORD = "segment"
     tolerance: float = 0.01
     min_points: int = 50
     max_objects: int = 64
@@ -55,15 +57,6 @@ class SegmentParams:
             raise ValueError("segment: assign_radius must be non-negative and finite")
         if self.top_k_per_object is not None and int(self.top_k_per_object) < 1:
             raise ValueError("segment: top_k_per_object must be None or at least 1")
-
-    @classmethod
-    def coerce(cls, value):
-        """None -> None, a SegmentParams -> itself, a dict -> SegmentParams(**dict)."""
-        if value is None or isinstance(value, cls):
-            return value
-        if isinstance(value, dict):
-            return cls(**value)
-        raise TypeError("segment must be None, a dict or a SegmentParams")
 
 
 class Segmentation:
@@ -90,26 +83,21 @@ def workspace_bytes(n, max_objects):
     return int(_L.regnet_cluster_workspace_bytes(int(n), int(max_objects)))
 
 
-def _cuda(name, x, dtype, cols=None):
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise RuntimeError("%s must be a CUDA tensor (no CPU path)" % name)
-    if x.dtype != dtype or (cols is not None and (x.dim() != 2 or x.shape[1] != cols)) or (cols is None and x.dim() != 1):
-        raise RuntimeError("%s must be %s %s" % (name, dtype, "(n,%d)" % cols if cols else "(n)"))
-    return x.contiguous()
+def _cuda(name, x, dtype=None, cols=None, at_least=False):
+    """Every argument check of this module is a RuntimeError."""
+    return require_cuda(name, x, dtype, cols, at_least, error=RuntimeError)
 
 
 def cluster_points(xyz, mask=None, tolerance=0.01, min_points=50, max_objects=64):
     """``xyz`` (N,3) float32 on the GPU, any strides; ``mask`` (N) bool / uint8 or None -> ``Segmentation``.  Two launches of
     the kernels with one ``torch.sort`` of the component sizes between them; no host read."""
-    xyz = _cuda("xyz", xyz, torch.float32, 3)
+    xyz = _cuda("xyz", xyz, torch.float32, 3).contiguous()
     n, k = int(xyz.shape[0]), int(max_objects)
     dev = xyz.device
     mask_ptr = 0
     if mask is not None:
-        if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
-            raise RuntimeError("mask must be a CUDA tensor (no CPU path)")
-        if mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != (n,):
-            raise RuntimeError("mask must be bool or uint8 (n)")
+        if _cuda("mask", mask, (torch.bool, torch.uint8)).shape[0] != n:
+            raise RuntimeError("mask must have one entry per row of xyz")
         mask = mask.to(torch.uint8).contiguous()
         mask_ptr = mask.data_ptr()
     need = workspace_bytes(n, k)
@@ -140,13 +128,9 @@ def assign_grasps(grasp, xyz, label, radius=0.03):
     """``grasp`` (Q, >=3) float32 (the centre is columns 0:3), ``xyz`` (N,3) float32, ``label`` (N) int32, all on the GPU ->
     ``(object (Q) int32, point (Q) int32)`` on the device: the nearest labelled row within ``radius`` of the centre and its
     object, -1 without one."""
-    if not isinstance(grasp, torch.Tensor) or not grasp.is_cuda:
-        raise RuntimeError("grasp must be a CUDA tensor (no CPU path)")
-    if grasp.dtype != torch.float32 or grasp.dim() != 2 or grasp.shape[1] < 3:
-        raise RuntimeError("grasp must be float32 (q, >=3)")
-    query = grasp[:, :3].contiguous()
-    xyz = _cuda("xyz", xyz, torch.float32, 3)
-    label = _cuda("label", label, torch.int32)
+    query = _cuda("grasp", grasp, torch.float32, 3, at_least=True)[:, :3].contiguous()
+    xyz = _cuda("xyz", xyz, torch.float32, 3).contiguous()
+    label = _cuda("label", label, torch.int32).contiguous()
     if label.shape[0] != xyz.shape[0]:
         raise RuntimeError("label must have one entry per row of xyz")
     q = int(query.shape[0])
@@ -159,10 +143,7 @@ def assign_grasps(grasp, xyz, label, radius=0.03):
 
 def above_table_mask(points32, table_height, clearance):
     """(N,3) float32 -> (N) bool: ``z > float32(float32(table_height) + float32(clearance))``, compared as float32."""
-    if not isinstance(points32, torch.Tensor) or not points32.is_cuda:
-        raise RuntimeError("points32 must be a CUDA tensor (no CPU path)")
-    if points32.dtype != torch.float32:
-        raise RuntimeError("points32 must be float32")
+    _cuda("points32", points32, torch.float32, 3, at_least=True)
     level = np.float32(np.float32(table_height) + np.float32(clearance))
     return points32[:, 2] > float(level)
 
@@ -174,10 +155,8 @@ def select_per_object(grasp, object, num_objects, k, **nms):
     host read sizes the result."""
     if "top_k" in nms:
         raise TypeError("select_per_object: top_k is not a keyword (the NMS runs over the whole set)")
-    if not isinstance(object, torch.Tensor) or not object.is_cuda:
-        raise RuntimeError("object must be a CUDA tensor (no CPU path)")
     n = int(grasp.shape[0])
-    if tuple(object.shape) != (n,):
+    if tuple(_cuda("object", object).shape) != (n,):
         raise RuntimeError("object must have one entry per grasp")
     grasp_select._grasp_ok(grasp)
     if n == 0:

@@ -15,10 +15,10 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib
+from ._frame_util import MAX_FRAME_POINTS, require_cuda, to_device      # (MAX_*: regnet_plane_estimate_*'s documented limits)
 
 _L = _lib.lib
 
-MAX_FRAME_POINTS = 1 << 21          # regnet_plane_estimate_*'s documented limits
 MAX_HYPOTHESES = 4096
 DEFAULT_THRESHOLD = 0.005
 DEFAULT_HYPOTHESES = 1024
@@ -48,12 +48,7 @@ def estimate_device(xyz, threshold=DEFAULT_THRESHOLD, hypotheses=DEFAULT_HYPOTHE
     on the current stream, no host read.  ``result`` is 96 bytes (uint8): the ten float64 moments, then int32 winner and
     count.  ``out``: a previous call's return value, to run without an allocation; ``stages``: see the header (measurements)."""
     import torch
-    if not isinstance(xyz, torch.Tensor) or not xyz.is_cuda:
-        raise RuntimeError("xyz must be a CUDA tensor (no CPU path)")
-    if xyz.dim() != 2 or xyz.shape[1] != 3:
-        raise ValueError("xyz must be (M, 3)")
-    if xyz.dtype not in (torch.float32, torch.float64):
-        raise TypeError("xyz must be float32 or float64")
+    xyz = require_cuda("xyz", xyz, (torch.float32, torch.float64), 3).contiguous()
     M, H, dev = int(xyz.shape[0]), int(hypotheses), xyz.device
     if M > MAX_FRAME_POINTS:
         raise ValueError("frames of more than 2^21 points are not supported")
@@ -73,7 +68,6 @@ def estimate_device(xyz, threshold=DEFAULT_THRESHOLD, hypotheses=DEFAULT_HYPOTHE
         if hint.shape != (3,):
             raise ValueError("up_hint must be (3,)")
         c2 = cos2_tilt(max_tilt_deg)
-    xyz = xyz.contiguous()
     if out is None:
         result = torch.empty((96,), dtype=torch.uint8, device=dev)
         details = PlaneDetails(torch.empty((H,), dtype=torch.int32, device=dev),
@@ -131,10 +125,7 @@ def estimate_plane(xyz, threshold=DEFAULT_THRESHOLD, hypotheses=DEFAULT_HYPOTHES
     also ``PlaneDetails(counts (H) int32, hypotheses (H,8) float32, inlier_mask (M) uint8, moments (10) float64)`` on the
     device.  Raises ``ValueError`` when no plane is found (no eligible hypothesis with at least 3 inliers)."""
     import torch
-    from . import ingest
-    if not (isinstance(xyz, torch.Tensor) and xyz.is_cuda):
-        xyz = ingest._to_device(xyz, torch.device(device))
-    xyz = xyz.contiguous()
+    xyz = to_device(xyz, torch.device(device))
     result, details, _ = estimate_device(xyz, threshold, hypotheses, seed, range, up_hint, max_tilt_deg)
     moments_fixed_order(xyz, details.inlier_mask, out=details.moments)      # the refit's input, reproducible to the last bit
     host = result.cpu().numpy()                                    # the one blocking read: 96 bytes

@@ -113,7 +113,7 @@ def torch_formulation(depth, color, consts, W, H, t, k, registered=None):
 def host_route(frame, device):
     """(b): what a user does today -- deproject on the host in float64, colours / 255 in float64, upload both."""
     import numpy as np
-    from regnet_for_3d_grasping_amd import ingest
+    from regnet_for_3d_grasping_amd._frame_util import to_device
     fx, fy, cx, cy = frame.intrinsics
     H, W = frame.depth.shape
     z = frame.depth.astype(np.float64) * 0.001
@@ -121,7 +121,7 @@ def host_route(frame, device):
     u, v = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
     xyz = np.stack([(u - cx) * z / fx, (v - cy) * z / fy, z], axis=-1).reshape(-1, 3)
     rgb = frame.color_aligned.reshape(-1, 3).astype(np.float64) / 255.0
-    return ingest._to_device(xyz, device), ingest._to_device(rgb, device)
+    return to_device(xyz, device), to_device(rgb, device)
 
 
 def step_kernels(lines):

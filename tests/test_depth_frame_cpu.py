@@ -333,3 +333,92 @@ def test_detect_helpers():
     assert detect.save_path_for("/x/plain/000.p", False) == "/x/plain/000.p"
     assert detect.save_path_for("/x/test_data/frame.npz", False) == "/x/test_data_predict/frame.npz"
     assert detect.RESULT_KEYS[0] == "points" and len(detect.RESULT_KEYS) == 7
+
+
+# ---- the front end's shared pieces: one coerce, one flag table ------------------------------------------------------------------
+def _params_classes():
+    from regnet_for_3d_grasping_amd import depth_frame, fusion, grasp_select, segment
+    return {"select": (grasp_select.SelectParams, False, {"top_k": 5}), "segment": (segment.SegmentParams, False, {"max_objects": 3}),
+            "depth": (depth_frame.DepthParams, True, {"depth_range": [0.2, 3], "min_neighbours": 2}),
+            "fuse": (fusion.FuseParams, True, {"voxel": 0.005, "origin": [1, 2, 3]})}
+
+
+@pytest.mark.parametrize("word", ["select", "segment", "depth", "fuse"])
+def test_params_coerce(word):
+    """None -> None (select, segment) or the defaults (depth, fuse); an instance -> itself; a dict -> the instance of its fields;
+    anything else -> a TypeError that names the detector's keyword."""
+    cls, none_is_default, fields = _params_classes()[word]
+    got = cls.coerce(None)
+    assert (got == cls() and type(got) is cls) if none_is_default else got is None
+    p = cls()
+    assert cls.coerce(p) is p
+    q = cls.coerce(fields)
+    assert type(q) is cls and q == cls(**fields)
+    for key, value in fields.items():
+        want = tuple(float(v) for v in value) if isinstance(value, list) else value
+        assert getattr(q, key) == want and type(getattr(q, key)) is type(want), key
+    for bad in ("x", 3, [1], (1, 2)):
+        with pytest.raises(TypeError, match=r"^%s must be None, a dict or a %s$" % (word, cls.__name__)):
+            cls.coerce(bad)
+    with pytest.raises(TypeError):
+        cls.coerce({"no_such_field": 1})
+
+
+CLI_REQUIRED = ["--folder", "f", "--load-score-path", "s", "--load-region-path", "r"]
+CLI_FULL = CLI_REQUIRED + [
+    "--top-k", "7", "--nms-translation", "0.02", "--nms-rotation", "15", "--select-from", "grasp_stage2",
+    "--auto-table", "--table-range", "0.5", "1.2", "--plane-threshold", "0.004",
+    "--depth-range", "0.2", "2.5", "--edge-threshold", "0.02", "--min-neighbours", "3", "--occlusion-margin", "0.02",
+    "--keep-uncoloured", "--segment", "--cluster-tolerance", "0.02", "--min-object-points", "30", "--max-objects", "5",
+    "--top-k-per-object", "2", "--voxel", "0.004", "--max-voxels", "100", "--min-voxel-points", "2"]
+# what the five functions returned for CLI_FULL before they shared one table (printed by a run of that commit)
+CLI_FULL_DICTS = {
+    "select": {"top_k": 7, "translation_thresh": 0.02, "rotation_thresh_deg": 15.0, "source": "grasp_stage2"},
+    "segment": {"tolerance": 0.02, "min_points": 30, "max_objects": 5, "top_k_per_object": 2},
+    "transform": {"range": (0.5, 1.2), "threshold": 0.004},
+    "depth": {"edge_threshold": 0.02, "min_neighbours": 3, "occlusion_margin": 0.02, "depth_range": (0.2, 2.5),
+              "keep_uncoloured": True},
+    "fuse": {"voxel": 0.004, "max_voxels": 100, "min_count": 2}}
+
+
+def test_cli_dicts_of_an_empty_and_a_full_command_line():
+    from regnet_for_3d_grasping_amd import detect
+    parser = detect.build_parser()
+    empty, full = parser.parse_args(CLI_REQUIRED), parser.parse_args(CLI_FULL)
+    for name, want in CLI_FULL_DICTS.items():
+        from_args = getattr(detect, name + "_from_args")
+        assert from_args(empty) is None, name
+        got = from_args(full)
+        assert got == want and {key: type(value) for key, value in got.items()} == {key: type(value) for key, value in want.items()}, name
+    # the switches on their own
+    assert detect.transform_from_args(parser.parse_args(CLI_REQUIRED + ["--auto-table"])) == "auto"
+    assert detect.segment_from_args(parser.parse_args(CLI_REQUIRED + ["--segment"])) == {}
+    assert detect.depth_from_args(parser.parse_args(CLI_REQUIRED + ["--keep-uncoloured"])) == {"keep_uncoloured": True}
+
+
+def test_help_shows_the_dataclass_defaults():
+    """Every numeric default at the end of a flag's help is the default of the field the flag sets."""
+    from regnet_for_3d_grasping_amd import detect, table_plane
+    classes = {word: entry[0]() for word, entry in _params_classes().items()}
+    field_of = {"nms_translation": ("select", "translation_thresh"), "nms_rotation": ("select", "rotation_thresh_deg"),
+                "min_neighbours": ("depth", "min_neighbours"), "occlusion_margin": ("depth", "occlusion_margin"),
+                "cluster_tolerance": ("segment", "tolerance"), "min_object_points": ("segment", "min_points"),
+                "max_objects": ("segment", "max_objects"), "voxel": ("fuse", "voxel"), "max_voxels": ("fuse", "max_voxels"),
+                "min_voxel_points": ("fuse", "min_count")}
+    seen = set()
+    for action in detect.build_parser()._actions:
+        shown = re.search(r"\(([-+0-9.einf ]+)\)$", action.help or "")
+        if shown is None:
+            continue
+        seen.add(action.dest)
+        values = [float(v) for v in shown.group(1).split()]
+        if action.dest == "plane_threshold":
+            assert values == [table_plane.DEFAULT_THRESHOLD]
+        elif action.dest == "depth_range":
+            assert tuple(values) == classes["depth"].depth_range
+        else:
+            word, field = field_of[action.dest]
+            assert values == [getattr(classes[word], field)], action.dest
+    assert seen == set(field_of) | {"plane_threshold", "depth_range"}
+    by_dest = {action.dest: action.help for action in detect.build_parser()._actions}
+    assert by_dest["select_from"].endswith("(%s)" % classes["select"].source)

@@ -308,3 +308,72 @@ def test_two_view_scene_overlaps():
     print("K = %d, seen by both = %d, rows merged %d, dropped %d" % (K, both, out["num"][1], out["num"][2]))
     assert K == ref.TWO_VIEW_K and both > 50 and out["num"][3] == 0
 
+
+
+# ---- the per-frame .npz codec both formats share ---------------------------------------------------------------------------------
+def _tiny_frames():
+    """Two 4 x 3 pixel frames: one with every optional entry, one with none."""
+    from regnet_for_3d_grasping_amd import depth_frame
+    depth = np.arange(12, dtype=np.uint16).reshape(3, 4) * 100
+    full = depth_frame.DepthFrame(depth=depth, intrinsics=(4.0, 4.5, 2.0, 1.5), color=np.arange(2 * 5 * 3, dtype=np.uint8).reshape(2, 5, 3),
+                                  color_intrinsics=(5.0, 5.5, 2.5, 1.0), depth_to_color=np.eye(4) + np.arange(16).reshape(4, 4) / 64.0,
+                                  depth_scale=0.002)
+    bare = depth_frame.DepthFrame(depth=(depth[::-1] / 1000.0).astype(np.float32), intrinsics=(3.0, 3.5, 1.5, 1.0))
+    return full, bare
+
+
+def _same_frame(got, want):
+    assert got.depth.dtype == want.depth.dtype and np.array_equal(got.depth, want.depth)
+    assert got.intrinsics == want.intrinsics and got.color_intrinsics == want.color_intrinsics
+    assert got.depth_scale == want.depth_scale and got.mode() == want.mode()
+    for a, b in ((got.color, want.color), (got.depth_to_color, want.depth_to_color)):
+        assert (a is None) == (b is None) and (a is None or (a.dtype == b.dtype and np.array_equal(a, b)))
+
+
+def test_npz_round_trips_through_the_shared_codec(tmp_path):
+    from regnet_for_3d_grasping_amd import depth_frame, fusion
+    full, bare = _tiny_frames()
+    optional = {"color", "color_intrinsics", "depth_to_color"}
+    assert set(depth_frame.frame_items(full)) == {"depth", "intrinsics", "depth_scale"} | optional
+    assert set(depth_frame.frame_items(bare, "view3_")) == {"view3_depth", "view3_intrinsics", "view3_depth_scale"}
+    path = str(tmp_path / "frame.npz")
+    for frame in (full, bare):
+        depth_frame.save_npz(path, frame)
+        with np.load(path) as data:
+            assert set(data.files) == set(depth_frame.frame_items(frame))
+        _same_frame(depth_frame.load_npz(path), frame)
+    pose = np.eye(4)
+    pose[:3, 3] = (0.1, -0.2, 0.3)
+    for frames, poses in (((full, bare), [None, pose]), ((bare, full), [pose, None])):
+        mv = fusion.MultiView(list(frames), poses)
+        fusion.save_npz(path, mv)
+        with np.load(path) as data:
+            want = {"views", "view0_pose", "view1_pose"} | set(depth_frame.frame_items(frames[0], "view0_")) \
+                | set(depth_frame.frame_items(frames[1], "view1_"))
+            assert set(data.files) == want and int(data["views"]) == 2
+        back = fusion.load_npz(path)
+        for got, frame, p in zip(back.frames, frames, poses):
+            _same_frame(got, frame)
+        assert [p.tolist() for p in back.poses] == [(np.eye(4) if p is None else p).tolist() for p in poses]
+    # the errors of both formats, as they have always read
+    depth_frame.save_npz(path, full)
+    with np.load(path) as data:
+        one = {key: data[key] for key in data.files}
+    fusion.save_npz(path, fusion.MultiView([full, bare], [None, pose]))
+    with np.load(path) as data:
+        two = {key: data[key] for key in data.files}
+
+    def refused(load, items, message):
+        with open(path, "wb") as f:
+            np.savez(f, **items)
+        with pytest.raises(ValueError, match=message):
+            load(path)
+    refused(depth_frame.load_npz, dict(one, pose=np.eye(4), extra=np.zeros(1)), r"^depth frame .*frame\.npz: unknown entries extra, pose$")
+    for missing in ("depth", "intrinsics"):
+        refused(depth_frame.load_npz, {k: v for k, v in one.items() if k != missing}, r"^depth frame .*frame\.npz: no '%s' entry$" % missing)
+    refused(fusion.load_npz, dict(two, extra=np.zeros(1), view2_depth=np.zeros((2, 2))),
+            r"^multi-view frame .*frame\.npz: unknown entries extra, view2_depth$")
+    for missing in ("view0_depth", "view1_intrinsics", "view1_pose"):
+        refused(fusion.load_npz, {k: v for k, v in two.items() if k != missing}, r"^multi-view frame .*frame\.npz: no '%s' entry$" % missing)
+    refused(fusion.load_npz, one, r"^multi-view frame .*frame\.npz: no 'views' entry$")
+    refused(fusion.load_npz, dict(two, views=np.int64(9)), r"^multi-view frame .*frame\.npz: views must be 1\.\.8$")

@@ -138,3 +138,34 @@ def test_a_single_depth_frame_never_sees_fuse(parts):
         detect.GraspDetector(parts[0], parts[1], fuse="yes")
     with pytest.raises(ValueError):
         detect.GraspDetector(parts[0], parts[1], fuse={"voxel": 0.0})
+
+
+def test_every_optional_stage_at_once_and_the_state_they_hand_over(parts):
+    """``select``, ``segment`` with a per-object selection, the table estimated in the frame and a two-view ``MultiView``
+    together: the record's keys in their documented order, and what ``ingest`` found -- on the frame it returns, then on the
+    detector -- forgotten again by the next plain frame."""
+    from regnet_for_3d_grasping_amd import detect, np_random
+    detector = detect.GraspDetector(parts[0], parts[1], fuse=FUSE, transform={"range": (0.5, 1.2)}, select={"top_k": 5},
+                                    segment={"top_k_per_object": 2, "min_points": 20})
+    np.random.seed(SEED)
+    with np_random.deferred(), torch.no_grad():
+        frame = detector.ingest(parts[2])
+    assert detector.fused is None and detector.table is None          # ingest() hands over on the frame alone
+    assert frame.fused is not None and frame.table is not None
+    np.random.seed(SEED)
+    out = detector.detect(parts[2])
+    assert tuple(out) == detect.RESULT_KEYS + detect.SEGMENT_SELECT_KEYS + detect.SEGMENT_KEYS + detect.TABLE_KEYS + detect.FUSE_KEYS
+    # the merge and the estimate are deterministic: the detector's copies and the ones on ingest()'s frame are the same values
+    assert torch.equal(detector.fused.num, frame.fused.num) and detector.fused.num_views == frame.fused.num_views == 2
+    K = int(frame.fused.num[0])
+    assert torch.equal(detector.fused.xyz[:K], frame.fused.xyz[:K]) and torch.equal(detector.fused.views, frame.fused.views)
+    assert np.array_equal(detector.table[0], frame.table[0])
+    for got, want in zip(detector.table[1], frame.table[1]):          # normal, offset, inliers, rms, hypothesis
+        assert np.array_equal(got, want)
+    assert np.array_equal(out["table_transform"], detector.table[0]) and out["table_plane"][3] == detector.table[1].offset
+    assert np.array_equal(out["fuse_num"], detector.fused.num.cpu().numpy())
+    assert len(out["grasp_selected"]) == len(out["grasp_selected_object"]) and len(out["point_object"]) == len(out["points"])
+    np.random.seed(SEED)
+    after = detector.detect(parts[3].cloud())                        # a plain (xyz, rgb) frame: nothing was fused
+    assert detector.fused is None and detector.table is not None
+    assert tuple(after) == detect.RESULT_KEYS + detect.SEGMENT_SELECT_KEYS + detect.SEGMENT_KEYS + detect.TABLE_KEYS
