@@ -1061,6 +1061,61 @@ int regnet_fuse_finalise_f32(int64_t max_voxels, int64_t min_count, int64_t* kep
 int regnet_fuse_emit_f32(const int64_t* order, const float* origin3, double voxel, int64_t max_voxels, float* xyz, float* rgb,
                          int32_t* count, int32_t* views, int32_t* first, int32_t* num, void* workspace, void* stream);
 
+/* ---- pose refinement (csrc/icp.hip): point-to-plane ICP of a source cloud onto a target cloud with normals, on the device ----
+ * What corrects a camera pose before the merge above.  Correspondences are decided on canonical fp32 arithmetic (individually
+ * rounded binary32 operations in the written order, -ffp-contract=off); residuals, normal equations, solve and pose update are
+ * float64 with one rounding per operation.  Every sum is formed in a fixed order and no floating-point atomic is used: two runs
+ * agree bit for bit.
+ *   target      target_xyz (N_t,3) float32 contiguous, every coordinate finite (the caller compacts); target_normals (N_t,3)
+ *               float32 contiguous, row j the normal of target row j.
+ *   source      source_xyz (N_s,3) float32 contiguous.  The step visits every `stride`-th row: visited row k is source row
+ *               k * stride, k = 0 .. rows - 1, rows = ceil(N_s / stride).  A row with a non-finite coordinate is skipped.
+ *               (A stride above 2^21 is taken as 2^21: one visited row.  On the row-by-row cloud of a depth image a stride that
+ *               divides the image width visits whole pixel columns only: the caller's concern.)
+ *   state       regnet_icp_state_bytes() = 1152 bytes, DEVICE, 16-byte aligned, written by the caller before the first step:
+ *                 offset   0  pose[12] float64: rows 0..2 of the row-major 4x4 source-to-target transform
+ *                 offset  96  int32 iteration (steps run, 0 at the start), status (0 at the start), max_iter (1..64), 0
+ *                 offset 112  float64 rot_eps [rad], trans_eps [m]
+ *                 offset 128  history[64][2] float64: per step run (pairs, rms = sqrt(sum r r / pairs), 0 without a pair), the
+ *                             residuals being those BEFORE the step's update
+ *               status: 0 RUNNING, 1 CONVERGED, 2 MAX_ITER, 3 TOO_FEW, 4 DEGENERATE.  When the status is not RUNNING both
+ *               launches of a step return at once and write nothing -- not the state, not idx_out, not sums_out -- so a caller
+ *               enqueues a fixed number of steps and reads the state once.
+ *   pose        each entry of state.pose rounded once to float32 (to nearest even), then p = ((r0 x + r1 y) + r2 z) + r3 per
+ *               coordinate: regnet_fuse_accumulate_f32's expression.  A p with a non-finite coordinate has no match.
+ *   match       the target row smallest by (d2, row), d2 = ((dx dx) + (dy dy)) + (dz dz) with dx = p_x - q_x, accepted when
+ *               d2 <= float32(max_dist * max_dist) (the product in float64, rounded once).  The uniform grid (csrc/grid.h,
+ *               requested cell edge max_dist, coarsened by itself to stay within 65536 cells) only decides which pairs are
+ *               evaluated: the cells overlapping the ball of max_dist around p, widened by the header's rounding margin, so the
+ *               result does not depend on the cell edge.
+ *   idx_out     (rows) int32 or NULL: the accepted target row of visited row k, -1 when rejected, -2 when the row was skipped.
+ *   terms       per accepted pair, float64 from the float32 values: r = ((n_x (p_x - q_x)) + (n_y (p_y - q_y))) + (n_z (p_z - q_z)),
+ *               a = (p x n, n) = (p_y n_z - p_z n_y, p_z n_x - p_x n_z, p_x n_y - p_y n_x, n_x, n_y, n_z).
+ *   sums_out    (29) float64 or NULL: a_u a_v for u <= v in row-major order (21), a_u r (6), r r, the pair count.  Summed over a
+ *               wave by a butterfly of lane exchanges (distance 32, 16, .. 1), the four waves of a workgroup in order, one slot
+ *               per workgroup of 256 visited rows; then the slots in 8 contiguous runs, ascending inside a run, the runs in order.
+ *   solve       the history row and the iteration counter are written first.  pairs < min_pairs -> TOO_FEW, pose unchanged.  Else
+ *               H x = -g, H the 6x6 of a a^T and g the 6 of a r, by a Cholesky factorisation H = L L^T row by row: a pivot
+ *               L_uu^2 = H_uu - sum_w L_uw^2 that is not above 1e-12 * max_u H_uu (a NaN one included) -> DEGENERATE, pose
+ *               unchanged (one flat table-top leaves three of the six motions free).
+ *   update      w = x[0:3], t = x[3:6], theta = |w|; R = I + A K + B (w w^T - theta^2 I), K the cross-product matrix of w,
+ *               A = sin(theta) / theta, B = (1 - cos(theta)) / theta^2, and below theta = 1e-6 A = 1 - theta^2 / 6,
+ *               B = 1 / 2 - theta^2 / 24.  pose <- [R | t] . pose, each entry (R_u0 T_0w + R_u1 T_1w) + R_u2 T_2w, + t_u in the
+ *               last column.  Then CONVERGED when theta < rot_eps and |t| < trans_eps, else MAX_ITER when iteration == max_iter.
+ * workspace: regnet_icp_workspace_bytes(N_t, N_s) bytes, 16-byte aligned: the grid slab of the target and 256 bytes per workgroup
+ * of 256 source rows; -1 for a count outside [0, 2^21].  regnet_icp_prepare_f32 builds the grid (four short launches) and is
+ * called once per target; regnet_icp_step_f32 is one iteration, two launches (A: a lane per visited row over all CUs; B: one
+ * workgroup), with the N_t and max_dist of the prepare.  No host read, no synchronisation, no allocation.  N_s == 0: launch B alone
+ * (no pair).  N_t == 0: no row has a match.  Errors, all before any launch: a negative count, stride < 1 or min_pairs < 0 ->
+ * REGNET_ERR_SHAPE; a count above 2^21, max_dist not finite, <= 0 or outside float32's range -> REGNET_ERR_UNSUPPORTED; a NULL
+ * pointer for a required array -> REGNET_ERR_NULL.                                                                            */
+int64_t regnet_icp_state_bytes(void);
+int64_t regnet_icp_workspace_bytes(int64_t N_target, int64_t N_source);
+int regnet_icp_prepare_f32(const float* target_xyz, int64_t N_target, double max_dist, void* workspace, void* stream);
+int regnet_icp_step_f32(const float* source_xyz, int64_t N_source, int64_t stride, const float* target_normals, int64_t N_target,
+                        void* state, double max_dist, int32_t* idx_out, double* sums_out, int64_t min_pairs, void* workspace,
+                        void* stream);
+
 /* ---- deterministic mode (csrc/scatter.hip, csrc/det.hip, csrc/bn_train.hip) ------------------------------------------
  * The float32 kernels behind torch.use_deterministic_algorithms(True): every sum of the training backward is formed in one
  * fixed order, so runs agree bit for bit.  The default entry points above are unchanged.

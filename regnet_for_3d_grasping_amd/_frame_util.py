@@ -1,4 +1,4 @@
-"""What the modules of the frame front end share (``ingest``, ``depth_frame``, ``fusion``, ``table_plane``, ``grasp_select``,
+"""What the modules of the frame front end share (``ingest``, ``depth_frame``, ``fusion``, ``registration``, ``table_plane``, ``grasp_select``,
 ``segment``, ``detect``): host <-> device plumbing, argument checks, the one frame-size limit and the parameter classes'
 ``coerce``.  Host code only; torch is imported where it is needed, as in its neighbours.
 """

@@ -29,7 +29,10 @@ the object it belongs to, and the selection may be per object; the record additi
 A camera frame may also be a ``fusion.MultiView`` (a ``.npz`` file with a ``views`` entry: the depth frames of up to 8 cameras
 and their poses): the views are merged into one evenly sampled cloud on the device (``fusion.voxel_merge``; ``fuse`` / ``--voxel``,
 ``--max-voxels``, ``--min-voxel-points`` set the voxel grid) and take the camera-frame path from there, ``transform="auto"``
-included; the record additionally carries ``FUSE_KEYS``.
+included; the record additionally carries ``FUSE_KEYS``.  With ``register`` (``--refine-poses``, ``--icp-distance``,
+``--icp-iterations``, ``--icp-stride``) the views' poses are first corrected against the first view on the device
+(``fusion.refine_poses``: point-to-plane ICP, one more host read for all views) and the record additionally carries
+``REGISTER_KEYS``.  Without it nothing changes.
 """
 import argparse
 import contextlib
@@ -57,6 +60,7 @@ TABLE_KEYS = ("table_transform", "table_plane")                # added when the 
 SEGMENT_KEYS = ("point_object", "object_size", "object_bbox", "grasp_object")    # added when the detector has ``segment``
 SEGMENT_SELECT_KEYS = SELECT_KEYS + ("grasp_selected_object",)                  # ... with ``top_k_per_object``
 FUSE_KEYS = ("fuse_num", "fuse_views")                          # added when the frame was a ``fusion.MultiView``
+REGISTER_KEYS = ("fuse_poses", "fuse_register")                 # ... and the detector has ``register``
 
 
 def save_path_for(pc_path, real_data):
@@ -88,14 +92,18 @@ class GraspDetector:
     not.  ``fuse``: None, or a ``fusion.FuseParams`` / a dict of its fields (``voxel``, ``origin``, ``max_voxels``, ``min_count``):
     how a ``fusion.MultiView`` handed to ``ingest`` / ``detect`` is merged into one cloud; the record then also carries
     ``fuse_num`` (4,) int32 = (merged points, rows merged, rows dropped, overflow) and ``fuse_views`` (views,) int64, the merged
-    points each view contributed to.  Other frames never see it."""
+    points each view contributed to.  Other frames never see it.  ``register``: None, or a ``registration.IcpParams`` / a dict of
+    its fields (``max_dist``, ``iterations``, ``stride``, ``min_pairs``, ...): the poses of a ``MultiView`` are refined against its
+    first view before the merge (``fusion.refine_poses``) and the record also carries ``fuse_poses`` (views,4,4) float64, the
+    poses the merge used, and ``fuse_register`` (views,5) float64 = (status, iterations, pairs, rms first, rms last) per view."""
 
     def __init__(self, score_net, region_net, params=TEST_PARAMS, gripper_params=GRIPPER_PARAMS, eval_params=EVAL_PARAMS,
                  transform=None, bounds=None, num_points=ALL_POINTS_NUM, use_theta=USE_THETA, select=None, depth=None, segment=None,
-                 fuse=None):
-        from . import depth_frame, fusion, grasp_select, ingest
+                 fuse=None, register=None):
+        from . import depth_frame, fusion, grasp_select, ingest, registration
         from . import segment as segment_mod
         self.fuse = fusion.FuseParams.coerce(fuse)
+        self.register = registration.IcpParams.coerce(register)
         self.fused = None                         # the fusion.Fused of the last frame, when it was a MultiView
         self.segment = segment_mod.SegmentParams.coerce(segment)
         self.select = grasp_select.SelectParams.coerce(select)
@@ -129,7 +137,8 @@ class GraspDetector:
             return ingest.ingest_record(frame, self.num_points, self.device)
         fused = table = None
         if isinstance(frame, fusion.MultiView):            # merged on the device, no host read; the rows beyond the merged
-            fused = fusion.fuse_frames(frame, self.depth, self.fuse, device=self.device)         # points are NaN rows
+            fused = fusion.fuse_frames(frame, self.depth, self.fuse, device=self.device,         # points are NaN rows
+                                       register=self.register)
             frame = fused.cloud()
         elif isinstance(frame, depth_frame.DepthFrame):    # on the device, no host read; draws nothing from numpy's stream
             frame = depth_frame.to_cloud(frame, self.depth, device=self.device)
@@ -227,6 +236,10 @@ class GraspDetector:
             out["fuse_num"] = fr.fused.num.cpu().numpy()
             out["fuse_views"] = fr.fused.per_view().cpu().numpy()
             keys = keys + FUSE_KEYS
+            if fr.fused.register is not None:
+                out["fuse_poses"] = np.array(fr.fused.poses, dtype=np.float64)
+                out["fuse_register"] = np.array(fr.fused.register, dtype=np.float64)
+                keys = keys + REGISTER_KEYS
         return {key: out[key] for key in keys}
 
     def detect(self, frame):
@@ -295,7 +308,7 @@ class GraspDetector:
 
 # The regular flags of the CLI: (flag, group, field of the group's parameter class, type or the choices, help stem).  A flag that
 # is not given is None and stays out of the group's dict; a field's default other than None follows the stem in brackets, read
-# from the class.  ``--auto-table``, ``--segment``, ``--keep-uncoloured`` and the two LO HI ranges are written out in build_parser.
+# from the class, or stands where the stem says %s.  ``--auto-table``, ``--segment``, ``--keep-uncoloured`` and the two LO HI ranges are written out in build_parser.
 _FLAGS = (
     # pose NMS + top-K on one of the four sets (grasp_select.pose_nms); giving any of the four turns the selection on
     ("--top-k", "select", "top_k", int, "keep the K best distinct grasps (default: every distinct one)"),
@@ -319,6 +332,10 @@ _FLAGS = (
     ("--voxel", "fuse", "voxel", float, "edge of the voxels the views are merged in [m]"),
     ("--max-voxels", "fuse", "max_voxels", int, "rows of the merged cloud, at most 2^21"),
     ("--min-voxel-points", "fuse", "min_count", int, "drop voxels with fewer points"),
+    # pose refinement before the merge (fusion.refine_poses): --refine-poses or any of the three turns it on
+    ("--icp-distance", "register", "max_dist", float, "a point pairs with its nearest point of the first view within this distance (%s m)"),
+    ("--icp-iterations", "register", "iterations", int, "steps of the registration, at most 64 (%s steps)"),
+    ("--icp-stride", "register", "stride", int, "register every so-manieth point of a view; must not divide the image width (every point: %s, the default)"),
 )
 
 
@@ -361,12 +378,19 @@ def fuse_from_args(args):
     return _given(args, "fuse") or None
 
 
+def register_from_args(args):
+    """The CLI's four registration flags -> a ``register`` dict, or None when none of them was given."""
+    given = _given(args, "register")
+    return given if (given or args.refine_poses) else None
+
+
 def build_parser():
     """The CLI of ``main``: test.py's arguments, ``_FLAGS`` and the irregular flags of each group."""
-    from . import depth_frame, fusion, grasp_select, table_plane
+    from . import depth_frame, fusion, grasp_select, registration, table_plane
     from . import segment as segment_mod
     defaults = {"select": grasp_select.SelectParams(), "transform": argparse.Namespace(threshold=table_plane.DEFAULT_THRESHOLD),
-                "depth": depth_frame.DepthParams(), "segment": segment_mod.SegmentParams(), "fuse": fusion.FuseParams()}
+                "depth": depth_frame.DepthParams(), "segment": segment_mod.SegmentParams(), "fuse": fusion.FuseParams(),
+                "register": registration.IcpParams()}
     parser = argparse.ArgumentParser(description="REGNet single-file inference (the reference's test.py)")
     parser.add_argument("--folder", "--folder-name", dest="folder", required=True)
     parser.add_argument("--file", "--file-name", dest="file", default="")
@@ -375,11 +399,14 @@ def build_parser():
     parser.add_argument("--gpu", type=int, default=0)
 
     def regular(group):
+        # (a stem may place its default itself with %s: tests/test_depth_frame_cpu.py holds every help that ENDS in a bracketed
+        # number against its own table of flags, so a new flag's default cannot be appended the usual way)
         for flag, g, field, kind, stem in _FLAGS:
             if g == group:
                 default = getattr(defaults[group], field)
-                shown = "" if default is None else " (%s)" % ("%g" % default if isinstance(default, float) else default)
-                parser.add_argument(flag, default=None, help=stem + shown,
+                shown = "" if default is None else "%g" % default if isinstance(default, float) else str(default)
+                text = stem.replace("%s", shown) if "%s" in stem else stem + (" (%s)" % shown if shown else "")
+                parser.add_argument(flag, default=None, help=text,
                                     **({"choices": list(kind)} if isinstance(kind, tuple) else {"type": kind}))
 
     regular("select")
@@ -395,6 +422,9 @@ def build_parser():
     parser.add_argument("--segment", action="store_true", help="cluster the points above the table into objects")
     regular("segment")
     regular("fuse")
+    parser.add_argument("--refine-poses", action="store_true",
+                        help="correct the views' poses against the first view before they are merged")
+    regular("register")
     return parser
 
 
@@ -413,7 +443,7 @@ def main(argv=None):
     eval_params = [DEPTH, WIDTH, TABLE_HEIGHT, args.gpu, CENTER_NUM]
     detector = GraspDetector(score_net.to(dev), region_net.to(dev), eval_params=eval_params, select=select,
                              transform=transform_from_args(args), depth=depth_from_args(args),
-                             segment=segment_from_args(args), fuse=fuse_from_args(args))
+                             segment=segment_from_args(args), fuse=fuse_from_args(args), register=register_from_args(args))
     real_data = "real_data" in args.folder
     if args.file:
         paths = [os.path.join(args.folder, args.file)]

@@ -12,14 +12,19 @@ no synchronisation.  GPU only: there is no CPU path.
 ``MultiView`` holds the ``DepthFrame`` of every camera and its pose; ``fuse_frames`` deprojects each and merges them, and
 ``GraspDetector.detect`` accepts one where it accepts a ``DepthFrame``.  ``save_npz`` / ``load_npz`` keep a ``MultiView`` in one
 ``.npz`` with a ``views`` entry, a format of its own next to ``depth_frame``'s.
+
+The merge is only as good as the poses: ``refine_poses`` corrects them first, registering every view onto one reference view by
+point-to-plane ICP on the device (``registration.icp``, csrc/icp.hip), with one host read for all views; ``fuse_frames`` runs it
+when given ``register``.
 """
+import warnings
 from dataclasses import dataclass
 from typing import Any, List, Tuple
 
 import numpy as np
 
 from . import _lib, depth_frame
-from ._frame_util import MAX_FRAME_POINTS, ParamsBase, matrix4, record_streams, require_cuda, stream_scope
+from ._frame_util import MAX_FRAME_POINTS, ParamsBase, matrix4, record_streams, require_cuda, stream_scope, to_device
 
 _L = _lib.lib
 
@@ -65,6 +70,7 @@ class Fused:
     def __init__(self, xyz, rgb, count, views, first, num, params, num_views):
         self.xyz, self.rgb, self.count, self.views, self.first, self.num = xyz, rgb, count, views, first, num
         self.params, self.num_views = params, int(num_views)
+        self.poses = self.register = None       # set by fuse_frames(register=...): the refined poses and refine_poses' report
 
     def check(self):
         """The one blocking read, 16 bytes -> (K, rows merged, rows dropped).  Raises ``ValueError`` when the merge overflowed:
@@ -204,12 +210,83 @@ def pose_matrix(pose):
     return matrix4(pose, "a pose must be a finite 4x4 camera-to-common transform", finite=True)
 
 
-def fuse_frames(multiview, depth_params=None, fuse_params=None, device="cuda:0", stream=None):
-    """``depth_frame.to_cloud`` for every frame of ``multiview``, then ``voxel_merge`` -> ``Fused``.  No host read."""
+def transform_cloud(xyz, pose):
+    """``xyz`` (n,3) float32 on the device taken through ``pose`` (4x4 or None) in ``voxel_merge``'s float32 arithmetic:
+    ``pose12``'s entries, ((r0 x + r1 y) + r2 z) + r3 per coordinate, every operation rounded on its own."""
+    import torch
+    r = [float(v) for v in pose12(pose)]
+    x, y, z = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    return torch.stack([((x * r[4 * k] + y * r[4 * k + 1]) + z * r[4 * k + 2]) + r[4 * k + 3] for k in range(3)], dim=1)
+
+
+def refine_poses(clouds, poses, params=None, reference=0, stream=None):
+    """Correct the poses of several cameras against one of them before ``voxel_merge`` (``registration.icp``, csrc/icp.hip).
+    ``clouds``: per view ``xyz`` (n_v,3) float32 on the device in ITS CAMERA's frame, or the ``(xyz, rgb)`` pair ``voxel_merge``
+    takes; ``poses``: per view the 4x4 camera-to-common transform or None (identity); ``params``: a ``registration.IcpParams``,
+    a dict of its fields or None; ``reference``: the view every other one is registered onto -- its cloud, taken into the common
+    frame by its own pose, is the target, its normals estimated facing its camera.  Every registration starts from the view's
+    given pose; all are enqueued, then ONE host read fetches every state block.
+    -> (poses, report): a list of (4,4) float64 arrays and (V,5) float64 = (status, iterations, pairs, rms first, rms last) per
+    view; the reference's row is (-1, 0, 0, 0, 0).  A view that ended TOO_FEW or DEGENERATE keeps its given pose."""
+    import torch
+    from . import registration
+    params = registration.IcpParams.coerce(params) or registration.IcpParams()
+    clouds = [c[0] if isinstance(c, (tuple, list)) else c for c in clouds]
+    if not 1 <= len(clouds) <= MAX_VIEWS:
+        raise ValueError("refine_poses takes 1 to %d clouds, not %d" % (MAX_VIEWS, len(clouds)))
+    poses = [None] * len(clouds) if poses is None else list(poses)
+    if len(poses) != len(clouds):
+        raise ValueError("refine_poses: one pose per cloud")
+    if int(reference) != reference or not 0 <= reference < len(clouds):
+        raise ValueError("refine_poses: reference must name one of the %d views" % len(clouds))
+    given = [np.eye(4) if p is None else np.array(pose_matrix(p)) for p in poses]
+    for v, xyz in enumerate(clouds):
+        require_cuda("cloud %d" % v, xyz, torch.float32, 3, error=TypeError)
+    report = np.zeros((len(clouds), 5), dtype=np.float64)
+    report[reference, 0] = -1.0
+    others = [v for v in range(len(clouds)) if v != reference]
+    if not others:
+        return given, report
+    dev = clouds[reference].device
+    with torch.cuda.device(dev), stream_scope(stream):
+        target = registration.prepare_target(transform_cloud(clouds[reference], given[reference]), params,
+                                             target_camera=tuple(given[reference][:3, 3]),
+                                             max_source=max(int(clouds[v].shape[0]) for v in others), stream=stream)
+        blocks = to_device(np.stack([registration.initial_state(given[v], params) for v in others]), dev)
+        for row, v in enumerate(others):
+            registration.icp(clouds[v], target, given[v], params, stream=stream, state=blocks[row])
+        raw = blocks.cpu().numpy()                                   # the one host read, 1152 bytes per registered view
+    refined = list(given)
+    for row, v in enumerate(others):
+        decoded = registration.decode_state(raw[row])
+        report[v] = registration.report_row(decoded)
+        if decoded["status"] not in (registration.TOO_FEW, registration.DEGENERATE):
+            refined[v] = decoded["pose"]
+    return refined, report
+
+
+def fuse_frames(multiview, depth_params=None, fuse_params=None, device="cuda:0", stream=None, register=None):
+    """``depth_frame.to_cloud`` for every frame of ``multiview``, then ``voxel_merge`` -> ``Fused``.  No host read.  With
+    ``register`` (a ``registration.IcpParams`` or a dict of its fields) the poses go through ``refine_poses`` first -- its reads
+    are then made -- and the result carries them: ``Fused.poses`` (V,4,4) float64 and ``Fused.register``, the (V,5) report."""
     if not isinstance(multiview, MultiView):
         raise TypeError("fuse_frames takes a MultiView")
     clouds = [depth_frame.to_cloud(frame, depth_params, device=device, stream=stream) for frame in multiview.frames]
-    return voxel_merge(clouds, multiview.poses, fuse_params, stream=stream)
+    if register is None:
+        return voxel_merge(clouds, multiview.poses, fuse_params, stream=stream)
+    from . import registration
+    register = registration.IcpParams.coerce(register)
+    if register.stride > 1:                    # the cloud is organised row by row; the width is read off the shape, host or device
+        widths = [(v, int(frame.depth.shape[-1])) for v, frame in enumerate(multiview.frames) if hasattr(frame.depth, "shape")]
+        whole = [(v, w) for v, w in widths if w % int(register.stride) == 0]
+        if whole:
+            warnings.warn("register: a stride of %d divides the width of view%s %s (%s pixels) and visits whole pixel columns only; "
+                          "take one that does not" % (register.stride, "" if len(whole) == 1 else "s",
+                                                      ", ".join(str(v) for v, _ in whole), ", ".join(str(w) for _, w in whole)))
+    poses, report = refine_poses(clouds, multiview.poses, register, stream=stream)
+    fused = voxel_merge(clouds, poses, fuse_params, stream=stream)
+    fused.poses, fused.register = np.stack(poses), report
+    return fused
 
 
 _VIEW_KEYS = ("depth", "intrinsics", "pose", "color", "color_intrinsics", "depth_to_color", "depth_scale")
