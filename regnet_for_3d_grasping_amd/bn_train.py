@@ -3,8 +3,12 @@
 
 What it replaces, at the reference's operator granularity: ``nn.BatchNorm1d/2d`` followed by ``nn.ReLU(inplace=True)``
 inside every Conv1d / Conv2d block (multi_model/utils/pn2_utils/nn/modules/conv.py:30-36, :70-76) and the
-``torch.max(new_feature, 3)`` that ends a set-abstraction block (modules.py:245).  Same values up to fp32 rounding
-(statistics are accumulated in fp64); running statistics and ``num_batches_tracked`` are updated exactly like torch.
+``torch.max(new_feature, 3)`` that ends a set-abstraction block (modules.py:245).  Same values up to fp32 rounding: the
+batch statistics are the fp64 sum and sum of squares of the elements, each widened before it is added or squared, so the
+variance ``q / n - mean^2`` holds at any |mean| / std an fp32 tensor can carry and a constant channel gives ``beta`` exactly
+(tests/test_gpu_bn_train_edges.py); running statistics and ``num_batches_tracked`` are updated exactly like torch.  A NaN or
+an infinity in a channel turns that channel's output and running statistics into NaN, as torch's modules do -- the ReLU and the
+pooled maximum propagate NaN.  One value per channel (B L = 1) is rejected, as by torch.
 GPU only -- there is no CPU path; callers keep torch's modules for anything ``supported`` rejects.
 
 Deterministic mode (determinism.py): the ``_det`` entry points, whose per-workgroup partial sums are added in a fixed order
@@ -26,6 +30,8 @@ def supported(bn, x, pool_group=0):
     if not (bn.affine and bn.track_running_stats and bn.momentum is not None and bn.weight.dtype == torch.float32):
         return False
     if x.numel() == 0 or x.shape[0] > 65535 or x.shape[1] > 65535:
+        return False
+    if x.numel() // x.shape[1] < 2:      # one value per channel: torch's module raises, and so does the caller's fall-back to it
         return False
     if pool_group:
         return x.dim() == 4 and x.shape[3] == pool_group and 4 <= pool_group <= 256 and pool_group & (pool_group - 1) == 0

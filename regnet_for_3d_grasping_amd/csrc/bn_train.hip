@@ -12,8 +12,11 @@
 // The ReLU mask is recomputed from x with the same expression as the forward, so y is not needed by the backward.
 //
 // Layout: x (B, C, L) contiguous, channel statistics over (B, L); L = M * K for grouped tensors with the K neighbours of
-// a centroid innermost (what conv2d over (B,C,M,K) produces).  Per-channel sums are accumulated in fp64 (thread partials
-// of <= 32 fp32 values, then fp64 wave/workgroup reduction and one fp64 atomic per workgroup).
+// a centroid innermost (what conv2d over (B,C,M,K) produces).  The forward's per-channel sum and sum of squares are fp64
+// from the first addition: each element is widened, then added and squared (bn_stats_kernel), then an fp64 wave/workgroup
+// reduction and one fp64 atomic per workgroup.  The backward's two sums are fp32 per thread (<= 32 elements), fp64 from there.
+// A NaN or an infinity in a channel makes that channel's statistics, output and running statistics NaN, as in torch: the
+// ReLU is max_nan (common.h), not fmaxf.
 //
 // Deterministic mode (the _det entry points, torch.use_deterministic_algorithms): no atomics -- every workgroup writes its
 // (sum, sum of squares) partial to a slot of its own, and bn_partials_reduce_kernel adds a channel's slots in one fixed
@@ -80,31 +83,33 @@ __global__ __launch_bounds__(BN_T) void bn_stats_kernel(const float* __restrict_
   const int c = blockIdx.y;
   const float* row = x + ((int64_t)blockIdx.z * C + c) * L;
   const int64_t beg = (int64_t)blockIdx.x * BN_STATS_CHUNK, end = min(L, beg + BN_STATS_CHUNK);
-  double s = 0.0, q = 0.0;          // fp32 over 8 float4 (32 values) at a time, fp64 across them
+  // Every element is widened BEFORE it is added and squared: the variance is q / n - mean^2, so a relative error e of either
+  // sum comes back multiplied by (mean / std)^2 -- fp32 partials (e ~ 1e-7) cost 5e-3 of the variance at |mean| / std = 1000
+  // and moved a constant channel's mean off the constant.  A product of two fp32 values is exact in fp64.  Two independent
+  // accumulator pairs per thread; the pass stays HBM-bound (3 fp64 operations per 4 bytes read).
+  double s = 0.0, q = 0.0;
   if ((L & 3) == 0) {
+    double s1 = 0.0, q1 = 0.0;
     for (int64_t i0 = beg + threadIdx.x * 4; i0 < end; i0 += BN_T * 4 * 8) {
-      float s32 = 0.f, q32 = 0.f;
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         const int64_t i = i0 + (int64_t)u * BN_T * 4;
         if (i < end) {
           const float4 v = *reinterpret_cast<const float4*>(row + i);
-          s32 += (v.x + v.y) + (v.z + v.w);
-          q32 += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+          const double x0 = v.x, x1 = v.y, x2 = v.z, x3 = v.w;
+          s += x0; q = fma(x0, x0, q);
+          s1 += x1; q1 = fma(x1, x1, q1);
+          s += x2; q = fma(x2, x2, q);
+          s1 += x3; q1 = fma(x3, x3, q1);
         }
       }
-      s += (double)s32;
-      q += (double)q32;
     }
+    s += s1; q += q1;
   } else {
-    float s32 = 0.f, q32 = 0.f;
-    int n = 0;
     for (int64_t i = beg + threadIdx.x; i < end; i += BN_T) {
-      const float v = row[i];
-      s32 += v; q32 += v * v;
-      if (++n == 32) { s += (double)s32; q += (double)q32; s32 = q32 = 0.f; n = 0; }
+      const double v = row[i];
+      s += v; q = fma(v, v, q);
     }
-    s += (double)s32; q += (double)q32;
   }
   block_accumulate(s, q, sums + 2 * c, part ? part + (int64_t)c * gridDim.x * gridDim.z * 2 : nullptr);
 }
@@ -149,20 +154,27 @@ __global__ __launch_bounds__(BN_T) void bn_apply_kernel(const float* __restrict_
     for (int64_t i = beg + threadIdx.x * 4; i < end; i += BN_T * 4) {
       const float4 v = *reinterpret_cast<const float4*>(x + off + i);
       float4 o;
-      o.x = fmaxf(bn_value(v.x, mean, invstd, g, bt), lo);
-      o.y = fmaxf(bn_value(v.y, mean, invstd, g, bt), lo);
-      o.z = fmaxf(bn_value(v.z, mean, invstd, g, bt), lo);
-      o.w = fmaxf(bn_value(v.w, mean, invstd, g, bt), lo);
+      o.x = max_nan(bn_value(v.x, mean, invstd, g, bt), lo);
+      o.y = max_nan(bn_value(v.y, mean, invstd, g, bt), lo);
+      o.z = max_nan(bn_value(v.z, mean, invstd, g, bt), lo);
+      o.w = max_nan(bn_value(v.w, mean, invstd, g, bt), lo);
       *reinterpret_cast<float4*>(y + off + i) = o;
     }
   } else {
-    for (int64_t i = beg + threadIdx.x; i < end; i += BN_T) y[off + i] = fmaxf(bn_value(x[off + i], mean, invstd, g, bt), lo);
+    for (int64_t i = beg + threadIdx.x; i < end; i += BN_T) y[off + i] = max_nan(bn_value(x[off + i], mean, invstd, g, bt), lo);
   }
 }
 
 // BN + ReLU + max over each run of `group` consecutive elements (group = 4 * lanes, lanes a power of two <= 64): a lane
 // holds 4 elements, `lanes` adjacent lanes one group.  Writes the maxima and the position (0..group-1, smallest on
-// ties) of the element that produced them.
+// ties) of the element that produced them.  A NaN member is the group's maximum, as for torch.max (the first of several).
+//
+// does the candidate (t, position ta) replace (best, arg)?
+__device__ __forceinline__ bool pool_takes(float t, int ta, float best, int arg) {
+  const bool tn = t != t, bn = best != best;
+  return tn == bn ? (t > best || ((t == best || tn) && ta < arg)) : tn;
+}
+
 __global__ __launch_bounds__(BN_T) void bn_pool_kernel(const float* __restrict__ x, int C, int64_t L, int group,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
                                                        const float* __restrict__ save_mean,
@@ -180,19 +192,19 @@ __global__ __launch_bounds__(BN_T) void bn_pool_kernel(const float* __restrict__
     float best = bn_value(v.x, mean, invstd, g, bt);
     int arg = k0;
     float t = bn_value(v.y, mean, invstd, g, bt);
-    if (t > best) { best = t; arg = k0 + 1; }
+    if (pool_takes(t, k0 + 1, best, arg)) { best = t; arg = k0 + 1; }
     t = bn_value(v.z, mean, invstd, g, bt);
-    if (t > best) { best = t; arg = k0 + 2; }
+    if (pool_takes(t, k0 + 2, best, arg)) { best = t; arg = k0 + 2; }
     t = bn_value(v.w, mean, invstd, g, bt);
-    if (t > best) { best = t; arg = k0 + 3; }
+    if (pool_takes(t, k0 + 3, best, arg)) { best = t; arg = k0 + 3; }
     for (int o = 1; o < lanes; o <<= 1) {
       const float ob = __shfl_xor(best, o);
       const int oa = __shfl_xor(arg, o);
-      if (ob > best || (ob == best && oa < arg)) { best = ob; arg = oa; }
+      if (pool_takes(ob, oa, best, arg)) { best = ob; arg = oa; }
     }
     if (k0 == 0) {
       const int64_t m = i / group;
-      y[row * M + m] = relu ? fmaxf(best, 0.f) : best;
+      y[row * M + m] = relu ? max_nan(best, 0.f) : best;
       index[row * M + m] = arg;
     }
   }

@@ -30,6 +30,10 @@ __device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, fl
   return s + zz;
 }
 
+// The larger of a and b, NaN when either is one (IEEE 754-2019 maximum; fmaxf returns the OTHER operand, so a ReLU written
+// with it turns a NaN activation into 0), +0 for (-0, +0); any other pair gives fmaxf's bits.  One v_maximum3_f32 on gfx950.
+__device__ __forceinline__ float max_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 
 // number of set bits of `mask` below this lane

@@ -119,7 +119,7 @@ __global__ __launch_bounds__(HT_THREADS) void ht_fwd_kernel(const HtFwd p) {
     if (n >= p.N) continue;
     const float xh = (zbuf[idx] - s_mean[j]) * s_inv[j];
     float y = p.gamma[n] * xh + p.beta[n];
-    if (p.relu) y = fmaxf(y, 0.f);
+    if (p.relu) y = max_nan(y, 0.f);
     p.XH[(long long)r * p.N + n] = xh;
     p.Y[(long long)r * p.N + n] = y;
   }

@@ -186,7 +186,7 @@ __global__ __launch_bounds__(TG_THREADS, 4) void tgemm_kernel(const TgArgs p) {
           b[kk][ni][0] = v.x; b[kk][ni][1] = v.y; b[kk][ni][2] = v.z; b[kk][ni][3] = v.w;                          \
           if (B_AFFINE) {                                                                                          \
             _Pragma("unroll") for (int t = 0; t < 4; ++t)                                                          \
-              b[kk][ni][t] = fmaxf(fmaf(b[kk][ni][t], bsc[ni], bsh[ni]), blo);                                     \
+              b[kk][ni][t] = max_nan(fmaf(b[kk][ni][t], bsc[ni], bsh[ni]), blo);                                   \
           }                                                                                                        \
         }                                                                                                          \
       }                                                                                                            \
@@ -451,10 +451,10 @@ __global__ __launch_bounds__(TG_THREADS, 4) void tgemm_stream_kernel(const TgArg
             const float4 c23 = *reinterpret_cast<const float4*>(&btab[2 * (TG_BK * kt + 8 * kk + 4 * fhb) + 4]);
 #pragma unroll
             for (int ni = 0; ni < TNI; ++ni) {
-              b[kk][ni][0] = fmaxf(fmaf(b[kk][ni][0], c01.x, c01.y), blo);
-              b[kk][ni][1] = fmaxf(fmaf(b[kk][ni][1], c01.z, c01.w), blo);
-              b[kk][ni][2] = fmaxf(fmaf(b[kk][ni][2], c23.x, c23.y), blo);
-              b[kk][ni][3] = fmaxf(fmaf(b[kk][ni][3], c23.z, c23.w), blo);
+              b[kk][ni][0] = max_nan(fmaf(b[kk][ni][0], c01.x, c01.y), blo);
+              b[kk][ni][1] = max_nan(fmaf(b[kk][ni][1], c01.z, c01.w), blo);
+              b[kk][ni][2] = max_nan(fmaf(b[kk][ni][2], c23.x, c23.y), blo);
+              b[kk][ni][3] = max_nan(fmaf(b[kk][ni][3], c23.z, c23.w), blo);
             }
           }
         }

@@ -133,7 +133,7 @@ __global__ __launch_bounds__(TS_THREADS, 2) void tsplit_kernel(const TsArgs p) {
         float x = b_cur[ni][i];
         if (AFFINE) {
           const int k = 16 * kc + 8 * h + i;
-          x = fmaxf(btab[k] * x + btab[TS_AFF_MAXK + k], blo);
+          x = max_nan(btab[k] * x + btab[TS_AFF_MAXK + k], blo);
         }
         if (!col_ok[ni]) x = 0.f;
         const __bf16 u = (__bf16)x;
