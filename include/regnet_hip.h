@@ -1116,6 +1116,42 @@ int regnet_icp_step_f32(const float* source_xyz, int64_t N_source, int64_t strid
                         void* state, double max_dist, int32_t* idx_out, double* sums_out, int64_t min_pairs, void* workspace,
                         void* stream);
 
+/* ---- approach analysis (csrc/approach.hip): clearance on the way in, closing extent and contact check per grasp, on the device ----
+ * What turns a collision-free grasp into a motion.  regnet_grasp_collision_counts_f32 above tests the hand at the final pose
+ * only; this scan also sweeps the hand back along -approach, measures the object between the fingers and judges the two contact
+ * bands on the cloud's normals.  points (N,3) float32, element strides (pn, pc) for (point, coordinate); normals (N,3) float32,
+ * element strides (nn, nc), row j the normal of point j, or NULL; T (B,4,4) row-major global->local, contiguous;
+ * x_hi_per_grasp (B) overrides x_hi when not NULL.  One workgroup per grasp, two passes over the cloud.  Canonical fp32
+ * arithmetic: individually rounded binary32 operations in the written order (-ffp-contract=off), the local point being
+ *   x = ((t00 px + t01 py) + t02 pz) + t03,  y and z likewise from rows 1 and 2 of T[b]
+ * (regnet_grasp_collision_counts_f32's expression).  Every comparison is strict, as in the reference's box tests; a point with a
+ * NaN coordinate is in nothing.  With xh the grasp's x_hi, ht = half_thickness, hw = half_width, hs = half_space, S = standoff:
+ *   section   z < ht && z > -ht && y < hw && y > -hw
+ *   inner     section && y < hs && y > -hs
+ *   region    inner && x > x_lo && x < xh: the reference's closing region, counts[:,3] of regnet_grasp_collision_counts_f32
+ *   pass 1    n_region; y_min, y_max, x_min over the region; n_hand = behind the hand + inside a finger exactly as
+ *             regnet_grasp_collision_counts_f32 counts them (its columns 1 + 2: a hand that collides at the final pose shows).
+ *             The sweep: a point is a BLOCKER when section && x < front && x > x_lo - S, front = back_x for inner points and xh
+ *             for the rest of the section (the finger lanes, |y| == hs included); x_lo - S is one float32 subtraction.  Its
+ *             retreat is s = fmaxf(x_lo - x, 0.0f).  n_block = the number of blockers; clearance = fminf(S, min s) over them, S
+ *             without one: the longest straight retreat along -approach from the final pose that touches nothing, capped at S.
+ *   pass 2    skipped when normals == NULL (its four counts are then 0).  band = min((y_max - y_min) / 3.0f, contact_depth);
+ *             left band = the region points with y > y_max - band, right band = those with y < y_min + band
+ *             (regnet_grasp_antipodal_stats_f32's rule).  Per band, n = its size and ok = the number of its points with
+ *             fabsf((t10 nx + t11 ny) + t12 nz) >= cos_friction; a NaN normal fails.
+ *   counts    (B,8) int32: { n_region, n_block, n_hand, n_left, ok_left, n_right, ok_right, 0 }.
+ *   values    (B,4) float32: { y_min, y_max, clearance, x_min }, each + 0.0f before the store (-0.0 never leaves the kernel);
+ *             with n_region == 0: +inf, -inf, clearance, +inf.
+ * Only integer sums and float min / max are reduced: no floating-point sum and no atomic, so the result does not depend on the
+ * order of the reduction and two runs agree bit for bit.  One launch; no host read, no synchronisation, no allocation: capturable.
+ * B == 0: success without a launch.  N == 0: launches and writes the empty results.  Errors, all before any launch: a negative
+ * count -> REGNET_ERR_SHAPE; a count >= 2^31, or a standoff that is negative or not finite -> REGNET_ERR_UNSUPPORTED; a NULL T,
+ * counts or values, or NULL points with N > 0 -> REGNET_ERR_NULL.                                                             */
+int regnet_grasp_approach_f32(const float* points, int64_t pn, int64_t pc, const float* normals, int64_t nn, int64_t nc,
+                              int64_t N, const float* T, int64_t B, float x_lo, float x_hi, const float* x_hi_per_grasp,
+                              float half_thickness, float half_width, float half_space, float back_x, float standoff,
+                              float contact_depth, float cos_friction, int32_t* counts, float* values, void* stream);
+
 /* ---- deterministic mode (csrc/scatter.hip, csrc/det.hip, csrc/bn_train.hip) ------------------------------------------
  * The float32 kernels behind torch.use_deterministic_algorithms(True): every sum of the training backward is formed in one
  * fixed order, so runs agree bit for bit.  The default entry points above are unchanged.

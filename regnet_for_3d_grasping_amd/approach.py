@@ -1,0 +1,167 @@
+"""Approach analysis on the device (csrc/approach.hip): what a robot needs in order to execute a collision-free grasp.
+
+The collision filter (``eval_collision.no_collision_mask``) tests the hand at the final pose only and every grasp is reported at
+the reference's fixed 8 cm opening.  ``analyse`` scans the cloud once more in every grasp's local frame and gives, per grasp,
+
+* ``clearance``: the longest straight retreat along ``-approach`` from the final pose, capped at ``standoff``, on which the hand
+  (palm and fingers, swept back) touches no point of the cloud -- a grasp behind which the neighbouring object stands has less
+  than the standoff;
+* ``width`` / ``offset`` / ``opening``: the extent of the object between the fingers along the closing axis, how far its middle
+  sits off the gripper's centre line, and the opening to command (the extent plus a pad on either side, at most the gripper's);
+* ``contact``: with ``friction_deg``, the share of the points in either contact band whose normal lies within the friction
+  cone of the closing axis, left share times right share -- the antipodal test of the validation score
+  (``eval_collision.antipodal_scores``) as counts on the observed cloud, without ground-truth normals and without a
+  floating-point sum;
+* ``pregrasp``: the point the gripper's centre starts its straight approach from, ``centre - approach * clearance``.
+
+The arithmetic is pinned (include/regnet_hip.h, DESIGN.md par. 5): float32, every operation rounded on its own, integer counts
+and min / max only, so ``tests/approach_reference.py`` restates it in numpy and the two agree exactly.  Nothing here reads from the
+device or waits for it: ``analyse`` can be captured into a graph.  GPU only: there is no CPU path.
+"""
+import math
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib, eval_collision, grasp_select
+from ._frame_util import ParamsBase, require_cuda, to_device
+
+
+@dataclass
+class ApproachParams(ParamsBase):
+    """What ``GraspDetector(approach=...)`` takes (a dict with these keys works too).  ``source``: the grasp set that is analysed
+    (None: the ``select`` source, else ``"grasp_stage3"``); ``standoff``: how far back the approach is swept [m];
+    ``contact_depth``: the depth of a contact band [m]; ``friction_deg``: the half angle of the friction cone -- None: no normals
+    are estimated, the contact check does not run and ``contact`` is 0; ``normal_radius`` / ``normal_max_nn``: the neighbourhood
+    ``eval_collision.estimate_normals`` fits a normal to; ``pad``: added to the measured width on either side for the opening
+    [m]; ``min_clearance`` / ``min_contact``: None, or the least clearance [m] / contact share a grasp must have to be selected.
+
+    The defaults are a choice made from the reference's gripper constants (6 cm palm-to-tip, 8 cm opening, the validation score's
+    5 mm band and 1 cm / 30-neighbour normals).  Nobody has measured them on a robot."""
+    WORD = "approach"
+    source: Optional[str] = None
+    standoff: float = 0.10
+    contact_depth: float = eval_collision.NEIGHBOR_DEPTH
+    friction_deg: Optional[float] = None
+    normal_radius: float = eval_collision.NORMAL_RADIUS
+    normal_max_nn: int = eval_collision.NORMAL_MAX_NN
+    pad: float = 0.005
+    min_clearance: Optional[float] = None
+    min_contact: Optional[float] = None
+
+    def __post_init__(self):
+        if self.source is not None and self.source not in grasp_select.SOURCES:
+            raise ValueError("approach: source must be None or one of %s, not %r" % (", ".join(grasp_select.SOURCES), self.source))
+        if not (float(self.standoff) >= 0.0 and np.isfinite(self.standoff)):
+            raise ValueError("approach: standoff must be non-negative and finite")
+        if not (float(self.contact_depth) >= 0.0 and float(self.pad) >= 0.0):
+            raise ValueError("approach: contact_depth and pad must be non-negative")
+        if self.friction_deg is not None and not 0.0 <= float(self.friction_deg) <= 90.0:
+            raise ValueError("approach: friction_deg must be None or within [0, 90]")
+        if not (float(self.normal_radius) > 0.0 and int(self.normal_max_nn) >= 3):
+            raise ValueError("approach: normal_radius must be positive and normal_max_nn at least 3")
+
+    def filters(self):
+        """Whether ``passes()`` can drop a grasp at all."""
+        return self.min_clearance is not None or self.min_contact is not None
+
+
+def cos_friction(friction_deg):
+    """cos(friction angle) evaluated in float64 and rounded once to float32, as a Python float; None (no contact check) -> 0."""
+    return 0.0 if friction_deg is None else float(np.float32(math.cos(math.radians(float(friction_deg)))))
+
+
+class Approach:
+    """``analyse``'s result, all on the device.  ``counts`` (B,8) int32 = (n_region, n_block, n_hand, n_left, ok_left, n_right,
+    ok_right, 0) and ``values`` (B,4) float32 = (y_min, y_max, clearance, x_min) are the kernel's; ``frame`` (B,3,3) / ``center``
+    (B,3) are ``eval_collision.grasp_frames``'.  The derived tensors are float32, one operation per step."""
+
+    def __init__(self, counts, values, frame, center, params, half_space):
+        self.counts, self.values, self.frame, self.center, self.params = counts, values, frame, center, params
+        self.half_space = float(np.float32(half_space))
+
+    @property
+    def clearance(self):
+        return self.values[:, 2]
+
+    @property
+    def empty(self):
+        """(B) bool: nothing lies between the fingers."""
+        return self.counts[:, 0] == 0
+
+    @property
+    def width(self):
+        """y_max - y_min, 0 where the region is empty."""
+        w = self.values[:, 1] - self.values[:, 0]
+        return torch.where(self.empty, torch.zeros_like(w), w)
+
+    @property
+    def offset(self):
+        """(y_max + y_min) * 0.5: the object's middle off the gripper's centre line, along axis_y; 0 where the region is empty."""
+        o = (self.values[:, 1] + self.values[:, 0]) * 0.5
+        return torch.where(self.empty, torch.zeros_like(o), o)
+
+    @property
+    def opening(self):
+        """min(width + (pad + pad), hs + hs), the float32 constants formed first."""
+        pad = np.float32(self.params.pad)
+        hs = np.float32(self.half_space)
+        return torch.clamp(self.width + float(np.float32(pad + pad)), max=float(np.float32(hs + hs)))
+
+    @property
+    def contact(self):
+        """(ok_left / n_left) * (ok_right / n_right), 0 where either band is empty or the contact check did not run."""
+        c = self.counts.to(torch.float32)
+        share = (c[:, 4] / c[:, 3]) * (c[:, 6] / c[:, 5])
+        return torch.where((self.counts[:, 3] == 0) | (self.counts[:, 5] == 0), torch.zeros_like(share), share)
+
+    @property
+    def pregrasp(self):
+        """(B,3): centre - approach * clearance."""
+        return self.center - self.frame[:, :, 0] * self.clearance.unsqueeze(1)
+
+    def passes(self):
+        """(B) bool: clearance >= min_clearance and contact >= min_contact, compared as float32; a bound that is None is not
+        applied."""
+        p = self.params
+        ok = torch.ones((self.counts.shape[0],), dtype=torch.bool, device=self.counts.device)
+        if p.min_clearance is not None:
+            ok = ok & (self.clearance >= float(np.float32(p.min_clearance)))
+        if p.min_contact is not None:
+            ok = ok & (self.contact >= float(np.float32(p.min_contact)))
+        return ok
+
+
+def analyse(points, grasp, depth, width, params=None, normals=None):
+    """``points`` (N,3) float32 on the GPU, any strides; ``grasp`` (B, >=8) float32 on the GPU; ``depth``: a float or one depth
+    per grasp; ``width``: the gripper's opening (``eval_collision``'s box); ``params``: ``ApproachParams`` / a dict / None (the
+    defaults); ``normals`` (N,3) float32 on the GPU, any strides, or None -- with ``friction_deg`` set they are then estimated
+    (``eval_collision.estimate_normals``; the sign of a normal does not matter to |n_y|), without it the contact check does not
+    run.  -> ``Approach``.  One launch on the current stream, no host read."""
+    params = ApproachParams.coerce(params) or ApproachParams()
+    require_cuda("points", points, torch.float32, 3, error=RuntimeError)
+    require_cuda("grasp", grasp, torch.float32, 8, at_least=True, error=RuntimeError)
+    dev = points.device
+    N, B = int(points.shape[0]), int(grasp.shape[0])
+    frame, center = eval_collision.grasp_frames(grasp[:, :8].contiguous())
+    T = eval_collision.global_to_local(frame, center).contiguous()
+    if not isinstance(depth, torch.Tensor) and np.ndim(depth) > 0:
+        depth = to_device(np.asarray(depth, dtype=np.float32), dev)
+    box, keep = eval_collision._box_args(depth, width, B, dev)
+    if params.friction_deg is None:
+        normals = None
+    elif normals is None:
+        normals = eval_collision.estimate_normals(points, radius=params.normal_radius, max_nn=params.normal_max_nn)
+    if normals is not None:
+        require_cuda("normals", normals, torch.float32, 3, error=RuntimeError)
+        if normals.shape[0] != N or normals.device != dev:
+            raise RuntimeError("normals must have one row per point, on the points' device")
+    counts = torch.empty((B, 8), dtype=torch.int32, device=dev)
+    values = torch.empty((B, 4), dtype=torch.float32, device=dev)
+    n_args = (None, 0, 0) if normals is None else (normals.data_ptr(), normals.stride(0), normals.stride(1))
+    _lib.call("regnet_grasp_approach_f32", points, points.data_ptr(), points.stride(0), points.stride(1), *n_args, N,
+              T.data_ptr(), B, *box, float(params.standoff), float(params.contact_depth), cos_friction(params.friction_deg),
+              counts.data_ptr(), values.data_ptr())
+    return Approach(counts, values, frame, center, params, box[5])

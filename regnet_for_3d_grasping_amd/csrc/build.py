@@ -44,6 +44,7 @@ SOURCES = [
     ("cluster.hip", ["-ffp-contract=off"]),   # object segmentation: every edge is decided on individually rounded fp32 distances
     ("fuse.hip", ["-ffp-contract=off"]),   # multi-view fusion: every voxel is decided on individually rounded fp32 arithmetic
     ("icp.hip", ["-ffp-contract=off"]),   # pose refinement: every correspondence is decided on individually rounded fp32 distances
+    ("approach.hip", ["-ffp-contract=off"]),   # approach analysis: every box, sweep and band test is on individually rounded fp32 coordinates
 ]
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc"]

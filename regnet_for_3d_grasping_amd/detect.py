@@ -33,6 +33,12 @@ included; the record additionally carries ``FUSE_KEYS``.  With ``register`` (``-
 ``--icp-iterations``, ``--icp-stride``) the views' poses are first corrected against the first view on the device
 (``fusion.refine_poses``: point-to-plane ICP, one more host read for all views) and the record additionally carries
 ``REGISTER_KEYS``.  Without it nothing changes.
+
+With ``approach`` (``--approach``, ``--approach-standoff``, ``--approach-from``, ``--friction-angle``, ``--min-clearance``,
+``--min-contact``) every grasp of one collision-filtered set is analysed on the device (``approach.analyse``): how far the hand can
+retreat straight back before it touches the cloud, the extent and offset of the object between the fingers, the opening to
+command, the contact check and the pre-grasp point; the record additionally carries ``APPROACH_KEYS``, row-aligned with that set,
+and with ``min_clearance`` / ``min_contact`` the selection sees only the rows that pass.  Without it nothing changes.
 """
 import argparse
 import contextlib
@@ -61,6 +67,8 @@ SEGMENT_KEYS = ("point_object", "object_size", "object_bbox", "grasp_object")   
 SEGMENT_SELECT_KEYS = SELECT_KEYS + ("grasp_selected_object",)                  # ... with ``top_k_per_object``
 FUSE_KEYS = ("fuse_num", "fuse_views")                          # added when the frame was a ``fusion.MultiView``
 REGISTER_KEYS = ("fuse_poses", "fuse_register")                 # ... and the detector has ``register``
+APPROACH_KEYS = ("grasp_clearance", "grasp_width", "grasp_offset", "grasp_opening", "grasp_contact",
+                 "grasp_pregrasp")                             # added when the detector has ``approach``: one row per source grasp
 
 
 def save_path_for(pc_path, real_data):
@@ -95,11 +103,17 @@ class GraspDetector:
     points each view contributed to.  Other frames never see it.  ``register``: None, or a ``registration.IcpParams`` / a dict of
     its fields (``max_dist``, ``iterations``, ``stride``, ``min_pairs``, ...): the poses of a ``MultiView`` are refined against its
     first view before the merge (``fusion.refine_poses``) and the record also carries ``fuse_poses`` (views,4,4) float64, the
-    poses the merge used, and ``fuse_register`` (views,5) float64 = (status, iterations, pairs, rms first, rms last) per view."""
+    poses the merge used, and ``fuse_register`` (views,5) float64 = (status, iterations, pairs, rms first, rms last) per view.
+    ``approach``: None, or an ``approach.ApproachParams`` / a dict of its fields (``source``, ``standoff``, ``friction_deg``,
+    ``min_clearance``, ``min_contact``, ...): every grasp of the collision-filtered set ``source`` is analysed against the cloud
+    and the record also carries, one row per grasp of that set, float32 ``grasp_clearance`` (k,) [m], ``grasp_width`` (k,),
+    ``grasp_offset`` (k,), ``grasp_opening`` (k,), ``grasp_contact`` (k,) and ``grasp_pregrasp`` (k,3).  With ``min_clearance`` /
+    ``min_contact`` the per-frame or per-object selection sees only the rows that pass (its source must then be the analysed
+    set); ``grasp_selected_index`` still holds rows of the full set, and the four sets are never shortened."""
 
     def __init__(self, score_net, region_net, params=TEST_PARAMS, gripper_params=GRIPPER_PARAMS, eval_params=EVAL_PARAMS,
                  transform=None, bounds=None, num_points=ALL_POINTS_NUM, use_theta=USE_THETA, select=None, depth=None, segment=None,
-                 fuse=None, register=None):
+                 fuse=None, register=None, approach=None):
         from . import depth_frame, fusion, grasp_select, ingest, registration
         from . import segment as segment_mod
         self.fuse = fusion.FuseParams.coerce(fuse)
@@ -108,6 +122,17 @@ class GraspDetector:
         self.segment = segment_mod.SegmentParams.coerce(segment)
         self.select = grasp_select.SelectParams.coerce(select)
         self.depth = depth_frame.DepthParams.coerce(depth)
+        self.approach = self.approach_source = None
+        if approach is not None:                  # (the module is not even imported without it)
+            from . import approach as approach_mod
+            self.approach = approach_mod.ApproachParams.coerce(approach)
+            selected = self.select.source if self.select is not None else "grasp_stage3"
+            self.approach_source = self.approach.source or selected
+            if self.segment is not None and self.segment.top_k_per_object is not None:
+                selected = self.segment.source or selected
+            if self.approach.filters() and self.approach_source != selected:
+                raise ValueError("approach: min_clearance / min_contact filter the selection, whose source is %s, not %s"
+                                 % (selected, self.approach_source))
         self.score_net, self.region_net = score_net, region_net
         self.params, self.gripper_params, self.eval_params = list(params), list(gripper_params), list(eval_params)
         self.auto_table = None                    # estimate_plane's keywords when the transform is estimated per frame
@@ -202,9 +227,14 @@ class GraspDetector:
         sel, seg = self.select, self.segment
         nms = {} if sel is None else sel.nms()
         keys, extra, segmented = (), {}, None
+        approach_extra, passing = self._approach(sets, points32)
         if sel is not None and (seg is None or seg.top_k_per_object is None):      # (a per-object selection replaces it)
             keys = SELECT_KEYS
-            sets.update(zip(keys, grasp_select.pose_nms(sets[sel.source], top_k=sel.top_k, return_index=True, **nms)))
+            if passing is None:
+                sets.update(zip(keys, grasp_select.pose_nms(sets[sel.source], top_k=sel.top_k, return_index=True, **nms)))
+            else:                                 # the selection sees the passing rows; its indices are rows of the full set
+                rows, index = grasp_select.pose_nms(sets[sel.source][passing], top_k=sel.top_k, return_index=True, **nms)
+                sets.update(zip(keys, (rows, passing[index])))
         if seg is not None:
             source = seg.source or (sel.source if sel is not None else "grasp_stage3")
             above = segment_mod.above_table_mask(points32, self.eval_params[2], seg.table_clearance)
@@ -212,11 +242,32 @@ class GraspDetector:
             grasp_object, _ = segment_mod.assign_grasps(sets[source], points32, segmented.label, seg.assign_radius)
             if seg.top_k_per_object is not None:
                 keys = SEGMENT_SELECT_KEYS
-                sets.update(zip(keys, segment_mod.select_per_object(sets[source], grasp_object, seg.max_objects,
-                                                                    seg.top_k_per_object, **nms)))
+                if passing is None:
+                    sets.update(zip(keys, segment_mod.select_per_object(sets[source], grasp_object, seg.max_objects,
+                                                                        seg.top_k_per_object, **nms)))
+                else:
+                    rows, index, objects = segment_mod.select_per_object(sets[source][passing], grasp_object[passing],
+                                                                         seg.max_objects, seg.top_k_per_object, **nms)
+                    sets.update(zip(keys, (rows, passing[index], objects)))
             keys = keys + SEGMENT_KEYS
             extra = {"point_object": segmented.label, "grasp_object": grasp_object}
+        if approach_extra is not None:
+            keys = keys + APPROACH_KEYS
+            extra.update(approach_extra)
         return keys, extra, segmented
+
+    def _approach(self, sets, points32):
+        """The approach analysis of the source set -> (its six record entries on the device, the int64 rows that pass
+        ``min_clearance`` / ``min_contact`` or None when neither is set); (None, None) without ``approach``."""
+        if self.approach is None:
+            return None, None
+        from . import approach as approach_mod
+        depth, width = self.eval_params[0], self.eval_params[1]
+        result = approach_mod.analyse(points32, sets[self.approach_source][:, :8], depth, width, self.approach)
+        extra = dict(zip(APPROACH_KEYS, (result.clearance, result.width, result.offset, result.opening, result.contact,
+                                         result.pregrasp)))
+        passing = result.passes().nonzero().view(-1) if self.approach.filters() else None
+        return extra, passing
 
     def _record(self, fr, kept, output_score, sets, keys, extra, segmented):
         """The downloads, in the order they have always been made -> the record, its keys in the documented order."""
@@ -245,7 +296,8 @@ class GraspDetector:
     def detect(self, frame):
         """test.py:97-148 for one frame -> ``eval_notruth``'s dict of numpy arrays: ``points`` / ``colors`` (the cropped,
         un-jittered cloud: float64 for a camera frame, float32 for a record), ``scores`` (N,1) float32 and the four
-        collision-filtered grasp sets (k,8) float32; with ``select`` also ``SELECT_KEYS``, with ``segment`` ``SEGMENT_KEYS``."""
+        collision-filtered grasp sets (k,8) float32; with ``select`` also ``SELECT_KEYS``, with ``segment`` ``SEGMENT_KEYS``,
+        with ``approach`` ``APPROACH_KEYS``."""
         import torch
         from . import np_random
         was_training = self.score_net.training, self.region_net.training
@@ -275,7 +327,8 @@ class GraspDetector:
         """``test_one_file`` (test.py:94-148): ``.pcd`` -> camera frame, ``.npz`` -> depth frame (with a ``views`` entry: the depth frames of several
         cameras, ``fusion.load_npz``), anything else -> dataset record, unless ``real_data`` says so.  The dict is pickled to ``save_path`` (default: the rule of :143-145; no file when that rule leaves the path
         unchanged, which would overwrite the input).  Prints the reference's three count lines, and the selected count when
-        the detector has ``select``, and the object count when it has ``segment``.  -> (dict, save path or None)."""
+        the detector has ``select``, the object count when it has ``segment``, and with ``approach`` the number of grasps of its set that
+        can retreat the whole standoff.  -> (dict, save path or None)."""
         from . import depth_frame, fusion, ingest
         is_depth = path.endswith(".npz")
         if real_data is None:
@@ -296,6 +349,9 @@ class GraspDetector:
             print("selected grasp num (%s):" % self.select.source, len(out["grasp_selected"]))
         if self.segment is not None:
             print("object num:", len(out["object_size"]))
+        if self.approach is not None:
+            print("free approach grasp num (%s):" % self.approach_source,
+                  int((out["grasp_clearance"] >= np.float32(self.approach.standoff)).sum()))
         if save_path is None:
             save_path = save_path_for(path, real_data)
             if save_path == path:
@@ -336,6 +392,13 @@ _FLAGS = (
     ("--icp-distance", "register", "max_dist", float, "a point pairs with its nearest point of the first view within this distance (%s m)"),
     ("--icp-iterations", "register", "iterations", int, "steps of the registration, at most 64 (%s steps)"),
     ("--icp-stride", "register", "stride", int, "register every so-manieth point of a view; must not divide the image width (every point: %s, the default)"),
+    # approach analysis of one set (approach.analyse): --approach or any of the five turns it on
+    ("--approach-standoff", "approach", "standoff", float, "sweep the hand this far back along its approach (%s m)"),
+    ("--approach-from", "approach", "source", RESULT_KEYS[3:], "the set to analyse (default: the selection's)"),
+    ("--friction-angle", "approach", "friction_deg", float,
+     "judge the contacts: half angle of the friction cone about the closing axis [deg] (off)"),
+    ("--min-clearance", "approach", "min_clearance", float, "select only grasps that can retreat this far [m]"),
+    ("--min-contact", "approach", "min_contact", float, "select only grasps whose contact share is at least this"),
 )
 
 
@@ -384,13 +447,20 @@ def register_from_args(args):
     return given if (given or args.refine_poses) else None
 
 
+def approach_from_args(args):
+    """The CLI's six approach flags -> an ``approach`` dict, or None when none of them was given."""
+    given = _given(args, "approach")
+    return given if (given or args.approach) else None
+
+
 def build_parser():
     """The CLI of ``main``: test.py's arguments, ``_FLAGS`` and the irregular flags of each group."""
+    from . import approach as approach_mod
     from . import depth_frame, fusion, grasp_select, registration, table_plane
     from . import segment as segment_mod
     defaults = {"select": grasp_select.SelectParams(), "transform": argparse.Namespace(threshold=table_plane.DEFAULT_THRESHOLD),
                 "depth": depth_frame.DepthParams(), "segment": segment_mod.SegmentParams(), "fuse": fusion.FuseParams(),
-                "register": registration.IcpParams()}
+                "register": registration.IcpParams(), "approach": approach_mod.ApproachParams()}
     parser = argparse.ArgumentParser(description="REGNet single-file inference (the reference's test.py)")
     parser.add_argument("--folder", "--folder-name", dest="folder", required=True)
     parser.add_argument("--file", "--file-name", dest="file", default="")
@@ -425,6 +495,9 @@ def build_parser():
     parser.add_argument("--refine-poses", action="store_true",
                         help="correct the views' poses against the first view before they are merged")
     regular("register")
+    parser.add_argument("--approach", action="store_true",
+                        help="analyse every grasp of one set: approach clearance, closing width, opening and pre-grasp point")
+    regular("approach")
     return parser
 
 
@@ -443,7 +516,8 @@ def main(argv=None):
     eval_params = [DEPTH, WIDTH, TABLE_HEIGHT, args.gpu, CENTER_NUM]
     detector = GraspDetector(score_net.to(dev), region_net.to(dev), eval_params=eval_params, select=select,
                              transform=transform_from_args(args), depth=depth_from_args(args),
-                             segment=segment_from_args(args), fuse=fuse_from_args(args), register=register_from_args(args))
+                             segment=segment_from_args(args), fuse=fuse_from_args(args), register=register_from_args(args),
+                             approach=approach_from_args(args))
     real_data = "real_data" in args.folder
     if args.file:
         paths = [os.path.join(args.folder, args.file)]
