@@ -960,6 +960,24 @@ int regnet_depth_to_cloud_f32(const float* depth, int64_t W, int64_t H, const fl
                               int64_t Hc, int mode, int use_edge, int min_neighbours, int splat, int keep_uncoloured, float* xyz,
                               float* rgb, uint8_t* status, int32_t* counts, void* workspace, void* stream);
 
+/* regnet_depth_normals_f32: the normals of an organised cloud from its own pixel grid (csrc/depth.hip), what the projective mode
+ * of the pose refinement below takes.  xyz (H W, 3) float32 DEVICE, row v W + u for pixel (u, v), NaN rows for removed pixels
+ * (regnet_depth_to_cloud_*'s output, or any cloud laid out like it).  A lane per pixel, individually rounded binary32 operations in
+ * the written order.  Per pixel with a finite centre c:
+ *   neighbour   the pixel `step` columns (rows) to either side is valid when it is inside the image, its three coordinates are
+ *               finite and fabsf(z_nb - z_c) <= float32(max_jump) (inclusive): a difference never spans a depth discontinuity.
+ *   h           along the image row: R - L (per coordinate) when both neighbours are valid, else R - c, else c - L, else the
+ *               pixel has no normal.  g along the column the same way, D - U with v + step down.
+ *   normal      n = h x g = ((h_y g_z) - (h_z g_y), (h_z g_x) - (h_x g_z), (h_x g_y) - (h_y g_x)); len2 = ((n_x n_x) + (n_y n_y))
+ *               + (n_z n_z); not finite or <= 0: no normal.  Else every component is divided (correctly rounded) by the
+ *               correctly rounded sqrtf(len2), and n is negated when ((n_x c_x) + (n_y c_y)) + (n_z c_z) > 0: it faces the
+ *               camera at the origin.
+ * normals (H W, 3) float32 DEVICE, written whole: a pixel without a normal -- a NaN centre included -- holds three quiet NaNs.
+ * One launch, no host read, no synchronisation, no allocation: capturable.  Errors, all before the launch: W < 1, H < 1 or
+ * step < 1 -> REGNET_ERR_SHAPE; W H > 2^21, max_jump not finite or not positive in float32 -> REGNET_ERR_UNSUPPORTED; a NULL
+ * pointer -> REGNET_ERR_NULL.  (A step beyond the image leaves every pixel without a normal.)                               */
+int regnet_depth_normals_f32(const float* xyz, int64_t W, int64_t H, int64_t step, double max_jump, float* normals, void* stream);
+
 /* ---- object segmentation (csrc/cluster.hip): Euclidean cluster extraction over one cloud, on the device --------------------
  * regnet_cluster_points_f32: xyz (N,3) float32 contiguous; mask (N) uint8 or NULL.  Canonical fp32 arithmetic: individually
  * rounded binary32 operations in the written order (-ffp-contract=off).
@@ -1115,6 +1133,35 @@ int regnet_icp_prepare_f32(const float* target_xyz, int64_t N_target, double max
 int regnet_icp_step_f32(const float* source_xyz, int64_t N_source, int64_t stride, const float* target_normals, int64_t N_target,
                         void* state, double max_dist, int32_t* idx_out, double* sums_out, int64_t min_pairs, void* workspace,
                         void* stream);
+
+/* Projective association: regnet_icp_step_projective_f32 is the same step for a target that is the ORGANISED cloud of a depth
+ * image in the TARGET CAMERA's frame -- a lookup in the target's image instead of a search over a grid, and no prepare call.
+ * State block, status codes, terms, sums, solve and update are those above; only launch A differs (icp_project_kernel).
+ *   target      target_xyz, target_normals (H W, 3) float32 DEVICE, row v W + u for pixel (u, v); NaN marks a removed pixel or a
+ *               pixel without a normal (regnet_depth_normals_f32).  state.pose takes the source into the target CAMERA's frame.
+ *   intrinsics  (4) float64 HOST memory: fx, fy, cx, cy of the target's camera, each rounded once to float32.
+ *   row         visited as above; a row with a non-finite coordinate is skipped (-2).  p as above; a p with a non-finite
+ *               coordinate, or whose p_z is not > 0, has no match (-1).
+ *   pixel       regnet_depth_to_cloud_*'s projection: uf = (p_x / p_z) * fx + cx with the correctly rounded division,
+ *               fu = floorf(uf + 0.5f), inside when fu >= 0 && fu < W in float (a NaN fails); likewise fv.  Outside: -1.
+ *   candidates  the pixels (u + a, v + b), |a|, |b| <= window (0..2), inside the image, whose three coordinates and three normal
+ *               components are all finite.
+ *   normal gate on unless min_cos < -1: source_normals (N_s, 3) float32 DEVICE, row i the normal of source row i in the SOURCE's
+ *               frame; m = R s with the float32 rotation of p, m_x = ((r0 s_x) + (r1 s_y)) + (r2 s_z) and likewise m_y, m_z; a
+ *               candidate must satisfy ((m_x n_x) + (m_y n_y)) + (m_z n_z) >= float32(min_cos).  A source row with a non-finite
+ *               normal has no candidate (-1).  source_normals may be NULL exactly when the gate is off (or N_s == 0).
+ *   match       the candidate smallest by (d2, row), row = v W + u, accepted when d2 <= float32(max_dist * max_dist).
+ *   idx_out     (rows) int32 or NULL: the accepted target row, -1, or -2.
+ * workspace: regnet_icp_projective_workspace_bytes(N_s) bytes, 16-byte aligned: 256 bytes per workgroup of 256 visited rows (at
+ * least one); -1 for a count outside [0, 2^21].  Two launches, no host read, no synchronisation, no allocation, no floating-point
+ * atomic.  N_s == 0: launch B alone.  Errors, all before any launch: as regnet_icp_step_f32 with W < 1 or H < 1 for the target's
+ * count, and window outside 0..2 -> REGNET_ERR_SHAPE; W H > 2^21, fx or fy not finite or not positive (in float32 too), min_cos
+ * > 1 or NaN -> REGNET_ERR_UNSUPPORTED.                                                                                      */
+int64_t regnet_icp_projective_workspace_bytes(int64_t N_source);
+int regnet_icp_step_projective_f32(const float* source_xyz, int64_t N_source, int64_t stride, const float* source_normals,
+                                   const float* target_xyz, const float* target_normals, int64_t W, int64_t H,
+                                   const double* intrinsics, int64_t window, void* state, double max_dist, double min_cos,
+                                   int32_t* idx_out, double* sums_out, int64_t min_pairs, void* workspace, void* stream);
 
 /* ---- approach analysis (csrc/approach.hip): clearance on the way in, closing extent and contact check per grasp, on the device ----
  * What turns a collision-free grasp into a motion.  regnet_grasp_collision_counts_f32 above tests the hand at the final pose

@@ -14,6 +14,9 @@
 //     Registered mode leaves provisional rows and does the footprint atomicMin's into the colour camera's z-buffer.
 //   * depth_colour_kernel (registered mode only): recomputes the projection through the same depth_project(), tests visibility
 //     against the z-buffer, gathers the colour, finalises xyz / rgb / status and the histogram.
+//   * depth_normals_kernel (regnet_depth_normals_f32): the normals of an organised cloud from its own pixel grid, a lane per
+//     pixel: the cross product of the differences `step` pixels along the row and the column, neighbours across a depth jump
+//     left out.  What registration's projective mode takes as the target's (and the source's) normals.
 // The launches are ordered by the stream: no workgroup waits for another, no flags, no cooperative launch.  Integer atomics only
 // (the z-buffer's unsigned min on float bits -- positive finite floats order as their bits -- and one histogram add per
 // workgroup and code); everything else is a plain vector store.
@@ -237,6 +240,53 @@ __global__ __launch_bounds__(DP_BLOCK) void depth_colour_kernel(const uint8_t* _
   depth_histogram(active, st, s_hist, counts);
 }
 
+// one neighbour of the normal's difference: inside the image, finite, and within the jump of the centre's depth
+__device__ __forceinline__ bool depth_neighbour(const float* __restrict__ xyz, int W, int H, int u, int v, float zc, float jump,
+                                                float& x, float& y, float& z) {
+  if (u < 0 || u >= W || v < 0 || v >= H) return false;
+  const long long row = (long long)v * W + u;
+  x = xyz[row * 3 + 0]; y = xyz[row * 3 + 1]; z = xyz[row * 3 + 2];
+  return __builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z) && fabsf(z - zc) <= jump;
+}
+
+// the difference along one image axis: far minus near when both neighbours are valid, else the valid one against the centre
+__device__ __forceinline__ bool depth_difference(const float* __restrict__ xyz, int W, int H, int u, int v, int du, int dv,
+                                                 float cx, float cy, float cz, float jump, float& dx, float& dy, float& dz) {
+  float ax = 0.0f, ay = 0.0f, az = 0.0f, bx = 0.0f, by = 0.0f, bz = 0.0f;
+  const bool near = depth_neighbour(xyz, W, H, u - du, v - dv, cz, jump, ax, ay, az);
+  const bool far = depth_neighbour(xyz, W, H, u + du, v + dv, cz, jump, bx, by, bz);
+  if (!near && !far) return false;
+  if (!near) { ax = cx; ay = cy; az = cz; }
+  if (!far) { bx = cx; by = cy; bz = cz; }
+  dx = bx - ax; dy = by - ay; dz = bz - az;
+  return true;
+}
+
+// depth_normals_kernel: a lane per pixel of an organised cloud; the normal is the cross product of the differences along the
+// image row and column, scaled to length 1 and turned to face the camera at the origin.  No normal: three NaNs.
+__global__ __launch_bounds__(DP_BLOCK) void depth_normals_kernel(const float* __restrict__ xyz, int W, int H, int step, float jump,
+                                                                 float* __restrict__ normals) {
+  const long long row = (long long)blockIdx.x * DP_BLOCK + threadIdx.x;
+  if (row >= (long long)W * H) return;
+  const int u = (int)(row % W), v = (int)(row / W);
+  const float nan = __uint_as_float(DP_QNAN);
+  float nx = nan, ny = nan, nz = nan;
+  const float cx = xyz[row * 3 + 0], cy = xyz[row * 3 + 1], cz = xyz[row * 3 + 2];
+  float hx, hy, hz, gx, gy, gz;
+  if (__builtin_isfinite(cx) && __builtin_isfinite(cy) && __builtin_isfinite(cz) &&
+      depth_difference(xyz, W, H, u, v, step, 0, cx, cy, cz, jump, hx, hy, hz) &&
+      depth_difference(xyz, W, H, u, v, 0, step, cx, cy, cz, jump, gx, gy, gz)) {
+    const float ax = (hy * gz) - (hz * gy), ay = (hz * gx) - (hx * gz), az = (hx * gy) - (hy * gx);
+    const float len2 = ((ax * ax) + (ay * ay)) + (az * az);
+    if (__builtin_isfinite(len2) && len2 > 0.0f) {
+      const float len = sqrtf(len2);      // correctly rounded (this toolchain's __fsqrt_rn is the native approximation, an ulp off)
+      nx = __fdiv_rn(ax, len); ny = __fdiv_rn(ay, len); nz = __fdiv_rn(az, len);
+      if (((nx * cx) + (ny * cy)) + (nz * cz) > 0.0f) { nx = -nx; ny = -ny; nz = -nz; }
+    }
+  }
+  store3(normals, row, nx, ny, nz);
+}
+
 int depth_check(int64_t W, int64_t H, int64_t Wc, int64_t Hc, int mode) {
   if (W < 1 || H < 1 || mode < DP_NONE || mode > DP_REGISTERED) return REGNET_ERR_SHAPE;
   if (mode == DP_ALIGNED && (Wc != W || Hc != H)) return REGNET_ERR_SHAPE;
@@ -324,4 +374,19 @@ extern "C" int regnet_depth_to_cloud_f32(const float* depth, int64_t W, int64_t 
                                          void* workspace, void* stream) {
   return depth_launch<float>(depth, W, H, params, colour, Wc, Hc, mode, use_edge, min_neighbours, splat, keep_uncoloured, xyz, rgb,
                              status, counts, workspace, stream);
+}
+
+extern "C" int regnet_depth_normals_f32(const float* xyz, int64_t W, int64_t H, int64_t step, double max_jump, float* normals,
+                                        void* stream) {
+  if (W < 1 || H < 1 || step < 1) return REGNET_ERR_SHAPE;
+  if (W > DP_MAX_PIXELS || H > DP_MAX_PIXELS || W * H > DP_MAX_PIXELS) return REGNET_ERR_UNSUPPORTED;
+  const float jump = (float)max_jump;
+  if (!(max_jump > 0.0 && jump > 0.0f && jump < __builtin_inff())) return REGNET_ERR_UNSUPPORTED;   // (a NaN too)
+  if (!xyz || !normals) return REGNET_ERR_NULL;
+  if (step > DP_MAX_PIXELS) step = DP_MAX_PIXELS;      // (beyond the image either way, and no overflow in u + step)
+  const long long n = (long long)(W * H);
+  hipLaunchKernelGGL(depth_normals_kernel, dim3((unsigned)((n + DP_BLOCK - 1) / DP_BLOCK)), dim3(DP_BLOCK), 0, as_stream(stream),
+                     xyz, (int)W, (int)H, (int)step, jump, normals);
+  REGNET_LAUNCH_CHECK();
+  return REGNET_OK;
 }

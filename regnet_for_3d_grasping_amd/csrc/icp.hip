@@ -10,7 +10,10 @@
 //             the ball of max_dist (27 cells; one more along an axis only where the rounding margin reaches into it), the
 //             point-to-plane residual and the row's 28 float64 terms; a shuffle tree per wave, the waves in order, one slot of
 //             partial sums per workgroup.
-//   step, launch B  icp_solve_kernel       one workgroup: the slots in ascending order, a 6x6 Cholesky, Rodrigues, the pose update,
+//   projective step, launch A  icp_project_kernel  the same lane per visited row, for a target that is the organised cloud of a
+//             depth image in its camera's frame: the row's pixel in that image and the (2 window + 1)^2 pixels around it are the
+//             candidates, optionally gated by the angle between the normals; no grid, no prepare.  The same tail.
+//   step, launch B  icp_solve_kernel      one workgroup: the slots in ascending order, a 6x6 Cholesky, Rodrigues, the pose update,
 //             the status word.
 // Both kernels of a step return at once when the status is no longer RUNNING: a caller enqueues a fixed number of steps and
 // reads the state block once.  No thread waits for another and every loop ends on its own count.
@@ -44,6 +47,52 @@ __host__ inline int64_t icp_slots(int64_t rows) { return (rows + ICP_BLOCK - 1) 
 __host__ inline bool icp_dist_ok(double d) { return d > 0.0 && d < __builtin_inf() && (float)d > 0.f && (float)d < __builtin_inff(); }
 
 __device__ __forceinline__ bool icp_finite(float v) { return fabsf(v) < __builtin_inff(); }   // (NaN fails)
+
+// the tail of launch A, shared by both association modes: the accepted pair's residual and its 28 float64 terms, a shuffle tree
+// per wave, the waves in order, the workgroup's slot.  Every thread of the workgroup calls it (a barrier inside).
+__device__ __forceinline__ void icp_accumulate(int found, float px, float py, float pz, float qx, float qy, float qz,
+                                               const float* __restrict__ normals, double (*s_part)[ICP_SLOT],
+                                               double* __restrict__ partial) {
+  const int tid = threadIdx.x;
+  const bool paired = found >= 0;
+  double t[ICP_TERMS];
+#pragma unroll
+  for (int c = 0; c < ICP_TERMS; ++c) t[c] = 0.0;
+  if (paired) {
+    const double nx = (double)normals[(int64_t)found * 3], ny = (double)normals[(int64_t)found * 3 + 1],
+                 nz = (double)normals[(int64_t)found * 3 + 2];
+    const double dx = (double)px, dy = (double)py, dz = (double)pz;
+    const double res = ((nx * (dx - (double)qx)) + (ny * (dy - (double)qy))) + (nz * (dz - (double)qz));
+    const double a[6] = {dy * nz - dz * ny, dz * nx - dx * nz, dx * ny - dy * nx, nx, ny, nz};     // (p x n, n)
+    int c = 0;
+#pragma unroll
+    for (int u = 0; u < 6; ++u) {
+#pragma unroll
+      for (int v = u; v < 6; ++v) t[c++] = a[u] * a[v];
+    }
+#pragma unroll
+    for (int u = 0; u < 6; ++u) t[21 + u] = a[u] * res;
+    t[27] = res * res;
+  }
+#pragma unroll
+  for (int c = 0; c < ICP_TERMS; ++c) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) t[c] += __shfl_xor(t[c], d, 64);       // a fixed tree: every lane ends with the wave's sum
+  }
+  const int pairs = (int)__popcll(__ballot(paired));
+  if (lane_id() == 0) {
+#pragma unroll
+    for (int c = 0; c < ICP_TERMS; ++c) s_part[tid >> 6][c] = t[c];
+    s_part[tid >> 6][ICP_TERMS] = (double)pairs;
+  }
+  __syncthreads();
+  if (tid < ICP_SUMS) {
+    double v = 0.0;
+#pragma unroll
+    for (int w = 0; w < ICP_BLOCK / 64; ++w) v += s_part[w][tid];              // the waves in order
+    partial[(int64_t)blockIdx.x * ICP_SLOT + tid] = v;
+  }
+}
 
 __global__ __launch_bounds__(ICP_BLOCK) void icp_correspond_kernel(const float* __restrict__ src, int stride, int rows,
                                                                    const float* __restrict__ normals, int n_target,
@@ -95,44 +144,77 @@ __global__ __launch_bounds__(ICP_BLOCK) void icp_correspond_kernel(const float* 
     }
     if (idx_out != nullptr) idx_out[k] = found;
   }
-  const bool paired = found >= 0;
-  double t[ICP_TERMS];
+  icp_accumulate(found, px, py, pz, qx, qy, qz, normals, s_part, partial);
+}
+
+struct IcpCamera {   // the target's image: intrinsics rounded once to float32, the window's half width
+  int W, H, window;
+  float fx, fy, cx, cy;
+};
+
+// Launch A of the projective step: the target is the organised cloud of a depth image in ITS camera's frame, so the candidates
+// of a source row are the (2 window + 1)^2 pixels around the pixel it projects to -- at most 25 reads of 12 + 12 bytes a lane,
+// neighbouring lanes on neighbouring pixels -- instead of the cells of a grid.  The pixel is csrc/depth.hip's depth_project()
+// expression.  src_normals == nullptr: the normal gate is off.
+__global__ __launch_bounds__(ICP_BLOCK) void icp_project_kernel(const float* __restrict__ src, int stride, int rows,
+                                                                const float* __restrict__ src_normals,
+                                                                const float* __restrict__ target,
+                                                                const float* __restrict__ normals, const IcpCamera cam,
+                                                                const IcpState* __restrict__ state, float max2, float min_cos,
+                                                                int* __restrict__ idx_out, double* __restrict__ partial) {
+  __shared__ double s_part[ICP_BLOCK / 64][ICP_SLOT];
+  if (state->status != ICP_RUNNING) return;                    // the same word for every thread of the grid
+  const int k = blockIdx.x * ICP_BLOCK + threadIdx.x;
+  float px = 0.f, py = 0.f, pz = 0.f, qx = 0.f, qy = 0.f, qz = 0.f;
+  int found = -3;                                              // -3: no row behind this lane
+  if (k < rows) {
+    const int64_t i = (int64_t)k * stride;
+    const float x = src[i * 3], y = src[i * 3 + 1], z = src[i * 3 + 2];
+    found = -2;
+    if (icp_finite(x) && icp_finite(y) && icp_finite(z)) {
+      found = -1;
+      float r[12];
 #pragma unroll
-  for (int c = 0; c < ICP_TERMS; ++c) t[c] = 0.0;
-  if (paired) {
-    const double nx = (double)normals[(int64_t)found * 3], ny = (double)normals[(int64_t)found * 3 + 1],
-                 nz = (double)normals[(int64_t)found * 3 + 2];
-    const double dx = (double)px, dy = (double)py, dz = (double)pz;
-    const double res = ((nx * (dx - (double)qx)) + (ny * (dy - (double)qy))) + (nz * (dz - (double)qz));
-    const double a[6] = {dy * nz - dz * ny, dz * nx - dx * nz, dx * ny - dy * nx, nx, ny, nz};     // (p x n, n)
-    int c = 0;
-#pragma unroll
-    for (int u = 0; u < 6; ++u) {
-#pragma unroll
-      for (int v = u; v < 6; ++v) t[c++] = a[u] * a[v];
+      for (int j = 0; j < 12; ++j) r[j] = (float)state->pose[j];       // rounded once, to nearest even
+      px = ((r[0] * x + r[1] * y) + r[2] * z) + r[3];
+      py = ((r[4] * x + r[5] * y) + r[6] * z) + r[7];
+      pz = ((r[8] * x + r[9] * y) + r[10] * z) + r[11];
+      bool usable = icp_finite(px) && icp_finite(py) && icp_finite(pz) && pz > 0.f;
+      float mx = 0.f, my = 0.f, mz = 0.f;
+      if (usable && src_normals != nullptr) {
+        const float sx = src_normals[i * 3], sy = src_normals[i * 3 + 1], sz = src_normals[i * 3 + 2];
+        usable = icp_finite(sx) && icp_finite(sy) && icp_finite(sz);
+        mx = (r[0] * sx + r[1] * sy) + r[2] * sz;
+        my = (r[4] * sx + r[5] * sy) + r[6] * sz;
+        mz = (r[8] * sx + r[9] * sy) + r[10] * sz;
+      }
+      if (usable) {
+        const float uf = (__fdiv_rn(px, pz) * cam.fx) + cam.cx;
+        const float vf = (__fdiv_rn(py, pz) * cam.fy) + cam.cy;
+        const float fu = floorf(uf + 0.5f), fv = floorf(vf + 0.5f);
+        if (fu >= 0.0f && fu < (float)cam.W && fv >= 0.0f && fv < (float)cam.H) {      // in float: a NaN fails
+          const int u = (int)fu, v = (int)fv;
+          const int ulo = max(u - cam.window, 0), uhi = min(u + cam.window, cam.W - 1);
+          const int vlo = max(v - cam.window, 0), vhi = min(v + cam.window, cam.H - 1);
+          float bd = __builtin_inff();
+          int bj = -1;
+          for (int cv = vlo; cv <= vhi; ++cv)
+            for (int cu = ulo; cu <= uhi; ++cu) {                      // ascending rows: of equal d2 the first, the lowest row, stays
+              const int j = cv * cam.W + cu;
+              const float tx = target[(int64_t)j * 3], ty = target[(int64_t)j * 3 + 1], tz = target[(int64_t)j * 3 + 2];
+              const float nx = normals[(int64_t)j * 3], ny = normals[(int64_t)j * 3 + 1], nz = normals[(int64_t)j * 3 + 2];
+              bool ok = icp_finite(tx) && icp_finite(ty) && icp_finite(tz) && icp_finite(nx) && icp_finite(ny) && icp_finite(nz);
+              if (src_normals != nullptr) ok = ok && ((mx * nx + my * ny) + mz * nz) >= min_cos;   // (a NaN product fails)
+              const float d2 = sqdist3(px, py, pz, tx, ty, tz);
+              if (ok && d2 < bd) { bd = d2; bj = j; qx = tx; qy = ty; qz = tz; }
+            }
+          if (bj >= 0 && bd <= max2) found = bj;
+        }
+      }
     }
-#pragma unroll
-    for (int u = 0; u < 6; ++u) t[21 + u] = a[u] * res;
-    t[27] = res * res;
+    if (idx_out != nullptr) idx_out[k] = found;
   }
-#pragma unroll
-  for (int c = 0; c < ICP_TERMS; ++c) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) t[c] += __shfl_xor(t[c], d, 64);       // a fixed tree: every lane ends with the wave's sum
-  }
-  const int pairs = (int)__popcll(__ballot(paired));
-  if (lane_id() == 0) {
-#pragma unroll
-    for (int c = 0; c < ICP_TERMS; ++c) s_part[tid >> 6][c] = t[c];
-    s_part[tid >> 6][ICP_TERMS] = (double)pairs;
-  }
-  __syncthreads();
-  if (tid < ICP_SUMS) {
-    double v = 0.0;
-#pragma unroll
-    for (int w = 0; w < ICP_BLOCK / 64; ++w) v += s_part[w][tid];              // the waves in order
-    partial[(int64_t)blockIdx.x * ICP_SLOT + tid] = v;
-  }
+  icp_accumulate(found, px, py, pz, qx, qy, qz, normals, s_part, partial);
 }
 
 __global__ __launch_bounds__(ICP_BLOCK) void icp_solve_kernel(const double* __restrict__ partial, int slots,
@@ -274,6 +356,45 @@ extern "C" int regnet_icp_step_f32(const float* source_xyz, int64_t N_source, in
                        (int)stride, (int)rows, target_normals, (int)N_target,
                        (const IcpState*)state, (float)max_dist, (float)(max_dist * max_dist), (const char*)workspace, (int*)idx_out,
                        partial);
+    REGNET_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(icp_solve_kernel, dim3(1), dim3(ICP_BLOCK), 0, st, (const double*)partial, (int)slots, (IcpState*)state,
+                     sums_out, (double)min_pairs);
+  REGNET_LAUNCH_CHECK();
+  return REGNET_OK;
+}
+
+extern "C" int64_t regnet_icp_projective_workspace_bytes(int64_t N_source) {
+  if (N_source < 0 || N_source > ICP_MAX_POINTS) return -1;
+  const int64_t slots = icp_slots(N_source);
+  return (slots > 0 ? slots : 1) * ICP_SLOT * (int64_t)sizeof(double);
+}
+
+extern "C" int regnet_icp_step_projective_f32(const float* source_xyz, int64_t N_source, int64_t stride,
+                                              const float* source_normals, const float* target_xyz, const float* target_normals,
+                                              int64_t W, int64_t H, const double* intrinsics, int64_t window, void* state,
+                                              double max_dist, double min_cos, int32_t* idx_out, double* sums_out,
+                                              int64_t min_pairs, void* workspace, void* stream) {
+  if (N_source < 0 || W < 1 || H < 1 || stride < 1 || min_pairs < 0 || window < 0 || window > 2) return REGNET_ERR_SHAPE;
+  if (N_source > ICP_MAX_POINTS || W > ICP_MAX_POINTS || H > ICP_MAX_POINTS || W * H > ICP_MAX_POINTS || !icp_dist_ok(max_dist))
+    return REGNET_ERR_UNSUPPORTED;
+  if (!(min_cos <= 1.0)) return REGNET_ERR_UNSUPPORTED;        // (a NaN too)
+  if (!intrinsics) return REGNET_ERR_NULL;
+  if (!icp_dist_ok(intrinsics[0]) || !icp_dist_ok(intrinsics[1])) return REGNET_ERR_UNSUPPORTED;
+  const bool gate = !(min_cos < -1.0);
+  if (!state || !workspace || !target_xyz || !target_normals || (N_source > 0 && (!source_xyz || (gate && !source_normals))))
+    return REGNET_ERR_NULL;
+  hipStream_t st = as_stream(stream);
+  if (stride > ICP_MAX_POINTS) stride = ICP_MAX_POINTS;        // (N_source <= 2^21: the same single visited row, and no overflow below)
+  const int64_t rows = icp_rows(N_source, stride), slots = icp_slots(rows);
+  double* partial = reinterpret_cast<double*>(workspace);
+  if (slots > 0) {
+    IcpCamera cam;
+    cam.W = (int)W; cam.H = (int)H; cam.window = (int)window;
+    cam.fx = (float)intrinsics[0]; cam.fy = (float)intrinsics[1]; cam.cx = (float)intrinsics[2]; cam.cy = (float)intrinsics[3];
+    hipLaunchKernelGGL(icp_project_kernel, dim3((unsigned)slots), dim3(ICP_BLOCK), 0, st, source_xyz, (int)stride, (int)rows,
+                       gate ? source_normals : (const float*)nullptr, target_xyz, target_normals, cam, (const IcpState*)state,
+                       (float)(max_dist * max_dist), gate ? (float)min_cos : 0.f, (int*)idx_out, partial);
     REGNET_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(icp_solve_kernel, dim3(1), dim3(ICP_BLOCK), 0, st, (const double*)partial, (int)slots, (IcpState*)state,

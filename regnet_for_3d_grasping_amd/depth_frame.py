@@ -16,7 +16,7 @@ from typing import Any, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from ._frame_util import MAX_FRAME_POINTS, ParamsBase, matrix4, record_streams, stream_scope, to_device, to_host
+from ._frame_util import MAX_FRAME_POINTS, ParamsBase, matrix4, record_streams, require_cuda, stream_scope, to_device, to_host
 
 _L = _lib.lib
 
@@ -207,6 +207,26 @@ def to_cloud(frame, params=None, device="cuda:0", stream=None, return_status=Fal
                   ws.data_ptr())
         record_streams(stream, depth, color)       # the inputs are read on `stream`: keep them alive for it
     return (xyz, rgb, status, counts) if return_status else (xyz, rgb)
+
+
+def normals(xyz, width, height, step=2, max_jump=0.02, stream=None):
+    """The normals of an organised cloud from its own pixel grid (regnet_depth_normals_f32): ``xyz`` (H W, 3) float32 on the
+    device, row ``v W + u`` for pixel (u, v), as ``to_cloud`` gives it -> (H W, 3) float32 on the device.  A normal is the cross
+    product of the differences ``step`` pixels along the image row and column, of length 1 and facing the camera at the origin;
+    a neighbour whose depth differs from the centre's by more than ``max_jump`` [m] is left out (one-sided then), and a pixel
+    without a normal -- removed itself, or without a neighbour along either axis -- holds three NaNs.  One launch, no host read."""
+    import torch
+    require_cuda("xyz", xyz, torch.float32, 3)
+    width, height = int(width), int(height)
+    if width < 1 or height < 1 or int(xyz.shape[0]) != width * height:
+        raise ValueError("normals: xyz must have width * height rows")
+    xyz = xyz.contiguous()
+    with torch.cuda.device(xyz.device), stream_scope(stream):
+        out = torch.empty((width * height, 3), dtype=torch.float32, device=xyz.device)
+        _lib.call("regnet_depth_normals_f32", xyz, xyz.data_ptr(), width, height, int(step), float(max_jump), out.data_ptr(),
+                  stream=None if stream is None else stream.cuda_stream)
+        record_streams(stream, xyz)
+    return out
 
 
 _NPZ_KEYS = ("depth", "intrinsics", "color", "color_intrinsics", "depth_to_color", "depth_scale")

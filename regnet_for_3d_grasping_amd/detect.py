@@ -30,8 +30,9 @@ A camera frame may also be a ``fusion.MultiView`` (a ``.npz`` file with a ``view
 and their poses): the views are merged into one evenly sampled cloud on the device (``fusion.voxel_merge``; ``fuse`` / ``--voxel``,
 ``--max-voxels``, ``--min-voxel-points`` set the voxel grid) and take the camera-frame path from there, ``transform="auto"``
 included; the record additionally carries ``FUSE_KEYS``.  With ``register`` (``--refine-poses``, ``--icp-distance``,
-``--icp-iterations``, ``--icp-stride``) the views' poses are first corrected against the first view on the device
-(``fusion.refine_poses``: point-to-plane ICP, one more host read for all views) and the record additionally carries
+``--icp-iterations``, ``--icp-stride``, ``--icp-association``, ``--icp-window``, ``--icp-normal-angle``) the views' poses are
+first corrected against the first view on the device (``fusion.refine_poses``: point-to-plane ICP, by the nearest point or by a
+lookup in the first view's depth image, one more host read for all views) and the record additionally carries
 ``REGISTER_KEYS``.  Without it nothing changes.
 
 With ``approach`` (``--approach``, ``--approach-standoff``, ``--approach-from``, ``--friction-angle``, ``--min-clearance``,
@@ -388,10 +389,15 @@ _FLAGS = (
     ("--voxel", "fuse", "voxel", float, "edge of the voxels the views are merged in [m]"),
     ("--max-voxels", "fuse", "max_voxels", int, "rows of the merged cloud, at most 2^21"),
     ("--min-voxel-points", "fuse", "min_count", int, "drop voxels with fewer points"),
-    # pose refinement before the merge (fusion.refine_poses): --refine-poses or any of the three turns it on
+    # pose refinement before the merge (fusion.refine_poses): --refine-poses or any of the six turns it on
     ("--icp-distance", "register", "max_dist", float, "a point pairs with its nearest point of the first view within this distance (%s m)"),
     ("--icp-iterations", "register", "iterations", int, "steps of the registration, at most 64 (%s steps)"),
     ("--icp-stride", "register", "stride", int, "register every so-manieth point of a view; must not divide the image width (every point: %s, the default)"),
+    ("--icp-association", "register", "association", ("nearest", "projective"),
+     "how a point finds its partner: the nearest point over a grid, or a lookup in the first view's depth image"),
+    ("--icp-window", "register", "window", int, "projective association looks this many pixels (%s, at most 2) around the pixel a point falls on"),
+    ("--icp-normal-angle", "register", "normal_angle", float,
+     "projective association pairs only points whose normals are within this angle [deg] (off)"),
     # approach analysis of one set (approach.analyse): --approach or any of the five turns it on
     ("--approach-standoff", "approach", "standoff", float, "sweep the hand this far back along its approach (%s m)"),
     ("--approach-from", "approach", "source", RESULT_KEYS[3:], "the set to analyse (default: the selection's)"),
@@ -442,7 +448,7 @@ def fuse_from_args(args):
 
 
 def register_from_args(args):
-    """The CLI's four registration flags -> a ``register`` dict, or None when none of them was given."""
+    """The CLI's seven registration flags -> a ``register`` dict, or None when none of them was given."""
     given = _given(args, "register")
     return given if (given or args.refine_poses) else None
 

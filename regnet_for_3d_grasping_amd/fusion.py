@@ -15,7 +15,8 @@ no synchronisation.  GPU only: there is no CPU path.
 
 The merge is only as good as the poses: ``refine_poses`` corrects them first, registering every view onto one reference view by
 point-to-plane ICP on the device (``registration.icp``, csrc/icp.hip), with one host read for all views; ``fuse_frames`` runs it
-when given ``register``.
+when given ``register``.  The pairs are found by a grid search or, with ``association="projective"``, by a lookup in the reference
+view's depth image.
 """
 import warnings
 from dataclasses import dataclass
@@ -219,7 +220,18 @@ def transform_cloud(xyz, pose):
     return torch.stack([((x * r[4 * k] + y * r[4 * k + 1]) + z * r[4 * k + 2]) + r[4 * k + 3] for k in range(3)], dim=1)
 
 
-def refine_poses(clouds, poses, params=None, reference=0, stream=None):
+def _frame_geometry(v, frame):
+    """A view's ``DepthFrame``, or its ``(width, height, Intrinsics)`` -> (width, height, Intrinsics)."""
+    if isinstance(frame, depth_frame.DepthFrame):
+        if not hasattr(frame.depth, "shape") or len(frame.depth.shape) != 2:
+            raise ValueError("refine_poses: the depth image of view %d must be (H, W)" % v)
+        return int(frame.depth.shape[1]), int(frame.depth.shape[0]), frame.intrinsics
+    if not isinstance(frame, (tuple, list)) or len(frame) != 3:
+        raise TypeError("refine_poses: frames[%d] must be a DepthFrame or (width, height, Intrinsics)" % v)
+    return int(frame[0]), int(frame[1]), depth_frame.Intrinsics.coerce(frame[2])
+
+
+def refine_poses(clouds, poses, params=None, reference=0, stream=None, frames=None):
     """Correct the poses of several cameras against one of them before ``voxel_merge`` (``registration.icp``, csrc/icp.hip).
     ``clouds``: per view ``xyz`` (n_v,3) float32 on the device in ITS CAMERA's frame, or the ``(xyz, rgb)`` pair ``voxel_merge``
     takes; ``poses``: per view the 4x4 camera-to-common transform or None (identity); ``params``: a ``registration.IcpParams``,
@@ -227,7 +239,12 @@ def refine_poses(clouds, poses, params=None, reference=0, stream=None):
     frame by its own pose, is the target, its normals estimated facing its camera.  Every registration starts from the view's
     given pose; all are enqueued, then ONE host read fetches every state block.
     -> (poses, report): a list of (4,4) float64 arrays and (V,5) float64 = (status, iterations, pairs, rms first, rms last) per
-    view; the reference's row is (-1, 0, 0, 0, 0).  A view that ended TOO_FEW or DEGENERATE keeps its given pose."""
+    view; the reference's row is (-1, 0, 0, 0, 0).  A view that ended TOO_FEW or DEGENERATE keeps its given pose.
+
+    With ``params.association == "projective"`` the pairs are looked up in the reference's depth image and ``frames`` is needed:
+    per view its ``DepthFrame``, or ``(width, height, Intrinsics)``, whose organised cloud ``clouds[v]`` is.  The reference's cloud
+    then stays in its own camera's frame and is not compacted (no host read before the one at the end); view v starts from
+    inv(P_ref) P_v, a float64 product on the host, and ends as P_ref T_v."""
     import torch
     from . import registration
     params = registration.IcpParams.coerce(params) or registration.IcpParams()
@@ -248,6 +265,35 @@ def refine_poses(clouds, poses, params=None, reference=0, stream=None):
     if not others:
         return given, report
     dev = clouds[reference].device
+    if params.association == "projective":
+        if frames is None:
+            raise ValueError("refine_poses: association='projective' needs frames, the depth frames (or (width, height, "
+                             "Intrinsics)) the clouds were made from")
+        frames = list(frames)
+        if len(frames) != len(clouds):
+            raise ValueError("refine_poses: one frame per cloud")
+        shapes = [_frame_geometry(v, frame) for v, frame in enumerate(frames)]
+        for v, (w, h, _) in enumerate(shapes):
+            if int(clouds[v].shape[0]) != w * h:
+                raise ValueError("refine_poses: cloud %d is not the organised cloud of its %d x %d frame" % (v, w, h))
+        to_reference = np.linalg.inv(given[reference])
+        with torch.cuda.device(dev), stream_scope(stream):
+            w, h, k = shapes[reference]
+            target = registration.prepare_projective_target(clouds[reference], w, h, k, params, stream=stream,
+                                                            max_source=max(int(clouds[v].shape[0]) for v in others))
+            starts = [to_reference @ given[v] for v in others]
+            blocks = to_device(np.stack([registration.initial_state(start, params) for start in starts]), dev)
+            for row, v in enumerate(others):
+                registration.icp(clouds[v], target, starts[row], params, stream=stream, state=blocks[row],
+                                 source_shape=shapes[v][:2])
+            raw = blocks.cpu().numpy()                               # the one host read, 1152 bytes per registered view
+        refined = list(given)
+        for row, v in enumerate(others):
+            decoded = registration.decode_state(raw[row])
+            report[v] = registration.report_row(decoded)
+            if decoded["status"] not in (registration.TOO_FEW, registration.DEGENERATE):
+                refined[v] = given[reference] @ decoded["pose"]
+        return refined, report
     with torch.cuda.device(dev), stream_scope(stream):
         target = registration.prepare_target(transform_cloud(clouds[reference], given[reference]), params,
                                              target_camera=tuple(given[reference][:3, 3]),
@@ -283,7 +329,7 @@ def fuse_frames(multiview, depth_params=None, fuse_params=None, device="cuda:0",
             warnings.warn("register: a stride of %d divides the width of view%s %s (%s pixels) and visits whole pixel columns only; "
                           "take one that does not" % (register.stride, "" if len(whole) == 1 else "s",
                                                       ", ".join(str(v) for v, _ in whole), ", ".join(str(w) for _, w in whole)))
-    poses, report = refine_poses(clouds, multiview.poses, register, stream=stream)
+    poses, report = refine_poses(clouds, multiview.poses, register, stream=stream, frames=multiview.frames)
     fused = voxel_merge(clouds, poses, fuse_params, stream=stream)
     fused.poses, fused.register = np.stack(poses), report
     return fused
