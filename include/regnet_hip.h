@@ -1024,6 +1024,43 @@ int regnet_cluster_points_f32(const float* xyz, const uint8_t* mask, int64_t N, 
 int regnet_cluster_assign_f32(const float* query, int64_t Q, const float* xyz, const int32_t* label, int64_t N, float radius,
                               int32_t* object, int32_t* point, void* stream);
 
+/* ---- outlier removal (csrc/outlier.hip): radius and statistical cloud filters over one cloud, on the device -------------------
+ * xyz (N,3) float32 contiguous; mask (N) uint8 or NULL.  Canonical fp32 arithmetic: individually rounded binary32 operations in
+ * the written order (-ffp-contract=off).
+ *   graph rows  row i is in the graph iff (mask == NULL or mask[i] != 0) and its three coordinates are finite.  The other rows
+ *               are compacted away before the uniform grid (csrc/grid.h) is built; the count of graph rows stays on the device.
+ *   distance    d2 = ((dx dx) + (dy dy)) + (dz dz); j is within range of i iff d2 <= R2 (inclusive), R2 = R * R (one float32
+ *               product).  The grid's cell edge starts at R and coarsens under its cell limit; the walk visits the cells
+ *               overlapping the ball, and only decides which pairs are evaluated.
+ * regnet_outlier_radius_f32: n(i) = the graph rows j != i within `radius` of i, compared by ROW (a duplicate point counts).
+ *   count       (N) int32: min(n(i), min_neighbours); -1 for a row outside the graph.  A row is an inlier iff count[i] ==
+ *               min_neighbours (open3d's remove_radius_outlier: the neighbours found, the point itself among them, exceed
+ *               nb_points).  A row's walk stops as soon as it has min_neighbours.
+ * regnet_outlier_knn_f32: among the graph rows j != i within `max_radius`, the k smallest d2 (1 <= k <= 64; ties need no rule,
+ *   only the multiset of values is used).
+ *   found       (N) int32: min(n(i), k); -1 for a row outside the graph.
+ *   mean_dist   (N) float32: where found == k, float32(S / k) with S the float64 sum of the correctly rounded float32 sqrt(d2)
+ *               taken in ascending order of d2, one addition after the other, and a float64 division; the quiet NaN 0x7FC00000
+ *               elsewhere.  Independent of the order in which candidates are met: two runs give the same bytes.
+ * regnet_outlier_stats_f64: over the rows with found == k, in float64 and a fixed order (one workgroup: thread t of 1024 adds
+ *   rows t, t + 1024, ... one after the other, then a binary tree over the threads):
+ *   stats       (4) float64 DEVICE = n, mu = sum(m) / n, sigma = sqrt(sum((m - mu)^2) / (n - 1)) in a second pass (open3d's
+ *               form), thr = float32(mu + ratio * sigma) stored as a double.  n < 2: sigma = NaN, thr = +inf; n == 0: mu = NaN.
+ *               A row passes the statistical filter iff mean_dist <= thr (a NaN fails).
+ *   workspace   regnet_outlier_workspace_bytes(N), 16-byte aligned: a counter, the compacted rows and their source rows, the
+ *               grid slab; -1 for unsupported sizes.
+ * No host read, no synchronisation, no allocation.  Errors, all before any launch: N < 0 -> REGNET_ERR_SHAPE; N >= 2^31, k
+ * outside 1..64, min_neighbours < 1, a radius that is not positive and finite, a ratio that is negative or not finite ->
+ * REGNET_ERR_UNSUPPORTED; a NULL pointer for a required array -> REGNET_ERR_NULL.  N == 0: success, the radius and knn entries
+ * touch no output (the statistics are those of no row).                                                                       */
+int64_t regnet_outlier_workspace_bytes(int64_t N);
+int regnet_outlier_radius_f32(const float* xyz, const uint8_t* mask, int64_t N, float radius, int64_t min_neighbours,
+                              int32_t* count, void* workspace, void* stream);
+int regnet_outlier_knn_f32(const float* xyz, const uint8_t* mask, int64_t N, int64_t k, float max_radius, float* mean_dist,
+                           int32_t* found, void* workspace, void* stream);
+int regnet_outlier_stats_f64(const float* mean_dist, const int32_t* found, int64_t N, int64_t k, double ratio, double* stats,
+                             void* stream);
+
 /* ---- multi-view fusion (csrc/fuse.hip): a voxel-grid merge of up to 8 posed clouds into one cloud, on the device ------------
  * One output point per occupied voxel: the centroid of the voxel's points and colours.  Canonical fp32 arithmetic: individually
  * rounded binary32 operations in the written order (-ffp-contract=off); no float is ever summed, so the result is bitwise

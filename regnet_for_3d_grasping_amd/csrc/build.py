@@ -45,6 +45,7 @@ SOURCES = [
     ("fuse.hip", ["-ffp-contract=off"]),   # multi-view fusion: every voxel is decided on individually rounded fp32 arithmetic
     ("icp.hip", ["-ffp-contract=off"]),   # pose refinement: every correspondence is decided on individually rounded fp32 distances
     ("approach.hip", ["-ffp-contract=off"]),   # approach analysis: every box, sweep and band test is on individually rounded fp32 coordinates
+    ("outlier.hip", ["-ffp-contract=off"]),   # outlier removal: every neighbour is decided on individually rounded fp32 distances
 ]
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc"]
@@ -78,7 +79,7 @@ NO_VGPR_SPILL = {"mlp.o": ["mlp_gemm_kernelILi0E", "gemm2_kernel"], "sa_chain.o"
                  "heads.o": ["heads_chain_kernel", "heads_tree_kernel"], "ops_f64.o": ["_f64_kernel"],
                  "scatter.o": ["scatter_", "segsum_"], "det.o": ["det_"],
                  "ingest.o": ["ingest_"], "nms.o": ["nms_"], "plane.o": ["plane_"], "depth.o": ["depth_"],
-                 "fuse.o": ["fuse_"], "icp.o": ["icp_"]}
+                 "fuse.o": ["fuse_"], "icp.o": ["icp_"], "outlier.o": ["outlier_"]}
 
 
 def check_no_vgpr_spill(obj_path, fragments):

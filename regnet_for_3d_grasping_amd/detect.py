@@ -40,6 +40,12 @@ With ``approach`` (``--approach``, ``--approach-standoff``, ``--approach-from``,
 retreat straight back before it touches the cloud, the extent and offset of the object between the fingers, the opening to
 command, the contact check and the pre-grasp point; the record additionally carries ``APPROACH_KEYS``, row-aligned with that set,
 and with ``min_clearance`` / ``min_contact`` the selection sees only the rows that pass.  Without it nothing changes.
+
+With ``denoise`` (``--denoise``, ``--outlier-mode``, ``--outlier-radius``, ``--outlier-min-neighbours``, ``--outlier-knn``,
+``--outlier-max-radius``, ``--outlier-std-ratio``) the cloud of a camera frame -- an ``(xyz, rgb)`` pair, a depth frame's or a
+multi-view merge's -- loses its outliers on the device (``outliers.filter_cloud``: the reference's radius filter, the statistical
+filter, or both) before the table plane is estimated and the frame is cropped; the record additionally carries ``DENOISE_KEYS``.
+Dataset records never see it.  Without it nothing changes and the module is not imported.
 """
 import argparse
 import contextlib
@@ -70,6 +76,7 @@ FUSE_KEYS = ("fuse_num", "fuse_views")                          # added when the
 REGISTER_KEYS = ("fuse_poses", "fuse_register")                 # ... and the detector has ``register``
 APPROACH_KEYS = ("grasp_clearance", "grasp_width", "grasp_offset", "grasp_opening", "grasp_contact",
                  "grasp_pregrasp")                             # added when the detector has ``approach``: one row per source grasp
+DENOISE_KEYS = ("denoise_num",)                                 # added when the detector has ``denoise`` and the frame was a camera frame
 
 
 def save_path_for(pc_path, real_data):
@@ -110,11 +117,16 @@ class GraspDetector:
     and the record also carries, one row per grasp of that set, float32 ``grasp_clearance`` (k,) [m], ``grasp_width`` (k,),
     ``grasp_offset`` (k,), ``grasp_opening`` (k,), ``grasp_contact`` (k,) and ``grasp_pregrasp`` (k,3).  With ``min_clearance`` /
     ``min_contact`` the per-frame or per-object selection sees only the rows that pass (its source must then be the analysed
-    set); ``grasp_selected_index`` still holds rows of the full set, and the four sets are never shortened."""
+    set); ``grasp_selected_index`` still holds rows of the full set, and the four sets are never shortened.
+    ``denoise``: None, or an ``outliers.OutlierParams`` / a dict of its fields (``mode``, ``radius``, ``min_neighbours``, ``knn``,
+    ``max_radius``, ``std_ratio``): the cloud of a camera frame is filtered on the device after ``to_cloud`` / ``fuse_frames`` and
+    before the table plane and the crop -- the removed rows become NaN rows, which both treat as absent -- and the record also
+    carries ``denoise_num`` (5,) int32, the rows that were no point, had too few rows within ``radius``, fewer than ``knn`` rows
+    within ``max_radius``, a mean distance above the threshold, and were kept.  Records and ``ingest.Frame``s never see it."""
 
     def __init__(self, score_net, region_net, params=TEST_PARAMS, gripper_params=GRIPPER_PARAMS, eval_params=EVAL_PARAMS,
                  transform=None, bounds=None, num_points=ALL_POINTS_NUM, use_theta=USE_THETA, select=None, depth=None, segment=None,
-                 fuse=None, register=None, approach=None):
+                 fuse=None, register=None, approach=None, denoise=None):
         from . import depth_frame, fusion, grasp_select, ingest, registration
         from . import segment as segment_mod
         self.fuse = fusion.FuseParams.coerce(fuse)
@@ -134,6 +146,10 @@ class GraspDetector:
             if self.approach.filters() and self.approach_source != selected:
                 raise ValueError("approach: min_clearance / min_contact filter the selection, whose source is %s, not %s"
                                  % (selected, self.approach_source))
+        self.denoise = None
+        if denoise is not None:                   # (the module is not even imported without it)
+            from . import outliers
+            self.denoise = outliers.OutlierParams.coerce(denoise)
         self.score_net, self.region_net = score_net, region_net
         self.params, self.gripper_params, self.eval_params = list(params), list(gripper_params), list(eval_params)
         self.auto_table = None                    # estimate_plane's keywords when the transform is estimated per frame
@@ -154,14 +170,15 @@ class GraspDetector:
     def ingest(self, frame):
         """``frame``: an ``ingest.Frame``, an ``(xyz, rgb)`` pair of a camera frame, a ``depth_frame.DepthFrame``, a
         ``fusion.MultiView`` or a record dict -> ``ingest.Frame``; what was found on the way rides on it: ``fused`` (the
-        ``fusion.Fused`` of a ``MultiView``) and ``table`` (the (transform, plane) estimated in the frame), else None."""
+        ``fusion.Fused`` of a ``MultiView``), ``table`` (the (transform, plane) estimated in the frame) and ``denoised`` (the
+        ``outliers.Filtered`` of a camera frame's cloud when the detector has ``denoise``), else None."""
         from . import depth_frame, fusion, ingest
         from ._frame_util import to_device
         if isinstance(frame, ingest.Frame):
             return frame
         if isinstance(frame, dict):
             return ingest.ingest_record(frame, self.num_points, self.device)
-        fused = table = None
+        fused = table = denoised = None
         if isinstance(frame, fusion.MultiView):            # merged on the device, no host read; the rows beyond the merged
             fused = fusion.fuse_frames(frame, self.depth, self.fuse, device=self.device,         # points are NaN rows
                                        register=self.register)
@@ -169,6 +186,11 @@ class GraspDetector:
         elif isinstance(frame, depth_frame.DepthFrame):    # on the device, no host read; draws nothing from numpy's stream
             frame = depth_frame.to_cloud(frame, self.depth, device=self.device)
         xyz, rgb = frame
+        if self.denoise is not None:              # on the device, no host read; draws nothing from numpy's stream
+            from . import outliers
+            xyz, rgb = to_device(xyz, self.device), to_device(rgb, self.device)
+            denoised = outliers.filter_cloud(xyz, self.denoise)
+            xyz, rgb = denoised.apply(xyz, rgb)
         transform = self.transform
         if self.auto_table is not None:           # draws nothing from numpy's stream; one 96-byte read
             from . import table_plane
@@ -176,7 +198,7 @@ class GraspDetector:
             table = table_plane.calibrate(xyz, self.eval_params[2], **self.auto_table)
             transform = table[0]
         fr = ingest.ingest_frame(xyz, rgb, transform, self.bounds, self.num_points, self.device)
-        fr.fused, fr.table = fused, table
+        fr.fused, fr.table, fr.denoised = fused, table, denoised
         return fr
 
     def calibrate(self, frame, **estimate_kwargs):
@@ -292,6 +314,9 @@ class GraspDetector:
                 out["fuse_poses"] = np.array(fr.fused.poses, dtype=np.float64)
                 out["fuse_register"] = np.array(fr.fused.register, dtype=np.float64)
                 keys = keys + REGISTER_KEYS
+        if getattr(fr, "denoised", None) is not None:
+            out["denoise_num"] = fr.denoised.num.cpu().numpy()
+            keys = keys + DENOISE_KEYS
         return {key: out[key] for key in keys}
 
     def detect(self, frame):
@@ -405,6 +430,15 @@ _FLAGS = (
      "judge the contacts: half angle of the friction cone about the closing axis [deg] (off)"),
     ("--min-clearance", "approach", "min_clearance", float, "select only grasps that can retreat this far [m]"),
     ("--min-contact", "approach", "min_contact", float, "select only grasps whose contact share is at least this"),
+    # outlier removal of a camera frame's cloud (outliers.filter_cloud): --denoise or any of the six turns it on
+    ("--outlier-mode", "outliers", "mode", ("radius", "statistical", "both"),
+     "the radius filter, the statistical filter, or the first and then the second on its survivors"),
+    ("--outlier-radius", "outliers", "radius", float, "a point stays when enough others lie within this distance (%s m)"),
+    ("--outlier-min-neighbours", "outliers", "min_neighbours", int, "... at least so many (%s points)"),
+    ("--outlier-knn", "outliers", "knn", int, "the statistical filter takes the mean distance to so many nearest points, at most 64 (%s points)"),
+    ("--outlier-max-radius", "outliers", "max_radius", float, "... looked for within this distance (%s m)"),
+    ("--outlier-std-ratio", "outliers", "std_ratio", float,
+     "a point stays when its mean distance is at most the cloud's mean plus so many standard deviations (%s deviations)"),
 )
 
 
@@ -459,14 +493,21 @@ def approach_from_args(args):
     return given if (given or args.approach) else None
 
 
+def outliers_from_args(args):
+    """The CLI's seven outlier flags -> a ``denoise`` dict, or None when none of them was given."""
+    given = _given(args, "outliers")
+    return given if (given or args.denoise) else None
+
+
 def build_parser():
     """The CLI of ``main``: test.py's arguments, ``_FLAGS`` and the irregular flags of each group."""
     from . import approach as approach_mod
-    from . import depth_frame, fusion, grasp_select, registration, table_plane
+    from . import depth_frame, fusion, grasp_select, outliers, registration, table_plane
     from . import segment as segment_mod
     defaults = {"select": grasp_select.SelectParams(), "transform": argparse.Namespace(threshold=table_plane.DEFAULT_THRESHOLD),
                 "depth": depth_frame.DepthParams(), "segment": segment_mod.SegmentParams(), "fuse": fusion.FuseParams(),
-                "register": registration.IcpParams(), "approach": approach_mod.ApproachParams()}
+                "register": registration.IcpParams(), "approach": approach_mod.ApproachParams(),
+                "outliers": outliers.OutlierParams()}
     parser = argparse.ArgumentParser(description="REGNet single-file inference (the reference's test.py)")
     parser.add_argument("--folder", "--folder-name", dest="folder", required=True)
     parser.add_argument("--file", "--file-name", dest="file", default="")
@@ -504,6 +545,9 @@ def build_parser():
     parser.add_argument("--approach", action="store_true",
                         help="analyse every grasp of one set: approach clearance, closing width, opening and pre-grasp point")
     regular("approach")
+    parser.add_argument("--denoise", action="store_true",
+                        help="remove the outliers of a camera frame's cloud before the table plane and the crop")
+    regular("outliers")
     return parser
 
 
@@ -523,7 +567,7 @@ def main(argv=None):
     detector = GraspDetector(score_net.to(dev), region_net.to(dev), eval_params=eval_params, select=select,
                              transform=transform_from_args(args), depth=depth_from_args(args),
                              segment=segment_from_args(args), fuse=fuse_from_args(args), register=register_from_args(args),
-                             approach=approach_from_args(args))
+                             approach=approach_from_args(args), denoise=outliers_from_args(args))
     real_data = "real_data" in args.folder
     if args.file:
         paths = [os.path.join(args.folder, args.file)]
