@@ -1116,6 +1116,75 @@ int regnet_fuse_finalise_f32(int64_t max_voxels, int64_t min_count, int64_t* kep
 int regnet_fuse_emit_f32(const int64_t* order, const float* origin3, double voxel, int64_t max_voxels, float* xyz, float* rgb,
                          int32_t* count, int32_t* views, int32_t* first, int32_t* num, void* workspace, void* stream);
 
+/* ---- TSDF volume (csrc/tsdf.hip): depth views fused into a truncated signed distance volume, its surface extracted -----------
+ * Voxel-parallel, one owner per voxel: no floating-point atomic and no sum whose order is open.  Canonical fp32 arithmetic:
+ * individually rounded binary32 operations in the written order (-ffp-contract=off), divisions correctly rounded (__fdiv_rn),
+ * roots correctly rounded (sqrtf).  voxel_f = float32(voxel), trunc_f = float32(trunc), rtrunc = float32(1.0 / trunc) with the
+ * division in float64; origin3 (3 float32, HOST), rounded once by the caller.
+ *   volume      nx x ny x nz voxels, N = nx ny nz <= 2^28; the linear index of voxel (ix, iy, iz) is l = (iz ny + iy) nx + ix.
+ *               `volume` is FIVE PLANES of N 4-byte words, 20 bytes per voxel, 4-byte aligned: D (N float32, the running mean of
+ *               the truncated distance in units of trunc), W (N int32, the observation count), C_r, C_g, C_b (N float32 each, the
+ *               running mean colour).  Planes and not interleaved records: a wave of 64 consecutive ix then reads and writes 256
+ *               contiguous bytes of every plane, and the extraction, which needs D and W only, leaves the colours in HBM.
+ *               regnet_tsdf_bytes(nx, ny, nz) = 20 N, -1 for dims < 1 or N > 2^28.  regnet_tsdf_integrate_workgroups: the
+ *               workgroups of one integrate launch for these dims (the tiling below), -1 likewise; tests size a case by it.
+ *   centre      p_k = o_k + ((float)i_k + 0.5f) * voxel_f per axis k.
+ * regnet_tsdf_reset: D = 1, W = 0, C = 0 for every voxel.  One launch.
+ * regnet_tsdf_integrate_f32: ONE view into the volume; the views' order is the call order and is part of the result.
+ *   xyz         (height width, 3) float32: the view's organised cloud in ITS CAMERA's frame, row v width + u for pixel (u, v), a
+ *               row without a point holding a non-finite z (regnet_depth_to_cloud_*'s output); only z is read.
+ *   rgb         (height width, 3) float32 or NULL (colour 0).
+ *   intrinsics4 (4 float32, HOST): fx, fy, cx, cy.   pose12 (12 float32, HOST): rows 0..2 of the row-major 4x4 COMMON-TO-CAMERA
+ *               transform, inverted in float64 by the caller and rounded once.
+ *   per voxel   1. x = (((r00 px) + (r01 py)) + (r02 pz)) + t0 and likewise y, z.  z not finite or z <= 0: NOT IN VIEW.
+ *               2. u = (__fdiv_rn(x, z) * fx) + cx, fu = floorf(u + 0.5f); inside iff fu >= 0 && fu < (float)width, compared in
+ *                  float (a NaN fails); likewise v with fy, cy, height.  Outside: NOT IN VIEW.  (regnet_depth_to_cloud_*'s
+ *                  projection, restated.)
+ *               3. zd = xyz[(fv width + fu) 3 + 2].  Not finite: NO DEPTH.
+ *               4. sdf = zd - z.  sdf < -trunc_f: BEHIND the surface, the voxel is untouched.  Else t = fminf(sdf * rtrunc, 1.0f).
+ *               5. Wf = (float)W;  D = __fdiv_rn((D * Wf) + t, Wf + 1.0f);  C_c = __fdiv_rn((C_c * Wf) + rgb_c, Wf + 1.0f) for
+ *                  the pixel's colour (0 with rgb NULL);  W = min(W + 1, max_weight).  UPDATED.
+ *   counts      (4) int32 DEVICE, this call's histogram: updated, not in view, no depth, behind (their sum is N).  Cleared by a
+ *               one-workgroup kernel, then one integer atomic per workgroup and code.
+ *               Two launches.  A 64 x 4 tile of voxels per 256-thread workgroup, ix on the lane, over 16 z layers one after the
+ *               other.  A layer of the tile none of whose voxels is in view (decided by step 1-2 of every one of them) only adds
+ *               its voxel count to the not-in-view code; a workgroup all of whose layers are so never touches the volume.
+ * Extraction.  A candidate is (voxel v, axis a in 0..2 = x, y, z) whose neighbour n = v + e_a is inside the volume.  It is kept iff
+ *               W_v >= min_weight && W_n >= min_weight, D_v < 1 && D_n < 1, and (D_v < 0) != (D_n < 0).  Its key is 3 l(v) + a.
+ *   row         s = __fdiv_rn(D_v, D_v - D_n).  xyz = p_v with (p_v[a] + (s * voxel_f)) on axis a.  rgb_c = C_v + (s * (C_n - C_v)).
+ *               gradient of a voxel q along axis k, with lo = q - e_k, hi = q + e_k `usable` iff inside and W >= min_weight:
+ *               both: D(hi) - D(lo); hi only: (D(hi) - D(q)) * 2.0f; lo only: (D(q) - D(lo)) * 2.0f; neither: 0.
+ *               g_k = gv_k + (s * (gn_k - gv_k)); len2 = ((gx gx) + (gy gy)) + (gz gz); len2 finite and > 0: normal_k =
+ *               __fdiv_rn(g_k, sqrtf(len2)), else three quiet NaNs.  D grows towards free space: the normal points out of the
+ *               surface.  weight = min(W_v, W_n).
+ *   regnet_tsdf_count   pass 1: block_counts (regnet_tsdf_blocks(nx, ny, nz) = ceil(N / 256)) int32 DEVICE, the kept candidates
+ *               of the voxels l in [256 b, 256 b + 256); num[2] = the voxels with W >= min_weight (num is cleared first).  Two
+ *               launches; a workgroup takes 16 blocks one after the other and adds to num[2] once.
+ *   (the caller)        block_base = the exclusive prefix sum of block_counts, int32 DEVICE.
+ *   regnet_tsdf_emit_f32  pass 2: recomputes the predicate, ranks the kept candidates of a workgroup in key order (ballots within a
+ *               wave, the waves' totals through LDS) and writes row block_base[b] + rank when that is below max_points: rows
+ *               ascend by key with no sort.  With T = block_base[last] + block_counts[last] and K = min(T, max_points):
+ *               xyz, rgb, normal (max_points,3) float32 and weight (max_points) int32, rows >= K holding the quiet NaN
+ *               0x7FC00000 / 0 / NaN / -1; num (4) int32 DEVICE = K, T, (pass 1's) voxels with W >= min_weight, overflow = T >
+ *               max_points.  On overflow the rows are those of the max_points smallest keys.  Two launches.  num must be the
+ *               array pass 1 was given.
+ * No host read, no synchronisation, no allocation, no cooperative launch; no workgroup waits for another.  Errors, all before any
+ * launch: a dim, width, height, max_weight, min_weight or max_points < 1 -> REGNET_ERR_SHAPE; N > 2^28, width height > 2^21,
+ * max_points > 2^21, voxel or trunc not finite or not positive (in float32 too), 1 / trunc not finite in float32 ->
+ * REGNET_ERR_UNSUPPORTED; a NULL pointer for a required array -> REGNET_ERR_NULL.                                          */
+int64_t regnet_tsdf_bytes(int64_t nx, int64_t ny, int64_t nz);
+int64_t regnet_tsdf_blocks(int64_t nx, int64_t ny, int64_t nz);
+int64_t regnet_tsdf_integrate_workgroups(int64_t nx, int64_t ny, int64_t nz);
+int regnet_tsdf_reset(void* volume, int64_t nx, int64_t ny, int64_t nz, void* stream);
+int regnet_tsdf_integrate_f32(void* volume, int64_t nx, int64_t ny, int64_t nz, const float* origin3, double voxel, double trunc,
+                              int64_t max_weight, const float* xyz, const float* rgb, int64_t width, int64_t height,
+                              const float* intrinsics4, const float* pose12, int32_t* counts, void* stream);
+int regnet_tsdf_count(const void* volume, int64_t nx, int64_t ny, int64_t nz, int64_t min_weight, int32_t* block_counts,
+                      int32_t* num, void* stream);
+int regnet_tsdf_emit_f32(const void* volume, int64_t nx, int64_t ny, int64_t nz, const float* origin3, double voxel,
+                         int64_t min_weight, const int32_t* block_counts, const int32_t* block_base, int64_t max_points,
+                         float* xyz, float* rgb, float* normal, int32_t* weight, int32_t* num, void* stream);
+
 /* ---- pose refinement (csrc/icp.hip): point-to-plane ICP of a source cloud onto a target cloud with normals, on the device ----
  * What corrects a camera pose before the merge above.  Correspondences are decided on canonical fp32 arithmetic (individually
  * rounded binary32 operations in the written order, -ffp-contract=off); residuals, normal equations, solve and pose update are

@@ -46,6 +46,12 @@ With ``denoise`` (``--denoise``, ``--outlier-mode``, ``--outlier-radius``, ``--o
 multi-view merge's -- loses its outliers on the device (``outliers.filter_cloud``: the reference's radius filter, the statistical
 filter, or both) before the table plane is estimated and the frame is cropped; the record additionally carries ``DENOISE_KEYS``.
 Dataset records never see it.  Without it nothing changes and the module is not imported.
+
+With ``volume`` (``--tsdf``, ``--tsdf-voxel``, ``--tsdf-trunc``, ``--tsdf-origin``, ``--tsdf-dims``, ``--tsdf-min-weight``) a
+``fusion.MultiView`` is not merged point by point but integrated view by view into a truncated signed distance volume on the
+device, whose surface becomes the cloud (``tsdf.fuse_volume``): noise along the viewing rays averages out and what one view sees
+another may declare empty; ``register`` applies as before.  The record then carries ``TSDF_KEYS`` (and ``REGISTER_KEYS``) instead of
+``FUSE_KEYS``.  Without it nothing changes and the module is not imported.
 """
 import argparse
 import contextlib
@@ -76,6 +82,7 @@ FUSE_KEYS = ("fuse_num", "fuse_views")                          # added when the
 REGISTER_KEYS = ("fuse_poses", "fuse_register")                 # ... and the detector has ``register``
 APPROACH_KEYS = ("grasp_clearance", "grasp_width", "grasp_offset", "grasp_opening", "grasp_contact",
                  "grasp_pregrasp")                             # added when the detector has ``approach``: one row per source grasp
+TSDF_KEYS = ("tsdf_num", "tsdf_counts")                        # added when the frame was a ``MultiView`` and the detector has ``volume``
 DENOISE_KEYS = ("denoise_num",)                                 # added when the detector has ``denoise`` and the frame was a camera frame
 
 
@@ -122,11 +129,17 @@ class GraspDetector:
     ``max_radius``, ``std_ratio``): the cloud of a camera frame is filtered on the device after ``to_cloud`` / ``fuse_frames`` and
     before the table plane and the crop -- the removed rows become NaN rows, which both treat as absent -- and the record also
     carries ``denoise_num`` (5,) int32, the rows that were no point, had too few rows within ``radius``, fewer than ``knn`` rows
-    within ``max_radius``, a mean distance above the threshold, and were kept.  Records and ``ingest.Frame``s never see it."""
+    within ``max_radius``, a mean distance above the threshold, and were kept.  Records and ``ingest.Frame``s never see it.
+    ``volume``: None, or a ``tsdf.TsdfParams`` / a dict of its fields (``voxel``, ``trunc``, ``origin``, ``dims``, ``max_weight``,
+    ``min_weight``, ``max_points``): a ``MultiView`` goes through ``tsdf.fuse_volume`` instead of ``fusion.fuse_frames`` -- the views
+    are integrated in their order into a TSDF volume, kept between frames, and its surface is the cloud -- and the record carries
+    ``tsdf_num`` (4,) int32 = (surface rows, kept candidates, observed voxels, overflow) and ``tsdf_counts`` (views,4) int32, per
+    view the voxels updated, not in view, without depth and behind the surface, and with ``register`` ``fuse_poses`` /
+    ``fuse_register`` as above, in place of ``fuse_num`` / ``fuse_views``.  Together with ``fuse`` it is a ValueError."""
 
     def __init__(self, score_net, region_net, params=TEST_PARAMS, gripper_params=GRIPPER_PARAMS, eval_params=EVAL_PARAMS,
                  transform=None, bounds=None, num_points=ALL_POINTS_NUM, use_theta=USE_THETA, select=None, depth=None, segment=None,
-                 fuse=None, register=None, approach=None, denoise=None):
+                 fuse=None, register=None, approach=None, denoise=None, volume=None):
         from . import depth_frame, fusion, grasp_select, ingest, registration
         from . import segment as segment_mod
         self.fuse = fusion.FuseParams.coerce(fuse)
@@ -146,6 +159,12 @@ class GraspDetector:
             if self.approach.filters() and self.approach_source != selected:
                 raise ValueError("approach: min_clearance / min_contact filter the selection, whose source is %s, not %s"
                                  % (selected, self.approach_source))
+        self.volume = self.tsdf_volume = None     # the parameters, and the tsdf.Volume kept between frames
+        if volume is not None:                    # (the module is not even imported without it)
+            if fuse is not None:
+                raise ValueError("volume: a MultiView is either merged (fuse) or integrated into a volume, not both")
+            from . import tsdf
+            self.volume = tsdf.TsdfParams.coerce(volume)
         self.denoise = None
         if denoise is not None:                   # (the module is not even imported without it)
             from . import outliers
@@ -170,7 +189,8 @@ class GraspDetector:
     def ingest(self, frame):
         """``frame``: an ``ingest.Frame``, an ``(xyz, rgb)`` pair of a camera frame, a ``depth_frame.DepthFrame``, a
         ``fusion.MultiView`` or a record dict -> ``ingest.Frame``; what was found on the way rides on it: ``fused`` (the
-        ``fusion.Fused`` of a ``MultiView``), ``table`` (the (transform, plane) estimated in the frame) and ``denoised`` (the
+        ``fusion.Fused`` of a ``MultiView``, or with ``volume`` its ``tsdf.Surface``), ``table`` (the (transform, plane)
+        estimated in the frame) and ``denoised`` (the
         ``outliers.Filtered`` of a camera frame's cloud when the detector has ``denoise``), else None."""
         from . import depth_frame, fusion, ingest
         from ._frame_util import to_device
@@ -179,7 +199,13 @@ class GraspDetector:
         if isinstance(frame, dict):
             return ingest.ingest_record(frame, self.num_points, self.device)
         fused = table = denoised = None
-        if isinstance(frame, fusion.MultiView):            # merged on the device, no host read; the rows beyond the merged
+        if isinstance(frame, fusion.MultiView) and self.volume is not None:     # integrated on the device, no host read
+            from . import tsdf
+            fused = tsdf.fuse_volume(frame, self.depth, self.volume, device=self.device, register=self.register,
+                                     volume=self.tsdf_volume)
+            self.tsdf_volume = fused.volume
+            frame = fused.cloud()
+        elif isinstance(frame, fusion.MultiView):          # merged on the device, no host read; the rows beyond the merged
             fused = fusion.fuse_frames(frame, self.depth, self.fuse, device=self.device,         # points are NaN rows
                                        register=self.register)
             frame = fused.cloud()
@@ -307,9 +333,18 @@ class GraspDetector:
             out["table_plane"] = np.array(list(plane.normal) + [plane.offset, plane.rms], dtype=np.float64)
             keys = keys + TABLE_KEYS
         if fr.fused is not None:
-            out["fuse_num"] = fr.fused.num.cpu().numpy()
-            out["fuse_views"] = fr.fused.per_view().cpu().numpy()
-            keys = keys + FUSE_KEYS
+            from_volume = False
+            if self.volume is not None:           # (the module is imported: the detector has ``volume``)
+                from . import tsdf
+                from_volume = isinstance(fr.fused, tsdf.Surface)
+            if from_volume:
+                out["tsdf_num"] = fr.fused.num.cpu().numpy()
+                out["tsdf_counts"] = fr.fused.counts.cpu().numpy()
+                keys = keys + TSDF_KEYS
+            else:
+                out["fuse_num"] = fr.fused.num.cpu().numpy()
+                out["fuse_views"] = fr.fused.per_view().cpu().numpy()
+                keys = keys + FUSE_KEYS
             if fr.fused.register is not None:
                 out["fuse_poses"] = np.array(fr.fused.poses, dtype=np.float64)
                 out["fuse_register"] = np.array(fr.fused.register, dtype=np.float64)
@@ -430,6 +465,10 @@ _FLAGS = (
      "judge the contacts: half angle of the friction cone about the closing axis [deg] (off)"),
     ("--min-clearance", "approach", "min_clearance", float, "select only grasps that can retreat this far [m]"),
     ("--min-contact", "approach", "min_contact", float, "select only grasps whose contact share is at least this"),
+    # a TSDF volume in place of the point merge (tsdf.fuse_volume): --tsdf or any of the five turns it on
+    ("--tsdf-voxel", "volume", "voxel", float, "edge of the voxels of the volume (%s m)"),
+    ("--tsdf-trunc", "volume", "trunc", float, "truncation distance, at least two voxels (%s m)"),
+    ("--tsdf-min-weight", "volume", "min_weight", int, "a voxel bounds a surface when so many views observed it (%s views)"),
     # outlier removal of a camera frame's cloud (outliers.filter_cloud): --denoise or any of the six turns it on
     ("--outlier-mode", "outliers", "mode", ("radius", "statistical", "both"),
      "the radius filter, the statistical filter, or the first and then the second on its survivors"),
@@ -499,15 +538,25 @@ def outliers_from_args(args):
     return given if (given or args.denoise) else None
 
 
+def volume_from_args(args):
+    """The CLI's six volume flags -> a ``volume`` dict, or None when none of them was given."""
+    given = _given(args, "volume")
+    if args.tsdf_origin is not None:
+        given["origin"] = tuple(float(v) for v in args.tsdf_origin)
+    if args.tsdf_dims is not None:
+        given["dims"] = tuple(int(v) for v in args.tsdf_dims)
+    return given if (given or args.tsdf) else None
+
+
 def build_parser():
     """The CLI of ``main``: test.py's arguments, ``_FLAGS`` and the irregular flags of each group."""
     from . import approach as approach_mod
-    from . import depth_frame, fusion, grasp_select, outliers, registration, table_plane
+    from . import depth_frame, fusion, grasp_select, outliers, registration, table_plane, tsdf
     from . import segment as segment_mod
     defaults = {"select": grasp_select.SelectParams(), "transform": argparse.Namespace(threshold=table_plane.DEFAULT_THRESHOLD),
                 "depth": depth_frame.DepthParams(), "segment": segment_mod.SegmentParams(), "fuse": fusion.FuseParams(),
                 "register": registration.IcpParams(), "approach": approach_mod.ApproachParams(),
-                "outliers": outliers.OutlierParams()}
+                "outliers": outliers.OutlierParams(), "volume": tsdf.TsdfParams()}
     parser = argparse.ArgumentParser(description="REGNet single-file inference (the reference's test.py)")
     parser.add_argument("--folder", "--folder-name", dest="folder", required=True)
     parser.add_argument("--file", "--file-name", dest="file", default="")
@@ -548,6 +597,14 @@ def build_parser():
     parser.add_argument("--denoise", action="store_true",
                         help="remove the outliers of a camera frame's cloud before the table plane and the crop")
     regular("outliers")
+    parser.add_argument("--tsdf", action="store_true",
+                        help="integrate the views of a multi-view frame into a TSDF volume and take its surface, instead of "
+                             "merging their points")
+    parser.add_argument("--tsdf-origin", type=float, nargs=3, metavar=("X", "Y", "Z"), default=None,
+                        help="corner of voxel (0, 0, 0) in the common frame (%g %g %g m)" % defaults["volume"].origin)
+    parser.add_argument("--tsdf-dims", type=int, nargs=3, metavar=("NX", "NY", "NZ"), default=None,
+                        help="voxels per axis, at most 2^28 in all (%d %d %d voxels)" % defaults["volume"].dims)
+    regular("volume")
     return parser
 
 
@@ -567,7 +624,8 @@ def main(argv=None):
     detector = GraspDetector(score_net.to(dev), region_net.to(dev), eval_params=eval_params, select=select,
                              transform=transform_from_args(args), depth=depth_from_args(args),
                              segment=segment_from_args(args), fuse=fuse_from_args(args), register=register_from_args(args),
-                             approach=approach_from_args(args), denoise=outliers_from_args(args))
+                             approach=approach_from_args(args), denoise=outliers_from_args(args),
+                             volume=volume_from_args(args))
     real_data = "real_data" in args.folder
     if args.file:
         paths = [os.path.join(args.folder, args.file)]
