@@ -1185,6 +1185,52 @@ int regnet_tsdf_emit_f32(const void* volume, int64_t nx, int64_t ny, int64_t nz,
                          int64_t min_weight, const int32_t* block_counts, const int32_t* block_base, int64_t max_points,
                          float* xyz, float* rgb, float* normal, int32_t* weight, int32_t* num, void* stream);
 
+/* regnet_tsdf_raycast_f32: the MODEL VIEW of the volume from a virtual pinhole camera -- per pixel the first zero crossing of D
+ * along its ray, with the normal of D's gradient and the colour there: the organised vertex and normal map
+ * regnet_icp_step_projective_f32 takes as its target (frame-to-model tracking), and a denoised depth image of the fused model.
+ * The volume is only read (D, W, and C when rgb is given).  A lane per pixel; the canonical fp32 arithmetic of the section above.
+ *   volume, dims, origin3, voxel, min_weight   as for regnet_tsdf_emit_f32; here every dim <= 2^24 (the inside test below then
+ *               compares exact floats).
+ *   intrinsics4 (4 float32, HOST): rfx = float32(1 / fx), rfy = float32(1 / fy), cx, cy, the reciprocals taken in float64.
+ *   pose12      (12 float32, HOST): rows 0..2 of the row-major 4x4 CAMERA-TO-COMMON transform, rounded once (not inverted).
+ *   near, step, n_steps   the depth of sample i is z_i = near_f + ((float)i * step_f), i = 0 .. n_steps - 1; never accumulated.
+ *   ray point   of pixel (u, v) at depth z.  Camera frame: c_x = (((float)u - cx) * z) * rfx, c_y = (((float)v - cy) * z) * rfy,
+ *               c_z = z (regnet_depth_to_cloud_*'s deprojection).  Common frame: p_k = (((r_k0 c_x) + (r_k1 c_y)) + (r_k2 c_z)) + t_k.
+ *   sample S(p) per axis g_k = __fdiv_rn(p_k - o_k, voxel_f) - 0.5f, i_k = floorf(g_k), f_k = g_k - i_k.  INSIDE iff for every axis
+ *               i_k >= 0 && i_k + 1.0f <= (float)(n_k - 1), compared in float (a NaN fails).  KNOWN iff inside and the eight
+ *               voxels (i_x + a, i_y + b, i_z + c), a, b, c in {0, 1}, all have W >= min_weight; else UNKNOWN.  The value of a
+ *               plane P there: along x c_bc = P_0bc + (f_x * (P_1bc - P_0bc)), along y c_c = c_0c + (f_y * (c_1c - c_0c)), along z
+ *               c_0 + (f_z * (c_1 - c_0)).  S is that value of D.
+ *   march       over i ascending, with "previous" = the sample i - 1 when it was known with a value > 0 (a NaN value is none):
+ *               an unknown sample: no previous.  A known sample with value v <= 0: with no previous the ray ends as BACK FACE (it
+ *               came out of unseen space behind a surface, or started inside one); with the previous v_prev it ends as a HIT,
+ *               s = __fdiv_rn(v_prev, v_prev - v), z_hit = z_{i-1} + (s * step_f).  Any other known sample becomes the previous
+ *               when its value is > 0.  A ray that ends neither way: NO SURFACE.
+ *   hit         xyz = the camera-frame ray point at z_hit; p = its common-frame point.
+ *   normal      g_k = S(p + voxel_f e_k) - S(p - voxel_f e_k); any of the six unknown: HIT, NO NORMAL.  Into the camera frame with
+ *               the transpose: n_x = ((r_00 g_x) + (r_10 g_y)) + (r_20 g_z), likewise n_y, n_z.  len2 = ((n_x n_x) + (n_y n_y)) +
+ *               (n_z n_z); not finite or <= 0: HIT, NO NORMAL.  Else n_k = __fdiv_rn(n_k, sqrtf(len2)), negated when
+ *               ((n_x c_x) + (n_y c_y)) + (n_z c_z) > 0: it faces the camera (regnet_depth_normals_f32's rule).
+ *   colour      rgb NULL: none.  Else the values of C_r, C_g, C_b at p when that sample is known, else 0.
+ * Outputs, DEVICE memory, written whole: xyz, normals (height width, 3) float32, row v width + u, IN THE VIRTUAL CAMERA's frame
+ * (regnet_icp_step_projective_f32's target layout): the quiet NaN 0x7FC00000 in xyz without a hit and in normals without a normal;
+ * rgb (height width, 3) float32 or NULL: 0 without a hit; status (height width) uint8: 0 no surface, 1 back face, 2 hit, 3 hit
+ * without normal; counts (4) int32: the histogram of status, cleared by a one-workgroup kernel, then one integer atomic per
+ * workgroup and code.  Two launches; 16 x 16 pixels per 256-thread workgroup, an 8 x 8 tile per wave.
+ *   clip        != 0: a ray visits only the samples between which a slab test (float64, the box of voxel centres grown by a voxel
+ *               and by 2^-18 of every magnitude entering p, the range by one sample either way) says it can be inside; the rest
+ *               are unknown by the sample rule, so clip changes the time and no bit of the result.  0: every sample is visited.
+ *               The slack is an ARGUED bound (at most 8 roundings of 2^-24 enter p and g, the slack allows 64), not a proven
+ *               one; it is held by the bit-for-bit comparison with a restatement that clips nothing, and clip = 0 is the way out.
+ * No host read, no synchronisation, no allocation, no cooperative launch, no floating-point atomic: capturable.  Errors, all before
+ * any launch: a dim, width, height, min_weight or n_steps < 1 -> REGNET_ERR_SHAPE; N > 2^28, a dim > 2^24, width height > 2^21,
+ * n_steps > 4096, voxel, near or step not finite or not positive (in float32 too) -> REGNET_ERR_UNSUPPORTED; a NULL pointer for a
+ * required array (all but rgb) -> REGNET_ERR_NULL.                                                                            */
+int regnet_tsdf_raycast_f32(const void* volume, int64_t nx, int64_t ny, int64_t nz, const float* origin3, double voxel,
+                            int64_t min_weight, const float* intrinsics4, const float* pose12, double near, double step,
+                            int64_t n_steps, int64_t width, int64_t height, int clip, float* xyz, float* normals, float* rgb,
+                            uint8_t* status, int32_t* counts, void* stream);
+
 /* ---- pose refinement (csrc/icp.hip): point-to-plane ICP of a source cloud onto a target cloud with normals, on the device ----
  * What corrects a camera pose before the merge above.  Correspondences are decided on canonical fp32 arithmetic (individually
  * rounded binary32 operations in the written order, -ffp-contract=off); residuals, normal equations, solve and pose update are

@@ -18,6 +18,11 @@
 //     prefix sum gives every block its first row; the emit pass recomputes the predicate and ranks in key order (three ballots
 //     per wave, the waves' totals through LDS).
 //   * tsdf_tail_kernel: the sentinels beyond the K rows, and num.
+//   * tsdf_raycast_kernel: a lane per pixel of a virtual pinhole camera marches its ray through the volume, which it only reads
+//     (tests/tsdf_raycast_reference.py restates it).  A wave is an 8 x 8 pixel tile, so its 64 rays stay in neighbouring cells
+//     and their eight corner loads fall on few cache lines.  Every ray starts and ends at the samples a float64 slab test
+//     against the box of voxel centres leaves it (conservatively: the samples skipped are unknown by the sample rule, so the
+//     clip changes no bit).  The histogram collects in LDS as integrate's does.
 // The launches are ordered by the stream: no workgroup waits for another, no flags, no cooperative launch.
 #include "common.h"
 
@@ -314,6 +319,209 @@ __global__ __launch_bounds__(TS_BLOCK) void tsdf_tail_kernel(const int32_t* __re
   weight[row] = -1;
 }
 
+// ---- raycast: the model view of a virtual pinhole camera --------------------------------------------------------------------
+constexpr int RC_TILE = 8;                          // a wave is an 8 x 8 pixel tile: neighbouring rays visit neighbouring voxels
+constexpr int RC_WX = 2, RC_WY = 2;                 // ... and a 256-thread workgroup 2 x 2 of them
+constexpr int RC_MAX_STEPS = 4096;
+constexpr int RC_MAX_DIM = 1 << 24;                 // the inside test compares exact floats up to here
+constexpr double RC_SLACK = 1.0 / 262144.0;         // 2^-18: 64 float32 roundings of the clip's magnitudes
+
+enum { RC_NO_SURFACE = 0, RC_BACK_FACE = 1, RC_HIT = 2, RC_HIT_NO_NORMAL = 3, RC_CODES = 4 };
+
+struct RaycastArgs {
+  int n[3], sy, sz;                                 // dims; words to the next voxel along y and z
+  int min_weight, n_steps, width, height, clip;
+  float top[3];                                     // (float)(n_k - 1)
+  float o[3], voxel;
+  float rfx, rfy, cx, cy;
+  float r[12];
+  float near, step;
+};
+
+// the ray point of pixel (du, dv) = ((float)u - cx, (float)v - cy) at depth z: camera frame, then common frame
+__device__ __forceinline__ void rc_point(const RaycastArgs& a, float du, float dv, float z, float c[3], float p[3]) {
+  c[0] = (du * z) * a.rfx;
+  c[1] = (dv * z) * a.rfy;
+  c[2] = z;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) p[k] = (((a.r[4 * k] * c[0]) + (a.r[4 * k + 1] * c[1])) + (a.r[4 * k + 2] * c[2])) + a.r[4 * k + 3];
+}
+
+// the cell of p: its lower corner's linear index and the three fractions; false when p is not inside the box of voxel centres
+__device__ __forceinline__ bool rc_cell(const RaycastArgs& a, const float p[3], int& l, float f[3]) {
+  bool inside = true;
+  int i[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float g = __fdiv_rn(p[k] - a.o[k], a.voxel) - 0.5f;
+    const float fl = floorf(g);
+    f[k] = g - fl;
+    inside = inside && fl >= 0.0f && (fl + 1.0f) <= a.top[k];      // in float: a NaN fails
+    i[k] = inside ? (int)fl : 0;
+  }
+  l = (i[2] * a.n[1] + i[1]) * a.n[0] + i[0];
+  return inside;
+}
+
+__device__ __forceinline__ bool rc_observed(const int32_t* __restrict__ W, const RaycastArgs& a, int l) {
+  int w = min(W[l], W[l + 1]);
+  w = min(w, min(W[l + a.sy], W[l + a.sy + 1]));
+  w = min(w, min(W[l + a.sz], W[l + a.sz + 1]));
+  w = min(w, min(W[l + a.sz + a.sy], W[l + a.sz + a.sy + 1]));
+  return w >= a.min_weight;
+}
+
+// a + (f * (b - a)) along x, then y, then z
+__device__ __forceinline__ float rc_trilinear(const float* __restrict__ P, const RaycastArgs& a, int l, const float f[3]) {
+  const float d000 = P[l], d100 = P[l + 1], d010 = P[l + a.sy], d110 = P[l + a.sy + 1];
+  const float d001 = P[l + a.sz], d101 = P[l + a.sz + 1], d011 = P[l + a.sz + a.sy], d111 = P[l + a.sz + a.sy + 1];
+  const float c00 = d000 + (f[0] * (d100 - d000)), c10 = d010 + (f[0] * (d110 - d010));
+  const float c01 = d001 + (f[0] * (d101 - d001)), c11 = d011 + (f[0] * (d111 - d011));
+  const float c0 = c00 + (f[1] * (c10 - c00)), c1 = c01 + (f[1] * (c11 - c01));
+  return c0 + (f[2] * (c1 - c0));
+}
+
+// S(p): whether the sample is known, and its value
+__device__ __forceinline__ bool rc_sample(const Planes& v, const RaycastArgs& a, const float p[3], float& value) {
+  int l;
+  float f[3];
+  if (!rc_cell(a, p, l, f) || !rc_observed(v.W, a, l)) return false;
+  value = rc_trilinear(v.D, a, l, f);
+  return true;
+}
+
+// the samples [first, last] outside which the ray's point cannot lie inside the box of voxel centres: a slab test in float64 on
+// the exact ray t + z d, the box grown by a voxel and by RC_SLACK of every magnitude that enters the float32 point (64 times the
+// roundings of rc_point and rc_cell), the range grown by a sample either way.  A NaN constrains nothing.
+__device__ __forceinline__ void rc_clip(const RaycastArgs& a, float du, float dv, int& first, int& last) {
+  const double near = (double)a.near, step = (double)a.step;
+  const double far = near + (double)(a.n_steps - 1) * step;
+  const double dcx = (double)du * (double)a.rfx, dcy = (double)dv * (double)a.rfy;
+  const double zs = RC_SLACK * (fabs(near) + far);
+  double za = near - zs, zb = far + zs;
+  bool empty = false;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double r0 = (double)a.r[4 * k], r1 = (double)a.r[4 * k + 1], r2 = (double)a.r[4 * k + 2], t = (double)a.r[4 * k + 3];
+    const double d = (r0 * dcx + r1 * dcy) + r2;
+    const double o = (double)a.o[k], vx = (double)a.voxel, extent = (double)a.n[k] * vx;
+    const double reach = (fabs(r0 * dcx) + fabs(r1 * dcy) + fabs(r2)) * far;
+    const double m = vx + RC_SLACK * (fabs(t) + reach + fabs(o) + extent);
+    const double lo = o + 0.5 * vx - m, hi = o + extent - 0.5 * vx + m;
+    if (d == 0.0) {
+      empty = empty || t < lo || t > hi;
+    } else {
+      const double z1 = (lo - t) / d, z2 = (hi - t) / d;
+      za = fmax(za, fmin(z1, z2));
+      zb = fmin(zb, fmax(z1, z2));
+    }
+  }
+  if (empty || za > zb) { first = 1; last = 0; return; }
+  const double top = (double)(a.n_steps - 1);
+  first = (int)fmin(fmax(floor((za - near) / step) - 1.0, 0.0), top);
+  last = (int)fmin(fmax(ceil((zb - near) / step) + 1.0, 0.0), top);
+}
+
+__global__ __launch_bounds__(TS_BLOCK) void tsdf_raycast_kernel(Planes vol, const RaycastArgs a, float* __restrict__ xyz,
+                                                                float* __restrict__ normals, float* __restrict__ rgb,
+                                                                uint8_t* __restrict__ status, int32_t* __restrict__ counts) {
+  __shared__ int s_hist[RC_CODES];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tiles_x = (a.width + RC_TILE * RC_WX - 1) / (RC_TILE * RC_WX);
+  const int bx = (int)(blockIdx.x % (unsigned)tiles_x), by = (int)(blockIdx.x / (unsigned)tiles_x);
+  const int u = (bx * RC_WX + (wave % RC_WX)) * RC_TILE + (lane & (RC_TILE - 1));
+  const int v = (by * RC_WY + (wave / RC_WX)) * RC_TILE + (lane / RC_TILE);
+  const bool active = u < a.width && v < a.height;
+  if (tid < RC_CODES) s_hist[tid] = 0;
+  __syncthreads();
+  const float nan = __uint_as_float(TS_QNAN);
+  int code = RC_NO_SURFACE;
+  float hit[3] = {nan, nan, nan}, nrm[3] = {nan, nan, nan}, col[3] = {0.0f, 0.0f, 0.0f};
+  if (active) {
+    const float du = (float)u - a.cx, dv = (float)v - a.cy;
+    int first = 0, last = a.n_steps - 1;
+    if (a.clip) rc_clip(a, du, dv, first, last);
+    bool prev_positive = false;
+    float v_prev = 0.0f, z_prev = 0.0f, z_hit = 0.0f;
+    for (int i = first; i <= last; ++i) {
+      const float z = a.near + ((float)i * a.step);
+      float c[3], p[3], value;
+      rc_point(a, du, dv, z, c, p);
+      if (!rc_sample(vol, a, p, value)) { prev_positive = false; continue; }
+      if (value <= 0.0f) {
+        code = RC_BACK_FACE;
+        if (prev_positive) {
+          code = RC_HIT_NO_NORMAL;
+          const float s = __fdiv_rn(v_prev, v_prev - value);
+          z_hit = z_prev + (s * a.step);
+        }
+        break;
+      }
+      prev_positive = value > 0.0f;      // (a NaN value is no previous sample either)
+      v_prev = value;
+      z_prev = z;
+    }
+    if (code == RC_HIT_NO_NORMAL) {
+      float p[3];
+      rc_point(a, du, dv, z_hit, hit, p);
+      if (rgb) {
+        int l;
+        float f[3];
+        if (rc_cell(a, p, l, f) && rc_observed(vol.W, a, l)) {
+#pragma unroll
+          for (int k = 0; k < 3; ++k) col[k] = rc_trilinear(vol.C[k], a, l, f);
+        }
+      }
+      float g[3];
+      bool known = true;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        float q[3] = {p[0], p[1], p[2]};
+        float hi = 0.0f, lo = 0.0f;
+        q[k] = p[k] + a.voxel;
+        known = rc_sample(vol, a, q, hi) && known;
+        q[k] = p[k] - a.voxel;
+        known = rc_sample(vol, a, q, lo) && known;
+        g[k] = hi - lo;
+      }
+      if (known) {
+        float n[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) n[k] = ((a.r[k] * g[0]) + (a.r[4 + k] * g[1])) + (a.r[8 + k] * g[2]);      // R^T
+        const float len2 = ((n[0] * n[0]) + (n[1] * n[1])) + (n[2] * n[2]);
+        if (__builtin_isfinite(len2) && len2 > 0.0f) {
+          const float len = sqrtf(len2);
+          n[0] = __fdiv_rn(n[0], len); n[1] = __fdiv_rn(n[1], len); n[2] = __fdiv_rn(n[2], len);
+          const float dot = ((n[0] * hit[0]) + (n[1] * hit[1])) + (n[2] * hit[2]);
+          const bool flip = dot > 0.0f;
+#pragma unroll
+          for (int k = 0; k < 3; ++k) nrm[k] = flip ? -n[k] : n[k];
+          code = RC_HIT;
+        }
+      }
+    }
+    const long long row = (long long)v * a.width + u;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      xyz[row * 3 + k] = hit[k];
+      normals[row * 3 + k] = nrm[k];
+      if (rgb) rgb[row * 3 + k] = col[k];
+    }
+    status[row] = (uint8_t)code;
+  }
+#pragma unroll
+  for (int c = 0; c < RC_CODES; ++c) {
+    const int n = __popcll(__ballot(active && code == c));
+    if (lane == 0 && n != 0) atomicAdd(&s_hist[c], n);
+  }
+  // one integer atomic per workgroup and code
+  __syncthreads();
+  if (tid < RC_CODES) {
+    const int n = s_hist[tid];
+    if (n != 0) atomicAdd(&counts[tid], n);
+  }
+}
+
 int tsdf_dims(int64_t nx, int64_t ny, int64_t nz) {
   if (nx < 1 || ny < 1 || nz < 1) return REGNET_ERR_SHAPE;
   if (nx > TS_MAX_VOXELS || ny > TS_MAX_VOXELS || nz > TS_MAX_VOXELS || nx * ny > TS_MAX_VOXELS || nx * ny * nz > TS_MAX_VOXELS)
@@ -423,6 +631,39 @@ extern "C" int regnet_tsdf_emit_f32(const void* volume, int64_t nx, int64_t ny, 
   REGNET_LAUNCH_CHECK();
   hipLaunchKernelGGL(tsdf_tail_kernel, dim3((unsigned)((max_points + TS_BLOCK - 1) / TS_BLOCK)), dim3(TS_BLOCK), 0, s, block_counts,
                      block_base, blocks, (int)max_points, xyz, rgb, normal, weight, num);
+  REGNET_LAUNCH_CHECK();
+  return REGNET_OK;
+}
+
+extern "C" int regnet_tsdf_raycast_f32(const void* volume, int64_t nx, int64_t ny, int64_t nz, const float* origin3, double voxel,
+                                       int64_t min_weight, const float* intrinsics4, const float* pose12, double near, double step,
+                                       int64_t n_steps, int64_t width, int64_t height, int clip, float* xyz, float* normals,
+                                       float* rgb, uint8_t* status, int32_t* counts, void* stream) {
+  const int bad = tsdf_dims(nx, ny, nz);
+  if (bad == REGNET_ERR_SHAPE || width < 1 || height < 1 || min_weight < 1 || n_steps < 1) return REGNET_ERR_SHAPE;
+  if (bad != REGNET_OK) return bad;
+  if (nx > RC_MAX_DIM || ny > RC_MAX_DIM || nz > RC_MAX_DIM) return REGNET_ERR_UNSUPPORTED;
+  if (width > TS_MAX_PIXELS || height > TS_MAX_PIXELS || width * height > TS_MAX_PIXELS || n_steps > RC_MAX_STEPS)
+    return REGNET_ERR_UNSUPPORTED;
+  if (!tsdf_length(voxel) || !tsdf_length(near) || !tsdf_length(step)) return REGNET_ERR_UNSUPPORTED;
+  if (!volume || !origin3 || !intrinsics4 || !pose12 || !xyz || !normals || !status || !counts) return REGNET_ERR_NULL;
+  RaycastArgs a;
+  a.n[0] = (int)nx; a.n[1] = (int)ny; a.n[2] = (int)nz;
+  a.sy = (int)nx; a.sz = (int)(nx * ny);
+  a.min_weight = (int)(min_weight < 0x7FFFFFFF ? min_weight : 0x7FFFFFFF);
+  a.n_steps = (int)n_steps; a.width = (int)width; a.height = (int)height; a.clip = clip != 0;
+  for (int k = 0; k < 3; ++k) { a.top[k] = (float)(a.n[k] - 1); a.o[k] = origin3[k]; }
+  a.voxel = (float)voxel;
+  a.rfx = intrinsics4[0]; a.rfy = intrinsics4[1]; a.cx = intrinsics4[2]; a.cy = intrinsics4[3];
+  for (int i = 0; i < 12; ++i) a.r[i] = pose12[i];
+  a.near = (float)near; a.step = (float)step;
+  hipStream_t s = as_stream(stream);
+  const long long n = (long long)(nx * ny * nz);
+  const long long grid = ((width + RC_TILE * RC_WX - 1) / (RC_TILE * RC_WX)) * ((height + RC_TILE * RC_WY - 1) / (RC_TILE * RC_WY));
+  hipLaunchKernelGGL(tsdf_clear_kernel, dim3(1), dim3(64), 0, s, counts);
+  REGNET_LAUNCH_CHECK();
+  hipLaunchKernelGGL(tsdf_raycast_kernel, dim3((unsigned)grid), dim3(TS_BLOCK), 0, s, planes_of(const_cast<void*>(volume), n), a,
+                     xyz, normals, rgb, status, counts);
   REGNET_LAUNCH_CHECK();
   return REGNET_OK;
 }

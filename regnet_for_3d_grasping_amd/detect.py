@@ -52,6 +52,12 @@ With ``volume`` (``--tsdf``, ``--tsdf-voxel``, ``--tsdf-trunc``, ``--tsdf-origin
 device, whose surface becomes the cloud (``tsdf.fuse_volume``): noise along the viewing rays averages out and what one view sees
 another may declare empty; ``register`` applies as before.  The record then carries ``TSDF_KEYS`` (and ``REGISTER_KEYS``) instead of
 ``FUSE_KEYS``.  Without it nothing changes and the module is not imported.
+
+With ``track`` (``--track``, ``--track-near``, ``--track-far``, ``--track-step``, ``--track-max-translation``,
+``--track-max-rotation``) the ``DepthFrame``s handed to ``detect`` -- on the command line the folder's ``.npz`` frames in the order
+of their names -- are one moving camera whose pose is not given: each is registered against the model view raycast from the
+volume at the last pose and integrated at the pose found (``tsdf.Tracker``), and the volume's surface is the frame's cloud.  The
+record then carries ``TSDF_KEYS`` and ``TRACK_KEYS``.  Without it nothing changes and the module is not imported.
 """
 import argparse
 import contextlib
@@ -83,6 +89,7 @@ REGISTER_KEYS = ("fuse_poses", "fuse_register")                 # ... and the de
 APPROACH_KEYS = ("grasp_clearance", "grasp_width", "grasp_offset", "grasp_opening", "grasp_contact",
                  "grasp_pregrasp")                             # added when the detector has ``approach``: one row per source grasp
 TSDF_KEYS = ("tsdf_num", "tsdf_counts")                        # added when the frame was a ``MultiView`` and the detector has ``volume``
+TRACK_KEYS = ("track_pose", "track_status", "track_report")    # added beside ``TSDF_KEYS`` when the detector has ``track``
 DENOISE_KEYS = ("denoise_num",)                                 # added when the detector has ``denoise`` and the frame was a camera frame
 
 
@@ -135,11 +142,20 @@ class GraspDetector:
     are integrated in their order into a TSDF volume, kept between frames, and its surface is the cloud -- and the record carries
     ``tsdf_num`` (4,) int32 = (surface rows, kept candidates, observed voxels, overflow) and ``tsdf_counts`` (views,4) int32, per
     view the voxels updated, not in view, without depth and behind the surface, and with ``register`` ``fuse_poses`` /
-    ``fuse_register`` as above, in place of ``fuse_num`` / ``fuse_views``.  Together with ``fuse`` it is a ValueError."""
+    ``fuse_register`` as above, in place of ``fuse_num`` / ``fuse_views``.  Together with ``fuse`` it is a ValueError.
+    ``track``: None, or a ``tsdf.TrackParams`` / a dict of its fields (``near``, ``far``, ``step``, ``max_translation``,
+    ``max_rotation``, ``min_hit_share``, ``max_dist``, ``iterations``, ...): the ``DepthFrame``s handed to ``detect`` are the
+    frames of ONE moving camera whose pose is not given.  Each goes through the detector's ``tsdf.Tracker`` (``tracker``; its
+    volume is ``volume``'s, ``tsdf.TsdfParams()`` when that is absent, and is never reset between frames): registered against
+    the model view from the last pose and integrated at the pose found, and the surface of the volume as it then stands is the
+    cloud, in the frame of the FIRST camera.  The record carries ``tsdf_num`` as above, ``tsdf_counts`` (1,4) int32 (zeros for
+    a frame that was LOST), ``track_pose`` (4,4) float64 camera-to-common, ``track_status`` () int32 (0 FIRST, 1 TRACKED, 2
+    LOST) and ``track_report`` (5,) float64 = (status, iterations, pairs, rms first, rms last) of the registration (NaN for
+    the first frame).  Together with ``fuse``, or for a ``MultiView`` (its views carry poses), it is a ValueError."""
 
     def __init__(self, score_net, region_net, params=TEST_PARAMS, gripper_params=GRIPPER_PARAMS, eval_params=EVAL_PARAMS,
                  transform=None, bounds=None, num_points=ALL_POINTS_NUM, use_theta=USE_THETA, select=None, depth=None, segment=None,
-                 fuse=None, register=None, approach=None, denoise=None, volume=None):
+                 fuse=None, register=None, approach=None, denoise=None, volume=None, track=None):
         from . import depth_frame, fusion, grasp_select, ingest, registration
         from . import segment as segment_mod
         self.fuse = fusion.FuseParams.coerce(fuse)
@@ -165,6 +181,14 @@ class GraspDetector:
                 raise ValueError("volume: a MultiView is either merged (fuse) or integrated into a volume, not both")
             from . import tsdf
             self.volume = tsdf.TsdfParams.coerce(volume)
+        self.track = self.tracker = None          # the parameters, and the tsdf.Tracker kept between frames
+        if track is not None:                     # (the module is not even imported without it)
+            if fuse is not None:
+                raise ValueError("track: the frames of a moving camera are integrated into a volume, not merged (fuse)")
+            from . import tsdf
+            self.track = tsdf.TrackParams.coerce(track)
+            if self.volume is None:
+                self.volume = tsdf.TsdfParams()
         self.denoise = None
         if denoise is not None:                   # (the module is not even imported without it)
             from . import outliers
@@ -198,8 +222,18 @@ class GraspDetector:
             return frame
         if isinstance(frame, dict):
             return ingest.ingest_record(frame, self.num_points, self.device)
-        fused = table = denoised = None
-        if isinstance(frame, fusion.MultiView) and self.volume is not None:     # integrated on the device, no host read
+        fused = table = denoised = tracked = None
+        if self.track is not None and isinstance(frame, fusion.MultiView):
+            raise ValueError("track: a MultiView's views carry their poses; track takes the DepthFrames of one moving camera")
+        if self.track is not None and isinstance(frame, depth_frame.DepthFrame):   # one blocking read: the registration's state
+            from . import tsdf
+            if self.tracker is None:
+                self.tracker = tsdf.Tracker(self.volume, self.track, self.device, depth_params=self.depth)
+                self.tsdf_volume = self.tracker.volume
+            tracked = self.tracker.track(frame)
+            fused = self.tracker.volume.extract()
+            frame = fused.cloud()
+        elif isinstance(frame, fusion.MultiView) and self.volume is not None:     # integrated on the device, no host read
             from . import tsdf
             fused = tsdf.fuse_volume(frame, self.depth, self.volume, device=self.device, register=self.register,
                                      volume=self.tsdf_volume)
@@ -224,7 +258,7 @@ class GraspDetector:
             table = table_plane.calibrate(xyz, self.eval_params[2], **self.auto_table)
             transform = table[0]
         fr = ingest.ingest_frame(xyz, rgb, transform, self.bounds, self.num_points, self.device)
-        fr.fused, fr.table, fr.denoised = fused, table, denoised
+        fr.fused, fr.table, fr.denoised, fr.tracked = fused, table, denoised, tracked
         return fr
 
     def calibrate(self, frame, **estimate_kwargs):
@@ -337,7 +371,18 @@ class GraspDetector:
             if self.volume is not None:           # (the module is imported: the detector has ``volume``)
                 from . import tsdf
                 from_volume = isinstance(fr.fused, tsdf.Surface)
-            if from_volume:
+            tracked = getattr(fr, "tracked", None)
+            if tracked is not None:
+                from . import registration
+                out["tsdf_num"] = fr.fused.num.cpu().numpy()
+                out["tsdf_counts"] = (np.zeros((1, 4), dtype=np.int32) if tracked.counts is None
+                                      else tracked.counts.cpu().numpy().reshape(1, 4))
+                out["track_pose"] = np.array(tracked.pose, dtype=np.float64)
+                out["track_status"] = np.array(tsdf.TRACK_STATUS.index(tracked.status), dtype=np.int32)
+                out["track_report"] = np.array([np.nan] * 5 if tracked.report is None else registration.report_row(tracked.report),
+                                               dtype=np.float64)
+                keys = keys + TSDF_KEYS + TRACK_KEYS
+            elif from_volume:
                 out["tsdf_num"] = fr.fused.num.cpu().numpy()
                 out["tsdf_counts"] = fr.fused.counts.cpu().numpy()
                 keys = keys + TSDF_KEYS
@@ -469,6 +514,12 @@ _FLAGS = (
     ("--tsdf-voxel", "volume", "voxel", float, "edge of the voxels of the volume (%s m)"),
     ("--tsdf-trunc", "volume", "trunc", float, "truncation distance, at least two voxels (%s m)"),
     ("--tsdf-min-weight", "volume", "min_weight", int, "a voxel bounds a surface when so many views observed it (%s views)"),
+    # a moving camera tracked against the volume (tsdf.Tracker): --track or any of the five turns it on
+    ("--track-near", "track", "near", float, "march the model view's rays from this depth (%s m)"),
+    ("--track-far", "track", "far", float, "... to this depth (%s m)"),
+    ("--track-step", "track", "step", float, "the distance between two samples of a ray [m] (half the truncation distance)"),
+    ("--track-max-translation", "track", "max_translation", float, "a frame that moved further than this is lost (%s m)"),
+    ("--track-max-rotation", "track", "max_rotation", float, "a frame that turned further than this is lost (%s rad)"),
     # outlier removal of a camera frame's cloud (outliers.filter_cloud): --denoise or any of the six turns it on
     ("--outlier-mode", "outliers", "mode", ("radius", "statistical", "both"),
      "the radius filter, the statistical filter, or the first and then the second on its survivors"),
@@ -548,6 +599,12 @@ def volume_from_args(args):
     return given if (given or args.tsdf) else None
 
 
+def track_from_args(args):
+    """The CLI's six tracking flags -> a ``track`` dict, or None when none of them was given."""
+    given = _given(args, "track")
+    return given if (given or args.track) else None
+
+
 def build_parser():
     """The CLI of ``main``: test.py's arguments, ``_FLAGS`` and the irregular flags of each group."""
     from . import approach as approach_mod
@@ -556,7 +613,7 @@ def build_parser():
     defaults = {"select": grasp_select.SelectParams(), "transform": argparse.Namespace(threshold=table_plane.DEFAULT_THRESHOLD),
                 "depth": depth_frame.DepthParams(), "segment": segment_mod.SegmentParams(), "fuse": fusion.FuseParams(),
                 "register": registration.IcpParams(), "approach": approach_mod.ApproachParams(),
-                "outliers": outliers.OutlierParams(), "volume": tsdf.TsdfParams()}
+                "outliers": outliers.OutlierParams(), "volume": tsdf.TsdfParams(), "track": tsdf.TrackParams()}
     parser = argparse.ArgumentParser(description="REGNet single-file inference (the reference's test.py)")
     parser.add_argument("--folder", "--folder-name", dest="folder", required=True)
     parser.add_argument("--file", "--file-name", dest="file", default="")
@@ -605,6 +662,10 @@ def build_parser():
     parser.add_argument("--tsdf-dims", type=int, nargs=3, metavar=("NX", "NY", "NZ"), default=None,
                         help="voxels per axis, at most 2^28 in all (%d %d %d voxels)" % defaults["volume"].dims)
     regular("volume")
+    parser.add_argument("--track", action="store_true",
+                        help="the folder's depth frames, in the order of their names, are one moving camera: track it against the "
+                             "TSDF volume it fills and take the volume's surface as every frame's cloud")
+    regular("track")
     return parser
 
 
@@ -625,7 +686,7 @@ def main(argv=None):
                              transform=transform_from_args(args), depth=depth_from_args(args),
                              segment=segment_from_args(args), fuse=fuse_from_args(args), register=register_from_args(args),
                              approach=approach_from_args(args), denoise=outliers_from_args(args),
-                             volume=volume_from_args(args))
+                             volume=volume_from_args(args), track=track_from_args(args))
     real_data = "real_data" in args.folder
     if args.file:
         paths = [os.path.join(args.folder, args.file)]

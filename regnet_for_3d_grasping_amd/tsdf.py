@@ -13,9 +13,16 @@ frames, and with a finite ``max_weight`` a moving average.
 
 ``fuse_volume`` is the counterpart of ``fusion.fuse_frames`` for a ``fusion.MultiView``, and ``GraspDetector(volume=...)`` uses
 it.  No host read except ``Surface.check()``; GPU only: there is no CPU path.
+
+``Volume.raycast`` renders the volume from any pose: per pixel of a virtual pinhole camera the first zero crossing along its
+ray, with the gradient's normal and the colour there -- a denoised depth and normal image of the fused model (``ModelView``),
+laid out as ``registration.ProjectiveTarget`` takes it.  ``Tracker`` closes the loop for a camera whose pose is NOT given (one
+on the robot's wrist): every new frame is registered against the model view from the last pose and integrated at the pose
+found -- frame-to-model tracking, KinectFusion's third leg.  ``tests/tsdf_raycast_reference.py`` restates both.
 """
 from dataclasses import dataclass
-from typing import Tuple
+import math
+from typing import Optional, Tuple
 
 import numpy as np
 
@@ -101,6 +108,107 @@ class Surface:
         """The ``(xyz, rgb)`` pair ``ingest.ingest_frame``, ``table_plane.calibrate`` and ``outliers.filter_cloud`` take as they
         are: the rows beyond ``K`` are NaN rows, which all three treat as absent."""
         return self.xyz, self.rgb
+
+
+NO_SURFACE, BACK_FACE, HIT, HIT_NO_NORMAL = 0, 1, 2, 3   # raycast's status codes, the entries of its counts
+MAX_RAY_STEPS = 4096                # regnet_tsdf_raycast_f32's documented limit
+FIRST, TRACKED, LOST = "FIRST", "TRACKED", "LOST"
+TRACK_STATUS = (FIRST, TRACKED, LOST)                    # a record's ``track_status`` is the index
+
+
+@dataclass(frozen=True)
+class TrackParams(ParamsBase):
+    """What ``GraspDetector(track=...)`` and ``Tracker`` take (a dict with these keys works too).
+
+    The registration is ``registration.icp`` with ``association="projective"`` against the model view; ``max_dist``,
+    ``iterations``, ``stride``, ``window``, ``min_pairs``, ``rot_eps``, ``trans_eps``, ``normal_angle``, ``normal_step`` and
+    ``normal_jump`` are ``IcpParams``' fields of those names and go to it as they are (the last two make the FRAME's normals,
+    which only ``normal_angle`` needs; the model's come from the volume).  ``near``, ``far`` [m]: the depths between which a ray
+    is marched; ``step`` [m]: the distance between two samples, None: half the volume's ``trunc``, so a ray cannot step over
+    the band in which the distance is known; at most 4096 samples per ray.  ``max_translation`` [m] / ``max_rotation`` [rad]:
+    a frame that moved further against the pose it was registered from is LOST; ``min_hit_share``: so is one whose model view
+    hit the surface in a smaller share of its pixels.
+
+    Every default is a choice: a frame-to-frame motion of centimetres and a few degrees, the capture range of the pose
+    refinement, twenty steps of which a tracked frame needs a handful; rays from 20 cm to 1.5 m, which spans the default volume
+    seen from about its first camera.  None is measured on real cameras."""
+    WORD = "track"
+    NONE_IS_DEFAULT = True
+    max_dist: float = 0.02
+    iterations: int = 20
+    stride: int = 1
+    window: int = 1
+    min_pairs: int = 100
+    rot_eps: float = 1e-5
+    trans_eps: float = 1e-6
+    normal_angle: Optional[float] = None
+    normal_step: int = 2
+    normal_jump: float = 0.02
+    near: float = 0.2
+    far: float = 1.5
+    step: Optional[float] = None
+    max_translation: float = 0.05
+    max_rotation: float = 0.1
+    min_hit_share: float = 0.05
+
+    def __post_init__(self):
+        self.icp_params()                                   # (its checks are the registration's)
+        check_ray_range(self.near, self.far, self.step, "track")
+        for name in ("max_translation", "max_rotation"):
+            if not float(getattr(self, name)) > 0.0:        # (a NaN too; inf: no gate)
+                raise ValueError("track: %s must be positive" % name)
+        if not 0.0 <= float(self.min_hit_share) <= 1.0:
+            raise ValueError("track: min_hit_share must be in 0..1")
+
+    def icp_params(self):
+        """The ``registration.IcpParams`` of a frame-to-model registration."""
+        from . import registration
+        return registration.IcpParams(max_dist=self.max_dist, iterations=self.iterations, stride=self.stride, window=self.window,
+                                      min_pairs=self.min_pairs, rot_eps=self.rot_eps, trans_eps=self.trans_eps,
+                                      normal_angle=self.normal_angle, normal_step=self.normal_step, normal_jump=self.normal_jump,
+                                      association="projective")
+
+
+def check_ray_range(near, far, step, word):
+    """``near`` < ``far``, both and ``step`` (None: not looked at) positive and finite in float32, else a ValueError."""
+    for name, value in (("near", near), ("far", far), ("step", step)):
+        if value is None and name == "step":
+            continue
+        with np.errstate(over="ignore", under="ignore"):
+            as32 = np.float32(value)
+        if not (float(value) > 0.0 and as32 > 0.0 and np.isfinite(as32)):
+            raise ValueError("%s: %s must be positive and finite in float32" % (word, name))
+    if not float(near) < float(far):
+        raise ValueError("%s: near must be below far" % word)
+
+
+def ray_steps(near, far, step):
+    """``ceil((far - near) / step)``, in float64: the samples of a ray."""
+    return int(math.ceil((float(far) - float(near)) / float(step)))
+
+
+class ModelView:
+    """``Volume.raycast``'s result, on the device: ``xyz`` / ``normals`` / ``rgb`` (H W, 3) float32 IN THE VIRTUAL CAMERA's frame,
+    row ``v W + u`` for pixel (u, v), NaN in ``xyz`` without a hit and in ``normals`` without a normal, ``rgb`` 0 without a hit
+    (None when no colour was asked for); ``status`` (H W) uint8: ``NO_SURFACE``, ``BACK_FACE``, ``HIT``, ``HIT_NO_NORMAL``;
+    ``counts`` (4) int32, its histogram.  ``width``, ``height``, ``intrinsics`` (an ``Intrinsics``) and ``pose`` (4,4) float64,
+    camera-to-common, say which camera."""
+
+    def __init__(self, xyz, normals, rgb, status, counts, width, height, intrinsics, pose):
+        self.xyz, self.normals, self.rgb, self.status, self.counts = xyz, normals, rgb, status, counts
+        self.width, self.height, self.intrinsics, self.pose = int(width), int(height), intrinsics, pose
+
+    def target(self, icp_params=None, max_source=None, stream=None):
+        """The view as the target of a projective registration (``registration.prepare_projective_target`` with the model's
+        own normals): nothing is compacted and nothing is read."""
+        from . import registration
+        return registration.prepare_projective_target(self.xyz, self.width, self.height, self.intrinsics, icp_params,
+                                                      target_normals=self.normals, stream=stream,
+                                                      max_source=registration.MAX_POINTS if max_source is None else max_source)
+
+    def depth(self):
+        """The denoised depth image (H, W) float32 on the device, NaN without a hit: a view of ``xyz``."""
+        return self.xyz[:, 2].view(self.height, self.width)
 
 
 def camera_from_common(pose):
@@ -211,6 +319,151 @@ class Volume:
                       normal.data_ptr(), weight.data_ptr(), num.data_ptr(), stream=raw)
             record_streams(stream, self.data)
         return Surface(xyz, rgb, normal, weight, num, p)
+
+    def raycast(self, pose, intrinsics, width, height, near=None, far=None, step=None, colour=True, stream=None, out=None,
+                clip=True):
+        """The model view of the volume as it stands from the virtual pinhole camera at ``pose`` (camera-to-common 4x4, None:
+        identity) with ``intrinsics`` (an ``Intrinsics`` or (fx, fy, cx, cy)) and ``width`` x ``height`` pixels -> ``ModelView``.
+        A ray is sampled every ``step`` (None: ``trunc / 2``) from ``near`` to ``far`` (None: ``TrackParams``' defaults):
+        ``ceil((far - near) / step)`` samples, at most 4096.  ``colour`` False: no ``rgb``, and the colour planes are not read.
+        ``out``: ``(xyz, normals, rgb, status, counts)`` contiguous device tensors of the result's shapes to write into (``rgb``
+        None without colour).  ``clip`` False visits every sample instead of those inside the volume's box: the same bytes,
+        more time (a measurement).  The volume is only read; no host read."""
+        import torch
+        p = self.params
+        width, height = int(width), int(height)
+        k = depth_frame.Intrinsics.coerce(intrinsics)
+        if k is None or not (np.isfinite(k.astuple()).all() and k.fx != 0.0 and k.fy != 0.0):
+            raise ValueError("raycast: the intrinsics must be finite with non-zero fx and fy")
+        defaults = TrackParams()
+        near = defaults.near if near is None else near
+        far = defaults.far if far is None else far
+        step = float(p.trunc) / 2.0 if step is None else step
+        check_ray_range(near, far, step, "raycast")
+        n_steps = ray_steps(near, far, step)
+        if n_steps > MAX_RAY_STEPS:
+            raise ValueError("raycast: %d samples per ray, more than %d; raise step or bring near and far together"
+                             % (n_steps, MAX_RAY_STEPS))
+        T = np.eye(4) if pose is None else matrix4(pose, "a pose must be a finite 4x4 camera-to-common transform", finite=True)
+        with np.errstate(over="ignore"):
+            rows = np.ascontiguousarray(T[:3, :].reshape(12).astype(np.float32))
+            k4 = np.ascontiguousarray(np.array([1.0 / k.fx, 1.0 / k.fy, k.cx, k.cy], dtype=np.float64).astype(np.float32))
+        if width < 1 or height < 1:
+            raise ValueError("raycast: width and height must be at least 1")
+        n = width * height
+        dev = self.device
+        shapes = (((n, 3), torch.float32), ((n, 3), torch.float32), ((n, 3), torch.float32), ((n,), torch.uint8),
+                  ((4,), torch.int32))
+        nx, ny, nz = p.dims
+        with torch.cuda.device(dev), stream_scope(stream):
+            if out is None:
+                out = tuple(torch.empty(shape, dtype=dtype, device=dev) if colour or j != 2 else None
+                            for j, (shape, dtype) in enumerate(shapes))
+            if len(out) != 5 or (out[2] is None) != (not colour):
+                raise ValueError("raycast: out must be (xyz, normals, rgb, status, counts), rgb None exactly without colour")
+            for t, (shape, dtype) in zip(out, shapes):
+                if t is not None and not (t.is_cuda and t.device == dev and tuple(t.shape) == shape and t.dtype == dtype
+                                          and t.is_contiguous()):
+                    raise ValueError("raycast: out must be contiguous device tensors (H W,3) x 3 float32, (H W) uint8, (4) int32")
+            xyz, normals, rgb, status, counts = out
+            _lib.call("regnet_tsdf_raycast_f32", self.data, self.data.data_ptr(), nx, ny, nz, self.origin.ctypes.data,
+                      float(p.voxel), int(p.min_weight), k4.ctypes.data, rows.ctypes.data, float(near), float(step), n_steps,
+                      width, height, 1 if clip else 0, xyz.data_ptr(), normals.data_ptr(),
+                      None if rgb is None else rgb.data_ptr(), status.data_ptr(), counts.data_ptr(),
+                      stream=None if stream is None else stream.cuda_stream)
+            record_streams(stream, self.data, *out)
+        return ModelView(xyz, normals, rgb, status, counts, width, height, k, T)
+
+
+class Tracked:
+    """``Tracker.track``'s result.  ``pose``: the tracker's pose after the frame, (4,4) float64 camera-to-common; ``status``:
+    ``FIRST`` (the first frame, integrated at the starting pose), ``TRACKED`` (registered and integrated) or ``LOST`` (nothing
+    integrated, the pose kept); ``report``: ``registration.decode_state``'s dict of the registration, whose ``pose`` takes the
+    frame into the model view's camera (None for FIRST); ``counts``: integrate's (4) int32 on the device (None when LOST);
+    ``model``: the ``ModelView`` the frame was registered against (None for FIRST), ``hits`` the pixels in which it hit."""
+
+    def __init__(self, pose, status, report, counts, model, hits=None):
+        self.pose, self.status, self.report, self.counts, self.model, self.hits = pose, status, report, counts, model, hits
+
+
+class Tracker:
+    """One moving depth camera against one volume.  ``Tracker(tsdf_params, track_params, device, volume)`` holds a ``Volume``
+    (``volume``: one to use, its parameters then hold; it is reset) that is NOT reset between frames, ``pose`` (4,4) float64,
+    the camera-to-common pose of the last frame that was not lost, and ``frames``, the frames integrated.  ``depth_params`` go
+    to ``depth_frame.to_cloud``."""
+
+    def __init__(self, tsdf_params=None, track_params=None, device="cuda:0", volume=None, depth_params=None):
+        self.params = TrackParams.coerce(track_params)
+        self.volume = Volume(tsdf_params, device) if volume is None else volume
+        self.device = self.volume.device
+        self.depth_params = depth_params
+        self.reset()
+
+    def reset(self, pose=None, stream=None):
+        """An empty volume, no frames, and ``pose`` (None: identity) as the pose the first frame is integrated at."""
+        self.pose = np.eye(4) if pose is None else matrix4(pose, "a pose must be a finite 4x4 camera-to-common transform",
+                                                           finite=True).copy()
+        self.frames = 0
+        self.volume.reset(stream=stream)
+
+    def _cloud(self, frame, stream):
+        import torch
+        if isinstance(frame, depth_frame.DepthFrame):
+            xyz, rgb = depth_frame.to_cloud(frame, self.depth_params, device=self.device, stream=stream)
+            return xyz, rgb, int(frame.depth.shape[1]), int(frame.depth.shape[0]), frame.intrinsics
+        if not isinstance(frame, (tuple, list)) or len(frame) != 5:
+            raise TypeError("track takes a DepthFrame or (xyz, rgb, width, height, Intrinsics)")
+        xyz, rgb, width, height, k = frame
+        xyz = require_cuda("xyz", xyz, torch.float32, 3, error=TypeError).contiguous()
+        if int(xyz.shape[0]) != int(width) * int(height):
+            raise ValueError("track: xyz must be the organised cloud of its %d x %d frame" % (int(width), int(height)))
+        return xyz, rgb, int(width), int(height), depth_frame.Intrinsics.coerce(k)
+
+    def track(self, frame, guess=None, stream=None):
+        """One frame (a ``depth_frame.DepthFrame``, or ``(xyz, rgb, width, height, Intrinsics)`` already on the device as
+        ``Volume.integrate`` takes it) -> ``Tracked``.  The first frame is integrated at ``pose``.  A later one: the model view
+        from ``guess`` (a camera-to-common 4x4; None: the last pose) with the frame's own intrinsics and size, the frame's cloud
+        registered onto it from the identity, ONE blocking read (the registration's 1152-byte state and the view's 16-byte
+        histogram, as one tensor), ``pose = pose_model @ T``, and the frame integrated there.  When the registration ends
+        TOO_FEW or DEGENERATE, moved further than ``max_translation`` / ``max_rotation``, or the view hit in fewer than
+        ``min_hit_share`` of its pixels, the frame is LOST: nothing is integrated and the pose is kept."""
+        import torch
+        from . import registration
+        t = self.params
+        xyz, rgb, width, height, k = self._cloud(frame, stream)
+        view = (xyz, rgb, width, height, k)
+        if self.frames == 0:
+            counts = self.volume.integrate(view, self.pose, stream=stream)
+            self.frames = 1
+            return Tracked(self.pose.copy(), FIRST, None, counts, None)
+        at = self.pose if guess is None else matrix4(guess, "a guess must be a finite 4x4 camera-to-common transform", finite=True)
+        model = self.volume.raycast(at, k, width, height, t.near, t.far, t.step, colour=False, stream=stream)
+        icp = t.icp_params()
+        n = int(xyz.shape[0])
+        reg = registration.icp(xyz, model.target(icp, max_source=n, stream=stream), None, icp, stream=stream,
+                               source_shape=(width, height))
+        with torch.cuda.device(self.device), stream_scope(stream):
+            both = torch.cat([reg.state, model.counts.view(torch.uint8)])
+            record_streams(stream, both)
+        raw = both.cpu().numpy()                             # the one blocking read
+        report = registration.decode_state(raw[:registration.STATE_BYTES])
+        hist = raw[registration.STATE_BYTES:].view(np.int32)
+        hits = int(hist[HIT]) + int(hist[HIT_NO_NORMAL])
+        moved, turned = relative_motion(report["pose"])
+        lost = (report["status"] in (registration.TOO_FEW, registration.DEGENERATE) or hits < t.min_hit_share * width * height
+                or moved > t.max_translation or turned > t.max_rotation)
+        if lost:
+            return Tracked(self.pose.copy(), LOST, report, None, model, hits)
+        self.pose = at @ report["pose"]
+        counts = self.volume.integrate(view, self.pose, stream=stream)
+        self.frames += 1
+        return Tracked(self.pose.copy(), TRACKED, report, counts, model, hits)
+
+
+def relative_motion(T):
+    """A rigid 4x4 -> (the length of its translation, its rotation angle [rad])."""
+    cos = min(1.0, max(-1.0, (float(np.trace(T[:3, :3])) - 1.0) / 2.0))
+    return float(np.linalg.norm(T[:3, 3])), math.acos(cos)
 
 
 def fuse_volume(multiview, depth_params=None, tsdf_params=None, device="cuda:0", stream=None, register=None, volume=None):
