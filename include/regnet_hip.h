@@ -1351,6 +1351,61 @@ int regnet_grasp_approach_f32(const float* points, int64_t pn, int64_t pc, const
                               float half_thickness, float half_width, float half_space, float back_x, float standoff,
                               float contact_depth, float cos_friction, int32_t* counts, float* values, void* stream);
 
+/* ---- approach analysis against the TSDF volume (csrc/approach_volume.hip): occupied and unseen space per grasp, on the device ----
+ * regnet_grasp_approach_f32 above holds the swept hand against the points a camera saw; to it the occluded back of an object and
+ * the space no view reached are free.  This scan holds the same hand against the volume of the TSDF section above, which knows
+ * three states per voxel: seen solid, seen free, never observed.  It scans no points but a LATTICE of samples of the swept hand
+ * in the grasp's local frame, so its cost follows the hand's volume.  The volume is only read (D and W).  One workgroup of 256
+ * threads per grasp.  Canonical fp32 arithmetic: individually rounded binary32 operations in the written order
+ * (-ffp-contract=off), divisions correctly rounded (__fdiv_rn), every comparison strict unless written otherwise.
+ *   volume, dims, origin3 (3 float32, HOST), voxel, min_weight   as for regnet_tsdf_emit_f32; every dim <= 2^24.
+ *               voxel_f = float32(voxel).  d_solid = float32(margin / trunc), the division in float64, rounded once.
+ *   box         x_lo, x_hi, x_hi_per_grasp (B, DEVICE, or NULL), half_thickness ht, half_width hw, half_space hs, back_x,
+ *               standoff S: regnet_grasp_approach_f32's, xh being the grasp's x_hi.
+ *   lattice     shared by all grasps of the call.  h = float32(step).  xs = x_lo - S, one float32 subtraction (the sweep's far
+ *               end of regnet_grasp_approach_f32).  n_x = max(1, ceil((x_extent - xs) / h)), n_y = max(1, ceil((hw + hw) / h)),
+ *               n_z = max(1, ceil((ht + ht) / h)), evaluated on the host in float64 from the float32 values.  x_extent is x_hi,
+ *               or with x_hi_per_grasp the caller's bound on them (samples beyond a grasp's own xh drop out by the strict
+ *               tests below; a grasp whose xh lies beyond x_extent is analysed up to x_extent only).  Sample (i, j, k), cell
+ *               centred and never accumulated:
+ *                 x_i = xs + (((float)i + 0.5f) * h),  y_j = (((float)j + 0.5f) * h) - hw,  z_k = (((float)k + 0.5f) * h) - ht.
+ *   sets        regnet_grasp_approach_f32's predicates, restated, on the sample's local (x, y, z):
+ *                 section = z < ht && z > -ht && y < hw && y > -hw;  inner = section && y < hs && y > -hs;
+ *                 close = x > x_lo && x < xh;  region = inner && close;
+ *                 back = section && close && x < back_x;  finger = section && close && (y > hs || y < -hs);
+ *                 HAND membership = (int)back + (int)finger (a sample that is both counts twice, as there);
+ *                 BLOCKER = section && x < front && x > xs, front = back_x for inner samples and xh for the rest of the section;
+ *                 its retreat s = fmaxf(x_lo - x, 0.0f).
+ *               A sample in none of region, hand, blocker is not looked up.
+ *   lookup      L (B,12) float32 DEVICE: per grasp rows 0..2 of the row-major 4x4 LOCAL-TO-VOLUME transform.
+ *                 wx = (((l00 x) + (l01 y)) + (l02 z)) + l03, wy and wz likewise from rows 1 and 2.
+ *               Per axis c = floorf(__fdiv_rn(w - o, voxel_f)): voxel i covers [o + i voxel, o + (i + 1) voxel), its centre being
+ *               the TSDF section's.  INSIDE iff c >= 0 && c < (float)n on all three axes, compared in float (a NaN fails).  The
+ *               voxel is the NEAREST one: nothing is interpolated.
+ *   class       OUTSIDE: not inside.  UNKNOWN: W < min_weight, or D is a NaN.  SOLID: D < d_solid.  FREE: everything else
+ *               (D == 1, the value of a voxel a view looked through, included).  UNSEEN = OUTSIDE or UNKNOWN.  One W is loaded
+ *               per looked-up sample and D only when W >= min_weight.
+ *   counts      (B,8) int32: { region SOLID, region UNSEEN, hand SOLID, hand UNSEEN, blockers SOLID, blockers UNSEEN, M, M_out }:
+ *               hand counts are sums of the hand membership; M = the sum over the looked-up samples of (hand membership +
+ *               (int)blocker), the denominator that goes with columns 3 + 5, and M_out the part of M on OUTSIDE samples.
+ *   values      (B,4) float32: { y_min, y_max over the region's SOLID samples, clearance_seen = fminf(S, min s over the SOLID
+ *               blockers), clearance_safe = fminf(S, min s over the SOLID or UNSEEN blockers) }, each + 0.0f before the store;
+ *               an empty set gives +inf, -inf, S, S.  Both clearances and y_min / y_max are sample coordinates: quantised to
+ *               the lattice.
+ * Only integer sums and float min / max are reduced (a wave butterfly, then the four waves through LDS): no atomic and no
+ * floating-point sum, so two runs agree bit for bit.  A wave takes 8 x 8 tiles of the lattice's x-y plane and walks the z layers.
+ * One launch; no host read, no synchronisation, no allocation: capturable.  A row of L with a non-finite entry launches and
+ * reports every looked-up sample OUTSIDE (M_out == M).  Errors, all before any launch: B < 0, a dim < 1 or min_weight < 1 ->
+ * REGNET_ERR_SHAPE; a dim > 2^24, nx ny nz > 2^28, B or min_weight >= 2^31, step, voxel or trunc not finite or not positive (in
+ * float32 too), a standoff that is negative or not finite, margin / trunc not finite in float32, a lattice count that is not
+ * finite or n_x n_y n_z > 2^22 -> REGNET_ERR_UNSUPPORTED; then B == 0: success without a launch; then a NULL volume, origin3, L,
+ * counts or values -> REGNET_ERR_NULL.                                                                                       */
+int regnet_grasp_approach_volume_f32(const void* volume, int64_t nx, int64_t ny, int64_t nz, const float* origin3, double voxel,
+                                     double trunc, int64_t min_weight, double margin, const float* L, int64_t B, float x_lo,
+                                     float x_hi, const float* x_hi_per_grasp, float half_thickness, float half_width,
+                                     float half_space, float back_x, float standoff, double step, float x_extent,
+                                     int32_t* counts, float* values, void* stream);
+
 /* ---- deterministic mode (csrc/scatter.hip, csrc/det.hip, csrc/bn_train.hip) ------------------------------------------
  * The float32 kernels behind torch.use_deterministic_algorithms(True): every sum of the training backward is formed in one
  * fixed order, so runs agree bit for bit.  The default entry points above are unchanged.

@@ -28,6 +28,9 @@ import torch
 from . import _lib, eval_collision, grasp_select
 from ._frame_util import ParamsBase, require_cuda, to_device
 
+SPACES = ("cloud", "volume")        # what the hand is held against: ``analyse``'s points or ``analyse_volume``'s TSDF volume
+UNSEEN = ("free", "blocked")        # what ``analyse_volume``'s clearance makes of space no camera has seen
+
 
 @dataclass
 class ApproachParams(ParamsBase):
@@ -39,7 +42,15 @@ class ApproachParams(ParamsBase):
     [m]; ``min_clearance`` / ``min_contact``: None, or the least clearance [m] / contact share a grasp must have to be selected.
 
     The defaults are a choice made from the reference's gripper constants (6 cm palm-to-tip, 8 cm opening, the validation score's
-    5 mm band and 1 cm / 30-neighbour normals).  Nobody has measured them on a robot."""
+    5 mm band and 1 cm / 30-neighbour normals).  Nobody has measured them on a robot.
+
+    ``space``: ``"cloud"`` -- ``analyse``, the hand against the points -- or ``"volume"``: ``analyse_volume``, the hand against
+    the detector's TSDF volume, which also knows what no camera has seen.  The other three are read in volume space only.
+    ``unseen``: what ``clearance`` (and so ``pregrasp`` and ``min_clearance``) makes of space that is outside the volume or was
+    never observed: ``"free"`` -- only seen surfaces block -- or ``"blocked"``.  ``step``: the distance between two samples of the
+    swept hand [m]; None: the volume's voxel.  ``margin``: a voxel counts as solid when its distance to the surface is below
+    this [m] (0: inside the surface), at most the volume's truncation distance to mean anything.  These defaults, too, are a
+    choice nobody has measured on a robot."""
     WORD = "approach"
     source: Optional[str] = None
     standoff: float = 0.10
@@ -50,8 +61,23 @@ class ApproachParams(ParamsBase):
     pad: float = 0.005
     min_clearance: Optional[float] = None
     min_contact: Optional[float] = None
+    space: str = "cloud"
+    unseen: str = "free"
+    step: Optional[float] = None
+    margin: float = 0.0
 
     def __post_init__(self):
+        if self.space not in SPACES:
+            raise ValueError("approach: space must be one of %s, not %r" % (", ".join(SPACES), self.space))
+        if self.unseen not in UNSEEN:
+            raise ValueError("approach: unseen must be one of %s, not %r" % (", ".join(UNSEEN), self.unseen))
+        if self.step is not None:
+            with np.errstate(over="ignore", under="ignore"):
+                step32 = np.float32(self.step)
+            if not (float(self.step) > 0.0 and step32 > 0.0 and np.isfinite(step32)):
+                raise ValueError("approach: step must be None or positive and finite in float32")
+        if not (float(self.margin) >= 0.0 and np.isfinite(self.margin)):
+            raise ValueError("approach: margin must be non-negative and finite")
         if self.source is not None and self.source not in grasp_select.SOURCES:
             raise ValueError("approach: source must be None or one of %s, not %r" % (", ".join(grasp_select.SOURCES), self.source))
         if not (float(self.standoff) >= 0.0 and np.isfinite(self.standoff)):
@@ -165,3 +191,17 @@ def analyse(points, grasp, depth, width, params=None, normals=None):
               T.data_ptr(), B, *box, float(params.standoff), float(params.contact_depth), cos_friction(params.friction_deg),
               counts.data_ptr(), values.data_ptr())
     return Approach(counts, values, frame, center, params, box[5])
+
+
+def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, surface=None, max_depth=None):
+    """The hand against a ``tsdf.Volume`` instead of a cloud: ``approach_volume.analyse_volume``, which is imported only here
+    (and ``approach.VolumeApproach`` is its result's class)."""
+    from . import approach_volume
+    return approach_volume.analyse_volume(volume, grasp, depth, width, params, to_volume, surface, max_depth)
+
+
+def __getattr__(name):
+    if name == "VolumeApproach":
+        from . import approach_volume
+        return approach_volume.VolumeApproach
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -1,0 +1,221 @@
+// approach_volume.hip -- per-grasp approach analysis against the TSDF volume on the device (gfx950): the swept hand is not held
+// against the points some camera saw (approach.hip) but against the volume's three states per voxel -- seen solid, seen free,
+// never observed -- so the occluded back of an object and the space no view reached can count as blocked.
+//
+// One workgroup of 256 threads per grasp.  Nothing is scanned but a LATTICE of samples of the swept hand in the grasp's local
+// frame, shared by all grasps of a call: n_x x n_y x n_z cell-centred samples of step h over [x_lo - S, x_extent] x [-hw, hw] x
+// [-ht, ht].  A wave takes 8 x 8 tiles of the lattice's x-y plane, tile t = wave, wave + 4, ..., lane l at (l & 7, l >> 3) of the
+// tile, and walks the n_z layers: its 64 samples are neighbours in space, so their voxels are neighbours in the volume.  Every
+// sample is taken into the volume's frame by the grasp's own L (rows 0..2 of a 4x4), looked up in the NEAREST voxel (one W, and
+// one D when W >= min_weight) and classified; approach.hip's predicates, restated here (this file includes nothing of it), say
+// which sets it belongs to.  Canonical fp32: individually rounded operations in the written order (-ffp-contract=off), __fdiv_rn,
+// strict comparisons.  Only integer sums and float min / max are reduced (wave butterfly, then the four waves through LDS): no
+// atomic, no floating-point sum.  The volume is only read.  Plain vector stores by thread 0.
+#include "common.h"
+
+#include <math.h>
+
+namespace {
+
+constexpr int AV_T = 256;
+constexpr int AV_W = AV_T / 64;
+constexpr int AV_TILE = 8;
+constexpr int AV_NI = 8, AV_NF = 4;                  // reduced integers and floats
+
+struct HandBox {    // the reference's box constants as float32, as in approach.hip
+  float x_lo, x_hi, half_thickness, half_width, half_space, back_x;
+};
+
+struct Lattice {
+  int nx, ny, nz;   // samples per axis
+  float xs, h;      // x_lo - S (one float32 subtraction, made by the host function) and the step
+};
+
+struct VolumeView {
+  const float* D;
+  const int32_t* W;
+  int nx, ny, nz;
+  float ox, oy, oz, voxel, d_solid;
+  int min_weight;
+};
+
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
+
+__global__ __launch_bounds__(AV_T) void approach_volume_kernel(VolumeView vol, const float* __restrict__ L, HandBox box,
+                                                               const float* __restrict__ x_hi_per_grasp, float standoff,
+                                                               Lattice lat, int32_t* __restrict__ counts,
+                                                               float* __restrict__ values) {
+  __shared__ int red_i[AV_NI][AV_W];
+  __shared__ float red_f[AV_NF][AV_W];
+  const float* l = L + (int64_t)blockIdx.x * 12;
+  const float l00 = l[0], l01 = l[1], l02 = l[2], l03 = l[3];
+  const float l10 = l[4], l11 = l[5], l12 = l[6], l13 = l[7];
+  const float l20 = l[8], l21 = l[9], l22 = l[10], l23 = l[11];
+  const float x_hi = x_hi_per_grasp ? x_hi_per_grasp[blockIdx.x] : box.x_hi;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int tiles_x = (lat.nx + AV_TILE - 1) / AV_TILE, tiles_y = (lat.ny + AV_TILE - 1) / AV_TILE;
+  const int tiles = tiles_x * tiles_y;               // (at most 2^22 samples in all: no overflow)
+  const float fnx = (float)vol.nx, fny = (float)vol.ny, fnz = (float)vol.nz;   // (every dim <= 2^24: exact)
+
+  int region_solid = 0, region_unseen = 0, hand_solid = 0, hand_unseen = 0, block_solid = 0, block_unseen = 0;
+  int members = 0, members_outside = 0;
+  float y_min = __builtin_inff(), y_max = -__builtin_inff(), s_seen = __builtin_inff(), s_safe = __builtin_inff();
+  for (int t = wave; t < tiles; t += AV_W) {
+    const int ty = t / tiles_x, tx = t - ty * tiles_x;
+    const int i = tx * AV_TILE + (lane & (AV_TILE - 1)), j = ty * AV_TILE + (lane >> 3);
+    if (i >= lat.nx || j >= lat.ny) continue;
+    const float x = lat.xs + (((float)i + 0.5f) * lat.h);
+    const float y = (((float)j + 0.5f) * lat.h) - box.half_width;
+    const bool y_in = y < box.half_width && y > -box.half_width;
+    const bool y_inner = y < box.half_space && y > -box.half_space;
+    const bool close = x > box.x_lo && x < x_hi;
+    const float s = fmaxf(box.x_lo - x, 0.0f);
+    for (int k = 0; k < lat.nz; ++k) {
+      const float z = (((float)k + 0.5f) * lat.h) - box.half_thickness;
+      const bool section = z < box.half_thickness && z > -box.half_thickness && y_in;
+      const bool inner = section && y_inner;
+      const bool region = inner && close;
+      const bool back = section && close && x < box.back_x;
+      const bool finger = section && close && (y > box.half_space || y < -box.half_space);
+      const float front = inner ? box.back_x : x_hi;
+      const bool blocker = section && x < front && x > (lat.xs);
+      const int hand = (int)back + (int)finger;
+      const int member = hand + (int)blocker;
+      if (!(region || member)) continue;             // in no set: no lookup
+      const float wx = (((l00 * x) + (l01 * y)) + (l02 * z)) + l03;
+      const float wy = (((l10 * x) + (l11 * y)) + (l12 * z)) + l13;
+      const float wz = (((l20 * x) + (l21 * y)) + (l22 * z)) + l23;
+      const float cx = floorf(__fdiv_rn(wx - vol.ox, vol.voxel));
+      const float cy = floorf(__fdiv_rn(wy - vol.oy, vol.voxel));
+      const float cz = floorf(__fdiv_rn(wz - vol.oz, vol.voxel));
+      const bool inside = cx >= 0.0f && cx < fnx && cy >= 0.0f && cy < fny && cz >= 0.0f && cz < fnz;   // (a NaN fails)
+      bool solid = false, unseen = true;
+      if (inside) {
+        const int64_t v = ((int64_t)(int)cz * vol.ny + (int)cy) * vol.nx + (int)cx;
+        if (vol.W[v] >= vol.min_weight) {
+          const float d = vol.D[v];
+          unseen = d != d;                           // a NaN distance: UNKNOWN
+          solid = d < vol.d_solid;
+        }
+      }
+      members += member;
+      members_outside += inside ? 0 : member;
+      if (solid) {
+        hand_solid += hand;
+        if (region) {
+          region_solid += 1;
+          y_min = fminf(y_min, y);
+          y_max = fmaxf(y_max, y);
+        }
+        if (blocker) {
+          block_solid += 1;
+          s_seen = fminf(s_seen, s);
+          s_safe = fminf(s_safe, s);
+        }
+      } else if (unseen) {
+        hand_unseen += hand;
+        region_unseen += (int)region;
+        if (blocker) {
+          block_unseen += 1;
+          s_safe = fminf(s_safe, s);
+        }
+      }
+    }
+  }
+  int ri[AV_NI] = {region_solid, region_unseen, hand_solid, hand_unseen, block_solid, block_unseen, members, members_outside};
+  float rf[AV_NF];
+#pragma unroll
+  for (int q = 0; q < AV_NI; ++q) ri[q] = wave_sum(ri[q]);
+  rf[0] = wave_min(y_min); rf[1] = wave_max(y_max); rf[2] = wave_min(s_seen); rf[3] = wave_min(s_safe);
+  if (lane == 0) {
+#pragma unroll
+    for (int q = 0; q < AV_NI; ++q) red_i[q][wave] = ri[q];
+#pragma unroll
+    for (int q = 0; q < AV_NF; ++q) red_f[q][wave] = rf[q];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int32_t* c = counts + (int64_t)blockIdx.x * 8;
+#pragma unroll
+    for (int q = 0; q < AV_NI; ++q) {
+      int sum = 0;
+#pragma unroll
+      for (int w = 0; w < AV_W; ++w) sum += red_i[q][w];
+      c[q] = sum;
+    }
+    y_min = red_f[0][0]; y_max = red_f[1][0]; s_seen = red_f[2][0]; s_safe = red_f[3][0];
+#pragma unroll
+    for (int w = 1; w < AV_W; ++w) {
+      y_min = fminf(y_min, red_f[0][w]); y_max = fmaxf(y_max, red_f[1][w]);
+      s_seen = fminf(s_seen, red_f[2][w]); s_safe = fminf(s_safe, red_f[3][w]);
+    }
+    float* v = values + (int64_t)blockIdx.x * 4;
+    v[0] = y_min + 0.0f; v[1] = y_max + 0.0f;        // (+ 0.0f: no -0.0 leaves the kernel)
+    v[2] = fminf(standoff, s_seen) + 0.0f; v[3] = fminf(standoff, s_safe) + 0.0f;
+  }
+}
+
+bool positive_f32(double v, float* out) {            // finite and positive, in float32 too
+  const float f = (float)v;
+  *out = f;
+  return v > 0.0 && f > 0.0f && f != __builtin_inff() && f == f;
+}
+
+// max(1, ceil(extent / h)) in float64; false when it cannot be a lattice count (not finite, or beyond the sample limit)
+bool lattice_count(double extent, double h, int* n) {
+  const double c = ceil(extent / h);
+  if (!(c <= (double)(1 << 22)) || c == -__builtin_inf()) return false;   // (a NaN fails the first test)
+  *n = c < 1.0 ? 1 : (int)c;
+  return true;
+}
+
+}  // namespace
+
+extern "C" int regnet_grasp_approach_volume_f32(const void* volume, int64_t nx, int64_t ny, int64_t nz, const float* origin3,
+                                                double voxel, double trunc, int64_t min_weight, double margin, const float* L,
+                                                int64_t B, float x_lo, float x_hi, const float* x_hi_per_grasp,
+                                                float half_thickness, float half_width, float half_space, float back_x,
+                                                float standoff, double step, float x_extent, int32_t* counts, float* values,
+                                                void* stream) {
+  if (B < 0 || nx < 1 || ny < 1 || nz < 1 || min_weight < 1) return REGNET_ERR_SHAPE;
+  const int64_t limit = (int64_t)1 << 24;             // (then (float)n is exact and the inside test compares exact floats)
+  if (nx > limit || ny > limit || nz > limit || nx * ny * nz > ((int64_t)1 << 28)) return REGNET_ERR_UNSUPPORTED;
+  if (B >= (int64_t)1 << 31 || min_weight >= (int64_t)1 << 31) return REGNET_ERR_UNSUPPORTED;
+  float voxel_f, trunc_f, h;
+  if (!positive_f32(voxel, &voxel_f) || !positive_f32(trunc, &trunc_f) || !positive_f32(step, &h)) return REGNET_ERR_UNSUPPORTED;
+  if (!(standoff >= 0.0f) || standoff == __builtin_inff()) return REGNET_ERR_UNSUPPORTED;   // negative, NaN or infinite
+  const float d_solid = (float)(margin / trunc);
+  if (!(d_solid == d_solid) || d_solid == __builtin_inff() || d_solid == -__builtin_inff()) return REGNET_ERR_UNSUPPORTED;
+  const float xs = x_lo - standoff;
+  int n_x, n_y, n_z;
+  if (!lattice_count((double)x_extent - (double)xs, (double)h, &n_x) ||
+      !lattice_count((double)half_width + (double)half_width, (double)h, &n_y) ||
+      !lattice_count((double)half_thickness + (double)half_thickness, (double)h, &n_z))
+    return REGNET_ERR_UNSUPPORTED;
+  if ((int64_t)n_x * n_y * n_z > ((int64_t)1 << 22)) return REGNET_ERR_UNSUPPORTED;
+  if (B == 0) return REGNET_OK;
+  if (!volume || !origin3 || !L || !counts || !values) return REGNET_ERR_NULL;
+  const int64_t n = nx * ny * nz;
+  const VolumeView vol{(const float*)volume, (const int32_t*)volume + n, (int)nx, (int)ny, (int)nz, origin3[0], origin3[1],
+                       origin3[2], voxel_f, d_solid, (int)min_weight};
+  const HandBox box{x_lo, x_hi, half_thickness, half_width, half_space, back_x};
+  const Lattice lat{n_x, n_y, n_z, xs, h};
+  hipLaunchKernelGGL(approach_volume_kernel, dim3((unsigned)B), dim3(AV_T), 0, as_stream(stream), vol, L, box, x_hi_per_grasp,
+                     standoff, lat, counts, values);
+  REGNET_LAUNCH_CHECK();
+  return REGNET_OK;
+}

@@ -40,6 +40,7 @@ With ``approach`` (``--approach``, ``--approach-standoff``, ``--approach-from``,
 retreat straight back before it touches the cloud, the extent and offset of the object between the fingers, the opening to
 command, the contact check and the pre-grasp point; the record additionally carries ``APPROACH_KEYS``, row-aligned with that set,
 and with ``min_clearance`` / ``min_contact`` the selection sees only the rows that pass.  Without it nothing changes.
+With ``space="volume"`` (``--approach-space``, ``--approach-unseen``, ``--approach-step``, ``--approach-margin``) the hand is held against the TSDF volume instead (``approach.analyse_volume``): ``APPROACH_VOLUME_KEYS`` follow.
 
 With ``denoise`` (``--denoise``, ``--outlier-mode``, ``--outlier-radius``, ``--outlier-min-neighbours``, ``--outlier-knn``,
 ``--outlier-max-radius``, ``--outlier-std-ratio``) the cloud of a camera frame -- an ``(xyz, rgb)`` pair, a depth frame's or a
@@ -88,6 +89,8 @@ FUSE_KEYS = ("fuse_num", "fuse_views")                          # added when the
 REGISTER_KEYS = ("fuse_poses", "fuse_register")                 # ... and the detector has ``register``
 APPROACH_KEYS = ("grasp_clearance", "grasp_width", "grasp_offset", "grasp_opening", "grasp_contact",
                  "grasp_pregrasp")                             # added when the detector has ``approach``: one row per source grasp
+APPROACH_VOLUME_KEYS = ("grasp_clearance_seen", "grasp_clearance_safe", "grasp_unseen",
+                        "grasp_solid_hand")                    # ... right after them when its ``space`` is "volume"
 TSDF_KEYS = ("tsdf_num", "tsdf_counts")                        # added when the frame was a ``MultiView`` and the detector has ``volume``
 TRACK_KEYS = ("track_pose", "track_status", "track_report")    # added beside ``TSDF_KEYS`` when the detector has ``track``
 DENOISE_KEYS = ("denoise_num",)                                 # added when the detector has ``denoise`` and the frame was a camera frame
@@ -131,7 +134,11 @@ class GraspDetector:
     and the record also carries, one row per grasp of that set, float32 ``grasp_clearance`` (k,) [m], ``grasp_width`` (k,),
     ``grasp_offset`` (k,), ``grasp_opening`` (k,), ``grasp_contact`` (k,) and ``grasp_pregrasp`` (k,3).  With ``min_clearance`` /
     ``min_contact`` the per-frame or per-object selection sees only the rows that pass (its source must then be the analysed
-    set); ``grasp_selected_index`` still holds rows of the full set, and the four sets are never shortened.
+    set); ``grasp_selected_index`` still holds rows of the full set, and the four sets are never shortened.  With its
+    ``space="volume"`` (the detector then needs ``volume`` or ``track``, and the frame must be one that fills the volume, else a
+    ValueError) the grasps are held against the TSDF volume and its surface's normals (``approach.analyse_volume``):
+    ``grasp_clearance`` is the clearance of the ``unseen`` policy, and right after the six come float32 ``grasp_clearance_seen``,
+    ``grasp_clearance_safe``, ``grasp_unseen`` (k,) and int32 ``grasp_solid_hand`` (k,).
     ``denoise``: None, or an ``outliers.OutlierParams`` / a dict of its fields (``mode``, ``radius``, ``min_neighbours``, ``knn``,
     ``max_radius``, ``std_ratio``): the cloud of a camera frame is filtered on the device after ``to_cloud`` / ``fuse_frames`` and
     before the table plane and the crop -- the removed rows become NaN rows, which both treat as absent -- and the record also
@@ -189,6 +196,8 @@ class GraspDetector:
             self.track = tsdf.TrackParams.coerce(track)
             if self.volume is None:
                 self.volume = tsdf.TsdfParams()
+        if self.approach is not None and self.approach.space == "volume" and self.volume is None:
+            raise ValueError("approach: space=\"volume\" analyses the detector's TSDF volume; give volume=... or track=...")
         self.denoise = None
         if denoise is not None:                   # (the module is not even imported without it)
             from . import outliers
@@ -335,7 +344,7 @@ class GraspDetector:
             keys = keys + SEGMENT_KEYS
             extra = {"point_object": segmented.label, "grasp_object": grasp_object}
         if approach_extra is not None:
-            keys = keys + APPROACH_KEYS
+            keys = keys + tuple(approach_extra)   # APPROACH_KEYS, in volume space followed by APPROACH_VOLUME_KEYS
             extra.update(approach_extra)
         return keys, extra, segmented
 
@@ -344,11 +353,32 @@ class GraspDetector:
         ``min_clearance`` / ``min_contact`` or None when neither is set); (None, None) without ``approach``."""
         if self.approach is None:
             return None, None
+        if self.approach.space == "volume":
+            return self._approach_volume(sets)
         from . import approach as approach_mod
         depth, width = self.eval_params[0], self.eval_params[1]
         result = approach_mod.analyse(points32, sets[self.approach_source][:, :8], depth, width, self.approach)
         extra = dict(zip(APPROACH_KEYS, (result.clearance, result.width, result.offset, result.opening, result.contact,
                                          result.pregrasp)))
+        passing = result.passes().nonzero().view(-1) if self.approach.filters() else None
+        return extra, passing
+
+    def _approach_volume(self, sets):
+        """``_approach`` in volume space: ``approach.analyse_volume`` on the detector's volume, the frame's surface and the
+        inverse (host, float64) of the transform the frame was ingested with; ``APPROACH_VOLUME_KEYS`` follow the six."""
+        from . import approach as approach_mod
+        from . import tsdf
+        if self.tsdf_volume is None or not isinstance(self.fused, tsdf.Surface):
+            raise ValueError("approach: space=\"volume\" analyses the detector's TSDF volume, and this frame has none: hand "
+                             "detect a MultiView (volume) or a DepthFrame (track), or use space=\"cloud\"")
+        transform = self.transform if self.table is None else self.table[0]
+        to_volume = np.linalg.inv(np.asarray(transform, dtype=np.float64))
+        depth, width = self.eval_params[0], self.eval_params[1]
+        result = approach_mod.analyse_volume(self.tsdf_volume, sets[self.approach_source][:, :8], depth, width, self.approach,
+                                             to_volume=to_volume, surface=self.fused)
+        extra = dict(zip(APPROACH_KEYS + APPROACH_VOLUME_KEYS,
+                         (result.clearance, result.width, result.offset, result.opening, result.contact, result.pregrasp,
+                          result.clearance_seen, result.clearance_safe, result.unseen_share, result.solid_hand)))
         passing = result.passes().nonzero().view(-1) if self.approach.filters() else None
         return extra, passing
 
@@ -510,6 +540,13 @@ _FLAGS = (
      "judge the contacts: half angle of the friction cone about the closing axis [deg] (off)"),
     ("--min-clearance", "approach", "min_clearance", float, "select only grasps that can retreat this far [m]"),
     ("--min-contact", "approach", "min_contact", float, "select only grasps whose contact share is at least this"),
+    ("--approach-space", "approach", "space", ("cloud", "volume"),
+     "hold the hand against the frame's points, or against the TSDF volume of --tsdf / --track"),
+    ("--approach-unseen", "approach", "unseen", ("free", "blocked"),
+     "in volume space: whether space no camera has seen lets the hand through"),
+    ("--approach-step", "approach", "step", float, "in volume space: the distance between two samples of the swept hand [m] (the voxel)"),
+    ("--approach-margin", "approach", "margin", float,
+     "in volume space: a voxel nearer than this (%s m) to a surface is solid"),
     # a TSDF volume in place of the point merge (tsdf.fuse_volume): --tsdf or any of the five turns it on
     ("--tsdf-voxel", "volume", "voxel", float, "edge of the voxels of the volume (%s m)"),
     ("--tsdf-trunc", "volume", "trunc", float, "truncation distance, at least two voxels (%s m)"),
@@ -578,7 +615,7 @@ def register_from_args(args):
 
 
 def approach_from_args(args):
-    """The CLI's six approach flags -> an ``approach`` dict, or None when none of them was given."""
+    """The CLI's ten approach flags -> an ``approach`` dict, or None when none of them was given."""
     given = _given(args, "approach")
     return given if (given or args.approach) else None
 
