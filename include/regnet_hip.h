@@ -978,6 +978,38 @@ int regnet_depth_to_cloud_f32(const float* depth, int64_t W, int64_t H, const fl
  * pointer -> REGNET_ERR_NULL.  (A step beyond the image leaves every pixel without a normal.)                               */
 int regnet_depth_normals_f32(const float* xyz, int64_t W, int64_t H, int64_t step, double max_jump, float* normals, void* stream);
 
+/* regnet_depth_bilateral_f32 / regnet_depth_halve_f32: the frame's side of a coarse-to-fine registration (csrc/depth.hip) -- the
+ * edge-preserving smoothing of a depth image and one level of its pyramid.  depth (H, W) float32 DEVICE, metres; "no depth" on
+ * input is a value that is not finite or <= 0, on output the quiet NaN 0x7FC00000.  Individually rounded binary32 operations in
+ * the written order; the correctly rounded division.
+ * regnet_depth_bilateral_f32: out (H, W).  radius r in 1..4.
+ *   tables      ((2 r + 1)^2 + 256) float32 DEVICE, made by the caller in float64 and rounded once per entry: the spatial weights
+ *               S[b][a] = float32(exp(-0.5 (a^2 + b^2) / sigma_space^2)), a, b = -r..r, row-major (b outer), then the range table
+ *               G[i] = float32(exp(-0.5 (3 (i + 0.5) / 256)^2)), i = 0..255: three sigma_depth in 256 bins.  The kernel takes them
+ *               as data and evaluates no exponential.
+ *   rbin        float32(256 / (3 sigma_depth)), the division in float64: bins per metre.
+ *   pixel       with a valid centre z_c: sw = sd = 0; for b = -r..r (outer), a = -r..r (inner), the centre in its place, every
+ *               neighbour q = (u + a, v + b) inside the image and valid: d = z_q - z_c, t = fabsf(d) * rbin; when !(t < 256.0f) q
+ *               is skipped (no weight beyond three sigma: nothing bleeds across a depth edge); else w = S[b][a] * G[(int)t],
+ *               sw = sw + w, sd = sd + (w * d).  out = z_c + (sd / sw); sw >= S[0][0] G[0] > 0.  An invalid centre: NaN -- holes
+ *               are not filled.
+ *   One launch: a lane per pixel, 32 x 8 tiles, the halo of r pixels and both tables staged in LDS.  Errors, all before the
+ *   launch: W < 1, H < 1 or radius outside 1..4 -> REGNET_ERR_SHAPE; W H > 2^21, rbin not finite or not positive in float32 ->
+ *   REGNET_ERR_UNSUPPORTED; a NULL pointer -> REGNET_ERR_NULL.
+ * regnet_depth_halve_f32: out (H / 2, W / 2) by integer division; an odd last column or row is dropped.
+ *   block       coarse pixel (u, v) reads (2u, 2v), (2u + 1, 2v), (2u, 2v + 1), (2u + 1, 2v + 1), in that order.
+ *   members     z_ref = the smallest valid depth of the four (the foreground wins; the rule is symmetric); a valid pixel is a
+ *               member when z - z_ref <= float32(cutoff) (inclusive).
+ *   out         (the sum of the members in block order, from 0) / float32(count); NaN without a valid pixel.
+ *   A coarse pixel u is the ray through fine coordinate 2u + 0.5 (pixel centres sit at integers): the caller halves the
+ *   intrinsics as fx / 2, fy / 2, (cx - 0.5) / 2, (cy - 0.5) / 2, in float64.
+ *   One launch, a lane per coarse pixel.  Errors, all before the launch: W < 2 or H < 2 -> REGNET_ERR_SHAPE; W H > 2^21, cutoff
+ *   not finite or not positive in float32 -> REGNET_ERR_UNSUPPORTED; a NULL pointer -> REGNET_ERR_NULL.
+ * Both: no host read, no synchronisation, no allocation: capturable.  out must not alias depth.                              */
+int regnet_depth_bilateral_f32(const float* depth, int64_t W, int64_t H, int64_t radius, const float* tables, double rbin,
+                               float* out, void* stream);
+int regnet_depth_halve_f32(const float* depth, int64_t W, int64_t H, double cutoff, float* out, void* stream);
+
 /* ---- object segmentation (csrc/cluster.hip): Euclidean cluster extraction over one cloud, on the device --------------------
  * regnet_cluster_points_f32: xyz (N,3) float32 contiguous; mask (N) uint8 or NULL.  Canonical fp32 arithmetic: individually
  * rounded binary32 operations in the written order (-ffp-contract=off).
@@ -1314,6 +1346,16 @@ int regnet_icp_step_projective_f32(const float* source_xyz, int64_t N_source, in
                                    const float* target_xyz, const float* target_normals, int64_t W, int64_t H,
                                    const double* intrinsics, int64_t window, void* state, double max_dist, double min_cos,
                                    int32_t* idx_out, double* sums_out, int64_t min_pairs, void* workspace, void* stream);
+
+/* regnet_icp_state_continue: the hand-over of ONE state block between the levels of a coarse-to-fine registration.  One thread,
+ * one launch, ordered by the stream after the steps enqueued before it.
+ *   mark        (2) int32 DEVICE or NULL: (iteration, status) as found, stored first.
+ *   rule        status CONVERGED or MAX_ITER: the pose and the history stay, status = RUNNING,
+ *               max_iter = min(64, iteration + budget) -- the steps enqueued next run, at most `budget` of them.  Any other
+ *               status leaves the block untouched: RUNNING is left alone, TOO_FEW and DEGENERATE stay final, so the steps of the
+ *               later levels return at once.
+ * Errors, before the launch: budget outside 1..64 -> REGNET_ERR_SHAPE; state NULL -> REGNET_ERR_NULL.                       */
+int regnet_icp_state_continue(void* state, int64_t budget, int32_t* mark, void* stream);
 
 /* ---- approach analysis (csrc/approach.hip): clearance on the way in, closing extent and contact check per grasp, on the device ----
  * What turns a collision-free grasp into a motion.  regnet_grasp_collision_counts_f32 above tests the hand at the final pose

@@ -17,6 +17,10 @@
 //   * depth_normals_kernel (regnet_depth_normals_f32): the normals of an organised cloud from its own pixel grid, a lane per
 //     pixel: the cross product of the differences `step` pixels along the row and the column, neighbours across a depth jump
 //     left out.  What registration's projective mode takes as the target's (and the source's) normals.
+//   * depth_bilateral_kernel (regnet_depth_bilateral_f32): the edge-preserving smoothing of a float32 depth image before it is
+//     tracked, the same 32 x 8 tile with a halo of `radius` pixels and the two weight tables staged in LDS; the weights are DATA
+//     (evaluated in float64 by the caller), so no device transcendental decides a bit.
+//   * depth_halve_kernel (regnet_depth_halve_f32): one level of the image pyramid, a lane per coarse pixel over its 2 x 2 block.
 // The launches are ordered by the stream: no workgroup waits for another, no flags, no cooperative launch.  Integer atomics only
 // (the z-buffer's unsigned min on float bits -- positive finite floats order as their bits -- and one histogram add per
 // workgroup and code); everything else is a plain vector store.
@@ -287,6 +291,82 @@ __global__ __launch_bounds__(DP_BLOCK) void depth_normals_kernel(const float* __
   store3(normals, row, nx, ny, nz);
 }
 
+// ---- smoothing and the pyramid (regnet_depth_bilateral_f32, regnet_depth_halve_f32) ------------------------------------------
+constexpr int DB_MAX_RADIUS = 4;
+constexpr int DB_RANGE = 256;                                                     // entries of the range table
+constexpr int DB_MAX_HALO = (DP_TX + 2 * DB_MAX_RADIUS) * (DP_TY + 2 * DB_MAX_RADIUS);
+constexpr int DB_MAX_TABLES = (2 * DB_MAX_RADIUS + 1) * (2 * DB_MAX_RADIUS + 1) + DB_RANGE;
+
+__device__ __forceinline__ bool depth_has(float z) { return __builtin_isfinite(z) && z > 0.0f; }
+
+// depth_bilateral_kernel: a lane per pixel of a 32 x 8 tile.  The tile's depths with a halo of `radius` pixels go to LDS once,
+// "no depth" and "beyond the image" as NaN, and so do the (2 radius + 1)^2 spatial weights and the 256 range weights; the
+// window then reads LDS only.  The sums run b outer, a inner, the centre in its place: the written order of the contract.
+__global__ __launch_bounds__(DP_BLOCK) void depth_bilateral_kernel(const float* __restrict__ depth, int W, int H, int radius,
+                                                                   const float* __restrict__ tables, float rbin, int tiles_x,
+                                                                   float* __restrict__ out) {
+  __shared__ float s_z[DB_MAX_HALO];
+  __shared__ float s_t[DB_MAX_TABLES];
+  const int tid = threadIdx.x;
+  const int side = 2 * radius + 1, hx = DP_TX + 2 * radius, halo = hx * (DP_TY + 2 * radius), n_tables = side * side + DB_RANGE;
+  const int u0 = (int)(blockIdx.x % (unsigned)tiles_x) * DP_TX, v0 = (int)(blockIdx.x / (unsigned)tiles_x) * DP_TY;
+  const float nan = __uint_as_float(DP_QNAN);
+  for (int i = tid; i < halo; i += DP_BLOCK) {
+    const int gu = u0 + i % hx - radius, gv = v0 + i / hx - radius;
+    float z = nan;
+    if (gu >= 0 && gu < W && gv >= 0 && gv < H) {
+      const float d = depth[(long long)gv * W + gu];
+      if (depth_has(d)) z = d;
+    }
+    s_z[i] = z;
+  }
+  for (int i = tid; i < n_tables; i += DP_BLOCK) s_t[i] = tables[i];
+  __syncthreads();
+  const int lx = tid % DP_TX, ly = tid / DP_TX;
+  const int u = u0 + lx, v = v0 + ly;
+  if (u >= W || v >= H) return;
+  const int at = (ly + radius) * hx + lx + radius;
+  const float zc = s_z[at];
+  float result = nan;
+  if (zc == zc) {                                             // a valid centre (LDS holds NaN for every other kind)
+    const float* range = s_t + side * side;
+    float sw = 0.0f, sd = 0.0f;
+    for (int b = -radius; b <= radius; ++b)
+      for (int a = -radius; a <= radius; ++a) {
+        const float zq = s_z[at + b * hx + a];
+        if (!(zq == zq)) continue;
+        const float d = zq - zc;
+        const float t = fabsf(d) * rbin;
+        if (!(t < (float)DB_RANGE)) continue;                 // beyond three sigma: no weight at all
+        const float w = s_t[(b + radius) * side + (a + radius)] * range[(int)t];
+        sw = sw + w;
+        sd = sd + (w * d);
+      }
+    result = zc + __fdiv_rn(sd, sw);                          // (the centre gave S[0][0] G[0] > 0)
+  }
+  out[(long long)v * W + u] = result;
+}
+
+// depth_halve_kernel: a lane per coarse pixel; its block (2u, 2v), (2u+1, 2v), (2u, 2v+1), (2u+1, 2v+1) in that order.
+__global__ __launch_bounds__(DP_BLOCK) void depth_halve_kernel(const float* __restrict__ depth, int W, int Wo, long long n_out,
+                                                               float cutoff, float* __restrict__ out) {
+  const long long row = (long long)blockIdx.x * DP_BLOCK + threadIdx.x;
+  if (row >= n_out) return;
+  const int u = (int)(row % Wo), v = (int)(row / Wo);
+  const float* top = depth + (long long)(2 * v) * W + 2 * u;  // (scalar loads: with an odd W the lower row is not 8-byte aligned)
+  const float z[4] = {top[0], top[1], top[W], top[W + 1]};
+  float ref = __builtin_inff();
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (depth_has(z[k]) && z[k] < ref) ref = z[k];
+  float sum = 0.0f;
+  int count = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (depth_has(z[k]) && z[k] - ref <= cutoff) { sum = sum + z[k]; ++count; }
+  out[row] = count > 0 ? __fdiv_rn(sum, (float)count) : __uint_as_float(DP_QNAN);
+}
+
 int depth_check(int64_t W, int64_t H, int64_t Wc, int64_t Hc, int mode) {
   if (W < 1 || H < 1 || mode < DP_NONE || mode > DP_REGISTERED) return REGNET_ERR_SHAPE;
   if (mode == DP_ALIGNED && (Wc != W || Hc != H)) return REGNET_ERR_SHAPE;
@@ -387,6 +467,34 @@ extern "C" int regnet_depth_normals_f32(const float* xyz, int64_t W, int64_t H, 
   const long long n = (long long)(W * H);
   hipLaunchKernelGGL(depth_normals_kernel, dim3((unsigned)((n + DP_BLOCK - 1) / DP_BLOCK)), dim3(DP_BLOCK), 0, as_stream(stream),
                      xyz, (int)W, (int)H, (int)step, jump, normals);
+  REGNET_LAUNCH_CHECK();
+  return REGNET_OK;
+}
+
+extern "C" int regnet_depth_bilateral_f32(const float* depth, int64_t W, int64_t H, int64_t radius, const float* tables, double rbin,
+                                          float* out, void* stream) {
+  if (W < 1 || H < 1 || radius < 1 || radius > DB_MAX_RADIUS) return REGNET_ERR_SHAPE;
+  if (W > DP_MAX_PIXELS || H > DP_MAX_PIXELS || W * H > DP_MAX_PIXELS) return REGNET_ERR_UNSUPPORTED;
+  const float bin = (float)rbin;
+  if (!(rbin > 0.0 && bin > 0.0f && bin < __builtin_inff())) return REGNET_ERR_UNSUPPORTED;           // (a NaN too)
+  if (!depth || !tables || !out) return REGNET_ERR_NULL;
+  const int tiles_x = (int)((W + DP_TX - 1) / DP_TX), tiles_y = (int)((H + DP_TY - 1) / DP_TY);
+  hipLaunchKernelGGL(depth_bilateral_kernel, dim3((unsigned)(tiles_x * tiles_y)), dim3(DP_BLOCK), 0, as_stream(stream), depth,
+                     (int)W, (int)H, (int)radius, tables, bin, tiles_x, out);
+  REGNET_LAUNCH_CHECK();
+  return REGNET_OK;
+}
+
+extern "C" int regnet_depth_halve_f32(const float* depth, int64_t W, int64_t H, double cutoff, float* out, void* stream) {
+  if (W < 2 || H < 2) return REGNET_ERR_SHAPE;
+  if (W > DP_MAX_PIXELS || H > DP_MAX_PIXELS || W * H > DP_MAX_PIXELS) return REGNET_ERR_UNSUPPORTED;
+  const float cut = (float)cutoff;
+  if (!(cutoff > 0.0 && cut > 0.0f && cut < __builtin_inff())) return REGNET_ERR_UNSUPPORTED;         // (a NaN too)
+  if (!depth || !out) return REGNET_ERR_NULL;
+  const int64_t Wo = W / 2, Ho = H / 2;
+  const long long n = (long long)(Wo * Ho);
+  hipLaunchKernelGGL(depth_halve_kernel, dim3((unsigned)((n + DP_BLOCK - 1) / DP_BLOCK)), dim3(DP_BLOCK), 0, as_stream(stream),
+                     depth, (int)W, (int)Wo, n, cut, out);
   REGNET_LAUNCH_CHECK();
   return REGNET_OK;
 }

@@ -15,6 +15,8 @@
 //             candidates, optionally gated by the angle between the normals; no grid, no prepare.  The same tail.
 //   step, launch B  icp_solve_kernel      one workgroup: the slots in ascending order, a 6x6 Cholesky, Rodrigues, the pose update,
 //             the status word.
+//   hand-over       icp_continue_kernel   one thread: between two levels of a coarse-to-fine registration on ONE state block, a
+//             finished-but-healthy status (CONVERGED, MAX_ITER) becomes RUNNING again with a new step budget.
 // Both kernels of a step return at once when the status is no longer RUNNING: a caller enqueues a fixed number of steps and
 // reads the state block once.  No thread waits for another and every loop ends on its own count.
 #include "grid.h"
@@ -324,7 +326,27 @@ __global__ __launch_bounds__(ICP_BLOCK) void icp_solve_kernel(const double* __re
   else if (it + 1 >= state->max_iter) state->status = ICP_MAX_ITER_REACHED;
 }
 
+// The hand-over of one state block between the levels of a coarse-to-fine registration: one thread.  A registration that ended
+// CONVERGED or MAX_ITER runs on -- the pose and the history stay -- with `budget` more steps; every other status is left as it is.
+__global__ void icp_continue_kernel(IcpState* __restrict__ state, int budget, int* __restrict__ mark) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const int it = state->iteration, status = state->status;
+  if (mark != nullptr) { mark[0] = it; mark[1] = status; }
+  if (status == ICP_CONVERGED || status == ICP_MAX_ITER_REACHED) {
+    state->status = ICP_RUNNING;
+    state->max_iter = min(ICP_MAX_ITER, it + budget);
+  }
+}
+
 }  // namespace
+
+extern "C" int regnet_icp_state_continue(void* state, int64_t budget, int32_t* mark, void* stream) {
+  if (budget < 1 || budget > ICP_MAX_ITER) return REGNET_ERR_SHAPE;
+  if (!state) return REGNET_ERR_NULL;
+  hipLaunchKernelGGL(icp_continue_kernel, dim3(1), dim3(1), 0, as_stream(stream), (IcpState*)state, (int)budget, (int*)mark);
+  REGNET_LAUNCH_CHECK();
+  return REGNET_OK;
+}
 
 extern "C" int64_t regnet_icp_state_bytes(void) { return (int64_t)sizeof(IcpState); }
 

@@ -229,6 +229,149 @@ def normals(xyz, width, height, step=2, max_jump=0.02, stream=None):
     return out
 
 
+MAX_SMOOTH_RADIUS = 4               # regnet_depth_bilateral_f32's documented limits
+RANGE_BINS = 256
+
+
+@dataclass(frozen=True)
+class SmoothParams(ParamsBase):
+    """The bilateral filter ``smooth`` applies to a depth image before it is tracked (``tsdf.TrackParams.smooth``; a dict with
+    these keys works too).  ``radius`` (1..4): the window is (2 radius + 1)^2 pixels; ``sigma_space`` [pixels]: the Gaussian over
+    the pixel distance; ``sigma_depth`` [m]: the Gaussian over the depth difference, cut to exactly zero beyond three of it, so
+    nothing is averaged across a depth edge higher than that.
+
+    Every default is a choice -- a 7 x 7 window, two pixels, a centimetre: the noise of a commodity depth camera at arm's
+    length -- and not a measurement on real cameras."""
+    WORD = "smooth"
+    radius: int = 3
+    sigma_space: float = 2.0
+    sigma_depth: float = 0.01
+
+    def __post_init__(self):
+        if int(self.radius) != self.radius or not 1 <= self.radius <= MAX_SMOOTH_RADIUS:
+            raise ValueError("smooth: radius must be in 1..%d" % MAX_SMOOTH_RADIUS)
+        for name in ("sigma_space", "sigma_depth"):
+            v = float(getattr(self, name))
+            if not (v > 0.0 and math.isfinite(v)):
+                raise ValueError("smooth: %s must be positive and finite" % name)
+        with np.errstate(over="ignore", under="ignore"):
+            rbin = np.float32(self.rbin())
+        if not (rbin > 0.0 and np.isfinite(rbin)):
+            raise ValueError("smooth: 256 / (3 sigma_depth) must be positive and finite in float32")
+
+    def rbin(self):
+        """Bins of the range table per metre, in float64: 256 / (3 sigma_depth)."""
+        return RANGE_BINS / (3.0 * float(self.sigma_depth))
+
+    def cutoff(self):
+        """Three ``sigma_depth``: beyond it a neighbour has no weight, and the pyramid takes it as its cutoff."""
+        return 3.0 * float(self.sigma_depth)
+
+
+def smooth_tables(params=None):
+    """The tables of regnet_depth_bilateral_f32 as ((2 radius + 1)^2 + 256,) float32 on the host, evaluated in float64 and rounded
+    once per entry: ``S[b][a] = exp(-0.5 (a^2 + b^2) / sigma_space^2)`` row-major, then ``G[i] = exp(-0.5 (3 (i + 0.5) / 256)^2)``."""
+    params = SmoothParams.coerce(params) or SmoothParams()
+    r = int(params.radius)
+    a = np.arange(-r, r + 1, dtype=np.float64)
+    s = np.exp(-0.5 * (a[None, :] ** 2 + a[:, None] ** 2) / float(params.sigma_space) ** 2)
+    g = np.exp(-0.5 * (3.0 * (np.arange(RANGE_BINS, dtype=np.float64) + 0.5) / RANGE_BINS) ** 2)
+    return np.ascontiguousarray(np.concatenate([s.reshape(-1), g]).astype(np.float32))
+
+
+def _depth_image(name, depth):
+    """``depth`` must be an (H, W) float32 device tensor -> (contiguous tensor, W, H)."""
+    import torch
+    if not isinstance(depth, torch.Tensor) or not depth.is_cuda:
+        raise RuntimeError("%s: depth must be a CUDA tensor (no CPU path)" % name)
+    if depth.dtype != torch.float32 or depth.dim() != 2:
+        raise TypeError("%s: depth must be (H, W) float32" % name)
+    return depth.contiguous(), int(depth.shape[1]), int(depth.shape[0])
+
+
+def _image_out(name, out, depth, height, width):
+    import torch
+    if out is None:
+        return torch.empty((height, width), dtype=torch.float32, device=depth.device)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.device == depth.device and out.dtype == torch.float32
+            and tuple(out.shape) == (height, width) and out.is_contiguous()):
+        raise ValueError("%s: out must be a contiguous (%d, %d) float32 tensor on the depth's device" % (name, height, width))
+    if out.data_ptr() == depth.data_ptr():
+        raise ValueError("%s: out must not be the input" % name)
+    return out
+
+
+def smooth(depth, params=None, stream=None, out=None, tables=None):
+    """The bilateral filter of a depth image (regnet_depth_bilateral_f32): ``depth`` (H, W) float32 metres on the device -> (H, W)
+    float32 on the device, NaN where the input has no depth (not finite, or <= 0): holes neither fill nor grow.  ``tables``: the
+    device copy of ``smooth_tables(params)`` to reuse instead of uploading one.  One launch, no host read."""
+    import torch
+    params = SmoothParams.coerce(params) or SmoothParams()
+    depth, W, H = _depth_image("smooth", depth)
+    if W < 1 or H < 1 or W * H > MAX_DEPTH_PIXELS:
+        raise ValueError("smooth: depth must have 1..2^21 pixels")
+    with torch.cuda.device(depth.device), stream_scope(stream):
+        if tables is None:
+            tables = to_device(smooth_tables(params), depth.device)
+        if not (tables.is_cuda and tables.device == depth.device and tables.dtype == torch.float32 and tables.is_contiguous()
+                and tables.numel() == (2 * int(params.radius) + 1) ** 2 + RANGE_BINS):
+            raise ValueError("smooth: tables must be smooth_tables(params) on the depth's device")
+        out = _image_out("smooth", out, depth, H, W)
+        _lib.call("regnet_depth_bilateral_f32", depth, depth.data_ptr(), W, H, int(params.radius), tables.data_ptr(),
+                  float(params.rbin()), out.data_ptr(), stream=None if stream is None else stream.cuda_stream)
+        record_streams(stream, depth, tables, out)
+    return out
+
+
+_smooth_image = smooth              # (``pyramid`` has a parameter of that name)
+
+
+def halve(depth, cutoff, stream=None, out=None):
+    """One level of the pyramid (regnet_depth_halve_f32): ``depth`` (H, W) float32 on the device -> (H // 2, W // 2) float32 on the
+    device.  A coarse pixel is the mean of those valid pixels of its 2 x 2 block that lie within ``cutoff`` [m] (inclusive) behind
+    the nearest of them, NaN when the block has none.  One launch, no host read."""
+    import torch
+    depth, W, H = _depth_image("halve", depth)
+    if W < 2 or H < 2 or W * H > MAX_DEPTH_PIXELS:
+        raise ValueError("halve: depth must be at least 2 x 2 and have at most 2^21 pixels")
+    with np.errstate(over="ignore", under="ignore"):
+        cut32 = np.float32(cutoff)
+    if not (float(cutoff) > 0.0 and cut32 > 0.0 and np.isfinite(cut32)):
+        raise ValueError("halve: cutoff must be positive and finite in float32")
+    with torch.cuda.device(depth.device), stream_scope(stream):
+        out = _image_out("halve", out, depth, H // 2, W // 2)
+        _lib.call("regnet_depth_halve_f32", depth, depth.data_ptr(), W, H, float(cutoff), out.data_ptr(),
+                  stream=None if stream is None else stream.cuda_stream)
+        record_streams(stream, depth, out)
+    return out
+
+
+def level_intrinsics(k):
+    """The intrinsics of the next coarser level, in float64: ``fx / 2, fy / 2, (cx - 0.5) / 2, (cy - 0.5) / 2``.  Pixel centres
+    sit at integers, so coarse pixel u is the ray through fine coordinate 2u + 0.5."""
+    k = Intrinsics.coerce(k)
+    return Intrinsics(k.fx / 2.0, k.fy / 2.0, (k.cx - 0.5) / 2.0, (k.cy - 0.5) / 2.0)
+
+
+def pyramid(depth, intrinsics, levels, cutoff, smooth=None, stream=None):
+    """``depth`` (H, W) float32 on the device, smoothed first when ``smooth`` (a ``SmoothParams`` or a dict) is given, and its
+    ``levels`` - 1 halvings -> a list of ``(depth_l, Intrinsics_l, W_l, H_l)``, finest first.  No host read."""
+    levels = int(levels)
+    if levels < 1:
+        raise ValueError("pyramid: levels must be at least 1")
+    k = Intrinsics.coerce(intrinsics)
+    depth, W, H = _depth_image("pyramid", depth)
+    if W >> (levels - 1) < 1 or H >> (levels - 1) < 1:
+        raise ValueError("pyramid: a %d x %d image has no %d levels" % (W, H, levels))
+    if smooth is not None:
+        depth = _smooth_image(depth, smooth, stream=stream)
+    out = [(depth, k, W, H)]
+    for _ in range(levels - 1):
+        depth, k, W, H = halve(depth, cutoff, stream=stream), level_intrinsics(k), W // 2, H // 2
+        out.append((depth, k, W, H))
+    return out
+
+
 _NPZ_KEYS = ("depth", "intrinsics", "color", "color_intrinsics", "depth_to_color", "depth_scale")
 
 

@@ -55,7 +55,8 @@ another may declare empty; ``register`` applies as before.  The record then carr
 ``FUSE_KEYS``.  Without it nothing changes and the module is not imported.
 
 With ``track`` (``--track``, ``--track-near``, ``--track-far``, ``--track-step``, ``--track-max-translation``,
-``--track-max-rotation``) the ``DepthFrame``s handed to ``detect`` -- on the command line the folder's ``.npz`` frames in the order
+``--track-max-rotation``; coarse to fine with ``--track-levels``, ``--track-level-iterations``, ``--track-dist-scale`` and
+``--track-smooth RADIUS SIGMA_SPACE SIGMA_DEPTH``, and the record of a frame registered that way also carries ``track_levels``) the ``DepthFrame``s handed to ``detect`` -- on the command line the folder's ``.npz`` frames in the order
 of their names -- are one moving camera whose pose is not given: each is registered against the model view raycast from the
 volume at the last pose and integrated at the pose found (``tsdf.Tracker``), and the volume's surface is the frame's cloud.  The
 record then carries ``TSDF_KEYS`` and ``TRACK_KEYS``.  Without it nothing changes and the module is not imported.
@@ -412,6 +413,9 @@ class GraspDetector:
                 out["track_report"] = np.array([np.nan] * 5 if tracked.report is None else registration.report_row(tracked.report),
                                                dtype=np.float64)
                 keys = keys + TSDF_KEYS + TRACK_KEYS
+                if tracked.levels is not None:    # the coarse-to-fine path ran (a FIRST frame has no registration)
+                    out["track_levels"] = np.array(tracked.levels, dtype=np.int32)
+                    keys = keys + ("track_levels",)
             elif from_volume:
                 out["tsdf_num"] = fr.fused.num.cpu().numpy()
                 out["tsdf_counts"] = fr.fused.counts.cpu().numpy()
@@ -557,6 +561,10 @@ _FLAGS = (
     ("--track-step", "track", "step", float, "the distance between two samples of a ray [m] (half the truncation distance)"),
     ("--track-max-translation", "track", "max_translation", float, "a frame that moved further than this is lost (%s m)"),
     ("--track-max-rotation", "track", "max_rotation", float, "a frame that turned further than this is lost (%s rad)"),
+    ("--track-levels", "track", "levels", int, "register coarse to fine over this many levels of the frame's depth pyramid, 1..4 "
+     "(%s: the frame's own resolution alone)"),
+    ("--track-dist-scale", "track", "level_dist_scale", float, "level l of the pyramid pairs within max_dist times this to the l "
+     "(%s per level)"),
     # outlier removal of a camera frame's cloud (outliers.filter_cloud): --denoise or any of the six turns it on
     ("--outlier-mode", "outliers", "mode", ("radius", "statistical", "both"),
      "the radius filter, the statistical filter, or the first and then the second on its survivors"),
@@ -637,8 +645,15 @@ def volume_from_args(args):
 
 
 def track_from_args(args):
-    """The CLI's six tracking flags -> a ``track`` dict, or None when none of them was given."""
+    """The CLI's ten tracking flags -> a ``track`` dict, or None when none of them was given."""
     given = _given(args, "track")
+    if args.track_level_iterations is not None:
+        given["level_iterations"] = tuple(int(v) for v in args.track_level_iterations)
+    if args.track_smooth is not None:
+        radius, sigma_space, sigma_depth = args.track_smooth
+        if radius != int(radius):
+            raise ValueError("--track-smooth: RADIUS must be a whole number of pixels")
+        given["smooth"] = {"radius": int(radius), "sigma_space": float(sigma_space), "sigma_depth": float(sigma_depth)}
     return given if (given or args.track) else None
 
 
@@ -703,6 +718,12 @@ def build_parser():
                         help="the folder's depth frames, in the order of their names, are one moving camera: track it against the "
                              "TSDF volume it fills and take the volume's surface as every frame's cloud")
     regular("track")
+    parser.add_argument("--track-level-iterations", type=int, nargs="+", metavar="STEPS", default=None,
+                        help="the registration steps per level of the pyramid, finest first, 64 in all at most (10 5 4 4 steps, as "
+                             "many of them as there are levels)")
+    parser.add_argument("--track-smooth", type=float, nargs=3, metavar=("RADIUS", "SIGMA_SPACE", "SIGMA_DEPTH"), default=None,
+                        help="smooth the frame's depth for the registration by a bilateral filter: window radius 1..4 pixels, "
+                             "spatial sigma [pixels], depth sigma [m] (off; 3 2 0.01 are the filter's own defaults)")
     return parser
 
 

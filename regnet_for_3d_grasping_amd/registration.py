@@ -318,6 +318,27 @@ def step(source, target, state, params=None, idx_out=None, sums_out=None, stream
               None if sums_out is None else sums_out.data_ptr(), int(params.min_pairs), target.ws.data_ptr(), stream=raw)
 
 
+def continue_state(state, budget, mark=None, stream=None):
+    """The hand-over of ``state`` ((1152,) uint8 on the device) between two levels of a coarse-to-fine registration
+    (regnet_icp_state_continue): ``mark`` ((2,) int32 on the device, or None) takes ``(iteration, status)`` as found; a block that
+    ended CONVERGED or MAX_ITER is RUNNING again for at most ``budget`` (1..64) more steps, 64 in all, with its pose and history;
+    any other status stays, so a registration that ended TOO_FEW or DEGENERATE on a coarse level stays ended.  One launch of one
+    thread, no host read."""
+    if not isinstance(state, torch.Tensor) or not state.is_cuda:
+        raise RuntimeError("continue_state: state must be a CUDA tensor")
+    if state.dtype != torch.uint8 or state.numel() != STATE_BYTES or not state.is_contiguous():
+        raise ValueError("state must be contiguous uint8 (%d)" % STATE_BYTES)
+    if int(budget) != budget or not 1 <= budget <= MAX_ITERATIONS:
+        raise ValueError("continue_state: budget must be in 1..%d" % MAX_ITERATIONS)
+    if mark is not None:
+        if not isinstance(mark, torch.Tensor) or not mark.is_cuda or mark.device != state.device:
+            raise RuntimeError("continue_state: mark must be a CUDA tensor on the state's device")
+        if mark.dtype != torch.int32 or mark.numel() != 2 or not mark.is_contiguous():
+            raise ValueError("mark must be contiguous int32 (2)")
+    _lib.call("regnet_icp_state_continue", state, state.data_ptr(), int(budget), None if mark is None else mark.data_ptr(),
+              stream=None if stream is None else stream.cuda_stream)
+
+
 class Registration:
     """``icp``'s result: ``state``, the (1152,) uint8 device block, and what ``result()`` reads from it."""
 

@@ -18,7 +18,10 @@ it.  No host read except ``Surface.check()``; GPU only: there is no CPU path.
 ray, with the gradient's normal and the colour there -- a denoised depth and normal image of the fused model (``ModelView``),
 laid out as ``registration.ProjectiveTarget`` takes it.  ``Tracker`` closes the loop for a camera whose pose is NOT given (one
 on the robot's wrist): every new frame is registered against the model view from the last pose and integrated at the pose
-found -- frame-to-model tracking, KinectFusion's third leg.  ``tests/tsdf_raycast_reference.py`` restates both.
+found -- frame-to-model tracking, KinectFusion's third leg.  ``tests/tsdf_raycast_reference.py`` restates both.  With
+``TrackParams.levels`` / ``smooth`` the registration descends a pyramid of the frame's (optionally bilateral-filtered) depth
+image coarse to fine on one state block (``depth_frame.pyramid``, ``registration.continue_state``;
+``tests/depth_pyramid_reference.py``); off by default.
 """
 from dataclasses import dataclass
 import math
@@ -27,7 +30,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import _lib, depth_frame
-from ._frame_util import MAX_FRAME_POINTS, ParamsBase, matrix4, record_streams, require_cuda, stream_scope
+from ._frame_util import MAX_FRAME_POINTS, ParamsBase, matrix4, record_streams, require_cuda, stream_scope, to_device
 
 _L = _lib.lib
 
@@ -114,6 +117,8 @@ NO_SURFACE, BACK_FACE, HIT, HIT_NO_NORMAL = 0, 1, 2, 3   # raycast's status code
 MAX_RAY_STEPS = 4096                # regnet_tsdf_raycast_f32's documented limit
 FIRST, TRACKED, LOST = "FIRST", "TRACKED", "LOST"
 TRACK_STATUS = (FIRST, TRACKED, LOST)                    # a record's ``track_status`` is the index
+MAX_LEVELS = 4                      # of the tracking pyramid
+LEVEL_ITERATIONS = (10, 5, 4, 4)    # the default steps per level, finest first
 
 
 @dataclass(frozen=True)
@@ -131,7 +136,16 @@ class TrackParams(ParamsBase):
 
     Every default is a choice: a frame-to-frame motion of centimetres and a few degrees, the capture range of the pose
     refinement, twenty steps of which a tracked frame needs a handful; rays from 20 cm to 1.5 m, which spans the default volume
-    seen from about its first camera.  None is measured on real cameras."""
+    seen from about its first camera.  None is measured on real cameras.
+
+    Coarse to fine.  ``levels`` (1..4): the frame's depth image is halved ``levels - 1`` times (``depth_frame.pyramid``) and the
+    registration descends from the coarsest level to the frame's own on ONE state block, the model raycast once per level at the
+    level's intrinsics and size.  ``level_iterations``: the steps per level, FINEST FIRST, 64 in all at most; None:
+    ``(10, 5, 4, 4)[:levels]`` (with one level ``iterations``, which stays the single-level budget).  ``level_dist_scale``: level
+    ``l`` pairs within ``max_dist * level_dist_scale**l``; the pixel ``window`` is the same on every level, so in fine pixels it
+    doubles per level.  ``smooth`` (a ``depth_frame.SmoothParams`` or a dict of its fields): the frame's depth goes through the
+    bilateral filter before the pyramid -- for the registration only; what is integrated is the frame as it came.  With
+    ``levels == 1`` and no ``smooth`` nothing of this runs.  These defaults are choices too."""
     WORD = "track"
     NONE_IS_DEFAULT = True
     max_dist: float = 0.02
@@ -150,9 +164,25 @@ class TrackParams(ParamsBase):
     max_translation: float = 0.05
     max_rotation: float = 0.1
     min_hit_share: float = 0.05
+    levels: int = 1
+    level_iterations: Optional[Tuple[int, ...]] = None
+    level_dist_scale: float = 2.0
+    smooth: Optional[depth_frame.SmoothParams] = None
 
     def __post_init__(self):
         self.icp_params()                                   # (its checks are the registration's)
+        if int(self.levels) != self.levels or not 1 <= self.levels <= MAX_LEVELS:
+            raise ValueError("track: levels must be in 1..%d" % MAX_LEVELS)
+        if self.level_iterations is not None:
+            budgets = tuple(self.level_iterations)
+            if len(budgets) != self.levels or any(int(b) != b or b < 1 for b in budgets) or sum(budgets) > 64:
+                raise ValueError("track: level_iterations must be `levels` positive step counts, finest first, 64 in all at most")
+            object.__setattr__(self, "level_iterations", tuple(int(b) for b in budgets))
+        if not (float(self.level_dist_scale) > 0.0 and math.isfinite(float(self.level_dist_scale))):
+            raise ValueError("track: level_dist_scale must be positive and finite")
+        for level in range(1, int(self.levels)):
+            self.icp_params(level)                          # (a max_dist that leaves float32's range on a coarse level)
+        object.__setattr__(self, "smooth", depth_frame.SmoothParams.coerce(self.smooth))
         check_ray_range(self.near, self.far, self.step, "track")
         for name in ("max_translation", "max_rotation"):
             if not float(getattr(self, name)) > 0.0:        # (a NaN too; inf: no gate)
@@ -160,9 +190,27 @@ class TrackParams(ParamsBase):
         if not 0.0 <= float(self.min_hit_share) <= 1.0:
             raise ValueError("track: min_hit_share must be in 0..1")
 
-    def icp_params(self):
-        """The ``registration.IcpParams`` of a frame-to-model registration."""
+    def pyramid(self):
+        """Whether ``Tracker.track`` takes the coarse-to-fine path: more than one level, or a smoothed frame."""
+        return self.levels > 1 or self.smooth is not None
+
+    def budgets(self):
+        """The steps enqueued per level, finest first: ``level_iterations``, else ``(10, 5, 4, 4)[:levels]``, and with one
+        level ``iterations``."""
+        if self.level_iterations is not None:
+            return self.level_iterations
+        return (int(self.iterations),) if self.levels == 1 else LEVEL_ITERATIONS[:self.levels]
+
+    def icp_params(self, level=None):
+        """The ``registration.IcpParams`` of a frame-to-model registration; ``level``: those of that level of the pyramid, its
+        own step budget and ``max_dist * level_dist_scale**level``."""
         from . import registration
+        if level is not None:
+            return registration.IcpParams(max_dist=float(self.max_dist) * float(self.level_dist_scale) ** level,
+                                          iterations=self.budgets()[level], stride=self.stride, window=self.window,
+                                          min_pairs=self.min_pairs, rot_eps=self.rot_eps, trans_eps=self.trans_eps,
+                                          normal_angle=self.normal_angle, normal_step=self.normal_step,
+                                          normal_jump=self.normal_jump, association="projective")
         return registration.IcpParams(max_dist=self.max_dist, iterations=self.iterations, stride=self.stride, window=self.window,
                                       min_pairs=self.min_pairs, rot_eps=self.rot_eps, trans_eps=self.trans_eps,
                                       normal_angle=self.normal_angle, normal_step=self.normal_step, normal_jump=self.normal_jump,
@@ -380,10 +428,13 @@ class Tracked:
     ``FIRST`` (the first frame, integrated at the starting pose), ``TRACKED`` (registered and integrated) or ``LOST`` (nothing
     integrated, the pose kept); ``report``: ``registration.decode_state``'s dict of the registration, whose ``pose`` takes the
     frame into the model view's camera (None for FIRST); ``counts``: integrate's (4) int32 on the device (None when LOST);
-    ``model``: the ``ModelView`` the frame was registered against (None for FIRST), ``hits`` the pixels in which it hit."""
+    ``model``: the ``ModelView`` the frame was registered against (None for FIRST), ``hits`` the pixels in which it hit;
+    ``levels``: on the coarse-to-fine path a (levels, 2) int32 array, row ``l`` the ``(iteration, status)`` the registration
+    stood at when level ``l`` had run -- row 0 is the end --, else None."""
 
-    def __init__(self, pose, status, report, counts, model, hits=None):
+    def __init__(self, pose, status, report, counts, model, hits=None, levels=None):
         self.pose, self.status, self.report, self.counts, self.model, self.hits = pose, status, report, counts, model, hits
+        self.levels = levels
 
 
 class Tracker:
@@ -437,6 +488,8 @@ class Tracker:
             self.frames = 1
             return Tracked(self.pose.copy(), FIRST, None, counts, None)
         at = self.pose if guess is None else matrix4(guess, "a guess must be a finite 4x4 camera-to-common transform", finite=True)
+        if t.pyramid():
+            return self._track_pyramid(view, at, stream)
         model = self.volume.raycast(at, k, width, height, t.near, t.far, t.step, colour=False, stream=stream)
         icp = t.icp_params()
         n = int(xyz.shape[0])
@@ -449,15 +502,64 @@ class Tracker:
         report = registration.decode_state(raw[:registration.STATE_BYTES])
         hist = raw[registration.STATE_BYTES:].view(np.int32)
         hits = int(hist[HIT]) + int(hist[HIT_NO_NORMAL])
+        return self._judge(view, at, report, model, hits, stream)
+
+
+    def _judge(self, view, at, report, model, hits, stream, levels=None):
+        """The gates, and the integration of a frame that passed them."""
+        from . import registration
+        t = self.params
         moved, turned = relative_motion(report["pose"])
-        lost = (report["status"] in (registration.TOO_FEW, registration.DEGENERATE) or hits < t.min_hit_share * width * height
+        lost = (report["status"] in (registration.TOO_FEW, registration.DEGENERATE) or hits < t.min_hit_share * view[2] * view[3]
                 or moved > t.max_translation or turned > t.max_rotation)
         if lost:
-            return Tracked(self.pose.copy(), LOST, report, None, model, hits)
+            return Tracked(self.pose.copy(), LOST, report, None, model, hits, levels)
         self.pose = at @ report["pose"]
         counts = self.volume.integrate(view, self.pose, stream=stream)
         self.frames += 1
-        return Tracked(self.pose.copy(), TRACKED, report, counts, model, hits)
+        return Tracked(self.pose.copy(), TRACKED, report, counts, model, hits, levels)
+
+    def _track_pyramid(self, view, at, stream):
+        """``track`` coarse to fine (``TrackParams.levels`` / ``smooth``): the z column of the frame's cloud is its depth image;
+        smoothed if asked, halved ``levels - 1`` times with the cutoff 3 ``sigma_depth`` (``max_dist`` without smoothing), every
+        level deprojected by ``to_cloud`` and the model raycast at the level's intrinsics and size; the steps of every level,
+        coarsest first, go onto ONE state block with ``registration.continue_state`` between two levels.  The one blocking read
+        holds the state, level 0's histogram and the hand-over marks; the gates are ``track``'s, ``min_hit_share`` judged on
+        level 0's view, and what is integrated is the frame's own cloud."""
+        import torch
+        from . import registration
+        t = self.params
+        xyz, _, width, height, k = view
+        budgets = t.budgets()
+        cutoff = t.smooth.cutoff() if t.smooth is not None else float(t.max_dist)
+        with torch.cuda.device(self.device), stream_scope(stream):
+            depth = xyz[:, 2].reshape(height, width).contiguous()
+            marks = torch.zeros((t.levels, 2), dtype=torch.int32, device=self.device)
+            state = to_device(registration.initial_state(None, t.icp_params(t.levels - 1)), self.device)
+            record_streams(stream, xyz, depth, marks, state)
+        pyramid = depth_frame.pyramid(depth, k, t.levels, cutoff, t.smooth, stream=stream)
+        model = None
+        for level in range(t.levels - 1, -1, -1):
+            depth_l, k_l, w_l, h_l = pyramid[level]
+            cloud, _ = depth_frame.to_cloud(depth_frame.DepthFrame(depth=depth_l, intrinsics=k_l), None, device=self.device,
+                                            stream=stream)
+            model = self.volume.raycast(at, k_l, w_l, h_l, t.near, t.far, t.step, colour=False, stream=stream)
+            icp = t.icp_params(level)
+            registration.icp(cloud, model.target(icp, max_source=w_l * h_l, stream=stream), None, icp, stream=stream, state=state,
+                             source_shape=(w_l, h_l))
+            if level > 0:
+                registration.continue_state(state, budgets[level - 1], marks[level], stream=stream)
+        with torch.cuda.device(self.device), stream_scope(stream):
+            all_of_it = torch.cat([state, model.counts.view(torch.uint8), marks.view(torch.uint8).reshape(-1)])
+            record_streams(stream, all_of_it)
+        raw = all_of_it.cpu().numpy()                        # the one blocking read
+        n_state = registration.STATE_BYTES
+        report = registration.decode_state(raw[:n_state])
+        hist = raw[n_state:n_state + 16].view(np.int32)
+        levels = raw[n_state + 16:].view(np.int32).reshape(t.levels, 2).copy()
+        levels[0] = (report["iterations"], report["status"])
+        hits = int(hist[HIT]) + int(hist[HIT_NO_NORMAL])
+        return self._judge(view, at, report, model, hits, stream, levels)
 
 
 def relative_motion(T):
