@@ -1411,7 +1411,7 @@ int regnet_grasp_approach_f32(const float* points, int64_t pn, int64_t pc, const
  *               tests below; a grasp whose xh lies beyond x_extent is analysed up to x_extent only).  Sample (i, j, k), cell
  *               centred and never accumulated:
  *                 x_i = xs + (((float)i + 0.5f) * h),  y_j = (((float)j + 0.5f) * h) - hw,  z_k = (((float)k + 0.5f) * h) - ht.
- *   sets        regnet_grasp_approach_f32's predicates, restated, on the sample's local (x, y, z):
+ *   sets        regnet_grasp_approach_f32's predicates (one definition, csrc/hand_box.h), on the sample's local (x, y, z):
  *                 section = z < ht && z > -ht && y < hw && y > -hw;  inner = section && y < hs && y > -hs;
  *                 close = x > x_lo && x < xh;  region = inner && close;
  *                 back = section && close && x < back_x;  finger = section && close && (y > hs || y < -hs);

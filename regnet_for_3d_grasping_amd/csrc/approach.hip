@@ -3,57 +3,23 @@
 // final pose only; this one also sweeps the hand back along -approach, measures the object between the fingers and judges the
 // two contact bands on the observed cloud's normals.
 //
-// One workgroup per grasp, the cloud walked twice in the grasp's local frame, with region.hip's arithmetic restated (this file
-// does not include it): x = ((t00*px + t01*py) + t02*pz) + t03 and likewise y, z, individually rounded fp32 in the written order
-// (built with -ffp-contract=off), every comparison strict.  A point with a NaN coordinate has NaN local coordinates and is in
-// nothing.  With ht / hw / hs the half thickness / half width / half space, xh the grasp's x_hi and S the standoff:
-//   section = |z| < ht && |y| < hw          inner = section && |y| < hs          region = inner && x_lo < x < xh
-//   pass 1: n_region, y_min / y_max / x_min over the region; n_hand = (behind the hand) + (inside a finger) as region.hip counts
-//           them; the blockers of the sweep, section && x < front && x > x_lo - S with front = back_x for inner points and xh in
-//           the finger lanes, their number and the least retreat s = fmaxf(x_lo - x, 0): clearance = fminf(S, min s).
+// One workgroup per grasp, the cloud walked twice in the grasp's local frame.  The local coordinates and the sets of a point
+// (section, inner, region, back, finger, blocker, retreat) are hand_box.h's, the one definition this kernel shares with
+// region.hip's collision scan and with approach_volume.hip: individually rounded fp32 in the written order (built with
+// -ffp-contract=off), every comparison strict, a NaN coordinate in nothing.  With xh the grasp's x_hi and S the standoff:
+//   pass 1: n_region, y_min / y_max / x_min over the region; n_hand = back + finger; the blockers of the sweep, their number and
+//           their least retreat: clearance = fminf(S, min retreat).
 //   pass 2 (normals given and the region not empty): band = min((y_max - y_min) / 3, contact_depth); per band (y > y_max - band,
 //           y < y_min + band, grasp_antipodal_kernel's rule) its size and how many of its points have
 //           |(t10*nx + t11*ny) + t12*nz| >= cos_friction.
-// Only integer sums and float min / max are reduced (wave butterfly, then the four waves through LDS): no floating-point sum and
-// no atomic, so the result does not depend on the order of anything.  Plain vector stores by thread 0.
-#include "common.h"
+// Only integer sums and float min / max are reduced (common.h: the wave butterfly, then the waves through LDS): no floating-point sum and no atomic, so
+// the result does not depend on the order of anything.  Plain vector stores by thread 0.
+#include "hand_box.h"
 
 namespace {
 
 constexpr int AP_T = 256;
 constexpr int AP_W = AP_T / 64;
-
-struct GraspBox {   // the reference's box constants as float32, as in region.hip
-  float x_lo, x_hi, half_thickness, half_width, half_space, back_x;
-};
-
-// local coordinates of point j for the matrix rows held in registers: region.hip's GC_LOCAL, restated
-#define AP_LOCAL(j)                                                          \
-  const float* p = points + (int64_t)(j) * pn;                               \
-  const float px = p[0], py = p[pc], pz = p[2 * pc];                         \
-  const float x = ((t00 * px + t01 * py) + t02 * pz) + t03;                  \
-  const float y = ((t10 * px + t11 * py) + t12 * pz) + t13;                  \
-  const float z = ((t20 * px + t21 * py) + t22 * pz) + t23;                  \
-  const bool section = z < box.half_thickness && z > -box.half_thickness && y < box.half_width && y > -box.half_width; \
-  const bool inner = section && y < box.half_space && y > -box.half_space;   \
-  const bool close = x > box.x_lo && x < x_hi;                               \
-  const bool region = inner && close;
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
 
 __global__ __launch_bounds__(AP_T) void approach_kernel(const float* __restrict__ points, int64_t pn, int64_t pc,
                                                         const float* __restrict__ normals, int64_t nn, int64_t nc, int N,
@@ -63,48 +29,38 @@ __global__ __launch_bounds__(AP_T) void approach_kernel(const float* __restrict_
                                                         int32_t* __restrict__ counts, float* __restrict__ values) {
   __shared__ int red_i[4][AP_W];
   __shared__ float red_f[4][AP_W];
-  const float* t = T + (int64_t)blockIdx.x * 16;
-  const float t00 = t[0], t01 = t[1], t02 = t[2], t03 = t[3];
-  const float t10 = t[4], t11 = t[5], t12 = t[6], t13 = t[7];
-  const float t20 = t[8], t21 = t[9], t22 = t[10], t23 = t[11];
+  const GraspRows g = grasp_rows(T, blockIdx.x, 16);
   const float x_hi = x_hi_per_grasp ? x_hi_per_grasp[blockIdx.x] : box.x_hi;
   const float sweep_lo = box.x_lo - standoff;
-  const int wave = threadIdx.x >> 6;
-  const bool lead = (threadIdx.x & 63) == 0;
 
   int n_region = 0, n_block = 0, n_hand = 0;
   float y_min = __builtin_inff(), y_max = -__builtin_inff(), x_min = __builtin_inff(), s_min = __builtin_inff();
   for (int64_t j = threadIdx.x; j < N; j += AP_T) {   // (64-bit: j + AP_T may pass 2^31)
-    AP_LOCAL(j)
-    if (region) {
+    const float* p = points + j * pn;
+    float x, y, z;
+    grasp_apply(g, p[0], p[pc], p[2 * pc], x, y, z);
+    const HandSets s = hand_sets(box, x_hi, sweep_lo, x, y, z);
+    if (s.region) {
       n_region += 1;
       y_min = fminf(y_min, y);
       y_max = fmaxf(y_max, y);
       x_min = fminf(x_min, x);
     }
-    const bool back = section && close && x < box.back_x;
-    const bool finger = section && close && (y > box.half_space || y < -box.half_space);
-    n_hand += (int)back + (int)finger;
-    const float front = inner ? box.back_x : x_hi;
-    if (section && x < front && x > sweep_lo) {
+    n_hand += (int)s.back + (int)s.finger;
+    if (s.blocker) {
       n_block += 1;
-      s_min = fminf(s_min, fmaxf(box.x_lo - x, 0.0f));
+      s_min = fminf(s_min, s.retreat);
     }
   }
   n_region = wave_sum(n_region); n_block = wave_sum(n_block); n_hand = wave_sum(n_hand);
   y_min = wave_min(y_min); y_max = wave_max(y_max); x_min = wave_min(x_min); s_min = wave_min(s_min);
-  if (lead) {
-    red_i[0][wave] = n_region; red_i[1][wave] = n_block; red_i[2][wave] = n_hand;
-    red_f[0][wave] = y_min; red_f[1][wave] = y_max; red_f[2][wave] = x_min; red_f[3][wave] = s_min;
-  }
+  block_put(n_region, red_i[0]); block_put(n_block, red_i[1]); block_put(n_hand, red_i[2]);
+  block_put(y_min, red_f[0]); block_put(y_max, red_f[1]); block_put(x_min, red_f[2]); block_put(s_min, red_f[3]);
   __syncthreads();
-  n_region = n_block = n_hand = 0;
-#pragma unroll
-  for (int w = 0; w < AP_W; ++w) {
-    n_region += red_i[0][w]; n_block += red_i[1][w]; n_hand += red_i[2][w];
-    y_min = fminf(y_min, red_f[0][w]); y_max = fmaxf(y_max, red_f[1][w]);
-    x_min = fminf(x_min, red_f[2][w]); s_min = fminf(s_min, red_f[3][w]);
-  }
+  n_region = block_sum<AP_W>(red_i[0]); n_block = block_sum<AP_W>(red_i[1]);
+  n_hand = block_sum<AP_W>(red_i[2]);
+  y_min = block_min<AP_W>(red_f[0]); y_max = block_max<AP_W>(red_f[1]);
+  x_min = block_min<AP_W>(red_f[2]); s_min = block_min<AP_W>(red_f[3]);
 
   int n_left = 0, ok_left = 0, n_right = 0, ok_right = 0;
   if (normals != nullptr && n_region > 0) {      // (uniform over the workgroup: every thread holds the reduced values)
@@ -112,24 +68,23 @@ __global__ __launch_bounds__(AP_T) void approach_kernel(const float* __restrict_
     const float band = third < contact_depth ? third : contact_depth;
     const float left_edge = y_max - band, right_edge = y_min + band;
     for (int64_t j = threadIdx.x; j < N; j += AP_T) {
-      AP_LOCAL(j)
-      if (!region) continue;
+      const float* p = points + j * pn;
+      float x, y, z;
+      grasp_apply(g, p[0], p[pc], p[2 * pc], x, y, z);
+      if (!hand_sets(box, x_hi, sweep_lo, x, y, z).region) continue;
       const bool left = y > left_edge, right = y < right_edge;
       if (!(left || right)) continue;
       const float* q = normals + j * nn;
-      const bool ok = fabsf((t10 * q[0] + t11 * q[nc]) + t12 * q[2 * nc]) >= cos_friction;   // (a NaN normal fails)
+      const bool ok = fabsf(dot3(g.r[1][0], g.r[1][1], g.r[1][2], q[0], q[nc], q[2 * nc])) >= cos_friction;   // (a NaN normal fails)
       n_left += (int)left; ok_left += (int)(left && ok);
       n_right += (int)right; ok_right += (int)(right && ok);
     }
     n_left = wave_sum(n_left); ok_left = wave_sum(ok_left); n_right = wave_sum(n_right); ok_right = wave_sum(ok_right);
     __syncthreads();                              // pass 1's reads of red_i are done
-    if (lead) { red_i[0][wave] = n_left; red_i[1][wave] = ok_left; red_i[2][wave] = n_right; red_i[3][wave] = ok_right; }
+    block_put(n_left, red_i[0]); block_put(ok_left, red_i[1]); block_put(n_right, red_i[2]); block_put(ok_right, red_i[3]);
     __syncthreads();
-    n_left = ok_left = n_right = ok_right = 0;
-#pragma unroll
-    for (int w = 0; w < AP_W; ++w) {
-      n_left += red_i[0][w]; ok_left += red_i[1][w]; n_right += red_i[2][w]; ok_right += red_i[3][w];
-    }
+    n_left = block_sum<AP_W>(red_i[0]); ok_left = block_sum<AP_W>(red_i[1]);
+    n_right = block_sum<AP_W>(red_i[2]); ok_right = block_sum<AP_W>(red_i[3]);
   }
   if (threadIdx.x == 0) {
     int32_t* c = counts + (int64_t)blockIdx.x * 8;

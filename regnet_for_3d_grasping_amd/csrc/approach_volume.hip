@@ -7,11 +7,12 @@
 // [-ht, ht].  A wave takes 8 x 8 tiles of the lattice's x-y plane, tile t = wave, wave + 4, ..., lane l at (l & 7, l >> 3) of the
 // tile, and walks the n_z layers: its 64 samples are neighbours in space, so their voxels are neighbours in the volume.  Every
 // sample is taken into the volume's frame by the grasp's own L (rows 0..2 of a 4x4), looked up in the NEAREST voxel (one W, and
-// one D when W >= min_weight) and classified; approach.hip's predicates, restated here (this file includes nothing of it), say
-// which sets it belongs to.  Canonical fp32: individually rounded operations in the written order (-ffp-contract=off), __fdiv_rn,
-// strict comparisons.  Only integer sums and float min / max are reduced (wave butterfly, then the four waves through LDS): no
-// atomic, no floating-point sum.  The volume is only read.  Plain vector stores by thread 0.
-#include "common.h"
+// one D when W >= min_weight) and classified; hand_box.h's sets, the ones approach.hip and region.hip use, say which it
+// belongs to.  Canonical fp32: individually rounded operations in the written order (-ffp-contract=off), __fdiv_rn, strict
+// comparisons.  Only integer sums and float min / max are reduced (common.h: the wave butterfly, then the waves through LDS): no atomic, no
+// floating-point sum.  The volume is only read (tsdf_volume.h: its planes).  Plain vector stores by thread 0.
+#include "hand_box.h"
+#include "tsdf_volume.h"
 
 #include <math.h>
 
@@ -21,10 +22,6 @@ constexpr int AV_T = 256;
 constexpr int AV_W = AV_T / 64;
 constexpr int AV_TILE = 8;
 constexpr int AV_NI = 8, AV_NF = 4;                  // reduced integers and floats
-
-struct HandBox {    // the reference's box constants as float32, as in approach.hip
-  float x_lo, x_hi, half_thickness, half_width, half_space, back_x;
-};
 
 struct Lattice {
   int nx, ny, nz;   // samples per axis
@@ -39,32 +36,13 @@ struct VolumeView {
   int min_weight;
 };
 
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-
-__global__ __launch_bounds__(AV_T) void approach_volume_kernel(VolumeView vol, const float* __restrict__ L, HandBox box,
+__global__ __launch_bounds__(AV_T) void approach_volume_kernel(VolumeView vol, const float* __restrict__ L, GraspBox box,
                                                                const float* __restrict__ x_hi_per_grasp, float standoff,
                                                                Lattice lat, int32_t* __restrict__ counts,
                                                                float* __restrict__ values) {
   __shared__ int red_i[AV_NI][AV_W];
   __shared__ float red_f[AV_NF][AV_W];
-  const float* l = L + (int64_t)blockIdx.x * 12;
-  const float l00 = l[0], l01 = l[1], l02 = l[2], l03 = l[3];
-  const float l10 = l[4], l11 = l[5], l12 = l[6], l13 = l[7];
-  const float l20 = l[8], l21 = l[9], l22 = l[10], l23 = l[11];
+  const GraspRows g = grasp_rows(L, blockIdx.x, 12);
   const float x_hi = x_hi_per_grasp ? x_hi_per_grasp[blockIdx.x] : box.x_hi;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int tiles_x = (lat.nx + AV_TILE - 1) / AV_TILE, tiles_y = (lat.ny + AV_TILE - 1) / AV_TILE;
@@ -80,32 +58,23 @@ __global__ __launch_bounds__(AV_T) void approach_volume_kernel(VolumeView vol, c
     if (i >= lat.nx || j >= lat.ny) continue;
     const float x = lat.xs + (((float)i + 0.5f) * lat.h);
     const float y = (((float)j + 0.5f) * lat.h) - box.half_width;
-    const bool y_in = y < box.half_width && y > -box.half_width;
-    const bool y_inner = y < box.half_space && y > -box.half_space;
-    const bool close = x > box.x_lo && x < x_hi;
-    const float s = fmaxf(box.x_lo - x, 0.0f);
     for (int k = 0; k < lat.nz; ++k) {
       const float z = (((float)k + 0.5f) * lat.h) - box.half_thickness;
-      const bool section = z < box.half_thickness && z > -box.half_thickness && y_in;
-      const bool inner = section && y_inner;
-      const bool region = inner && close;
-      const bool back = section && close && x < box.back_x;
-      const bool finger = section && close && (y > box.half_space || y < -box.half_space);
-      const float front = inner ? box.back_x : x_hi;
-      const bool blocker = section && x < front && x > (lat.xs);
-      const int hand = (int)back + (int)finger;
+      const HandSets in = hand_sets(box, x_hi, lat.xs, x, y, z);
+      const bool region = in.region, blocker = in.blocker;
+      const float s = in.retreat;
+      const int hand = (int)in.back + (int)in.finger;
       const int member = hand + (int)blocker;
       if (!(region || member)) continue;             // in no set: no lookup
-      const float wx = (((l00 * x) + (l01 * y)) + (l02 * z)) + l03;
-      const float wy = (((l10 * x) + (l11 * y)) + (l12 * z)) + l13;
-      const float wz = (((l20 * x) + (l21 * y)) + (l22 * z)) + l23;
+      float wx, wy, wz;
+      grasp_apply(g, x, y, z, wx, wy, wz);
       const float cx = floorf(__fdiv_rn(wx - vol.ox, vol.voxel));
       const float cy = floorf(__fdiv_rn(wy - vol.oy, vol.voxel));
       const float cz = floorf(__fdiv_rn(wz - vol.oz, vol.voxel));
       const bool inside = cx >= 0.0f && cx < fnx && cy >= 0.0f && cy < fny && cz >= 0.0f && cz < fnz;   // (a NaN fails)
       bool solid = false, unseen = true;
       if (inside) {
-        const int64_t v = ((int64_t)(int)cz * vol.ny + (int)cy) * vol.nx + (int)cx;
+        const int64_t v = voxel_index<int64_t>((int)cx, (int)cy, (int)cz, vol.nx, vol.ny);
         if (vol.W[v] >= vol.min_weight) {
           const float d = vol.D[v];
           unseen = d != d;                           // a NaN distance: UNKNOWN
@@ -137,32 +106,19 @@ __global__ __launch_bounds__(AV_T) void approach_volume_kernel(VolumeView vol, c
     }
   }
   int ri[AV_NI] = {region_solid, region_unseen, hand_solid, hand_unseen, block_solid, block_unseen, members, members_outside};
-  float rf[AV_NF];
 #pragma unroll
   for (int q = 0; q < AV_NI; ++q) ri[q] = wave_sum(ri[q]);
-  rf[0] = wave_min(y_min); rf[1] = wave_max(y_max); rf[2] = wave_min(s_seen); rf[3] = wave_min(s_safe);
-  if (lane == 0) {
+  y_min = wave_min(y_min); y_max = wave_max(y_max); s_seen = wave_min(s_seen); s_safe = wave_min(s_safe);
 #pragma unroll
-    for (int q = 0; q < AV_NI; ++q) red_i[q][wave] = ri[q];
-#pragma unroll
-    for (int q = 0; q < AV_NF; ++q) red_f[q][wave] = rf[q];
-  }
+  for (int q = 0; q < AV_NI; ++q) block_put(ri[q], red_i[q]);
+  block_put(y_min, red_f[0]); block_put(y_max, red_f[1]); block_put(s_seen, red_f[2]); block_put(s_safe, red_f[3]);
   __syncthreads();
   if (threadIdx.x == 0) {
     int32_t* c = counts + (int64_t)blockIdx.x * 8;
 #pragma unroll
-    for (int q = 0; q < AV_NI; ++q) {
-      int sum = 0;
-#pragma unroll
-      for (int w = 0; w < AV_W; ++w) sum += red_i[q][w];
-      c[q] = sum;
-    }
-    y_min = red_f[0][0]; y_max = red_f[1][0]; s_seen = red_f[2][0]; s_safe = red_f[3][0];
-#pragma unroll
-    for (int w = 1; w < AV_W; ++w) {
-      y_min = fminf(y_min, red_f[0][w]); y_max = fmaxf(y_max, red_f[1][w]);
-      s_seen = fminf(s_seen, red_f[2][w]); s_safe = fminf(s_safe, red_f[3][w]);
-    }
+    for (int q = 0; q < AV_NI; ++q) c[q] = block_sum<AV_W>(red_i[q]);
+    y_min = block_min<AV_W>(red_f[0]); y_max = block_max<AV_W>(red_f[1]);
+    s_seen = block_min<AV_W>(red_f[2]); s_safe = block_min<AV_W>(red_f[3]);
     float* v = values + (int64_t)blockIdx.x * 4;
     v[0] = y_min + 0.0f; v[1] = y_max + 0.0f;        // (+ 0.0f: no -0.0 leaves the kernel)
     v[2] = fminf(standoff, s_seen) + 0.0f; v[3] = fminf(standoff, s_safe) + 0.0f;
@@ -210,9 +166,10 @@ extern "C" int regnet_grasp_approach_volume_f32(const void* volume, int64_t nx, 
   if (B == 0) return REGNET_OK;
   if (!volume || !origin3 || !L || !counts || !values) return REGNET_ERR_NULL;
   const int64_t n = nx * ny * nz;
-  const VolumeView vol{(const float*)volume, (const int32_t*)volume + n, (int)nx, (int)ny, (int)nz, origin3[0], origin3[1],
+  const Planes planes = planes_of(const_cast<void*>(volume), n);
+  const VolumeView vol{planes.D, planes.W, (int)nx, (int)ny, (int)nz, origin3[0], origin3[1],
                        origin3[2], voxel_f, d_solid, (int)min_weight};
-  const HandBox box{x_lo, x_hi, half_thickness, half_width, half_space, back_x};
+  const GraspBox box{x_lo, x_hi, half_thickness, half_width, half_space, back_x};
   const Lattice lat{n_x, n_y, n_z, xs, h};
   hipLaunchKernelGGL(approach_volume_kernel, dim3((unsigned)B), dim3(AV_T), 0, as_stream(stream), vol, L, box, x_hi_per_grasp,
                      standoff, lat, counts, values);

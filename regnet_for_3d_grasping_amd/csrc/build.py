@@ -82,7 +82,7 @@ NO_VGPR_SPILL = {"mlp.o": ["mlp_gemm_kernelILi0E", "gemm2_kernel"], "sa_chain.o"
                  "scatter.o": ["scatter_", "segsum_"], "det.o": ["det_"],
                  "ingest.o": ["ingest_"], "nms.o": ["nms_"], "plane.o": ["plane_"], "depth.o": ["depth_"],
                  "fuse.o": ["fuse_"], "icp.o": ["icp_"], "outlier.o": ["outlier_"], "tsdf.o": ["tsdf_"],
-                 "approach_volume.o": ["approach_volume_"]}
+                 "approach.o": ["approach_kernel"], "approach_volume.o": ["approach_volume_"]}
 
 
 def check_no_vgpr_spill(obj_path, fragments):

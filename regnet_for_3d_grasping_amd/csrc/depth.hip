@@ -79,9 +79,9 @@ __device__ __forceinline__ Projection depth_project(const DepthArgs& a, float x,
   Projection p;
   p.inside = false;
   p.fu = p.fv = 0;
-  const float xp = (((a.r[0] * x) + (a.r[1] * y)) + (a.r[2] * z)) + a.tr[0];
-  const float yp = (((a.r[3] * x) + (a.r[4] * y)) + (a.r[5] * z)) + a.tr[1];
-  const float zp = (((a.r[6] * x) + (a.r[7] * y)) + (a.r[8] * z)) + a.tr[2];
+  const float xp = affine3(a.r[0], a.r[1], a.r[2], a.tr[0], x, y, z);
+  const float yp = affine3(a.r[3], a.r[4], a.r[5], a.tr[1], x, y, z);
+  const float zp = affine3(a.r[6], a.r[7], a.r[8], a.tr[2], x, y, z);
   p.zp = zp;
   if (!(__builtin_isfinite(zp) && zp > 0.0f)) return p;
   const float uc = (__fdiv_rn(xp, zp) * a.fxc) + a.cxc;

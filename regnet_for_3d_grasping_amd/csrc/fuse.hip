@@ -58,9 +58,9 @@ __host__ __device__ inline bool fuse_finite(float v) { return fabsf(v) < __built
 
 // Pose, voxel coordinate and fraction of one point, every operation rounded on its own.  false: out of range.
 __host__ __device__ inline bool fuse_voxel(float x, float y, float z, const FuseFrame& F, float* p, int* i, float* f) {
-  p[0] = ((F.r[0] * x + F.r[1] * y) + F.r[2] * z) + F.r[3];
-  p[1] = ((F.r[4] * x + F.r[5] * y) + F.r[6] * z) + F.r[7];
-  p[2] = ((F.r[8] * x + F.r[9] * y) + F.r[10] * z) + F.r[11];
+  p[0] = affine3(F.r, x, y, z);
+  p[1] = affine3(F.r + 4, x, y, z);
+  p[2] = affine3(F.r + 8, x, y, z);
   bool ok = true;
 #ifdef __HIP_DEVICE_COMPILE__
 #pragma unroll

@@ -116,9 +116,9 @@ __global__ __launch_bounds__(ICP_BLOCK) void icp_correspond_kernel(const float* 
       float r[12];
 #pragma unroll
       for (int j = 0; j < 12; ++j) r[j] = (float)state->pose[j];       // rounded once, to nearest even
-      px = ((r[0] * x + r[1] * y) + r[2] * z) + r[3];
-      py = ((r[4] * x + r[5] * y) + r[6] * z) + r[7];
-      pz = ((r[8] * x + r[9] * y) + r[10] * z) + r[11];
+      px = affine3(r, x, y, z);
+      py = affine3(r + 4, x, y, z);
+      pz = affine3(r + 8, x, y, z);
       if (n_target > 0 && icp_finite(px) && icp_finite(py) && icp_finite(pz)) {
         const GridHeader H = *reinterpret_cast<const GridHeader*>(slab);
         const int* cell_start = grid_cell_start(const_cast<char*>(slab));
@@ -178,17 +178,17 @@ __global__ __launch_bounds__(ICP_BLOCK) void icp_project_kernel(const float* __r
       float r[12];
 #pragma unroll
       for (int j = 0; j < 12; ++j) r[j] = (float)state->pose[j];       // rounded once, to nearest even
-      px = ((r[0] * x + r[1] * y) + r[2] * z) + r[3];
-      py = ((r[4] * x + r[5] * y) + r[6] * z) + r[7];
-      pz = ((r[8] * x + r[9] * y) + r[10] * z) + r[11];
+      px = affine3(r, x, y, z);
+      py = affine3(r + 4, x, y, z);
+      pz = affine3(r + 8, x, y, z);
       bool usable = icp_finite(px) && icp_finite(py) && icp_finite(pz) && pz > 0.f;
       float mx = 0.f, my = 0.f, mz = 0.f;
       if (usable && src_normals != nullptr) {
         const float sx = src_normals[i * 3], sy = src_normals[i * 3 + 1], sz = src_normals[i * 3 + 2];
         usable = icp_finite(sx) && icp_finite(sy) && icp_finite(sz);
-        mx = (r[0] * sx + r[1] * sy) + r[2] * sz;
-        my = (r[4] * sx + r[5] * sy) + r[6] * sz;
-        mz = (r[8] * sx + r[9] * sy) + r[10] * sz;
+        mx = dot3(r[0], r[1], r[2], sx, sy, sz);
+        my = dot3(r[4], r[5], r[6], sx, sy, sz);
+        mz = dot3(r[8], r[9], r[10], sx, sy, sz);
       }
       if (usable) {
         const float uf = (__fdiv_rn(px, pz) * cam.fx) + cam.cx;
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(ICP_BLOCK) void icp_project_kernel(const float* __r
               const float tx = target[(int64_t)j * 3], ty = target[(int64_t)j * 3 + 1], tz = target[(int64_t)j * 3 + 2];
               const float nx = normals[(int64_t)j * 3], ny = normals[(int64_t)j * 3 + 1], nz = normals[(int64_t)j * 3 + 2];
               bool ok = icp_finite(tx) && icp_finite(ty) && icp_finite(tz) && icp_finite(nx) && icp_finite(ny) && icp_finite(nz);
-              if (src_normals != nullptr) ok = ok && ((mx * nx + my * ny) + mz * nz) >= min_cos;   // (a NaN product fails)
+              if (src_normals != nullptr) ok = ok && dot3(mx, my, mz, nx, ny, nz) >= min_cos;   // (a NaN product fails)
               const float d2 = sqdist3(px, py, pz, tx, ty, tz);
               if (ok && d2 < bd) { bd = d2; bj = j; qx = tx; qy = ty; qz = tz; }
             }

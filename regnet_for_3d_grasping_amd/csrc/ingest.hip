@@ -38,9 +38,9 @@ __device__ __forceinline__ void load_point(const T* __restrict__ xyz, long long 
 
 __device__ __forceinline__ void transform_point(const CropArgs& a, double x, double y, double z, double& tx, double& ty,
                                                 double& tz) {
-  tx = ((a.T[0] * x + a.T[1] * y) + a.T[2] * z) + a.T[3];
-  ty = ((a.T[4] * x + a.T[5] * y) + a.T[6] * z) + a.T[7];
-  tz = ((a.T[8] * x + a.T[9] * y) + a.T[10] * z) + a.T[11];
+  tx = affine3(a.T, x, y, z);
+  ty = affine3(a.T + 4, x, y, z);
+  tz = affine3(a.T + 8, x, y, z);
 }
 
 // pass 1: one ballot per wave (kept for pass 3, so both passes agree by construction) + the workgroup's count

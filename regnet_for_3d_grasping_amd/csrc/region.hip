@@ -11,7 +11,7 @@
 // the points 64 at a time and appends the members in ascending index order with a ballot +
 // prefix-popcount, so the host receives every candidate list and count with a single sync and
 // only has to draw the numpy random positions.
-#include "common.h"
+#include "hand_box.h"
 
 #define RG_WAVES 4
 
@@ -384,66 +384,38 @@ extern "C" int regnet_crop_pick(const int32_t* cand, int64_t G, const int64_t* p
 // Python and, for each, multiplies the whole cloud by the grasp's 4x4 global->local matrix and builds five boolean
 // masks with torch ops (~25 launches and a host sync per grasp; 4000 grasps per scene in test.py).  Here: one workgroup
 // per grasp walks the cloud once and counts the points (0) in the closing slab -bottom < x < depth, (1) behind the hand,
-// (2) inside either finger -- the three numbers the reference's thresholds are applied to.  Arithmetic: individually
-// rounded fp32 in source order, x = ((t00*px + t01*py) + t02*pz) + t03 (this file is built with -ffp-contract=off), the
-// same as oracle/collision_oracle.py.
+// (2) inside either finger -- the three numbers the reference's thresholds are applied to.  The local coordinates and the
+// sets are hand_box.h's (shared with approach.hip and approach_volume.hip): individually rounded fp32 in source order (this
+// file is built with -ffp-contract=off), the same as oracle/collision_oracle.py.
 #define GC_T 256
-
-struct GraspBox {   // the reference's box constants as float32 (what torch compares a float32 tensor against)
-  float x_lo, x_hi, half_thickness, half_width, half_space, back_x;
-};
-
-// local coordinates of point j for the matrix rows held in registers; returns false when outside the closing slab
-#define GC_LOCAL(j)                                                          \
-  const float* p = points + (int64_t)(j) * pn;                               \
-  const float px = p[0], py = p[pc], pz = p[2 * pc];                         \
-  const float x = ((t00 * px + t01 * py) + t02 * pz) + t03;                  \
-  const bool close = x > box.x_lo && x < x_hi;                               \
-  const float y = ((t10 * px + t11 * py) + t12 * pz) + t13;                  \
-  const float z = ((t20 * px + t21 * py) + t22 * pz) + t23;                  \
-  const bool zc = close && z < box.half_thickness && z > -box.half_thickness;
-
-__device__ __forceinline__ int block_sum_int(int v, int* red) {   // red: GC_T / 64 ints of LDS; all threads get the sum
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int s = 0;
-#pragma unroll
-  for (int w = 0; w < GC_T / 64; ++w) s += red[w];
-  return s;
-}
+#define GC_W (GC_T / 64)
 
 // counts[b] = { closing slab, behind the hand, inside a finger, between the fingers (closing region) }
 __global__ __launch_bounds__(GC_T) void grasp_collision_kernel(const float* __restrict__ points, int64_t pn, int64_t pc,
                                                                int N, const float* __restrict__ T, GraspBox box,
                                                                const float* __restrict__ x_hi_per_grasp,
                                                                int32_t* __restrict__ counts) {
-  __shared__ int red[GC_T / 64];
-  const float* t = T + (int64_t)blockIdx.x * 16;
-  const float t00 = t[0], t01 = t[1], t02 = t[2], t03 = t[3];
-  const float t10 = t[4], t11 = t[5], t12 = t[6], t13 = t[7];
-  const float t20 = t[8], t21 = t[9], t22 = t[10], t23 = t[11];
+  __shared__ int red[4][GC_W];
+  const GraspRows g = grasp_rows(T, blockIdx.x, 16);
   const float x_hi = x_hi_per_grasp ? x_hi_per_grasp[blockIdx.x] : box.x_hi;
   int c_close = 0, c_back = 0, c_finger = 0, c_region = 0;
   for (int j = threadIdx.x; j < N; j += GC_T) {
-    GC_LOCAL(j)
-    const bool back = zc && y < box.half_width && y > -box.half_width && x < box.back_x;
-    const bool finger = zc && ((y < box.half_width && y > box.half_space) || (y > -box.half_width && y < -box.half_space));
-    const bool region = zc && y < box.half_space && y > -box.half_space;
-    c_close += close;
-    c_back += back;
-    c_finger += finger;
-    c_region += region;
+    const float* p = points + (int64_t)j * pn;
+    float x, y, z;
+    grasp_apply(g, p[0], p[pc], p[2 * pc], x, y, z);
+    const HandSets s = hand_sets(box, x_hi, box.x_lo, x, y, z);
+    c_close += s.close;                            // (the slab alone, whatever the section)
+    c_back += s.back;
+    c_finger += s.finger;
+    c_region += s.region;
   }
-  c_close = block_sum_int(c_close, red);
-  c_back = block_sum_int(c_back, red);
-  c_finger = block_sum_int(c_finger, red);
-  c_region = block_sum_int(c_region, red);
+  c_close = wave_sum(c_close); c_back = wave_sum(c_back); c_finger = wave_sum(c_finger); c_region = wave_sum(c_region);
+  block_put(c_close, red[0]); block_put(c_back, red[1]); block_put(c_finger, red[2]); block_put(c_region, red[3]);
+  __syncthreads();
   if (threadIdx.x == 0) {
     int32_t* o = counts + (int64_t)blockIdx.x * 4;
-    o[0] = c_close; o[1] = c_back; o[2] = c_finger; o[3] = c_region;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) o[q] = block_sum<GC_W>(red[q]);
   }
 }
 
@@ -457,51 +429,51 @@ __global__ __launch_bounds__(GC_T) void grasp_antipodal_kernel(const float* __re
                                                                const float* __restrict__ x_hi_per_grasp,
                                                                float neighbour_depth, float* __restrict__ stats,
                                                                int32_t* __restrict__ side_counts) {
-  __shared__ float redf[2][GC_T / 64];
-  __shared__ double redd[2][GC_T / 64];
-  __shared__ int red[GC_T / 64];
-  const float* t = T + (int64_t)blockIdx.x * 16;
-  const float t00 = t[0], t01 = t[1], t02 = t[2], t03 = t[3];
-  const float t10 = t[4], t11 = t[5], t12 = t[6], t13 = t[7];
-  const float t20 = t[8], t21 = t[9], t22 = t[10], t23 = t[11];
+  __shared__ float redf[2][GC_W];
+  __shared__ double redd[2][GC_W];
+  __shared__ int red[2][GC_W];
+  const GraspRows g = grasp_rows(T, blockIdx.x, 16);
   const float x_hi = x_hi_per_grasp ? x_hi_per_grasp[blockIdx.x] : box.x_hi;
   float ymax = -__builtin_inff(), ymin = __builtin_inff();
   for (int j = threadIdx.x; j < N; j += GC_T) {
-    GC_LOCAL(j)
-    if (zc && y < box.half_space && y > -box.half_space) { ymax = fmaxf(ymax, y); ymin = fminf(ymin, y); }
+    const float* p = points + (int64_t)j * pn;
+    float x, y, z;
+    grasp_apply(g, p[0], p[pc], p[2 * pc], x, y, z);
+    if (hand_sets(box, x_hi, box.x_lo, x, y, z).region) { ymax = fmaxf(ymax, y); ymin = fminf(ymin, y); }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { ymax = fmaxf(ymax, __shfl_xor(ymax, o)); ymin = fminf(ymin, __shfl_xor(ymin, o)); }
-  if ((threadIdx.x & 63) == 0) { redf[0][threadIdx.x >> 6] = ymax; redf[1][threadIdx.x >> 6] = ymin; }
+  ymax = wave_max(ymax); ymin = wave_min(ymin);
+  block_put(ymax, redf[0]); block_put(ymin, redf[1]);
   __syncthreads();
-#pragma unroll
-  for (int w = 0; w < GC_T / 64; ++w) { ymax = fmaxf(ymax, redf[0][w]); ymin = fminf(ymin, redf[1][w]); }
+  ymax = block_max<GC_W>(redf[0]); ymin = block_min<GC_W>(redf[1]);
   const float third = (ymax - ymin) / 3.0f;
   const float depth = third < neighbour_depth ? third : neighbour_depth;   // torch.min(a, b)
   const float left_edge = ymax - depth, right_edge = ymin + depth;
   double s_left = 0.0, s_right = 0.0;
   int n_left = 0, n_right = 0;
   for (int j = threadIdx.x; j < N; j += GC_T) {
-    GC_LOCAL(j)
-    if (!(zc && y < box.half_space && y > -box.half_space)) continue;
+    const float* p = points + (int64_t)j * pn;
+    float x, y, z;
+    grasp_apply(g, p[0], p[pc], p[2 * pc], x, y, z);
+    if (!hand_sets(box, x_hi, box.x_lo, x, y, z).region) continue;
     const float* q = normals + (int64_t)j * nn;
-    const float ny = fabsf((t10 * q[0] + t11 * q[nc]) + t12 * q[2 * nc]);
+    const float ny = fabsf(dot3(g.r[1][0], g.r[1][1], g.r[1][2], q[0], q[nc], q[2 * nc]));
     if (y > left_edge) { s_left += (double)ny; n_left += 1; }
     if (y < right_edge) { s_right += (double)ny; n_right += 1; }
   }
+  // the float64 sums keep their own fixed tree: the butterfly, then waves 0..3 added in order by thread 0
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) { s_left += __shfl_xor(s_left, o); s_right += __shfl_xor(s_right, o); }
-  if ((threadIdx.x & 63) == 0) { redd[0][threadIdx.x >> 6] = s_left; redd[1][threadIdx.x >> 6] = s_right; }
-  n_left = block_sum_int(n_left, red);     // (its barriers also publish redd)
-  n_right = block_sum_int(n_right, red);
+  n_left = wave_sum(n_left); n_right = wave_sum(n_right);
+  block_put(s_left, redd[0]); block_put(s_right, redd[1]); block_put(n_left, red[0]); block_put(n_right, red[1]);
+  __syncthreads();
   if (threadIdx.x == 0) {
     double a = 0.0, b = 0.0;
 #pragma unroll
-    for (int w = 0; w < GC_T / 64; ++w) { a += redd[0][w]; b += redd[1][w]; }
+    for (int w = 0; w < GC_W; ++w) { a += redd[0][w]; b += redd[1][w]; }
     float* o = stats + (int64_t)blockIdx.x * 4;
     o[0] = ymax; o[1] = ymin; o[2] = (float)a; o[3] = (float)b;
-    side_counts[(int64_t)blockIdx.x * 2] = n_left;
-    side_counts[(int64_t)blockIdx.x * 2 + 1] = n_right;
+    side_counts[(int64_t)blockIdx.x * 2] = block_sum<GC_W>(red[0]);
+    side_counts[(int64_t)blockIdx.x * 2 + 1] = block_sum<GC_W>(red[1]);
   }
 }
 

@@ -24,7 +24,7 @@
 //     against the box of voxel centres leaves it (conservatively: the samples skipped are unknown by the sample rule, so the
 //     clip changes no bit).  The histogram collects in LDS as integrate's does.
 // The launches are ordered by the stream: no workgroup waits for another, no flags, no cooperative launch.
-#include "common.h"
+#include "tsdf_volume.h"
 
 namespace {
 
@@ -40,20 +40,6 @@ constexpr unsigned TS_QNAN = 0x7FC00000u;
 
 enum { TS_UPDATED = 0, TS_NOT_IN_VIEW = 1, TS_NO_DEPTH = 2, TS_BEHIND = 3, TS_CODES = 4 };
 
-struct Planes {
-  float* D;
-  int32_t* W;
-  float* C[3];
-};
-
-__host__ __device__ __forceinline__ Planes planes_of(void* volume, long long n) {
-  Planes p;
-  p.D = (float*)volume;
-  p.W = (int32_t*)volume + n;
-  p.C[0] = (float*)volume + 2 * n; p.C[1] = (float*)volume + 3 * n; p.C[2] = (float*)volume + 4 * n;
-  return p;
-}
-
 struct IntegrateArgs {
   int nx, ny, nz, tiles_x, tiles_y;
   int width, height, max_weight;
@@ -61,8 +47,6 @@ struct IntegrateArgs {
   float fx, fy, cx, cy;
   float r[12];
 };
-
-__device__ __forceinline__ float centre(float o, int i, float voxel) { return o + (((float)i + 0.5f) * voxel); }
 
 __global__ __launch_bounds__(TS_BLOCK) void tsdf_reset_kernel(Planes p, long long n) {
   const long long l = (long long)blockIdx.x * TS_BLOCK + threadIdx.x;
@@ -97,9 +81,8 @@ __global__ __launch_bounds__(TS_BLOCK) void tsdf_integrate_kernel(Planes p, cons
     float z = 0.0f;
     if (active) {
       const float pz = centre(a.o[2], iz, a.voxel);
-      const float x = (((a.r[0] * px) + (a.r[1] * py)) + (a.r[2] * pz)) + a.r[3];
-      const float y = (((a.r[4] * px) + (a.r[5] * py)) + (a.r[6] * pz)) + a.r[7];
-      z = (((a.r[8] * px) + (a.r[9] * py)) + (a.r[10] * pz)) + a.r[11];
+      const float x = affine3(a.r, px, py, pz), y = affine3(a.r + 4, px, py, pz);
+      z = affine3(a.r + 8, px, py, pz);
       if (__builtin_isfinite(z) && z > 0.0f) {
         const float u = (__fdiv_rn(x, z) * a.fx) + a.cx;
         const float v = (__fdiv_rn(y, z) * a.fy) + a.cy;
@@ -123,7 +106,7 @@ __global__ __launch_bounds__(TS_BLOCK) void tsdf_integrate_kernel(Planes p, cons
         if (!(sdf < -a.trunc)) {
           code = TS_UPDATED;
           const float t = fminf(sdf * a.rtrunc, 1.0f);
-          const long long l = ((long long)iz * a.ny + iy) * a.nx + ix;
+          const long long l = voxel_index<long long>(ix, iy, iz, a.nx, a.ny);
           // every load before the first store: the five planes are one allocation, which the compiler must take to alias
           const int w = p.W[l];
           const float d = p.D[l];
@@ -344,7 +327,7 @@ __device__ __forceinline__ void rc_point(const RaycastArgs& a, float du, float d
   c[1] = (dv * z) * a.rfy;
   c[2] = z;
 #pragma unroll
-  for (int k = 0; k < 3; ++k) p[k] = (((a.r[4 * k] * c[0]) + (a.r[4 * k + 1] * c[1])) + (a.r[4 * k + 2] * c[2])) + a.r[4 * k + 3];
+  for (int k = 0; k < 3; ++k) p[k] = affine3(a.r + 4 * k, c[0], c[1], c[2]);
 }
 
 // the cell of p: its lower corner's linear index and the three fractions; false when p is not inside the box of voxel centres
@@ -359,7 +342,7 @@ __device__ __forceinline__ bool rc_cell(const RaycastArgs& a, const float p[3], 
     inside = inside && fl >= 0.0f && (fl + 1.0f) <= a.top[k];      // in float: a NaN fails
     i[k] = inside ? (int)fl : 0;
   }
-  l = (i[2] * a.n[1] + i[1]) * a.n[0] + i[0];
+  l = voxel_index<int>(i[0], i[1], i[2], a.n[0], a.n[1]);
   return inside;
 }
 
