@@ -1217,6 +1217,65 @@ int regnet_tsdf_emit_f32(const void* volume, int64_t nx, int64_t ny, int64_t nz,
                          int64_t min_weight, const int32_t* block_counts, const int32_t* block_base, int64_t max_points,
                          float* xyz, float* rgb, float* normal, int32_t* weight, int32_t* num, void* stream);
 
+/* Triangle mesh (csrc/tsdf_mesh.hip): marching cubes over the extraction above.  The mesh's vertices ARE the rows of
+ * regnet_tsdf_emit_f32; these entry points add the index buffer.  Integer work only: D < 0 and D < 1 are the only floating-point
+ * operations, so nothing is rounded, and two runs give the same bytes.
+ *   cell        addressed by the linear index l of its low corner voxel (ix, iy, iz), ix < nx - 1, iy < ny - 1, iz < nz - 1; any dim
+ *               < 2: no cell, a valid empty mesh.  Corner c in 0..7 is voxel (ix + (c & 1), iy + (c >> 1 & 1), iz + (c >> 2 & 1)).  A
+ *               corner is USABLE iff W >= min_weight && D < 1.0f (a NaN is not); a cell is MESHED iff all eight are.  Its case
+ *               is the 8-bit mask of the corners with D < 0.0f (+0 and -0 are both outside).  Every sign-changing edge of a
+ *               meshed cell is a kept candidate of the extraction: the mesh never needs a vertex the surface lacks.
+ *   edge        of a cell: (corner c, axis a) with bit a of c clear, joining c to c | 1 << a; the twelve are numbered in ascending
+ *               (c, a).  Its vertex is the surface row whose key is 3 l(voxel of c) + a.
+ *   case table  256 cases, at most 5 triangles each, as edge numbers; derived (csrc/tsdf_mesh_table.h at compile time,
+ *               tests/tsdf_mesh_reference.py in Python), not copied.  On each of the six faces (k, s) -- the corners whose bit k
+ *               is s, in the cyclic order q0..q3 = (0,0), (1,0), (1,1), (0,1) of their (u, v) = ((k + 1) % 3, (k + 2) % 3) bits,
+ *               face edge E_i joining q_i to q_(i+1) -- every maximal run q_i .. q_j of inside corners (not none, not all) is
+ *               cut off by ONE segment from E_(i-1) to E_j: two diagonal inside corners are cut off one by one, by the face's
+ *               own four signs, so two cells that share a face agree on it.  Seen from outside the cell a segment runs clockwise
+ *               round its run (E_(i-1) -> E_j for s = 1, reversed for s = 0).  A crossed edge ends one segment and starts one:
+ *               closed directed loops of 3 to 7 edges, in ascending order of their lowest edge.  Loop v_0 .. v_(n-1) becomes
+ *               the fan (v_0, v_i, v_(i+1)), i = 1 .. n - 2, from the apex v_0: the loop's edge with the fewest fan diagonals
+ *               that lie in a cube face (none for every loop of the 256 cases), the lowest edge number among equals.  The
+ *               right-hand-rule normal of every triangle points towards D > 0, where the surface's normals point.  820
+ *               triangles in all.  regnet_tsdf_mesh_case(case, edges16): HOST only, the compiled table's row -- three edge
+ *               numbers per triangle, -1 in the unused slots --, REGNET_ERR_SHAPE for a case outside 0..255.
+ *   order       triangles ascend by cell l and within a cell follow the table: no sort.
+ *   regnet_tsdf_mesh_blocks(nx, ny, nz) = ceil(N / 256), the blocks of 256 consecutive l; regnet_tsdf_mesh_scratch_bytes = 4 N; -1
+ *               each for dims < 1 or N > 2^28.
+ *   regnet_tsdf_mesh_count   pass 1: tri_block_counts (regnet_tsdf_mesh_blocks) int32 DEVICE, the triangles of the cells l in
+ *               [256 b, 256 b + 256); num_tri is cleared.  Two launches; a workgroup takes 16 blocks one after the other.
+ *   (the caller)        tri_block_base = the exclusive prefix sum of tri_block_counts, int32 DEVICE (at most 5 N < 2^31).
+ *   regnet_tsdf_mesh_emit    pass 2.  block_counts, block_base: the arrays regnet_tsdf_count left and the caller's prefix sum of
+ *               them, and K_source: the num array regnet_tsdf_emit_f32 wrote (K = K_source[0] is read on the device), all of
+ *               the SAME volume state and min_weight, enqueued before this call.  First the row lookup: the extraction's
+ *               predicate is recomputed and ranked as pass 2 of the extraction ranks it, and every voxel with a kept candidate
+ *               leaves (min(first row, 2^28 - 1) << 3) | kept axes in `scratch` (regnet_tsdf_mesh_scratch_bytes, 4-byte aligned,
+ *               the caller's; the other words are neither written nor read): the row of candidate (v, a) is v's first row plus
+ *               its kept axes below a.  Then the cells: the case is recomputed, the triangles of a block are ranked in cell
+ *               order (ballots over the bits of the per-cell count, the waves' totals through LDS), and triangle row
+ *               tri_block_base[b] + rank, when below max_triangles, receives its three vertex rows -- or (-1, -1, -1) IN ITS PLACE
+ *               when one of them is >= K (the surface overflowed max_points), so ranks do not move.
+ *   outputs     tri (max_triangles, 3) int32 DEVICE; with Tt = tri_block_base[last] + tri_block_counts[last] and Kt = min(Tt,
+ *               max_triangles), rows >= Kt hold -1.  num_tri (4) int32 DEVICE = Kt, Tt, dropped (the rows < Kt written as
+ *               (-1, -1, -1)), overflow = Tt > max_triangles; on overflow the rows are those of the smallest cells.  num_tri must
+ *               be the array pass 1 was given.  Three launches.
+ *   degenerate  D_v == 0 puts the vertices of up to three edges on one voxel centre: zero-area triangles, which are KEPT -- the
+ *               mesh stays closed.  A cell with a corner that is not usable is not meshed: the mesh has holes along the border
+ *               of observed space.
+ * No host read, no synchronisation, no allocation, no cooperative launch, no floating-point arithmetic; capturable.  Errors, all
+ * before any launch: a dim, min_weight or max_triangles < 1 -> REGNET_ERR_SHAPE; N > 2^28 or max_triangles > 2^22 ->
+ * REGNET_ERR_UNSUPPORTED; a NULL pointer -> REGNET_ERR_NULL.                                                                  */
+int64_t regnet_tsdf_mesh_blocks(int64_t nx, int64_t ny, int64_t nz);
+int64_t regnet_tsdf_mesh_scratch_bytes(int64_t nx, int64_t ny, int64_t nz);
+int regnet_tsdf_mesh_case(int64_t case_index, int8_t* edges16);
+int regnet_tsdf_mesh_count(const void* volume, int64_t nx, int64_t ny, int64_t nz, int64_t min_weight, int32_t* tri_block_counts,
+                           int32_t* num_tri, void* stream);
+int regnet_tsdf_mesh_emit(const void* volume, int64_t nx, int64_t ny, int64_t nz, int64_t min_weight, const int32_t* block_counts,
+                          const int32_t* block_base, const int32_t* K_source, const int32_t* tri_block_counts,
+                          const int32_t* tri_block_base, int64_t max_triangles, void* scratch, int32_t* tri, int32_t* num_tri,
+                          void* stream);
+
 /* regnet_tsdf_raycast_f32: the MODEL VIEW of the volume from a virtual pinhole camera -- per pixel the first zero crossing of D
  * along its ray, with the normal of D's gradient and the colour there: the organised vertex and normal map
  * regnet_icp_step_projective_f32 takes as its target (frame-to-model tracking), and a denoised depth image of the fused model.

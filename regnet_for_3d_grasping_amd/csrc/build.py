@@ -47,6 +47,7 @@ SOURCES = [
     ("approach.hip", ["-ffp-contract=off"]),   # approach analysis: every box, sweep and band test is on individually rounded fp32 coordinates
     ("outlier.hip", ["-ffp-contract=off"]),   # outlier removal: every neighbour is decided on individually rounded fp32 distances
     ("tsdf.hip", ["-ffp-contract=off"]),   # TSDF volume: every voxel's running means and every surface row are compared bit for bit with numpy
+    ("tsdf_mesh.hip", []),   # the volume's triangle mesh: integer work only (two float compares), nothing to round
     ("approach_volume.hip", ["-ffp-contract=off"]),   # approach against the volume: every sample's voxel and set are decided on individually rounded fp32
 ]
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
@@ -81,7 +82,7 @@ NO_VGPR_SPILL = {"mlp.o": ["mlp_gemm_kernelILi0E", "gemm2_kernel"], "sa_chain.o"
                  "heads.o": ["heads_chain_kernel", "heads_tree_kernel"], "ops_f64.o": ["_f64_kernel"],
                  "scatter.o": ["scatter_", "segsum_"], "det.o": ["det_"],
                  "ingest.o": ["ingest_"], "nms.o": ["nms_"], "plane.o": ["plane_"], "depth.o": ["depth_"],
-                 "fuse.o": ["fuse_"], "icp.o": ["icp_"], "outlier.o": ["outlier_"], "tsdf.o": ["tsdf_"],
+                 "fuse.o": ["fuse_"], "icp.o": ["icp_"], "outlier.o": ["outlier_"], "tsdf.o": ["tsdf_"], "tsdf_mesh.o": ["tsdf_mesh_"],
                  "approach.o": ["approach_kernel"], "approach_volume.o": ["approach_volume_"]}
 
 

@@ -138,39 +138,6 @@ __global__ __launch_bounds__(TS_BLOCK) void tsdf_integrate_kernel(Planes p, cons
   }
 }
 
-struct ExtractArgs {
-  int nx, ny, nz, n, min_weight;
-};
-
-// whether the candidate (l, axis) is kept, for the three axes: bit a of the result
-__device__ __forceinline__ int tsdf_kept(const float* __restrict__ D, const int32_t* __restrict__ W, const ExtractArgs& a, int l,
-                                         int ix, int iy, int iz, bool& observed) {
-  const int w = W[l];
-  observed = w >= a.min_weight;
-  if (!observed) return 0;
-  const float d = D[l];
-  if (!(d < 1.0f)) return 0;
-  const int inside[3] = {ix + 1 < a.nx, iy + 1 < a.ny, iz + 1 < a.nz};
-  const int step[3] = {1, a.nx, a.nx * a.ny};
-  int bits = 0;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    if (!inside[k]) continue;
-    const int m = l + step[k];
-    if (W[m] < a.min_weight) continue;
-    const float dn = D[m];
-    if (dn < 1.0f && ((d < 0.0f) != (dn < 0.0f))) bits |= 1 << k;
-  }
-  return bits;
-}
-
-__device__ __forceinline__ void tsdf_index(const ExtractArgs& a, int l, int& ix, int& iy, int& iz) {
-  ix = l % a.nx;
-  const int r = l / a.nx;
-  iy = r % a.ny;
-  iz = r / a.ny;
-}
-
 __global__ __launch_bounds__(TS_BLOCK) void tsdf_count_kernel(const float* __restrict__ D, const int32_t* __restrict__ W,
                                                               const ExtractArgs a, int32_t* __restrict__ block_counts,
                                                               int32_t* __restrict__ num) {

@@ -60,6 +60,10 @@ With ``track`` (``--track``, ``--track-near``, ``--track-far``, ``--track-step``
 of their names -- are one moving camera whose pose is not given: each is registered against the model view raycast from the
 volume at the last pose and integrated at the pose found (``tsdf.Tracker``), and the volume's surface is the frame's cloud.  The
 record then carries ``TSDF_KEYS`` and ``TRACK_KEYS``.  Without it nothing changes and the module is not imported.
+
+With ``mesh`` (``--tsdf-mesh``; beside ``volume`` or ``track``) the volume's surface is taken as a triangle mesh
+(``tsdf.Volume.extract_mesh``) and the record also carries ``TSDF_MESH_KEYS``; ``--tsdf-mesh-ply`` writes it as ``NAME.ply`` beside
+the record.  Without it no launch, no allocation and no key changes.
 """
 import argparse
 import contextlib
@@ -94,6 +98,8 @@ APPROACH_VOLUME_KEYS = ("grasp_clearance_seen", "grasp_clearance_safe", "grasp_u
                         "grasp_solid_hand")                    # ... right after them when its ``space`` is "volume"
 TSDF_KEYS = ("tsdf_num", "tsdf_counts")                        # added when the frame was a ``MultiView`` and the detector has ``volume``
 TRACK_KEYS = ("track_pose", "track_status", "track_report")    # added beside ``TSDF_KEYS`` when the detector has ``track``
+TSDF_MESH_KEYS = ("tsdf_triangles", "tsdf_vertices", "tsdf_vertex_normals",
+                  "tsdf_vertex_colors")                        # added after them when the detector has ``mesh``
 DENOISE_KEYS = ("denoise_num",)                                 # added when the detector has ``denoise`` and the frame was a camera frame
 
 
@@ -159,11 +165,17 @@ class GraspDetector:
     cloud, in the frame of the FIRST camera.  The record carries ``tsdf_num`` as above, ``tsdf_counts`` (1,4) int32 (zeros for
     a frame that was LOST), ``track_pose`` (4,4) float64 camera-to-common, ``track_status`` () int32 (0 FIRST, 1 TRACKED, 2
     LOST) and ``track_report`` (5,) float64 = (status, iterations, pairs, rms first, rms last) of the registration (NaN for
-    the first frame).  Together with ``fuse``, or for a ``MultiView`` (its views carry poses), it is a ValueError."""
+    the first frame).  Together with ``fuse``, or for a ``MultiView`` (its views carry poses), it is a ValueError.
+    ``mesh``: True (or a ``"mesh": True`` entry in the ``volume`` / ``track`` dict), with ``volume`` or ``track``: the surface is
+    taken by ``tsdf.Volume.extract_mesh`` and the record also carries ``tsdf_triangles`` (Kt,3) int32 -- rows of
+    ``tsdf_vertices`` per triangle, in cell order, normals out of the solid -- and float32 ``tsdf_vertices``,
+    ``tsdf_vertex_normals``, ``tsdf_vertex_colors`` (K,3): the WHOLE surface of the volume in the common frame, before the crop
+    chooses rows.  ``mesh_ply``: ``detect_file`` also writes them as a binary PLY beside the record.  Without ``mesh`` nothing
+    is launched or allocated for it."""
 
     def __init__(self, score_net, region_net, params=TEST_PARAMS, gripper_params=GRIPPER_PARAMS, eval_params=EVAL_PARAMS,
                  transform=None, bounds=None, num_points=ALL_POINTS_NUM, use_theta=USE_THETA, select=None, depth=None, segment=None,
-                 fuse=None, register=None, approach=None, denoise=None, volume=None, track=None):
+                 fuse=None, register=None, approach=None, denoise=None, volume=None, track=None, mesh=False, mesh_ply=False):
         from . import depth_frame, fusion, grasp_select, ingest, registration
         from . import segment as segment_mod
         self.fuse = fusion.FuseParams.coerce(fuse)
@@ -183,6 +195,16 @@ class GraspDetector:
             if self.approach.filters() and self.approach_source != selected:
                 raise ValueError("approach: min_clearance / min_contact filter the selection, whose source is %s, not %s"
                                  % (selected, self.approach_source))
+        self.mesh = bool(mesh) or bool(mesh_ply)  # the surface as a triangle mesh; may also ride in the volume / track dict
+        self.mesh_ply = bool(mesh_ply)
+        if isinstance(volume, dict) and "mesh" in volume:
+            volume = dict(volume)
+            self.mesh = bool(volume.pop("mesh")) or self.mesh
+        if isinstance(track, dict) and "mesh" in track:
+            track = dict(track)
+            self.mesh = bool(track.pop("mesh")) or self.mesh
+        if self.mesh and volume is None and track is None:
+            raise ValueError("mesh: the triangle mesh is that of the detector's TSDF volume; give volume=... or track=...")
         self.volume = self.tsdf_volume = None     # the parameters, and the tsdf.Volume kept between frames
         if volume is not None:                    # (the module is not even imported without it)
             if fuse is not None:
@@ -232,7 +254,7 @@ class GraspDetector:
             return frame
         if isinstance(frame, dict):
             return ingest.ingest_record(frame, self.num_points, self.device)
-        fused = table = denoised = tracked = None
+        fused = table = denoised = tracked = meshed = None
         if self.track is not None and isinstance(frame, fusion.MultiView):
             raise ValueError("track: a MultiView's views carry their poses; track takes the DepthFrames of one moving camera")
         if self.track is not None and isinstance(frame, depth_frame.DepthFrame):   # one blocking read: the registration's state
@@ -241,12 +263,18 @@ class GraspDetector:
                 self.tracker = tsdf.Tracker(self.volume, self.track, self.device, depth_params=self.depth)
                 self.tsdf_volume = self.tracker.volume
             tracked = self.tracker.track(frame)
-            fused = self.tracker.volume.extract()
+            if self.mesh:
+                meshed = self.tracker.volume.extract_mesh()
+                fused = meshed.surface
+            else:
+                fused = self.tracker.volume.extract()
             frame = fused.cloud()
         elif isinstance(frame, fusion.MultiView) and self.volume is not None:     # integrated on the device, no host read
             from . import tsdf
             fused = tsdf.fuse_volume(frame, self.depth, self.volume, device=self.device, register=self.register,
-                                     volume=self.tsdf_volume)
+                                     volume=self.tsdf_volume, mesh=self.mesh)
+            if self.mesh:
+                fused, meshed = fused
             self.tsdf_volume = fused.volume
             frame = fused.cloud()
         elif isinstance(frame, fusion.MultiView):          # merged on the device, no host read; the rows beyond the merged
@@ -268,7 +296,7 @@ class GraspDetector:
             table = table_plane.calibrate(xyz, self.eval_params[2], **self.auto_table)
             transform = table[0]
         fr = ingest.ingest_frame(xyz, rgb, transform, self.bounds, self.num_points, self.device)
-        fr.fused, fr.table, fr.denoised, fr.tracked = fused, table, denoised, tracked
+        fr.fused, fr.table, fr.denoised, fr.tracked, fr.meshed = fused, table, denoised, tracked, meshed
         return fr
 
     def calibrate(self, frame, **estimate_kwargs):
@@ -424,6 +452,10 @@ class GraspDetector:
                 out["fuse_num"] = fr.fused.num.cpu().numpy()
                 out["fuse_views"] = fr.fused.per_view().cpu().numpy()
                 keys = keys + FUSE_KEYS
+            if getattr(fr, "meshed", None) is not None:
+                (out["tsdf_vertices"], out["tsdf_vertex_normals"], out["tsdf_vertex_colors"],
+                 out["tsdf_triangles"]) = fr.meshed.to_host()
+                keys = keys + TSDF_MESH_KEYS
             if fr.fused.register is not None:
                 out["fuse_poses"] = np.array(fr.fused.poses, dtype=np.float64)
                 out["fuse_register"] = np.array(fr.fused.register, dtype=np.float64)
@@ -499,6 +531,10 @@ class GraspDetector:
         os.makedirs(os.path.dirname(os.path.abspath(save_path)), exist_ok=True)
         with open(save_path, "wb") as f:
             pickle.dump(out, f)
+        if self.mesh_ply and "tsdf_triangles" in out:
+            from . import tsdf
+            tsdf.write_ply(os.path.splitext(save_path)[0] + ".ply", out["tsdf_vertices"], out["tsdf_vertex_normals"],
+                           out["tsdf_vertex_colors"], out["tsdf_triangles"])
         return out, save_path
 
 
@@ -714,6 +750,10 @@ def build_parser():
     parser.add_argument("--tsdf-dims", type=int, nargs=3, metavar=("NX", "NY", "NZ"), default=None,
                         help="voxels per axis, at most 2^28 in all (%d %d %d voxels)" % defaults["volume"].dims)
     regular("volume")
+    parser.add_argument("--tsdf-mesh", action="store_true",
+                        help="with --tsdf or --track: take the volume's surface as a triangle mesh and add it to the record")
+    parser.add_argument("--tsdf-mesh-ply", action="store_true",
+                        help="... and write it as NAME.ply beside the record (implies --tsdf-mesh)")
     parser.add_argument("--track", action="store_true",
                         help="the folder's depth frames, in the order of their names, are one moving camera: track it against the "
                              "TSDF volume it fills and take the volume's surface as every frame's cloud")
@@ -744,7 +784,8 @@ def main(argv=None):
                              transform=transform_from_args(args), depth=depth_from_args(args),
                              segment=segment_from_args(args), fuse=fuse_from_args(args), register=register_from_args(args),
                              approach=approach_from_args(args), denoise=outliers_from_args(args),
-                             volume=volume_from_args(args), track=track_from_args(args))
+                             volume=volume_from_args(args), track=track_from_args(args), mesh=args.tsdf_mesh,
+                             mesh_ply=args.tsdf_mesh_ply)
     real_data = "real_data" in args.folder
     if args.file:
         paths = [os.path.join(args.folder, args.file)]

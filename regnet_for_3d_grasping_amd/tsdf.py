@@ -22,8 +22,13 @@ found -- frame-to-model tracking, KinectFusion's third leg.  ``tests/tsdf_raycas
 ``TrackParams.levels`` / ``smooth`` the registration descends a pyramid of the frame's (optionally bilateral-filtered) depth
 image coarse to fine on one state block (``depth_frame.pyramid``, ``registration.continue_state``;
 ``tests/depth_pyramid_reference.py``); off by default.
+
+``Volume.extract_mesh`` returns the surface as a triangle mesh (csrc/tsdf_mesh.hip): the rows of ``extract`` are the vertices,
+and marching cubes over the cells whose eight corners were observed adds the index buffer, in cell order with no sort -- integer
+work only, so ``tests/tsdf_mesh_reference.py`` restates it with plain loops.  ``Mesh.save_ply`` writes it for a viewer, a
+simulator or a planner's collision world.
 """
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 import math
 from typing import Optional, Tuple
 
@@ -36,6 +41,7 @@ _L = _lib.lib
 
 MAX_VOLUME_VOXELS = 1 << 28         # regnet_tsdf_*'s documented limits
 MAX_POINTS = MAX_FRAME_POINTS
+MAX_TRIANGLES = 1 << 22             # regnet_tsdf_mesh_emit's documented limit
 BLOCK = 256                         # voxels per workgroup of the two extraction passes
 UPDATED, NOT_IN_VIEW, NO_DEPTH, BEHIND = 0, 1, 2, 3      # the entries of integrate's counts
 
@@ -111,6 +117,65 @@ class Surface:
         """The ``(xyz, rgb)`` pair ``ingest.ingest_frame``, ``table_plane.calibrate`` and ``outliers.filter_cloud`` take as they
         are: the rows beyond ``K`` are NaN rows, which all three treat as absent."""
         return self.xyz, self.rgb
+
+
+class Mesh:
+    """``Volume.extract_mesh``'s result, on the device: ``surface``, the ``Surface`` of the same call and volume state, whose rows
+    are the vertices; ``triangles`` (max_triangles,3) int32, rows of ``surface`` per triangle in ascending order of the cell (the
+    linear index of its low corner voxel), -1 beyond the ``Kt`` rows; ``num_triangles`` (4) int32 = (Kt, triangles in all, dropped,
+    overflow).  A triangle one of whose vertices the surface dropped (it overflowed ``max_points``) is (-1, -1, -1) in its place
+    and counted in ``dropped``.  The right-hand-rule normal of a triangle points where the surface's normals point, out of the
+    solid.  Where a voxel's distance is exactly 0 up to three vertices coincide and the triangles between them have no area; they
+    are kept, so the mesh stays closed.  A cell with a corner that was not observed ``min_weight`` times has no triangles: the mesh
+    is open along the border of observed space."""
+
+    def __init__(self, surface, triangles, num_triangles, max_triangles):
+        self.surface, self.triangles, self.num_triangles, self.max_triangles = surface, triangles, num_triangles, int(max_triangles)
+
+    def check(self):
+        """Two blocking reads of 16 bytes -> (vertices K, triangles Kt).  Raises ``ValueError`` when the surface or the triangles
+        overflowed, or a triangle was dropped."""
+        k = self.surface.check()[0]
+        kt, total, dropped, overflow = (int(v) for v in self.num_triangles.cpu())
+        if overflow:
+            raise ValueError("tsdf: the mesh has %d triangles, more than max_triangles = %d; raise max_triangles (at most 2^22) or "
+                             "the voxel size" % (total, self.max_triangles))
+        if dropped:
+            raise ValueError("tsdf: %d triangles lost a vertex to the surface's max_points" % dropped)
+        return k, kt
+
+    def to_host(self):
+        """-> ``(vertices (K,3) float32, normals (K,3) float32, colours (K,3) float32, triangles (M,3) int32)`` as numpy arrays,
+        compacted: the K surface rows, and the triangles without the dropped ones.  Blocking reads; raises nothing."""
+        s = self.surface
+        k = int(s.num[0].item())
+        kt = int(self.num_triangles[0].item())
+        tri = self.triangles[:kt].cpu().numpy()
+        return (s.xyz[:k].cpu().numpy(), s.normal[:k].cpu().numpy(), s.rgb[:k].cpu().numpy(),
+                np.ascontiguousarray(tri[tri[:, 0] >= 0]))
+
+    def save_ply(self, path):
+        """Writes ``to_host()`` as a binary little-endian PLY: per vertex x y z nx ny nz float32 and red green blue uint8 (the
+        colour times 255, rounded, clipped), per face a uint8 3 and three int32."""
+        write_ply(path, *self.to_host())
+
+
+def write_ply(path, vertices, normals, colours, triangles):
+    """``Mesh.save_ply`` for host arrays."""
+    k, m = int(len(vertices)), int(len(triangles))
+    vertex = np.zeros((k,), dtype=[("xyz", "<f4", (3,)), ("n", "<f4", (3,)), ("rgb", "u1", (3,))])
+    vertex["xyz"], vertex["n"] = vertices, normals
+    with np.errstate(invalid="ignore"):
+        vertex["rgb"] = np.clip(np.nan_to_num(np.rint(np.asarray(colours, dtype=np.float64) * 255.0)), 0, 255).astype(np.uint8)
+    face = np.zeros((m,), dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    face["n"], face["v"] = 3, triangles
+    header = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+              "property float nx\nproperty float ny\nproperty float nz\nproperty uchar red\nproperty uchar green\n"
+              "property uchar blue\nelement face %d\nproperty list uchar int vertex_indices\nend_header\n" % (k, m))
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(vertex.tobytes())
+        f.write(face.tobytes())
 
 
 NO_SURFACE, BACK_FACE, HIT, HIT_NO_NORMAL = 0, 1, 2, 3   # raycast's status codes, the entries of its counts
@@ -284,6 +349,7 @@ class Volume:
         self.data = torch.empty((5 * n,), dtype=torch.float32, device=self.device)
         self.D, self.W, self.C = self.data[:n], self.data[n:2 * n].view(torch.int32), self.data[2 * n:].view(3, n)
         self.origin = np.ascontiguousarray(np.asarray(self.params.origin, dtype=np.float64).astype(np.float32))
+        self.mesh_scratch = None                # extract_mesh's row lookup plane, (N) int32: allocated on its first call
         self.reset()
 
     @property
@@ -343,8 +409,11 @@ class Volume:
         """The surface of the volume as it stands -> ``Surface``.  ``out``: ``(xyz, rgb, normal, weight, num)`` contiguous device
         tensors of the result's shapes to write into instead of new ones.  Two passes with an exclusive ``torch.cumsum`` of the
         per-workgroup counts between them; no host read."""
+        return self._extract(self.params, stream, out)[0]
+
+    def _extract(self, p, stream, out):
+        """``extract`` with the parameters ``p`` -> (the ``Surface``, block_counts, block_base)."""
         import torch
-        p = self.params
         nx, ny, nz = p.dims
         mp = int(p.max_points)
         dev = self.device
@@ -366,7 +435,48 @@ class Volume:
                       int(p.min_weight), block_counts.data_ptr(), block_base.data_ptr(), mp, xyz.data_ptr(), rgb.data_ptr(),
                       normal.data_ptr(), weight.data_ptr(), num.data_ptr(), stream=raw)
             record_streams(stream, self.data)
-        return Surface(xyz, rgb, normal, weight, num, p)
+        return Surface(xyz, rgb, normal, weight, num, p), block_counts, block_base
+
+    def extract_mesh(self, min_weight=None, max_points=None, max_triangles=None, stream=None, out=None, out_mesh=None):
+        """The surface of the volume as it stands as a triangle mesh -> ``Mesh``: ``extract`` (with ``min_weight`` / ``max_points``
+        in place of the volume's parameters when given; ``out`` goes to it) and, on the same state, marching cubes over the
+        cells all of whose corners are usable.  ``out_mesh``: ``(triangles, num_triangles)`` contiguous device tensors of the
+        result's shapes to write into.  ``max_triangles``: the rows of the index buffer, at most 2^22; None: twice
+        ``max_points`` (a closed surface has about two triangles per vertex), capped there.  Five more launches and one more
+        ``torch.cumsum``; no host read.  The row lookup's scratch plane, 4 bytes per voxel, is allocated on the first call and
+        kept on the volume."""
+        import torch
+        p = self.params
+        if min_weight is not None or max_points is not None:
+            p = replace(p, min_weight=p.min_weight if min_weight is None else min_weight,
+                        max_points=p.max_points if max_points is None else max_points)
+        mt = min(2 * int(p.max_points), MAX_TRIANGLES) if max_triangles is None else max_triangles
+        if int(mt) != mt or not 1 <= mt <= MAX_TRIANGLES:
+            raise ValueError("extract_mesh: max_triangles must be in 1..2^22")
+        mt = int(mt)
+        nx, ny, nz = p.dims
+        dev = self.device
+        raw = None if stream is None else stream.cuda_stream
+        surface, block_counts, block_base = self._extract(p, stream, out)
+        with torch.cuda.device(dev), stream_scope(stream):
+            if self.mesh_scratch is None:
+                self.mesh_scratch = torch.empty((int(_L.regnet_tsdf_mesh_scratch_bytes(nx, ny, nz)) // 4,), dtype=torch.int32,
+                                                device=dev)
+            if out_mesh is None:
+                out_mesh = (torch.empty((mt, 3), dtype=torch.int32, device=dev), torch.empty((4,), dtype=torch.int32, device=dev))
+            tri, num_tri = out_mesh
+            for t, shape in ((tri, (mt, 3)), (num_tri, (4,))):
+                if not (t.is_cuda and t.device == dev and tuple(t.shape) == shape and t.dtype == torch.int32 and t.is_contiguous()):
+                    raise ValueError("extract_mesh: out_mesh must be contiguous device tensors (max_triangles,3) and (4) int32")
+            tri_counts = torch.empty((int(_L.regnet_tsdf_mesh_blocks(nx, ny, nz)),), dtype=torch.int32, device=dev)
+            _lib.call("regnet_tsdf_mesh_count", self.data, self.data.data_ptr(), nx, ny, nz, int(p.min_weight), tri_counts.data_ptr(),
+                      num_tri.data_ptr(), stream=raw)
+            tri_base = torch.cumsum(tri_counts, 0, dtype=torch.int32) - tri_counts      # exclusive; at most 5 * 2^28 in all
+            _lib.call("regnet_tsdf_mesh_emit", self.data, self.data.data_ptr(), nx, ny, nz, int(p.min_weight),
+                      block_counts.data_ptr(), block_base.data_ptr(), surface.num.data_ptr(), tri_counts.data_ptr(),
+                      tri_base.data_ptr(), mt, self.mesh_scratch.data_ptr(), tri.data_ptr(), num_tri.data_ptr(), stream=raw)
+            record_streams(stream, self.data, self.mesh_scratch, block_counts, block_base, tri_counts, tri_base, tri, num_tri)
+        return Mesh(surface, tri, num_tri, mt)
 
     def raycast(self, pose, intrinsics, width, height, near=None, far=None, step=None, colour=True, stream=None, out=None,
                 clip=True):
@@ -568,7 +678,8 @@ def relative_motion(T):
     return float(np.linalg.norm(T[:3, 3])), math.acos(cos)
 
 
-def fuse_volume(multiview, depth_params=None, tsdf_params=None, device="cuda:0", stream=None, register=None, volume=None):
+def fuse_volume(multiview, depth_params=None, tsdf_params=None, device="cuda:0", stream=None, register=None, volume=None,
+                mesh=False):
     """``depth_frame.to_cloud`` for every frame of ``multiview`` (a ``fusion.MultiView``), then reset, ``integrate`` in view order
     and ``extract`` -> ``Surface``, which carries ``counts`` (views,4) int32 on the device and ``volume``.  No host read.  With
     ``register`` (a ``registration.IcpParams`` or a dict of its fields) the poses go through ``fusion.refine_poses`` first -- its
@@ -592,10 +703,11 @@ def fuse_volume(multiview, depth_params=None, tsdf_params=None, device="cuda:0",
     for (xyz, rgb), frame, pose in zip(clouds, multiview.frames, poses):
         height, width = int(frame.depth.shape[0]), int(frame.depth.shape[1])
         counts.append(volume.integrate((xyz, rgb, width, height, frame.intrinsics), pose, stream=stream))
-    surface = volume.extract(stream=stream)
+    meshed = volume.extract_mesh(stream=stream) if mesh else None
+    surface = meshed.surface if mesh else volume.extract(stream=stream)
     with stream_scope(stream):
         surface.counts = torch.stack(counts)
     surface.volume = volume
     if report is not None:
         surface.poses, surface.register = np.stack(poses), report
-    return surface
+    return (surface, meshed) if mesh else surface
