@@ -10,7 +10,8 @@
 //
 // Here a workgroup owns 16 output channels and ALL rows, so the batch statistics are local to it:
 //   forward   z = X . W^T by v_mfma_f32_16x16x4_f32 (exact fp32 products; a lane's float4 of K feeds four MFMAs) into LDS,
-//             mean / variance over the rows (two passes, fixed order: deterministic), running statistics, xhat and
+//             mean (as an fp32 sum plus the mean of the residuals, kept apart: mean_hi + mean_lo) / variance of the residuals
+//             over the rows (separate passes, fixed order: deterministic), running statistics, xhat and
 //             y = [relu](gamma * xhat + beta) written once.  The bias only moves the batch mean: it enters running_mean.
 //   backward  (a) dyh = dY * [y > 0];  dbeta = sum dyh;  dgamma = sum dyh * xhat;
 //                 dZ = gamma * invstd * (dyh - dbeta / n - xhat * dgamma / n)  -> LDS + global;  dbias = sum dZ;
@@ -58,7 +59,7 @@ __device__ __forceinline__ void ht_column_sums(int R, float (*red)[17], float* o
 __global__ __launch_bounds__(HT_THREADS) void ht_fwd_kernel(const HtFwd p) {
   extern __shared__ __attribute__((aligned(16))) float zbuf[];     // [16 * tiles][16]
   __shared__ float red[HT_THREADS / 16][17];
-  __shared__ float s_sum[16], s_mean[16], s_inv[16];
+  __shared__ float s_sum[16], s_mean[16], s_corr[16], s_inv[16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int i = lane & 15, g = lane >> 4;
   const int n0 = blockIdx.x * 16;
@@ -95,7 +96,15 @@ __global__ __launch_bounds__(HT_THREADS) void ht_fwd_kernel(const HtFwd p) {
   ht_column_sums(p.R, red, s_sum, [&](int r, int j) { return zbuf[r * 16 + j]; });
   if (tid < 16) s_mean[tid] = s_sum[tid] * inv_n;
   __syncthreads();
-  ht_column_sums(p.R, red, s_sum, [&](int r, int j) { const float d = zbuf[r * 16 + j] - s_mean[j]; return d * d; });
+  // the fp32 sum of R values of one sign is off by a few ulp of the MEAN, which invstd turns into an offset of every xhat
+  // (measured, not a bound: 64 or 1024 equal rows of z ~ 500 gave |Y - beta| of 0.12 .. 0.17 in the identical-rows cases of
+  // tests/test_gpu_heads_train_edges.py::test_conditioning).  The residuals are small and of both signs: their mean corrects
+  // the first one.  It stays a second word (the sum is mean + corr): one fp32 mean of z ~ 500 is only good to 1.5e-5, which
+  // leaves sum(xhat) = R invstd 1.5e-5 and with it a dbias = sum(dZ) of 1e-3 where it should be rounding noise.
+  ht_column_sums(p.R, red, s_sum, [&](int r, int j) { return zbuf[r * 16 + j] - s_mean[j]; });
+  if (tid < 16) s_corr[tid] = s_sum[tid] * inv_n;
+  __syncthreads();
+  ht_column_sums(p.R, red, s_sum, [&](int r, int j) { const float d = (zbuf[r * 16 + j] - s_mean[j]) - s_corr[j]; return d * d; });
   if (tid < 16) {
     const float var = s_sum[tid] * inv_n;
     const float inv = 1.f / sqrtf(var + p.eps);
@@ -104,7 +113,7 @@ __global__ __launch_bounds__(HT_THREADS) void ht_fwd_kernel(const HtFwd p) {
     if (n < p.N) {
       p.invstd[n] = inv;
       if (p.run_mean) {
-        const float m = s_mean[tid] + (p.bias ? p.bias[n] : 0.f);
+        const float m = (s_mean[tid] + s_corr[tid]) + (p.bias ? p.bias[n] : 0.f);
         const float unbiased = p.R > 1 ? var * ((float)p.R / (float)(p.R - 1)) : var;
         p.run_mean[n] = (1.f - p.momentum) * p.run_mean[n] + p.momentum * m;
         p.run_var[n] = (1.f - p.momentum) * p.run_var[n] + p.momentum * unbiased;
@@ -117,7 +126,7 @@ __global__ __launch_bounds__(HT_THREADS) void ht_fwd_kernel(const HtFwd p) {
   for (int idx = tid; idx < p.R * 16; idx += HT_THREADS) {
     const int r = idx >> 4, j = idx & 15, n = n0 + j;
     if (n >= p.N) continue;
-    const float xh = (zbuf[idx] - s_mean[j]) * s_inv[j];
+    const float xh = ((zbuf[idx] - s_mean[j]) - s_corr[j]) * s_inv[j];
     float y = p.gamma[n] * xh + p.beta[n];
     if (p.relu) y = max_nan(y, 0.f);
     p.XH[(long long)r * p.N + n] = xh;
