@@ -1507,6 +1507,81 @@ int regnet_grasp_approach_volume_f32(const void* volume, int64_t nx, int64_t ny,
                                      float half_space, float back_x, float standoff, double step, float x_extent,
                                      int32_t* counts, float* values, void* stream);
 
+/* ---- distance field of the TSDF volume (csrc/edt.hip): how much room there is, per voxel, per point and per grasp ----------------
+ * The approach analysis above says whether a sample of the hand is SOLID, UNSEEN or FREE.  The distance field says how far every
+ * voxel is from the nearest obstacle voxel: the exact Euclidean distance transform of the volume's lattice.  Squared distances in
+ * voxel units are integers, so everything below is integer work and is compared with tests/edt_reference.py with no tolerance;
+ * two runs give the same bytes.
+ *
+ * Field.  regnet_tsdf_edt(volume, dims, trunc, min_weight, margin, mode, outside, dist2, nearest, stream)
+ *   volume      the five planes of the section above; only D and W are read.
+ *   class       a voxel is classed as regnet_grasp_approach_volume_f32 classes a sample's voxel: UNKNOWN when W < min_weight or D
+ *               is a NaN; SOLID when D < d_solid = float32(margin / trunc) (the division in float64, rounded once); FREE
+ *               otherwise.  The OBSTACLES are the SOLID voxels (mode 0) or the SOLID and UNKNOWN voxels (mode 1).
+ *   dist2       (N) int32 DEVICE, word l = (iz ny + iy) nx + ix: the minimum over the obstacle voxels q of |v - q|^2 in voxel
+ *               units (between voxel centres), 0 on an obstacle, REGNET_EDT_NONE = 2^30 everywhere when there is no obstacle.
+ *   nearest     (N) int32 DEVICE or NULL: the linear index of an obstacle voxel at that distance; of all of them the one with the
+ *               SMALLEST LINEAR INDEX, i.e. the lexicographic minimum in (iz, iy, ix); -1 where dist2 == REGNET_EDT_NONE.
+ *   outside     1: everything beyond the six faces is an obstacle too (the approach analysis' OUTSIDE is UNSEEN).  The slab beyond
+ *               a face is nearest along that axis, so with m = min over the axes of min(i + 1, n - i): dist2 = min(dist2, m^2),
+ *               and nearest = -1 where m^2 is STRICTLY below the distance to every interior obstacle (an interior obstacle wins
+ *               a tie).
+ *   limits      every dim in 1..1024 and N <= 2^28, so dist2 <= 3 * 1023^2 < 2^22 wherever it is not REGNET_EDT_NONE.
+ * Three launches -- a line pass along x, y and z -- that run in place in dist2 / nearest, the only workspace; no host read, no
+ * synchronisation, no allocation: capturable.  No atomic, no sort.  Errors, all before any launch: a dim or min_weight < 1, mode or
+ * outside not 0 / 1 -> REGNET_ERR_SHAPE; a dim > 1024, N > 2^28, min_weight >= 2^31, trunc, margin or margin / trunc not finite in
+ * float32 -> REGNET_ERR_UNSUPPORTED; a NULL volume or dist2 -> REGNET_ERR_NULL.
+ * regnet_tsdf_edt_pass is ONE of the three launches, pass = 0, 1, 2 for x, y, z (a measurement; pass outside 0..2 ->
+ * REGNET_ERR_SHAPE): the three in order are regnet_tsdf_edt.  regnet_edt_tile(n, with_nearest): the lines of consecutive ix a
+ * workgroup of the y / z pass stages for an axis of n voxels -- 64, 32, 16 or 8, the largest whose tile stays within 64 KiB --,
+ * REGNET_ERR_UNSUPPORTED for n outside 1..1024; a host function.
+ *
+ * Query.  regnet_edt_query_f32: one lane per point, one launch.
+ *   points      (M,3) float32 DEVICE, element (m, k) at points[m stride_row + k stride_col].  T12: 12 float32 on the HOST, rows
+ *               0..2 of the row-major to-volume 4x4:  wx = (((t00 x) + (t01 y)) + (t02 z)) + t03, wy and wz likewise.
+ *   lookup      origin3, voxel as above, voxel_f = float32(voxel); per axis c = floorf(__fdiv_rn(w - o, voxel_f)), INSIDE iff
+ *               c >= 0 && c < (float)n on all three axes, compared in float (a NaN fails): the lookup of the section above.
+ *   distance    (M) float32: sqrtf((float)d2) * voxel_f, + 0.0f before the store -- the conversion is exact, the root correctly
+ *               rounded, the product one operation --; +inf for REGNET_EDT_NONE; the quiet NaN 0x7fc00000 for a point that is
+ *               not INSIDE.
+ *   nearest_xyz (M,3) float32 contiguous or NULL: the centre o_k + (((float)i_k + 0.5f) * voxel_f) of the nearest obstacle voxel,
+ *               in the volume's frame; NaN where there is none (nearest NULL or -1, or the point not INSIDE).
+ * M == 0: success without a launch.  Errors: M < 0 or a dim < 1 -> REGNET_ERR_SHAPE; a dim > 1024, N > 2^28, M >= 2^31, voxel not
+ * finite or not positive (in float32 too) -> REGNET_ERR_UNSUPPORTED; then M == 0; then a NULL dist2, origin3, points, T12 or
+ * distance -> REGNET_ERR_NULL.
+ * regnet_edt_metres_f32(dist2, n, voxel, out): out[l] = the query's distance of word l, for n words (the whole field, or any
+ * array of squared distances); n == 0: success; n < 0 -> REGNET_ERR_SHAPE, n > 2^28 or a bad voxel -> REGNET_ERR_UNSUPPORTED.
+ *
+ * Margin.  regnet_grasp_margin_volume_f32: the swept hand of regnet_grasp_approach_volume_f32 -- the same lattice, the same
+ * L (B,12), the same sets (csrc/hand_box.h) and the same lookup (one definition, csrc/hand_lattice.h) -- read against dist2.
+ *   samples     a HAND sample is one with back || finger at the final pose, a SWEPT sample one that is a hand sample or a
+ *               BLOCKER.  Only swept samples are looked up (the region between the fingers is not part of the hand).
+ *   margins     (B,2) int32: { the minimum dist2 over the hand samples, the minimum over the swept samples }, REGNET_EDT_NONE
+ *               where the set is empty.  An OUTSIDE sample contributes 0 when outside = 1 (it lies in an obstacle of a field
+ *               built with outside = 1) and nothing otherwise.
+ *   counts      (B,4) int32: { hand samples, hand samples OUTSIDE, swept samples, swept samples OUTSIDE } -- samples, not
+ *               memberships: a sample that is back and finger counts once.
+ * One workgroup of 256 threads per grasp, the tile walk of the approach analysis; integer minima and sums only (a wave butterfly,
+ * then the four waves through LDS), no atomic.  One launch, capturable.  A row of L with a non-finite entry reports every swept
+ * sample OUTSIDE.  Errors, all before the launch: B < 0, a dim < 1, outside not 0 / 1 -> REGNET_ERR_SHAPE; a dim > 1024, N > 2^28,
+ * B >= 2^31, step or voxel not finite or not positive (in float32 too), a standoff that is negative or not finite, a lattice count
+ * that is not finite or n_x n_y n_z > 2^22 -> REGNET_ERR_UNSUPPORTED; then B == 0: success without a launch; then a NULL dist2,
+ * origin3, L, margins or counts -> REGNET_ERR_NULL.                                                                          */
+#define REGNET_EDT_NONE (1 << 30)
+int regnet_edt_tile(int64_t n, int with_nearest);
+int regnet_tsdf_edt(const void* volume, int64_t nx, int64_t ny, int64_t nz, double trunc, int64_t min_weight, double margin,
+                    int mode, int outside, int32_t* dist2, int32_t* nearest, void* stream);
+int regnet_tsdf_edt_pass(const void* volume, int64_t nx, int64_t ny, int64_t nz, double trunc, int64_t min_weight, double margin,
+                         int mode, int outside, int pass, int32_t* dist2, int32_t* nearest, void* stream);
+int regnet_edt_query_f32(const int32_t* dist2, const int32_t* nearest, int64_t nx, int64_t ny, int64_t nz, const float* origin3,
+                         double voxel, const float* points, int64_t stride_row, int64_t stride_col, int64_t M, const float* T12,
+                         float* distance, float* nearest_xyz, void* stream);
+int regnet_edt_metres_f32(const int32_t* dist2, int64_t n, double voxel, float* out, void* stream);
+int regnet_grasp_margin_volume_f32(const int32_t* dist2, int64_t nx, int64_t ny, int64_t nz, const float* origin3, double voxel,
+                                   int outside, const float* L, int64_t B, float x_lo, float x_hi, const float* x_hi_per_grasp,
+                                   float half_thickness, float half_width, float half_space, float back_x, float standoff,
+                                   double step, float x_extent, int32_t* margins, int32_t* counts, void* stream);
+
 /* ---- deterministic mode (csrc/scatter.hip, csrc/det.hip, csrc/bn_train.hip) ------------------------------------------
  * The float32 kernels behind torch.use_deterministic_algorithms(True): every sum of the training backward is formed in one
  * fixed order, so runs agree bit for bit.  The default entry points above are unchanged.

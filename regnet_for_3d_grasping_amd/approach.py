@@ -50,7 +50,13 @@ class ApproachParams(ParamsBase):
     never observed: ``"free"`` -- only seen surfaces block -- or ``"blocked"``.  ``step``: the distance between two samples of the
     swept hand [m]; None: the volume's voxel.  ``margin``: a voxel counts as solid when its distance to the surface is below
     this [m] (0: inside the surface), at most the volume's truncation distance to mean anything.  These defaults, too, are a
-    choice nobody has measured on a robot."""
+    choice nobody has measured on a robot.
+
+    ``field``: in volume space, also build the volume's distance field (``tsdf.Volume.distance_field``) once per frame and read
+    the hand against it: ``margin_hand`` / ``margin_sweep``, the distance [m] from the hand / the swept hand to the nearest
+    obstacle -- solid voxels, and with ``unseen="blocked"`` unobserved voxels and the volume's outside too.  ``min_margin``:
+    None, or the least ``margin_hand`` [m] a grasp must have to be selected; it needs ``field``.  (``margin`` above is the SOLID
+    threshold, not this.)"""
     WORD = "approach"
     source: Optional[str] = None
     standoff: float = 0.10
@@ -65,8 +71,17 @@ class ApproachParams(ParamsBase):
     unseen: str = "free"
     step: Optional[float] = None
     margin: float = 0.0
+    field: bool = False
+    min_margin: Optional[float] = None
 
     def __post_init__(self):
+        if self.field and self.space != "volume":
+            raise ValueError("approach: field=True builds the distance field of the TSDF volume; use space=\"volume\" with it")
+        if self.min_margin is not None:
+            if not self.field:
+                raise ValueError("approach: min_margin is judged on the distance field; set field=True (and space=\"volume\")")
+            if not (float(self.min_margin) >= 0.0 and np.isfinite(self.min_margin)):
+                raise ValueError("approach: min_margin must be None or non-negative and finite")
         if self.space not in SPACES:
             raise ValueError("approach: space must be one of %s, not %r" % (", ".join(SPACES), self.space))
         if self.unseen not in UNSEEN:
@@ -91,7 +106,7 @@ class ApproachParams(ParamsBase):
 
     def filters(self):
         """Whether ``passes()`` can drop a grasp at all."""
-        return self.min_clearance is not None or self.min_contact is not None
+        return self.min_clearance is not None or self.min_contact is not None or self.min_margin is not None
 
 
 def cos_friction(friction_deg):
@@ -193,11 +208,11 @@ def analyse(points, grasp, depth, width, params=None, normals=None):
     return Approach(counts, values, frame, center, params, box[5])
 
 
-def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, surface=None, max_depth=None):
+def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, surface=None, max_depth=None, field=None):
     """The hand against a ``tsdf.Volume`` instead of a cloud: ``approach_volume.analyse_volume``, which is imported only here
     (and ``approach.VolumeApproach`` is its result's class)."""
     from . import approach_volume
-    return approach_volume.analyse_volume(volume, grasp, depth, width, params, to_volume, surface, max_depth)
+    return approach_volume.analyse_volume(volume, grasp, depth, width, params, to_volume, surface, max_depth, field)
 
 
 def __getattr__(name):

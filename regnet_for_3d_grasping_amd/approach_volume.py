@@ -45,12 +45,36 @@ class VolumeApproach(approach.Approach):
     UNSEEN, blockers SOLID, blockers UNSEEN, memberships, memberships OUTSIDE) and ``values`` (B,4) float32 = (y_min, y_max,
     clearance_seen, clearance_safe) are the kernel's; ``contact_counts`` (B,8) int32 is ``regnet_grasp_approach_f32``'s on the
     surface, or None; ``L`` (B,12) / ``T`` (B,4,4) float32 are the local-to-volume rows the kernel was given and the
-    volume-to-local matrices of the contact pass (None without it); ``samples`` = (n_x, n_y, n_z).  ``width``, ``offset``,
+    volume-to-local matrices of the contact pass (None without it); ``samples`` = (n_x, n_y, n_z).  With a ``field``:
+    ``margins`` (B,2) int32 and ``margin_counts`` (B,4) int32 are ``regnet_grasp_margin_volume_f32``'s, else None.  ``width``, ``offset``,
     ``opening``, ``pregrasp`` and ``passes()`` are ``Approach``'s, on the solid samples and the policy's clearance."""
 
-    def __init__(self, counts, values, frame, center, params, half_space, contact_counts, L, T, samples):
+    def __init__(self, counts, values, frame, center, params, half_space, contact_counts, L, T, samples, margins=None,
+                 margin_counts=None, margin_metres=None):
         super().__init__(counts, values, frame, center, params, half_space)
         self.contact_counts, self.L, self.T, self.samples = contact_counts, L, T, samples
+        self.margins, self.margin_counts, self._margin_metres = margins, margin_counts, margin_metres
+
+    @property
+    def margin_hand(self):
+        """(B) float32 [m]: the distance from the hand at its final pose (the samples behind the palm face and inside the
+        fingers) to the nearest obstacle of the ``field`` given to ``analyse_volume``, ``+inf`` when the field has no obstacle or
+        the hand no sample; None without a field.  Not the SOLID threshold ``params.margin``."""
+        return None if self._margin_metres is None else self._margin_metres[0]
+
+    @property
+    def margin_sweep(self):
+        """(B) float32 [m]: the same over the whole swept hand, so ``margin_sweep <= margin_hand``; None without a field."""
+        return None if self._margin_metres is None else self._margin_metres[1]
+
+    def passes(self):
+        """``Approach.passes()``, and ``margin_hand >= min_margin`` when that is set, compared as float32."""
+        ok = super().passes()
+        if self.params.min_margin is not None:
+            if self._margin_metres is None:
+                raise ValueError("approach: min_margin needs a distance field; give analyse_volume field=...")
+            ok = ok & (self.margin_hand >= float(np.float32(self.params.min_margin)))
+        return ok
 
     @property
     def clearance_seen(self):
@@ -99,7 +123,7 @@ def _times_rows(matrix, rows):
                          + rows[:, 2, :] * float(matrix[r, 2])) + rows[:, 3, :] * float(matrix[r, 3]) for r in range(4)], dim=1)
 
 
-def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, surface=None, max_depth=None):
+def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, surface=None, max_depth=None, field=None):
     """``volume``: a ``tsdf.Volume``; ``grasp`` (B, >=8) float32 on its device; ``depth``: a float or one depth per grasp -- then
     ``max_depth``, a bound on them, is the lattice's far end (nothing is read back to find it; a ValueError without it);
     ``width``: the gripper's opening; ``params``: ``ApproachParams`` / a dict / None -- ``standoff``, ``unseen``, ``step``,
@@ -111,7 +135,11 @@ def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, sur
     an input.  The contact pass runs ``regnet_grasp_approach_f32`` on ``surface.xyz`` / ``surface.normal`` with ``T = [frame^T |
     -frame^T centre] @ inverse(to_volume)``, float64 rounded once -- the inverse of ``L`` with the frame's transpose for its
     inverse and ``to_volume`` inverted on the host.  One launch (two with the contact pass) on the current stream, no host
-    read."""
+    read.
+
+    ``field``: a ``tsdf.DistanceField`` of the same volume (``volume.distance_field(...)``); the same lattice and ``L`` are then
+    also read against it (``regnet_grasp_margin_volume_f32``, one more launch and a conversion to metres) and the result has
+    ``margin_hand`` / ``margin_sweep``.  Nothing else of the result changes."""
     params = approach.ApproachParams.coerce(params) or approach.ApproachParams()
     p = volume.params
     require_cuda("grasp", grasp, torch.float32, 8, at_least=True, error=RuntimeError)
@@ -143,6 +171,16 @@ def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, sur
     _lib.call("regnet_grasp_approach_volume_f32", volume.data, volume.data.data_ptr(), nx, ny, nz, volume.origin.ctypes.data,
               float(p.voxel), float(p.trunc), int(p.min_weight), float(params.margin), L.data_ptr(), B, *box,
               float(params.standoff), step, x_extent, counts.data_ptr(), values.data_ptr())
+    margins = margin_counts = margin_metres = None
+    if field is not None:
+        if tuple(field.dims) != tuple(p.dims) or field.dist2.device != dev:
+            raise ValueError("analyse_volume: the field must be a DistanceField of this volume (same dims, same device)")
+        margins = torch.empty((B, 2), dtype=torch.int32, device=dev)
+        margin_counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
+        _lib.call("regnet_grasp_margin_volume_f32", field.dist2, field.dist2.data_ptr(), nx, ny, nz, volume.origin.ctypes.data,
+                  float(p.voxel), int(field.outside), L.data_ptr(), B, *box, float(params.standoff), step, x_extent,
+                  margins.data_ptr(), margin_counts.data_ptr())
+        margin_metres = field.metres(margins.t().contiguous())      # (2,B): row 0 the hand, row 1 the sweep
     contact_counts = T = None
     if params.friction_deg is not None and surface is not None:
         points = require_cuda("surface.xyz", surface.xyz, torch.float32, 3, error=RuntimeError)
@@ -162,4 +200,5 @@ def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, sur
                   normals.stride(0), normals.stride(1), int(points.shape[0]), T.data_ptr(), B, *box, float(params.standoff),
                   float(params.contact_depth), approach.cos_friction(params.friction_deg), contact_counts.data_ptr(),
                   contact_values.data_ptr())
-    return VolumeApproach(counts, values, frame, center, params, box[5], contact_counts, L, T, samples)
+    return VolumeApproach(counts, values, frame, center, params, box[5], contact_counts, L, T, samples, margins, margin_counts,
+                          margin_metres)

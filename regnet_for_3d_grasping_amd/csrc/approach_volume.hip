@@ -10,29 +10,21 @@
 // one D when W >= min_weight) and classified; hand_box.h's sets, the ones approach.hip and region.hip use, say which it
 // belongs to.  Canonical fp32: individually rounded operations in the written order (-ffp-contract=off), __fdiv_rn, strict
 // comparisons.  Only integer sums and float min / max are reduced (common.h: the wave butterfly, then the waves through LDS): no atomic, no
-// floating-point sum.  The volume is only read (tsdf_volume.h: its planes).  Plain vector stores by thread 0.
-#include "hand_box.h"
-#include "tsdf_volume.h"
-
-#include <math.h>
+// floating-point sum.  The volume is only read (tsdf_volume.h: its planes).  Plain vector stores by thread 0.  The lattice, its
+// walk and the voxel lookup are hand_lattice.h's, which edt.hip's margin kernel shares.
+#include "hand_lattice.h"
 
 namespace {
 
-constexpr int AV_T = 256;
-constexpr int AV_W = AV_T / 64;
-constexpr int AV_TILE = 8;
+constexpr int AV_T = HL_T;
+constexpr int AV_W = HL_W;
 constexpr int AV_NI = 8, AV_NF = 4;                  // reduced integers and floats
-
-struct Lattice {
-  int nx, ny, nz;   // samples per axis
-  float xs, h;      // x_lo - S (one float32 subtraction, made by the host function) and the step
-};
 
 struct VolumeView {
   const float* D;
   const int32_t* W;
-  int nx, ny, nz;
-  float ox, oy, oz, voxel, d_solid;
+  VoxelGrid grid;
+  float d_solid;
   int min_weight;
 };
 
@@ -44,67 +36,49 @@ __global__ __launch_bounds__(AV_T) void approach_volume_kernel(VolumeView vol, c
   __shared__ float red_f[AV_NF][AV_W];
   const GraspRows g = grasp_rows(L, blockIdx.x, 12);
   const float x_hi = x_hi_per_grasp ? x_hi_per_grasp[blockIdx.x] : box.x_hi;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int tiles_x = (lat.nx + AV_TILE - 1) / AV_TILE, tiles_y = (lat.ny + AV_TILE - 1) / AV_TILE;
-  const int tiles = tiles_x * tiles_y;               // (at most 2^22 samples in all: no overflow)
-  const float fnx = (float)vol.nx, fny = (float)vol.ny, fnz = (float)vol.nz;   // (every dim <= 2^24: exact)
 
   int region_solid = 0, region_unseen = 0, hand_solid = 0, hand_unseen = 0, block_solid = 0, block_unseen = 0;
   int members = 0, members_outside = 0;
   float y_min = __builtin_inff(), y_max = -__builtin_inff(), s_seen = __builtin_inff(), s_safe = __builtin_inff();
-  for (int t = wave; t < tiles; t += AV_W) {
-    const int ty = t / tiles_x, tx = t - ty * tiles_x;
-    const int i = tx * AV_TILE + (lane & (AV_TILE - 1)), j = ty * AV_TILE + (lane >> 3);
-    if (i >= lat.nx || j >= lat.ny) continue;
-    const float x = lat.xs + (((float)i + 0.5f) * lat.h);
-    const float y = (((float)j + 0.5f) * lat.h) - box.half_width;
-    for (int k = 0; k < lat.nz; ++k) {
-      const float z = (((float)k + 0.5f) * lat.h) - box.half_thickness;
-      const HandSets in = hand_sets(box, x_hi, lat.xs, x, y, z);
-      const bool region = in.region, blocker = in.blocker;
-      const float s = in.retreat;
-      const int hand = (int)in.back + (int)in.finger;
-      const int member = hand + (int)blocker;
-      if (!(region || member)) continue;             // in no set: no lookup
-      float wx, wy, wz;
-      grasp_apply(g, x, y, z, wx, wy, wz);
-      const float cx = floorf(__fdiv_rn(wx - vol.ox, vol.voxel));
-      const float cy = floorf(__fdiv_rn(wy - vol.oy, vol.voxel));
-      const float cz = floorf(__fdiv_rn(wz - vol.oz, vol.voxel));
-      const bool inside = cx >= 0.0f && cx < fnx && cy >= 0.0f && cy < fny && cz >= 0.0f && cz < fnz;   // (a NaN fails)
-      bool solid = false, unseen = true;
-      if (inside) {
-        const int64_t v = voxel_index<int64_t>((int)cx, (int)cy, (int)cz, vol.nx, vol.ny);
-        if (vol.W[v] >= vol.min_weight) {
-          const float d = vol.D[v];
-          unseen = d != d;                           // a NaN distance: UNKNOWN
-          solid = d < vol.d_solid;
-        }
+  lattice_walk(lat, box, x_hi, [&](float x, float y, float z, const HandSets& in) {
+    const bool region = in.region, blocker = in.blocker;
+    const float s = in.retreat;
+    const int hand = (int)in.back + (int)in.finger;
+    const int member = hand + (int)blocker;
+    if (!(region || member)) return;                 // in no set: no lookup
+    float wx, wy, wz;
+    grasp_apply(g, x, y, z, wx, wy, wz);
+    int64_t v;
+    const bool inside = grid_voxel(vol.grid, wx, wy, wz, v);
+    bool solid = false, unseen = true;
+    if (inside && vol.W[v] >= vol.min_weight) {
+      const float d = vol.D[v];
+      unseen = d != d;                               // a NaN distance: UNKNOWN
+      solid = d < vol.d_solid;
+    }
+    members += member;
+    members_outside += inside ? 0 : member;
+    if (solid) {
+      hand_solid += hand;
+      if (region) {
+        region_solid += 1;
+        y_min = fminf(y_min, y);
+        y_max = fmaxf(y_max, y);
       }
-      members += member;
-      members_outside += inside ? 0 : member;
-      if (solid) {
-        hand_solid += hand;
-        if (region) {
-          region_solid += 1;
-          y_min = fminf(y_min, y);
-          y_max = fmaxf(y_max, y);
-        }
-        if (blocker) {
-          block_solid += 1;
-          s_seen = fminf(s_seen, s);
-          s_safe = fminf(s_safe, s);
-        }
-      } else if (unseen) {
-        hand_unseen += hand;
-        region_unseen += (int)region;
-        if (blocker) {
-          block_unseen += 1;
-          s_safe = fminf(s_safe, s);
-        }
+      if (blocker) {
+        block_solid += 1;
+        s_seen = fminf(s_seen, s);
+        s_safe = fminf(s_safe, s);
+      }
+    } else if (unseen) {
+      hand_unseen += hand;
+      region_unseen += (int)region;
+      if (blocker) {
+        block_unseen += 1;
+        s_safe = fminf(s_safe, s);
       }
     }
-  }
+  });
   int ri[AV_NI] = {region_solid, region_unseen, hand_solid, hand_unseen, block_solid, block_unseen, members, members_outside};
 #pragma unroll
   for (int q = 0; q < AV_NI; ++q) ri[q] = wave_sum(ri[q]);
@@ -125,20 +99,6 @@ __global__ __launch_bounds__(AV_T) void approach_volume_kernel(VolumeView vol, c
   }
 }
 
-bool positive_f32(double v, float* out) {            // finite and positive, in float32 too
-  const float f = (float)v;
-  *out = f;
-  return v > 0.0 && f > 0.0f && f != __builtin_inff() && f == f;
-}
-
-// max(1, ceil(extent / h)) in float64; false when it cannot be a lattice count (not finite, or beyond the sample limit)
-bool lattice_count(double extent, double h, int* n) {
-  const double c = ceil(extent / h);
-  if (!(c <= (double)(1 << 22)) || c == -__builtin_inf()) return false;   // (a NaN fails the first test)
-  *n = c < 1.0 ? 1 : (int)c;
-  return true;
-}
-
 }  // namespace
 
 extern "C" int regnet_grasp_approach_volume_f32(const void* volume, int64_t nx, int64_t ny, int64_t nz, const float* origin3,
@@ -156,21 +116,15 @@ extern "C" int regnet_grasp_approach_volume_f32(const void* volume, int64_t nx, 
   if (!(standoff >= 0.0f) || standoff == __builtin_inff()) return REGNET_ERR_UNSUPPORTED;   // negative, NaN or infinite
   const float d_solid = (float)(margin / trunc);
   if (!(d_solid == d_solid) || d_solid == __builtin_inff() || d_solid == -__builtin_inff()) return REGNET_ERR_UNSUPPORTED;
-  const float xs = x_lo - standoff;
-  int n_x, n_y, n_z;
-  if (!lattice_count((double)x_extent - (double)xs, (double)h, &n_x) ||
-      !lattice_count((double)half_width + (double)half_width, (double)h, &n_y) ||
-      !lattice_count((double)half_thickness + (double)half_thickness, (double)h, &n_z))
-    return REGNET_ERR_UNSUPPORTED;
-  if ((int64_t)n_x * n_y * n_z > ((int64_t)1 << 22)) return REGNET_ERR_UNSUPPORTED;
+  Lattice lat;
+  if (!lattice_of(x_lo, standoff, half_thickness, half_width, x_extent, h, &lat)) return REGNET_ERR_UNSUPPORTED;
   if (B == 0) return REGNET_OK;
   if (!volume || !origin3 || !L || !counts || !values) return REGNET_ERR_NULL;
   const int64_t n = nx * ny * nz;
   const Planes planes = planes_of(const_cast<void*>(volume), n);
-  const VolumeView vol{planes.D, planes.W, (int)nx, (int)ny, (int)nz, origin3[0], origin3[1],
-                       origin3[2], voxel_f, d_solid, (int)min_weight};
+  const VolumeView vol{planes.D, planes.W, VoxelGrid{(int)nx, (int)ny, (int)nz, origin3[0], origin3[1], origin3[2], voxel_f},
+                       d_solid, (int)min_weight};
   const GraspBox box{x_lo, x_hi, half_thickness, half_width, half_space, back_x};
-  const Lattice lat{n_x, n_y, n_z, xs, h};
   hipLaunchKernelGGL(approach_volume_kernel, dim3((unsigned)B), dim3(AV_T), 0, as_stream(stream), vol, L, box, x_hi_per_grasp,
                      standoff, lat, counts, values);
   REGNET_LAUNCH_CHECK();

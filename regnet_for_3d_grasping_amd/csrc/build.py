@@ -49,6 +49,7 @@ SOURCES = [
     ("tsdf.hip", ["-ffp-contract=off"]),   # TSDF volume: every voxel's running means and every surface row are compared bit for bit with numpy
     ("tsdf_mesh.hip", []),   # the volume's triangle mesh: integer work only (two float compares), nothing to round
     ("approach_volume.hip", ["-ffp-contract=off"]),   # approach against the volume: every sample's voxel and set are decided on individually rounded fp32
+    ("edt.hip", ["-ffp-contract=off"]),   # distance field: integer passes; the query's and the margin's lookups are approach_volume.hip's
 ]
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc"]
@@ -83,7 +84,7 @@ NO_VGPR_SPILL = {"mlp.o": ["mlp_gemm_kernelILi0E", "gemm2_kernel"], "sa_chain.o"
                  "scatter.o": ["scatter_", "segsum_"], "det.o": ["det_"],
                  "ingest.o": ["ingest_"], "nms.o": ["nms_"], "plane.o": ["plane_"], "depth.o": ["depth_"],
                  "fuse.o": ["fuse_"], "icp.o": ["icp_"], "outlier.o": ["outlier_"], "tsdf.o": ["tsdf_"], "tsdf_mesh.o": ["tsdf_mesh_"],
-                 "approach.o": ["approach_kernel"], "approach_volume.o": ["approach_volume_"]}
+                 "approach.o": ["approach_kernel"], "approach_volume.o": ["approach_volume_"], "edt.o": ["edt_"]}
 
 
 def check_no_vgpr_spill(obj_path, fragments):

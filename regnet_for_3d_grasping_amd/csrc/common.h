@@ -77,6 +77,11 @@ __device__ __forceinline__ float wave_min(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
   return v;
 }
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
+  return v;
+}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
@@ -103,5 +108,7 @@ template <int WAVES>
 __device__ __forceinline__ int block_sum(const int* slot) { return block_join<WAVES>(slot, [](int a, int b) { return a + b; }); }
 template <int WAVES>
 __device__ __forceinline__ float block_min(const float* slot) { return block_join<WAVES>(slot, fminf); }
+template <int WAVES>
+__device__ __forceinline__ int block_min(const int* slot) { return block_join<WAVES>(slot, [](int a, int b) { return a < b ? a : b; }); }
 template <int WAVES>
 __device__ __forceinline__ float block_max(const float* slot) { return block_join<WAVES>(slot, fmaxf); }

@@ -1,0 +1,86 @@
+// hand_lattice.h -- the lattice of samples of the swept hand and its lookup in a voxel grid, shared by approach_volume.hip (which
+// classifies the sample's voxel of the TSDF volume) and edt.hip's margin kernel (which reads the distance field there): the
+// lattice's counts on the host, the tile walk of a workgroup of 256 threads, and the sample's nearest voxel.  include/regnet_hip.h
+// ("approach analysis against the TSDF volume": lattice, sets, lookup) is the contract of all three.  The translation unit must
+// be built with -ffp-contract=off (hand_box.h).
+#pragma once
+#include "hand_box.h"
+#include "tsdf_volume.h"
+
+#include <math.h>
+
+constexpr int HL_T = 256;            // threads of a workgroup that walks the lattice
+constexpr int HL_W = HL_T / 64;
+constexpr int HL_TILE = 8;
+
+struct Lattice {
+  int nx, ny, nz;   // samples per axis
+  float xs, h;      // x_lo - S (one float32 subtraction, made by the host function) and the step
+};
+
+struct VoxelGrid {  // where the voxels are: dims, the corner of voxel (0, 0, 0) and the edge
+  int nx, ny, nz;
+  float ox, oy, oz, voxel;
+};
+
+// The nearest voxel of the point (wx, wy, wz) of the grid's frame -> whether it is inside (a NaN is not), and then its linear
+// index.  (Every dim <= 2^24: (float)n is exact and the test compares exact floats.)
+__device__ __forceinline__ bool grid_voxel(const VoxelGrid& grid, float wx, float wy, float wz, int64_t& v) {
+  const float fnx = (float)grid.nx, fny = (float)grid.ny, fnz = (float)grid.nz;
+  const float cx = floorf(__fdiv_rn(wx - grid.ox, grid.voxel));
+  const float cy = floorf(__fdiv_rn(wy - grid.oy, grid.voxel));
+  const float cz = floorf(__fdiv_rn(wz - grid.oz, grid.voxel));
+  const bool inside = cx >= 0.0f && cx < fnx && cy >= 0.0f && cy < fny && cz >= 0.0f && cz < fnz;   // (a NaN fails)
+  if (inside) v = voxel_index<int64_t>((int)cx, (int)cy, (int)cz, grid.nx, grid.ny);
+  return inside;
+}
+
+// The walk of one workgroup of HL_T threads over the lattice: a wave takes 8 x 8 tiles of the x-y plane, tile t = wave, wave + 4,
+// ..., lane l at (l & 7, l >> 3) of the tile, and walks the n_z layers.  visit(x, y, z, sets) is called for every sample of
+// this thread, with hand_box.h's sets for the grasp's own x_hi.
+template <typename Visit>
+__device__ __forceinline__ void lattice_walk(const Lattice& lat, const GraspBox& box, float x_hi, Visit visit) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int tiles_x = (lat.nx + HL_TILE - 1) / HL_TILE, tiles_y = (lat.ny + HL_TILE - 1) / HL_TILE;
+  const int tiles = tiles_x * tiles_y;               // (at most 2^22 samples in all: no overflow)
+  for (int t = wave; t < tiles; t += HL_W) {
+    const int ty = t / tiles_x, tx = t - ty * tiles_x;
+    const int i = tx * HL_TILE + (lane & (HL_TILE - 1)), j = ty * HL_TILE + (lane >> 3);
+    if (i >= lat.nx || j >= lat.ny) continue;
+    const float x = lat.xs + (((float)i + 0.5f) * lat.h);
+    const float y = (((float)j + 0.5f) * lat.h) - box.half_width;
+    for (int k = 0; k < lat.nz; ++k) {
+      const float z = (((float)k + 0.5f) * lat.h) - box.half_thickness;
+      visit(x, y, z, hand_sets(box, x_hi, lat.xs, x, y, z));
+    }
+  }
+}
+
+// ---- the host's half: the checks and counts of an entry point that takes a lattice -----------------------------------------
+static inline bool positive_f32(double v, float* out) {   // finite and positive, in float32 too
+  const float f = (float)v;
+  *out = f;
+  return v > 0.0 && f > 0.0f && f != __builtin_inff() && f == f;
+}
+
+// max(1, ceil(extent / h)) in float64; false when it cannot be a lattice count (not finite, or beyond the sample limit)
+static inline bool lattice_count(double extent, double h, int* n) {
+  const double c = ceil(extent / h);
+  if (!(c <= (double)(1 << 22)) || c == -__builtin_inf()) return false;   // (a NaN fails the first test)
+  *n = c < 1.0 ? 1 : (int)c;
+  return true;
+}
+
+// The lattice of a call (include/regnet_hip.h "lattice") -> false when a count is not finite or there are more than 2^22 samples.
+static inline bool lattice_of(float x_lo, float standoff, float half_thickness, float half_width, float x_extent, float h,
+                              Lattice* lat) {
+  const float xs = x_lo - standoff;
+  int n_x, n_y, n_z;
+  if (!lattice_count((double)x_extent - (double)xs, (double)h, &n_x) ||
+      !lattice_count((double)half_width + (double)half_width, (double)h, &n_y) ||
+      !lattice_count((double)half_thickness + (double)half_thickness, (double)h, &n_z))
+    return false;
+  if ((int64_t)n_x * n_y * n_z > ((int64_t)1 << 22)) return false;
+  *lat = Lattice{n_x, n_y, n_z, xs, h};
+  return true;
+}

@@ -41,6 +41,8 @@ retreat straight back before it touches the cloud, the extent and offset of the 
 command, the contact check and the pre-grasp point; the record additionally carries ``APPROACH_KEYS``, row-aligned with that set,
 and with ``min_clearance`` / ``min_contact`` the selection sees only the rows that pass.  Without it nothing changes.
 With ``space="volume"`` (``--approach-space``, ``--approach-unseen``, ``--approach-step``, ``--approach-margin``) the hand is held against the TSDF volume instead (``approach.analyse_volume``): ``APPROACH_VOLUME_KEYS`` follow.
+With ``field=True`` (``--approach-field``, ``--min-margin``) the volume's distance field is built once per frame
+(``tsdf.Volume.distance_field``) and ``APPROACH_FIELD_KEYS`` follow those: how much room the hand has.
 
 With ``denoise`` (``--denoise``, ``--outlier-mode``, ``--outlier-radius``, ``--outlier-min-neighbours``, ``--outlier-knn``,
 ``--outlier-max-radius``, ``--outlier-std-ratio``) the cloud of a camera frame -- an ``(xyz, rgb)`` pair, a depth frame's or a
@@ -96,6 +98,7 @@ APPROACH_KEYS = ("grasp_clearance", "grasp_width", "grasp_offset", "grasp_openin
                  "grasp_pregrasp")                             # added when the detector has ``approach``: one row per source grasp
 APPROACH_VOLUME_KEYS = ("grasp_clearance_seen", "grasp_clearance_safe", "grasp_unseen",
                         "grasp_solid_hand")                    # ... right after them when its ``space`` is "volume"
+APPROACH_FIELD_KEYS = ("grasp_margin_hand", "grasp_margin_sweep")   # ... and right after those when it has ``field``
 TSDF_KEYS = ("tsdf_num", "tsdf_counts")                        # added when the frame was a ``MultiView`` and the detector has ``volume``
 TRACK_KEYS = ("track_pose", "track_status", "track_report")    # added beside ``TSDF_KEYS`` when the detector has ``track``
 TSDF_MESH_KEYS = ("tsdf_triangles", "tsdf_vertices", "tsdf_vertex_normals",
@@ -206,6 +209,7 @@ class GraspDetector:
         if self.mesh and volume is None and track is None:
             raise ValueError("mesh: the triangle mesh is that of the detector's TSDF volume; give volume=... or track=...")
         self.volume = self.tsdf_volume = None     # the parameters, and the tsdf.Volume kept between frames
+        self.distance_field = None                # the tsdf.DistanceField of approach.field, its buffers kept between frames
         if volume is not None:                    # (the module is not even imported without it)
             if fuse is not None:
                 raise ValueError("volume: a MultiView is either merged (fuse) or integrated into a volume, not both")
@@ -403,11 +407,19 @@ class GraspDetector:
         transform = self.transform if self.table is None else self.table[0]
         to_volume = np.linalg.inv(np.asarray(transform, dtype=np.float64))
         depth, width = self.eval_params[0], self.eval_params[1]
+        field = None
+        if self.approach.field:                   # once per frame, the volume being final: what blocks the clearance is an obstacle
+            blocked = self.approach.unseen == "blocked"
+            field = self.distance_field = self.tsdf_volume.distance_field(
+                mode="solid_or_unseen" if blocked else "solid", outside=blocked, margin=self.approach.margin,
+                out=self.distance_field)
         result = approach_mod.analyse_volume(self.tsdf_volume, sets[self.approach_source][:, :8], depth, width, self.approach,
-                                             to_volume=to_volume, surface=self.fused)
+                                             to_volume=to_volume, surface=self.fused, field=field)
         extra = dict(zip(APPROACH_KEYS + APPROACH_VOLUME_KEYS,
                          (result.clearance, result.width, result.offset, result.opening, result.contact, result.pregrasp,
                           result.clearance_seen, result.clearance_safe, result.unseen_share, result.solid_hand)))
+        if field is not None:
+            extra.update(zip(APPROACH_FIELD_KEYS, (result.margin_hand, result.margin_sweep)))
         passing = result.passes().nonzero().view(-1) if self.approach.filters() else None
         return extra, passing
 
@@ -587,6 +599,8 @@ _FLAGS = (
     ("--approach-step", "approach", "step", float, "in volume space: the distance between two samples of the swept hand [m] (the voxel)"),
     ("--approach-margin", "approach", "margin", float,
      "in volume space: a voxel nearer than this (%s m) to a surface is solid"),
+    ("--min-margin", "approach", "min_margin", float,
+     "select only grasps whose hand keeps this distance [m] to the nearest obstacle of the volume (implies --approach-field)"),
     # a TSDF volume in place of the point merge (tsdf.fuse_volume): --tsdf or any of the five turns it on
     ("--tsdf-voxel", "volume", "voxel", float, "edge of the voxels of the volume (%s m)"),
     ("--tsdf-trunc", "volume", "trunc", float, "truncation distance, at least two voxels (%s m)"),
@@ -659,8 +673,10 @@ def register_from_args(args):
 
 
 def approach_from_args(args):
-    """The CLI's ten approach flags -> an ``approach`` dict, or None when none of them was given."""
+    """The CLI's twelve approach flags -> an ``approach`` dict, or None when none of them was given."""
     given = _given(args, "approach")
+    if args.approach_field or "min_margin" in given:
+        given["field"] = True
     return given if (given or args.approach) else None
 
 
@@ -739,6 +755,9 @@ def build_parser():
     parser.add_argument("--approach", action="store_true",
                         help="analyse every grasp of one set: approach clearance, closing width, opening and pre-grasp point")
     regular("approach")
+    parser.add_argument("--approach-field", action="store_true",
+                        help="in volume space: build the volume's distance field once per frame and add every grasp's margin, the "
+                             "distance from the hand and from the swept hand to the nearest obstacle")
     parser.add_argument("--denoise", action="store_true",
                         help="remove the outliers of a camera frame's cloud before the table plane and the crop")
     regular("outliers")

@@ -533,6 +533,109 @@ class Volume:
         return ModelView(xyz, normals, rgb, status, counts, width, height, k, T)
 
 
+    def distance_field(self, mode="solid", outside=None, margin=0.0, nearest=False, min_weight=None, stream=None, out=None):
+        """The exact Euclidean distance field of the volume as it stands -> ``DistanceField``: per voxel the squared distance, in
+        voxels, to the nearest obstacle voxel (csrc/edt.hip).  ``mode``: ``"solid"`` -- the obstacles are the voxels seen solid,
+        ``D < margin / trunc`` -- or ``"solid_or_unseen"``: those and the voxels observed fewer than ``min_weight`` (None: the
+        volume's) times.  ``outside``: whether everything beyond the volume's six faces is an obstacle too; None: exactly with
+        ``"solid_or_unseen"``.  ``nearest``: also keep, per voxel, which obstacle voxel that is.  ``out``: a ``DistanceField`` of
+        this volume's dims whose buffers are written instead of new ones (4, with ``nearest`` 8 bytes per voxel).  Three
+        launches, no host read."""
+        import torch
+        p = self.params
+        if mode not in FIELD_MODES:
+            raise ValueError("distance_field: mode must be one of %s, not %r" % (", ".join(FIELD_MODES), mode))
+        outside = (mode == "solid_or_unseen") if outside is None else bool(outside)
+        min_weight = int(p.min_weight if min_weight is None else min_weight)
+        nx, ny, nz = p.dims
+        n = nx * ny * nz
+        dev = self.device
+        with torch.cuda.device(dev), stream_scope(stream):
+            if out is None:
+                dist2 = torch.empty((n,), dtype=torch.int32, device=dev)
+                near = torch.empty((n,), dtype=torch.int32, device=dev) if nearest else None
+            else:
+                if not isinstance(out, DistanceField) or out.dims != p.dims or out.dist2.device != dev:
+                    raise ValueError("distance_field: out must be a DistanceField of this volume's dims on its device")
+                if nearest and out.nearest is None:
+                    raise ValueError("distance_field: out has no nearest plane")
+                dist2, near = out.dist2, (out.nearest if nearest else None)
+            _lib.call("regnet_tsdf_edt", self.data, self.data.data_ptr(), nx, ny, nz, float(p.trunc), min_weight, float(margin),
+                      FIELD_MODES.index(mode), int(outside), dist2.data_ptr(), None if near is None else near.data_ptr(),
+                      stream=None if stream is None else stream.cuda_stream)
+            record_streams(stream, self.data, dist2, near)
+        if out is not None:
+            out.mode, out.outside, out.origin, out.voxel = mode, outside, self.origin, float(p.voxel)
+            out.has_nearest = nearest
+            return out
+        return DistanceField(dist2, near, p.dims, self.origin, float(p.voxel), mode, outside)
+
+
+FIELD_MODES = ("solid", "solid_or_unseen")      # regnet_tsdf_edt's mode 0 and 1
+EDT_NONE = 1 << 30                  # REGNET_EDT_NONE: the squared distance where there is no obstacle at all
+MAX_FIELD_DIM = 1024                # regnet_tsdf_edt's documented limit on every dim
+
+
+class DistanceField:
+    """``Volume.distance_field``'s result, on the device.  ``dist2`` (N) int32: per voxel ``(iz ny + iy) nx + ix`` the squared
+    distance in voxels (between voxel centres) to the nearest obstacle voxel, 0 on an obstacle, ``EDT_NONE`` = 2^30 when there is
+    none; ``nearest`` (N) int32 or None: that obstacle's linear index -- of several at the same distance the smallest --, -1
+    where there is none or the outside of the volume is strictly nearer.  ``dims``, ``origin`` (3 float32, host) and ``voxel`` are
+    the volume's; ``mode`` and ``outside`` say what counted as an obstacle.  Unsigned: 0 everywhere inside an obstacle."""
+
+    def __init__(self, dist2, nearest, dims, origin, voxel, mode, outside):
+        self.dist2, self.nearest, self.dims, self.origin, self.voxel = dist2, nearest, tuple(dims), origin, float(voxel)
+        self.mode, self.outside = mode, bool(outside)
+        self.has_nearest = nearest is not None      # (a reused field may hold a nearest plane its last call did not write)
+
+    def bytes(self):
+        """Bytes of the field on the device: 4 per voxel, 8 with ``nearest``."""
+        return int(self.dist2.numel()) * 4 * (1 if self.nearest is None else 2)
+
+    def query(self, points, to_volume=None, nearest=False, stream=None):
+        """``points`` (M,3) float32 on the field's device, any strides; ``to_volume``: the 4x4 that takes them into the volume's
+        frame (None: identity; its rows 0..2 are rounded to float32 once).  -> ``distance`` (M) float32, metres to the nearest
+        obstacle voxel's centre from the centre of the voxel the point lies in: ``+inf`` when there is no obstacle, NaN for a point
+        outside the volume or not finite.  With ``nearest`` -> ``(distance, nearest_xyz)``, (M,3) float32: that obstacle voxel's
+        centre in the volume's frame, NaN where there is none.  One launch, no host read."""
+        import torch
+        points = require_cuda("points", points, torch.float32, 3, error=TypeError)
+        dev = self.dist2.device
+        if points.device != dev:
+            raise RuntimeError("query: the points are on %s, the field on %s" % (points.device, dev))
+        if nearest and not self.has_nearest:
+            raise ValueError("query: the field was built without nearest=True")
+        T = np.eye(4) if to_volume is None else matrix4(to_volume, "to_volume must be a finite 4x4 transform", finite=True)
+        with np.errstate(over="ignore"):
+            rows = np.ascontiguousarray(T[:3, :].reshape(12).astype(np.float32))
+        m = int(points.shape[0])
+        nx, ny, nz = self.dims
+        with torch.cuda.device(dev), stream_scope(stream):
+            distance = torch.empty((m,), dtype=torch.float32, device=dev)
+            xyz = torch.empty((m, 3), dtype=torch.float32, device=dev) if nearest else None
+            _lib.call("regnet_edt_query_f32", self.dist2, self.dist2.data_ptr(),
+                      self.nearest.data_ptr() if self.has_nearest else None, nx, ny, nz, self.origin.ctypes.data, self.voxel,
+                      points.data_ptr(), points.stride(0), points.stride(1), m, rows.ctypes.data, distance.data_ptr(),
+                      None if xyz is None else xyz.data_ptr(), stream=None if stream is None else stream.cuda_stream)
+            record_streams(stream, points, self.dist2, self.nearest, distance, xyz)
+        return (distance, xyz) if nearest else distance
+
+    def metres(self, dist2=None, stream=None):
+        """The whole field as (N) float32 metres, by the query's two operations -- ``sqrtf((float)dist2) * float32(voxel)``,
+        ``+inf`` for ``EDT_NONE`` --: a dense grid to hand to a planner; ``view(nz, ny, nx)`` is its lattice.  ``dist2``: any
+        contiguous int32 device tensor of squared distances to convert instead (a grasp's margins)."""
+        import torch
+        source = self.dist2 if dist2 is None else dist2
+        if not (source.is_cuda and source.dtype == torch.int32 and source.is_contiguous()):
+            raise TypeError("metres: dist2 must be a contiguous int32 device tensor")
+        with torch.cuda.device(source.device), stream_scope(stream):
+            out = torch.empty(source.shape, dtype=torch.float32, device=source.device)
+            _lib.call("regnet_edt_metres_f32", source, source.data_ptr(), int(source.numel()), self.voxel, out.data_ptr(),
+                      stream=None if stream is None else stream.cuda_stream)
+            record_streams(stream, source, out)
+        return out
+
+
 class Tracked:
     """``Tracker.track``'s result.  ``pose``: the tracker's pose after the frame, (4,4) float64 camera-to-common; ``status``:
     ``FIRST`` (the first frame, integrated at the starting pose), ``TRACKED`` (registered and integrated) or ``LOST`` (nothing
