@@ -1276,6 +1276,58 @@ int regnet_tsdf_mesh_emit(const void* volume, int64_t nx, int64_t ny, int64_t nz
                           const int32_t* tri_block_base, int64_t max_triangles, void* scratch, int32_t* tri, int32_t* num_tri,
                           void* stream);
 
+/* Mesh simplification (csrc/mesh_simplify.hip): vertex clustering (Rossignac-Borrel) of the mesh above, or of any mesh laid out
+ * like it.  The vertices are merged per cell of a dense coarse grid -- the voxel merge of regnet_fuse_* applied to vertices --, the
+ * index buffer is remapped, triangles that collapse leave and, with dedupe, equal triangles are made one.  Integer accumulation
+ * only; the order of the grid is the order of the vertices and the order of the source rows that of the triangles: no sort, and two
+ * runs give the same bytes whatever the order in which threads arrive.  Canonical arithmetic: every operation individually rounded
+ * in the written order (-ffp-contract=off), __fdiv_rn.
+ *   inputs      xyz, normal, rgb (rows, 3) float32 DEVICE: the vertex rows of a surface; K_source: its num, K = K_source[0] is read
+ *               on the device (and held to 0..rows).  tri (max_tri_in, 3) int32 DEVICE and num_tri_in: the index buffer and num_tri
+ *               of regnet_tsdf_mesh_emit, Kt = num_tri_in[0] is read on the device (and held to 0..max_tri_in); only the rows t < Kt
+ *               are read.  origin3: 3 float32 on the HOST; cell: the edge of a grid cell, cell_f = (float)cell; the grid gx gy gz,
+ *               each >= 1, G = gx gy gz <= 2^21; dedupe 0 / 1; max_vertices in 1..2^21, max_triangles in 1..2^22.
+ *   cell        of a vertex, per axis: a = __fdiv_rn(x - o, cell_f), i = floorf(a), f = a - (float)i.  The vertex is VALID iff its
+ *               three coordinates are finite and 0 <= i < g on every axis, its cell then c = (iz gy + iy) gx + ix; else STRAY.
+ *   per cell    count (int32); S_k += (int32)(f_k * 16777216.0f), C_k += (int32)rintf(clamp(c_k, 0, 1) * 255.0f) (a NaN colour
+ *               counts as 0), both 64-bit; a vertex whose three normal components are finite adds (int32)rintf(clamp(n_k, -1, 1) *
+ *               1048576.0f) to N_k (64-bit) and 1 to ncount; first = the smallest vertex row (atomicMin).
+ *   triangles   row t < Kt: (-1, -1, -1) is ABSENT; an index outside [0, K) or a STRAY vertex makes it STRAY; two equal cells among
+ *               its three: COLLAPSED.  Otherwise the triple of cells is rotated cyclically until the smallest stands first -- the
+ *               orientation is kept -- and key = c0 << 42 | c1 << 21 | c2.  With dedupe the rows of one key are one triangle: the
+ *               SMALLEST source row survives, the others are DUPLICATE (an open-addressing set, linear probing from the home slot
+ *               regnet_mesh_simplify_home_slot_host(key, slots) -- the top log2(slots) bits of key * 0x9E3779B97F4A7C15, as
+ *               regnet_fuse_home_slot_host --, claimed by a 64-bit compare-and-swap, slots = regnet_mesh_simplify_table_slots =
+ *               2 next_pow2(max_tri_in), so it cannot fill).  Two triangles of opposite orientation have different keys: both
+ *               stay.  Without dedupe every row that is not COLLAPSED survives.
+ *   vertices    the cells that a surviving triangle references, in ascending c: Kv of them, row < min(Kv, max_vertices) written.
+ *               count == 1: position, normal and colour of row `first` as given, bit for bit.  Otherwise in float64, one rounding
+ *               per operation: x = (float)(o + ((double)i + (double)S / ((double)count * 2^24)) * (double)cell_f); colour = (float)
+ *               ((double)C / ((double)count * 255.0)); normal: m_k = (double)N_k / 1048576.0, len = sqrt((m_x m_x + m_y m_y) + m_z
+ *               m_z), (float)(m_k / len), the quiet NaN 0x7fc00000 when ncount == 0 or len == 0.  out_weight = count.  The rows
+ *               beyond hold NaN / NaN / 0 / -1 (xyz, normal, rgb, weight), as a surface's do.
+ *   out_tri     (max_triangles, 3) int32: the survivors in ascending source row, each as its rotated triple in NEW vertex rows;
+ *               -1 beyond the kept rows; a survivor with a vertex row >= max_vertices is (-1, -1, -1) IN ITS PLACE and dropped.
+ *   num         (12) int32 DEVICE: [0] min(Kv, max_vertices), [1] Kv, [2] Kv > max_vertices, [3] cells with count > 0, [4] STRAY
+ *               vertices, [5] min(Tt, max_triangles) with Tt the survivors, [6] Tt, [7] dropped (among the rows < [5]), [8] Tt >
+ *               max_triangles, [9] COLLAPSED, [10] DUPLICATE, [11] STRAY + ABSENT; [6] + [9] + [10] + [11] = Kt.  Words 5..8 are a
+ *               num_tri.  surface_num (4) int32 DEVICE or NULL: ([0], [1], K, [2]), the num of the new vertices as a surface.
+ *   workspace   regnet_mesh_simplify_workspace_bytes(G, max_tri_in) bytes, 8-byte aligned (else REGNET_ERR_UNSUPPORTED), the
+ *               caller's; -1 for sizes the call refuses.  Nothing in it outlives the call.
+ * Two fills and eight launches on `stream`.  No sort, no host read, no synchronisation, no allocation, no cooperative launch; no
+ * thread waits for another and every probe loop ends on the slot count; capturable.  K or Kt of 0: a valid empty mesh.  Errors, all
+ * before any launch: rows, max_tri_in, a grid dim, max_vertices or max_triangles < 1, dedupe not 0 / 1 -> REGNET_ERR_SHAPE; G > 2^21,
+ * rows or max_vertices > 2^21, max_triangles or max_tri_in > 2^22, cell not finite and positive (in float32 too) ->
+ * REGNET_ERR_UNSUPPORTED; a NULL pointer (all but surface_num) -> REGNET_ERR_NULL.                                              */
+int64_t regnet_mesh_simplify_workspace_bytes(int64_t G, int64_t max_tri_in);
+int64_t regnet_mesh_simplify_table_slots(int64_t max_tri_in);
+int64_t regnet_mesh_simplify_home_slot_host(uint64_t key, int64_t slots);
+int regnet_mesh_simplify_f32(const float* xyz, const float* normal, const float* rgb, int64_t rows, const int32_t* K_source,
+                             const int32_t* tri, int64_t max_tri_in, const int32_t* num_tri_in, const float* origin3, double cell,
+                             int64_t gx, int64_t gy, int64_t gz, int dedupe, int64_t max_vertices, int64_t max_triangles,
+                             void* workspace, float* out_xyz, float* out_normal, float* out_rgb, int32_t* out_weight,
+                             int32_t* out_tri, int32_t* num, int32_t* surface_num, void* stream);
+
 /* regnet_tsdf_raycast_f32: the MODEL VIEW of the volume from a virtual pinhole camera -- per pixel the first zero crossing of D
  * along its ray, with the normal of D's gradient and the colour there: the organised vertex and normal map
  * regnet_icp_step_projective_f32 takes as its target (frame-to-model tracking), and a denoised depth image of the fused model.

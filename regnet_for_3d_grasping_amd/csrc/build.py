@@ -48,6 +48,7 @@ SOURCES = [
     ("outlier.hip", ["-ffp-contract=off"]),   # outlier removal: every neighbour is decided on individually rounded fp32 distances
     ("tsdf.hip", ["-ffp-contract=off"]),   # TSDF volume: every voxel's running means and every surface row are compared bit for bit with numpy
     ("tsdf_mesh.hip", []),   # the volume's triangle mesh: integer work only (two float compares), nothing to round
+    ("mesh_simplify.hip", ["-ffp-contract=off"]),   # vertex clustering: cells on individually rounded fp32, the float64 finalise one rounding per operation
     ("approach_volume.hip", ["-ffp-contract=off"]),   # approach against the volume: every sample's voxel and set are decided on individually rounded fp32
     ("edt.hip", ["-ffp-contract=off"]),   # distance field: integer passes; the query's and the margin's lookups are approach_volume.hip's
 ]
@@ -84,6 +85,7 @@ NO_VGPR_SPILL = {"mlp.o": ["mlp_gemm_kernelILi0E", "gemm2_kernel"], "sa_chain.o"
                  "scatter.o": ["scatter_", "segsum_"], "det.o": ["det_"],
                  "ingest.o": ["ingest_"], "nms.o": ["nms_"], "plane.o": ["plane_"], "depth.o": ["depth_"],
                  "fuse.o": ["fuse_"], "icp.o": ["icp_"], "outlier.o": ["outlier_"], "tsdf.o": ["tsdf_"], "tsdf_mesh.o": ["tsdf_mesh_"],
+                 "mesh_simplify.o": ["ms_"],
                  "approach.o": ["approach_kernel"], "approach_volume.o": ["approach_volume_"], "edt.o": ["edt_"]}
 
 

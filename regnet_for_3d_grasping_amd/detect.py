@@ -65,7 +65,9 @@ record then carries ``TSDF_KEYS`` and ``TRACK_KEYS``.  Without it nothing change
 
 With ``mesh`` (``--tsdf-mesh``; beside ``volume`` or ``track``) the volume's surface is taken as a triangle mesh
 (``tsdf.Volume.extract_mesh``) and the record also carries ``TSDF_MESH_KEYS``; ``--tsdf-mesh-ply`` writes it as ``NAME.ply`` beside
-the record.  Without it no launch, no allocation and no key changes.
+the record.  Without it no launch, no allocation and no key changes.  With ``mesh_cell`` (``--tsdf-mesh-cell M``) that mesh is
+simplified on the device first (``tsdf.Mesh.simplify``, vertex clustering on cells of M metres): ``TSDF_MESH_KEYS`` and the
+``.ply`` then hold the simplified mesh and ``tsdf_mesh_report`` is added; the networks still see the full surface.
 """
 import argparse
 import contextlib
@@ -103,6 +105,7 @@ TSDF_KEYS = ("tsdf_num", "tsdf_counts")                        # added when the 
 TRACK_KEYS = ("track_pose", "track_status", "track_report")    # added beside ``TSDF_KEYS`` when the detector has ``track``
 TSDF_MESH_KEYS = ("tsdf_triangles", "tsdf_vertices", "tsdf_vertex_normals",
                   "tsdf_vertex_colors")                        # added after them when the detector has ``mesh``
+TSDF_MESH_REPORT_KEYS = ("tsdf_mesh_report",)                  # added after them when the detector has ``mesh_cell``
 DENOISE_KEYS = ("denoise_num",)                                 # added when the detector has ``denoise`` and the frame was a camera frame
 
 
@@ -174,11 +177,16 @@ class GraspDetector:
     ``tsdf_vertices`` per triangle, in cell order, normals out of the solid -- and float32 ``tsdf_vertices``,
     ``tsdf_vertex_normals``, ``tsdf_vertex_colors`` (K,3): the WHOLE surface of the volume in the common frame, before the crop
     chooses rows.  ``mesh_ply``: ``detect_file`` also writes them as a binary PLY beside the record.  Without ``mesh`` nothing
-    is launched or allocated for it."""
+    is launched or allocated for it.
+    ``mesh_cell`` [m] (implies ``mesh``; may ride in the dicts too): the mesh goes through ``tsdf.Mesh.simplify(cell=mesh_cell)``
+    on the device before it is downloaded -- the four mesh keys and the PLY are then the simplified mesh, whose triangles ascend
+    by the full mesh's rows, and ``tsdf_mesh_report`` (12,) int32 is ``SimplifiedMesh.report``.  The cloud the networks see is
+    the full surface either way.  Without it every key and file is what it is without the option."""
 
     def __init__(self, score_net, region_net, params=TEST_PARAMS, gripper_params=GRIPPER_PARAMS, eval_params=EVAL_PARAMS,
                  transform=None, bounds=None, num_points=ALL_POINTS_NUM, use_theta=USE_THETA, select=None, depth=None, segment=None,
-                 fuse=None, register=None, approach=None, denoise=None, volume=None, track=None, mesh=False, mesh_ply=False):
+                 fuse=None, register=None, approach=None, denoise=None, volume=None, track=None, mesh=False, mesh_ply=False,
+                 mesh_cell=None):
         from . import depth_frame, fusion, grasp_select, ingest, registration
         from . import segment as segment_mod
         self.fuse = fusion.FuseParams.coerce(fuse)
@@ -200,12 +208,20 @@ class GraspDetector:
                                  % (selected, self.approach_source))
         self.mesh = bool(mesh) or bool(mesh_ply)  # the surface as a triangle mesh; may also ride in the volume / track dict
         self.mesh_ply = bool(mesh_ply)
-        if isinstance(volume, dict) and "mesh" in volume:
+        self.mesh_cell = mesh_cell                # the cell edge [m] the mesh is simplified with, None: the full mesh
+        if isinstance(volume, dict) and ("mesh" in volume or "mesh_cell" in volume):
             volume = dict(volume)
-            self.mesh = bool(volume.pop("mesh")) or self.mesh
-        if isinstance(track, dict) and "mesh" in track:
+            self.mesh = bool(volume.pop("mesh", False)) or self.mesh
+            self.mesh_cell = volume.pop("mesh_cell", self.mesh_cell)
+        if isinstance(track, dict) and ("mesh" in track or "mesh_cell" in track):
             track = dict(track)
-            self.mesh = bool(track.pop("mesh")) or self.mesh
+            self.mesh = bool(track.pop("mesh", False)) or self.mesh
+            self.mesh_cell = track.pop("mesh_cell", self.mesh_cell)
+        if self.mesh_cell is not None:
+            self.mesh_cell = float(self.mesh_cell)
+            if not (self.mesh_cell > 0.0 and np.isfinite(self.mesh_cell)):
+                raise ValueError("mesh_cell: the cell edge must be positive and finite")
+            self.mesh = True
         if self.mesh and volume is None and track is None:
             raise ValueError("mesh: the triangle mesh is that of the detector's TSDF volume; give volume=... or track=...")
         self.volume = self.tsdf_volume = None     # the parameters, and the tsdf.Volume kept between frames
@@ -270,13 +286,15 @@ class GraspDetector:
             if self.mesh:
                 meshed = self.tracker.volume.extract_mesh()
                 fused = meshed.surface
+                if self.mesh_cell is not None:
+                    meshed = meshed.simplify(cell=self.mesh_cell)
             else:
                 fused = self.tracker.volume.extract()
             frame = fused.cloud()
         elif isinstance(frame, fusion.MultiView) and self.volume is not None:     # integrated on the device, no host read
             from . import tsdf
             fused = tsdf.fuse_volume(frame, self.depth, self.volume, device=self.device, register=self.register,
-                                     volume=self.tsdf_volume, mesh=self.mesh)
+                                     volume=self.tsdf_volume, mesh=self.mesh, mesh_cell=self.mesh_cell)
             if self.mesh:
                 fused, meshed = fused
             self.tsdf_volume = fused.volume
@@ -468,6 +486,9 @@ class GraspDetector:
                 (out["tsdf_vertices"], out["tsdf_vertex_normals"], out["tsdf_vertex_colors"],
                  out["tsdf_triangles"]) = fr.meshed.to_host()
                 keys = keys + TSDF_MESH_KEYS
+                if self.mesh_cell is not None:
+                    out["tsdf_mesh_report"] = fr.meshed.report.cpu().numpy()
+                    keys = keys + TSDF_MESH_REPORT_KEYS
             if fr.fused.register is not None:
                 out["fuse_poses"] = np.array(fr.fused.poses, dtype=np.float64)
                 out["fuse_register"] = np.array(fr.fused.register, dtype=np.float64)
@@ -773,6 +794,9 @@ def build_parser():
                         help="with --tsdf or --track: take the volume's surface as a triangle mesh and add it to the record")
     parser.add_argument("--tsdf-mesh-ply", action="store_true",
                         help="... and write it as NAME.ply beside the record (implies --tsdf-mesh)")
+    parser.add_argument("--tsdf-mesh-cell", type=float, metavar="M", default=None,
+                        help="simplify that mesh on the device by vertex clustering on cells of M metres before it goes into the "
+                             "record and the PLY (implies --tsdf-mesh)")
     parser.add_argument("--track", action="store_true",
                         help="the folder's depth frames, in the order of their names, are one moving camera: track it against the "
                              "TSDF volume it fills and take the volume's surface as every frame's cloud")
@@ -804,7 +828,7 @@ def main(argv=None):
                              segment=segment_from_args(args), fuse=fuse_from_args(args), register=register_from_args(args),
                              approach=approach_from_args(args), denoise=outliers_from_args(args),
                              volume=volume_from_args(args), track=track_from_args(args), mesh=args.tsdf_mesh,
-                             mesh_ply=args.tsdf_mesh_ply)
+                             mesh_ply=args.tsdf_mesh_ply, mesh_cell=args.tsdf_mesh_cell)
     real_data = "real_data" in args.folder
     if args.file:
         paths = [os.path.join(args.folder, args.file)]

@@ -26,7 +26,9 @@ image coarse to fine on one state block (``depth_frame.pyramid``, ``registration
 ``Volume.extract_mesh`` returns the surface as a triangle mesh (csrc/tsdf_mesh.hip): the rows of ``extract`` are the vertices,
 and marching cubes over the cells whose eight corners were observed adds the index buffer, in cell order with no sort -- integer
 work only, so ``tests/tsdf_mesh_reference.py`` restates it with plain loops.  ``Mesh.save_ply`` writes it for a viewer, a
-simulator or a planner's collision world.
+simulator or a planner's collision world.  ``Mesh.simplify`` merges its vertices per cell of a coarse grid and de-duplicates the
+index buffer (csrc/mesh_simplify.hip, vertex clustering): integer accumulation in the grid's order, so
+``tests/mesh_simplify_reference.py`` restates it bit for bit too.
 """
 from dataclasses import dataclass, replace
 import math
@@ -43,6 +45,7 @@ MAX_VOLUME_VOXELS = 1 << 28         # regnet_tsdf_*'s documented limits
 MAX_POINTS = MAX_FRAME_POINTS
 MAX_TRIANGLES = 1 << 22             # regnet_tsdf_mesh_emit's documented limit
 BLOCK = 256                         # voxels per workgroup of the two extraction passes
+MAX_SIMPLIFY_CELLS = 1 << 21        # regnet_mesh_simplify_f32's documented limit on the coarse grid
 UPDATED, NOT_IN_VIEW, NO_DEPTH, BEHIND = 0, 1, 2, 3      # the entries of integrate's counts
 
 
@@ -129,8 +132,10 @@ class Mesh:
     are kept, so the mesh stays closed.  A cell with a corner that was not observed ``min_weight`` times has no triangles: the mesh
     is open along the border of observed space."""
 
-    def __init__(self, surface, triangles, num_triangles, max_triangles):
+    def __init__(self, surface, triangles, num_triangles, max_triangles, volume=None):
         self.surface, self.triangles, self.num_triangles, self.max_triangles = surface, triangles, num_triangles, int(max_triangles)
+        self.volume = volume                    # the Volume it was extracted from: where ``simplify`` keeps its buffers
+        self.simplify_buffers = {}              # ... and where it keeps them for a mesh without one
 
     def check(self):
         """Two blocking reads of 16 bytes -> (vertices K, triangles Kt).  Raises ``ValueError`` when the surface or the triangles
@@ -158,6 +163,101 @@ class Mesh:
         """Writes ``to_host()`` as a binary little-endian PLY: per vertex x y z nx ny nz float32 and red green blue uint8 (the
         colour times 255, rounded, clipped), per face a uint8 3 and three int32."""
         write_ply(path, *self.to_host())
+
+    def simplify(self, cell=None, factor=4, dedupe=True, max_vertices=None, max_triangles=None, stream=None, out=None):
+        """Vertex clustering (csrc/mesh_simplify.hip) -> ``SimplifiedMesh``.  The vertices are merged per cell of a dense grid of
+        edge ``cell`` [m] (None: ``factor`` voxels) over the volume's box, ``g_k = ceil(n_k voxel / cell) + 1`` cells per axis from
+        the volume's origin, at most 2^21 in all: a cell's vertex is the mean of its vertices (one vertex alone is kept bit for
+        bit), with the mean colour and the normalised mean normal.  Triangles with two vertices in one cell leave; with ``dedupe``
+        triangles that became equal (as oriented triples) are one, the one of the smallest source row.  The new vertices ascend by
+        cell, the triangles by source row: no sort, and the same bytes on every run.  ``max_vertices`` (None: the smaller of the
+        surface's rows and the cells) and ``max_triangles`` (None: this mesh's) are the rows of the result; one that has more
+        sets its overflow flag.
+
+        The workspace and the outputs are allocated on the first call with these sizes and KEPT on the volume: a second call
+        allocates nothing and writes the same tensors, so a result is good until the next such call.  ``out``: a
+        ``SimplifiedMesh`` of the same sizes (an earlier result) to write into instead.  Two fills and eight launches; no host
+        read.  The mesh is no longer manifold in general (DESIGN.md par. 10)."""
+        import torch
+        s = self.surface
+        p = s.params
+        voxel = float(p.voxel)
+        cell = float(factor) * voxel if cell is None else float(cell)
+        with np.errstate(over="ignore", under="ignore"):
+            cell32 = np.float32(cell)
+        if not (cell > 0.0 and cell32 > 0.0 and np.isfinite(cell32)):
+            raise ValueError("simplify: cell must be positive and finite in float32")
+        grid = tuple(int(math.ceil(n * voxel / cell)) + 1 for n in p.dims)
+        cells = grid[0] * grid[1] * grid[2]
+        if cells > MAX_SIMPLIFY_CELLS:
+            raise ValueError("simplify: a grid of %d x %d x %d cells, more than 2^21; raise cell" % grid)
+        rows, mt_in = int(s.xyz.shape[0]), int(self.max_triangles)
+        mv = min(rows, cells) if max_vertices is None else max_vertices
+        mt = mt_in if max_triangles is None else max_triangles
+        if int(mv) != mv or not 1 <= mv <= MAX_POINTS:
+            raise ValueError("simplify: max_vertices must be in 1..2^21")
+        if int(mt) != mt or not 1 <= mt <= MAX_TRIANGLES:
+            raise ValueError("simplify: max_triangles must be in 1..2^22")
+        mv, mt = int(mv), int(mt)
+        dev = s.xyz.device
+        origin = np.ascontiguousarray(np.asarray(p.origin, dtype=np.float64).astype(np.float32))
+        raw = None if stream is None else stream.cuda_stream
+        keeper = self if self.volume is None else self.volume
+        kept = keeper.simplify_buffers
+        with torch.cuda.device(dev), stream_scope(stream):
+            sizes = (cells, mt_in, mv, mt)
+            if sizes not in kept:
+                workspace = torch.empty((int(_L.regnet_mesh_simplify_workspace_bytes(cells, mt_in)) // 8,), dtype=torch.int64,
+                                        device=dev)
+                kept[sizes] = (workspace, None if out is not None else SimplifiedMesh.empty(mv, mt, p, dev))
+            workspace, result = kept[sizes]
+            if out is not None:
+                if not (isinstance(out, SimplifiedMesh) and out.sizes() == (mv, mt) and out.triangles.device == dev):
+                    raise ValueError("simplify: out must be a SimplifiedMesh of %d vertex and %d triangle rows on %s" % (mv, mt, dev))
+                result = out
+            elif result is None:
+                result = SimplifiedMesh.empty(mv, mt, p, dev)
+                kept[sizes] = (workspace, result)
+            v = result.surface
+            _lib.call("regnet_mesh_simplify_f32", s.xyz, s.xyz.data_ptr(), s.normal.data_ptr(), s.rgb.data_ptr(), rows,
+                      s.num.data_ptr(), self.triangles.data_ptr(), mt_in, self.num_triangles.data_ptr(), origin.ctypes.data, cell,
+                      grid[0], grid[1], grid[2], 1 if dedupe else 0, mv, mt, workspace.data_ptr(), v.xyz.data_ptr(),
+                      v.normal.data_ptr(), v.rgb.data_ptr(), v.weight.data_ptr(), result.triangles.data_ptr(),
+                      result.report.data_ptr(), v.num.data_ptr(), stream=raw)
+            record_streams(stream, s.xyz, s.normal, s.rgb, s.num, self.triangles, self.num_triangles, workspace, v.xyz, v.normal,
+                           v.rgb, v.weight, v.num, result.triangles, result.report)
+        result.source, result.volume, result.cell, result.grid, result.dedupe = self, self.volume, cell, grid, bool(dedupe)
+        return result
+
+
+class SimplifiedMesh(Mesh):
+    """``Mesh.simplify``'s result, on the device: a ``Mesh`` whose ``surface`` is a ``Surface`` of the NEW vertices -- ``weight``
+    the source vertices merged into each, ``num`` (4) int32 = (Kv kept, Kv in all, the source's K, overflow) -- and whose
+    ``triangles`` index them; ``num_triangles`` has ``Mesh``'s meaning, so ``check``, ``to_host`` and ``save_ply`` work unchanged.
+    ``report`` (12) int32: (Kv kept, Kv in all, vertex overflow, occupied cells, stray vertices, Kt kept, survivors in all,
+    dropped, triangle overflow, collapsed, duplicate, stray or absent source triangles); ``num_triangles`` is a view of its words
+    5..8.  ``source``: the mesh it was made from; ``cell`` [m], ``grid`` and ``dedupe`` say how."""
+
+    def __init__(self, surface, triangles, report, max_triangles):
+        Mesh.__init__(self, surface, triangles, report[5:9], max_triangles)
+        self.report = report
+        self.source = self.cell = self.grid = self.dedupe = None
+
+    @classmethod
+    def empty(cls, max_vertices, max_triangles, params, device):
+        """The buffers of a result with these rows; what they hold is undefined until ``Mesh.simplify`` wrote them."""
+        import torch
+        mv, mt = int(max_vertices), int(max_triangles)
+        xyz, rgb, normal = (torch.empty((mv, 3), dtype=torch.float32, device=device) for _ in range(3))
+        weight = torch.empty((mv,), dtype=torch.int32, device=device)
+        num = torch.empty((4,), dtype=torch.int32, device=device)
+        surface = Surface(xyz, rgb, normal, weight, num, replace(params, max_points=mv))
+        return cls(surface, torch.empty((mt, 3), dtype=torch.int32, device=device),
+                   torch.empty((12,), dtype=torch.int32, device=device), mt)
+
+    def sizes(self):
+        """-> (vertex rows, triangle rows)."""
+        return int(self.surface.xyz.shape[0]), int(self.triangles.shape[0])
 
 
 def write_ply(path, vertices, normals, colours, triangles):
@@ -350,6 +450,7 @@ class Volume:
         self.D, self.W, self.C = self.data[:n], self.data[n:2 * n].view(torch.int32), self.data[2 * n:].view(3, n)
         self.origin = np.ascontiguousarray(np.asarray(self.params.origin, dtype=np.float64).astype(np.float32))
         self.mesh_scratch = None                # extract_mesh's row lookup plane, (N) int32: allocated on its first call
+        self.simplify_buffers = {}              # Mesh.simplify's (workspace, result) per sizes: allocated on the first call with them
         self.reset()
 
     @property
@@ -437,14 +538,16 @@ class Volume:
             record_streams(stream, self.data)
         return Surface(xyz, rgb, normal, weight, num, p), block_counts, block_base
 
-    def extract_mesh(self, min_weight=None, max_points=None, max_triangles=None, stream=None, out=None, out_mesh=None):
+    def extract_mesh(self, min_weight=None, max_points=None, max_triangles=None, stream=None, out=None, out_mesh=None,
+                     simplify=None):
         """The surface of the volume as it stands as a triangle mesh -> ``Mesh``: ``extract`` (with ``min_weight`` / ``max_points``
         in place of the volume's parameters when given; ``out`` goes to it) and, on the same state, marching cubes over the
         cells all of whose corners are usable.  ``out_mesh``: ``(triangles, num_triangles)`` contiguous device tensors of the
         result's shapes to write into.  ``max_triangles``: the rows of the index buffer, at most 2^22; None: twice
         ``max_points`` (a closed surface has about two triangles per vertex), capped there.  Five more launches and one more
         ``torch.cumsum``; no host read.  The row lookup's scratch plane, 4 bytes per voxel, is allocated on the first call and
-        kept on the volume."""
+        kept on the volume.  ``simplify``: a cell edge [m]: -> ``Mesh.simplify(cell=simplify)`` of that mesh, a
+        ``SimplifiedMesh`` whose ``source`` is the full one; None: nothing more is launched."""
         import torch
         p = self.params
         if min_weight is not None or max_points is not None:
@@ -476,7 +579,8 @@ class Volume:
                       block_counts.data_ptr(), block_base.data_ptr(), surface.num.data_ptr(), tri_counts.data_ptr(),
                       tri_base.data_ptr(), mt, self.mesh_scratch.data_ptr(), tri.data_ptr(), num_tri.data_ptr(), stream=raw)
             record_streams(stream, self.data, self.mesh_scratch, block_counts, block_base, tri_counts, tri_base, tri, num_tri)
-        return Mesh(surface, tri, num_tri, mt)
+        mesh = Mesh(surface, tri, num_tri, mt, volume=self)
+        return mesh if simplify is None else mesh.simplify(cell=simplify, stream=stream)
 
     def raycast(self, pose, intrinsics, width, height, near=None, far=None, step=None, colour=True, stream=None, out=None,
                 clip=True):
@@ -782,16 +886,20 @@ def relative_motion(T):
 
 
 def fuse_volume(multiview, depth_params=None, tsdf_params=None, device="cuda:0", stream=None, register=None, volume=None,
-                mesh=False):
+                mesh=False, mesh_cell=None):
     """``depth_frame.to_cloud`` for every frame of ``multiview`` (a ``fusion.MultiView``), then reset, ``integrate`` in view order
     and ``extract`` -> ``Surface``, which carries ``counts`` (views,4) int32 on the device and ``volume``.  No host read.  With
     ``register`` (a ``registration.IcpParams`` or a dict of its fields) the poses go through ``fusion.refine_poses`` first -- its
     reads are then made -- and the result carries them: ``Surface.poses`` (V,4,4) float64 and ``Surface.register``, the (V,5)
-    report.  ``volume``: a ``Volume`` to reuse instead of allocating one (its parameters then hold, and it is reset)."""
+    report.  ``volume``: a ``Volume`` to reuse instead of allocating one (its parameters then hold, and it is reset).  ``mesh``: ->
+    ``(Surface, Mesh)`` of ``extract_mesh``; with ``mesh_cell`` [m] the second is its ``SimplifiedMesh`` (the full mesh is its
+    ``source``), the ``Surface`` still the full one."""
     import torch
     from . import fusion
     if not isinstance(multiview, fusion.MultiView):
         raise TypeError("fuse_volume takes a MultiView")
+    if mesh_cell is not None and not mesh:
+        raise ValueError("fuse_volume: mesh_cell simplifies the mesh; give mesh=True")
     if volume is None:
         volume = Volume(tsdf_params, device)
     device = volume.device
@@ -808,6 +916,8 @@ def fuse_volume(multiview, depth_params=None, tsdf_params=None, device="cuda:0",
         counts.append(volume.integrate((xyz, rgb, width, height, frame.intrinsics), pose, stream=stream))
     meshed = volume.extract_mesh(stream=stream) if mesh else None
     surface = meshed.surface if mesh else volume.extract(stream=stream)
+    if mesh_cell is not None:
+        meshed = meshed.simplify(cell=mesh_cell, stream=stream)
     with stream_scope(stream):
         surface.counts = torch.stack(counts)
     surface.volume = volume
