@@ -1618,8 +1618,73 @@ int regnet_grasp_approach_volume_f32(const void* volume, int64_t nx, int64_t ny,
  * sample OUTSIDE.  Errors, all before the launch: B < 0, a dim < 1, outside not 0 / 1 -> REGNET_ERR_SHAPE; a dim > 1024, N > 2^28,
  * B >= 2^31, step or voxel not finite or not positive (in float32 too), a standoff that is negative or not finite, a lattice count
  * that is not finite or n_x n_y n_z > 2^22 -> REGNET_ERR_UNSUPPORTED; then B == 0: success without a launch; then a NULL dist2,
- * origin3, L, margins or counts -> REGNET_ERR_NULL.                                                                          */
+ * origin3, L, margins or counts -> REGNET_ERR_NULL.
+ *
+ * Signed, capped field.  regnet_tsdf_sdf(volume, dims, trunc, min_weight, margin, mode, outside, sign, cap, field, nearest, work,
+ * stream): volume, the classification, mode, outside, margin, min_weight and the limits are regnet_tsdf_edt's.
+ *   sign = 0    field is dist2 as above.
+ *   sign = 1    field (N) int32 holds SIGNED squared voxel distances: a non-obstacle voxel v gets +min |v - q|^2 over the obstacle
+ *               voxels q (>= 1), an obstacle voxel gets -min |v - p|^2 over the NON-obstacle voxels p of the lattice (<= -1); 0
+ *               never occurs.  No obstacle at all: every word +REGNET_EDT_NONE; no free voxel: every word -REGNET_EDT_NONE.
+ *               outside = 1 adds the slabs beyond the faces to the obstacles of the positive side (min(d2, m^2) as above); the
+ *               outside is never free space and does not enter the negative side.
+ *   cap         int64, in voxels: 0 none, else 1..1023.  Values saturate: min(d2, cap^2) on the positive side, max(-d2, -cap^2)
+ *               on the negative one, +-NONE becomes +-cap^2.  The search of every line pass stops at d > cap, at most 2 cap + 1
+ *               words per voxel and pass wherever the obstacles are; the result is exact all the same (DESIGN.md par. 5).  A
+ *               true distance of exactly cap is a real value.
+ *   nearest     (N) int32 or NULL: for a non-obstacle voxel the nearest obstacle voxel; for an obstacle voxel with sign = 1 the
+ *               nearest non-obstacle voxel, the way out; of several the smallest linear index on both sides.  -1 where the value
+ *               is +-NONE, where it is saturated STRICTLY beyond the cap (a distance of exactly cap keeps its nearest), or where a
+ *               face slab is strictly nearer.
+ *   work        DEVICE scratch of regnet_tsdf_sdf_workspace_bytes(nx, ny, nz, sign, with_nearest) bytes (a host function: 0 with
+ *               sign = 0 or bad dims, else 4 N, 8 N with nearest), 4-byte aligned: the planes of the second transform.
+ * sign = 0: the three launches above; sign = 1: six -- the three passes with the obstacles as seeds into field / nearest, then
+ * the three over the COMPLEMENT (the non-obstacle voxels as seeds) in work, whose z pass writes minus its result into the words
+ * of field that are 0.  No allocation, host read or synchronisation, no atomic: capturable, and two runs give the same bytes.
+ * With sign = 0 and cap = 0 the output equals regnet_tsdf_edt's byte for byte.  Errors, all before any launch and in
+ * regnet_tsdf_edt's order: sign not 0 / 1 or cap < 0 with the REGNET_ERR_SHAPE rules; cap > 1023 with the REGNET_ERR_UNSUPPORTED
+ * rules (after the dims); a NULL work where the size is non-zero with the REGNET_ERR_NULL rules.
+ *
+ * Signed metres.  regnet_edt_metres_signed_f32(field, n, voxel, out): for a signed word s, a = sqrtf((float)|s|) and
+ * out = copysignf((a - 0.5f) * voxel_f, (float)s), every operation rounded on its own, + 0.0f before the store; +-inf for +-NONE.
+ * The half voxel makes it the distance to the boundary FACE between the classes, not to a voxel centre: across an axis-aligned
+ * wall consecutive centres read ..., -1.5, -0.5, +0.5, +1.5, ... voxels, the true signed distance and a linear function.  n and
+ * voxel as in regnet_edt_metres_f32, which is unchanged.
+ *
+ * Signed query.  regnet_edt_query_signed_f32: one lane per point, one launch; points, T12, the transform and the INSIDE rule are
+ * regnet_edt_query_f32's; a point that is not INSIDE gets the quiet NaN 0x7fc00000 in every output.
+ *   interpolate = 0   distance (M) float32 = the signed metres of the point's nearest voxel; gradient, if given, NaN.
+ *   interpolate = 1   trilinear between the eight voxel centres around the point.  Per axis u = __fdiv_rn(w - o, voxel_f) - 0.5f,
+ *               i0 = floorf(u), t = u - i0; the corner indices i0 and i0 + 1 are each clamped to [0, n - 1] (in the outer
+ *               half-voxel rim the interpolation degenerates to the nearest layer along that axis).  The corner values are the
+ *               signed metres above; lerp(a, b, t) = a + (t * (b - a)), applied along x, then y, then z.
+ *   gradient    (M,3) float32 contiguous or NULL: the analytic derivative of that interpolant in the VOLUME's frame.  For an
+ *               axis, the four differences b - a of the corner values along it, each __fdiv_rn(b - a, voxel_f), lerped over the
+ *               other two axes, x before y before z.  Dimensionless, length 1 across a flat wall.
+ *   nearest_xyz as in regnet_edt_query_f32, for the point's nearest voxel (the way out for a point in an obstacle voxel).
+ * Non-finite results are what IEEE arithmetic gives (infinite corners of an uncapped field: inf - inf); any NaN is stored as
+ * 0x7fc00000.  Use a cap with interpolation.  Errors: regnet_edt_query_f32's; interpolate not 0 / 1 -> REGNET_ERR_SHAPE.
+ *
+ * Signed margin.  regnet_grasp_margin_volume_signed_f32: regnet_grasp_margin_volume_f32 (one kernel, a template parameter)
+ * reading a signed plane.  margins (B,2) int32 are the signed minima over the hand and over the swept samples: a negative value
+ * is minus the squared depth in voxels of the deepest sample.  An OUTSIDE sample under outside = 1 contributes -1 (an obstacle
+ * of unknown depth; 0 is not a value of a signed field).  counts (B,6) int32: the four above, then the hand samples with a
+ * negative value, then the swept samples with one (OUTSIDE samples under outside = 1 included).  Errors, launch and reductions
+ * as in the unsigned entry, which is unchanged.                                                                               */
 #define REGNET_EDT_NONE (1 << 30)
+int64_t regnet_tsdf_sdf_workspace_bytes(int64_t nx, int64_t ny, int64_t nz, int sign, int with_nearest);
+int regnet_tsdf_sdf(const void* volume, int64_t nx, int64_t ny, int64_t nz, double trunc, int64_t min_weight, double margin,
+                    int mode, int outside, int sign, int64_t cap, int32_t* field, int32_t* nearest, void* work, void* stream);
+int regnet_edt_metres_signed_f32(const int32_t* field, int64_t n, double voxel, float* out, void* stream);
+int regnet_edt_query_signed_f32(const int32_t* field, const int32_t* nearest, int64_t nx, int64_t ny, int64_t nz,
+                                const float* origin3, double voxel, const float* points, int64_t stride_row, int64_t stride_col,
+                                int64_t M, const float* T12, int interpolate, float* distance, float* gradient,
+                                float* nearest_xyz, void* stream);
+int regnet_grasp_margin_volume_signed_f32(const int32_t* field, int64_t nx, int64_t ny, int64_t nz, const float* origin3,
+                                          double voxel, int outside, const float* L, int64_t B, float x_lo, float x_hi,
+                                          const float* x_hi_per_grasp, float half_thickness, float half_width, float half_space,
+                                          float back_x, float standoff, double step, float x_extent, int32_t* margins,
+                                          int32_t* counts, void* stream);
 int regnet_edt_tile(int64_t n, int with_nearest);
 int regnet_tsdf_edt(const void* volume, int64_t nx, int64_t ny, int64_t nz, double trunc, int64_t min_weight, double margin,
                     int mode, int outside, int32_t* dist2, int32_t* nearest, void* stream);

@@ -56,7 +56,10 @@ class ApproachParams(ParamsBase):
     the hand against it: ``margin_hand`` / ``margin_sweep``, the distance [m] from the hand / the swept hand to the nearest
     obstacle -- solid voxels, and with ``unseen="blocked"`` unobserved voxels and the volume's outside too.  ``min_margin``:
     None, or the least ``margin_hand`` [m] a grasp must have to be selected; it needs ``field``.  (``margin`` above is the SOLID
-    threshold, not this.)"""
+    threshold, not this.)  ``field_signed``: build the field SIGNED (``distance_field(signed=True)``): a hand in collision reads a
+    negative ``margin_hand``, minus the depth of its deepest sample, the record gains ``grasp_colliding``, and ``min_margin``
+    judges the signed value: it may then be negative, e.g. -0.002 lets a hand through that is at most 2 mm inside an obstacle.  ``field_max_distance``: None, or ``distance_field``'s ``max_distance`` [m], the cap that bounds
+    the field's cost; margins saturate there.  Both need ``field``."""
     WORD = "approach"
     source: Optional[str] = None
     standoff: float = 0.10
@@ -73,15 +76,24 @@ class ApproachParams(ParamsBase):
     margin: float = 0.0
     field: bool = False
     min_margin: Optional[float] = None
+    field_signed: bool = False
+    field_max_distance: Optional[float] = None
 
     def __post_init__(self):
+        if (self.field_signed or self.field_max_distance is not None) and not self.field:
+            raise ValueError("approach: field_signed and field_max_distance shape the distance field; set field=True (and "
+                             "space=\"volume\")")
+        if self.field_max_distance is not None and not (float(self.field_max_distance) > 0.0
+                                                        and np.isfinite(self.field_max_distance)):
+            raise ValueError("approach: field_max_distance must be None or positive and finite")
         if self.field and self.space != "volume":
             raise ValueError("approach: field=True builds the distance field of the TSDF volume; use space=\"volume\" with it")
         if self.min_margin is not None:
             if not self.field:
                 raise ValueError("approach: min_margin is judged on the distance field; set field=True (and space=\"volume\")")
-            if not (float(self.min_margin) >= 0.0 and np.isfinite(self.min_margin)):
-                raise ValueError("approach: min_margin must be None or non-negative and finite")
+            if not np.isfinite(self.min_margin) or (float(self.min_margin) < 0.0 and not self.field_signed):
+                raise ValueError("approach: min_margin must be None or non-negative and finite (a signed field, field_signed=True, "
+                                 "also takes a negative one: the penetration that is tolerated)")
         if self.space not in SPACES:
             raise ValueError("approach: space must be one of %s, not %r" % (", ".join(SPACES), self.space))
         if self.unseen not in UNSEEN:

@@ -46,7 +46,8 @@ class VolumeApproach(approach.Approach):
     clearance_seen, clearance_safe) are the kernel's; ``contact_counts`` (B,8) int32 is ``regnet_grasp_approach_f32``'s on the
     surface, or None; ``L`` (B,12) / ``T`` (B,4,4) float32 are the local-to-volume rows the kernel was given and the
     volume-to-local matrices of the contact pass (None without it); ``samples`` = (n_x, n_y, n_z).  With a ``field``:
-    ``margins`` (B,2) int32 and ``margin_counts`` (B,4) int32 are ``regnet_grasp_margin_volume_f32``'s, else None.  ``width``, ``offset``,
+    ``margins`` (B,2) int32 and ``margin_counts`` (B,4) int32 are ``regnet_grasp_margin_volume_f32``'s, else None; with a SIGNED
+    field they are ``regnet_grasp_margin_volume_signed_f32``'s, ``margin_counts`` (B,6).  ``width``, ``offset``,
     ``opening``, ``pregrasp`` and ``passes()`` are ``Approach``'s, on the solid samples and the policy's clearance."""
 
     def __init__(self, counts, values, frame, center, params, half_space, contact_counts, L, T, samples, margins=None,
@@ -66,6 +67,17 @@ class VolumeApproach(approach.Approach):
     def margin_sweep(self):
         """(B) float32 [m]: the same over the whole swept hand, so ``margin_sweep <= margin_hand``; None without a field."""
         return None if self._margin_metres is None else self._margin_metres[1]
+
+    @property
+    def colliding_hand(self):
+        """(B) int32: the hand samples with a negative value of a SIGNED field -- inside an obstacle, or outside a volume whose
+        outside counts as one; None without a signed field.  ``margin_hand`` is then negative: minus the penetration depth."""
+        return self.margin_counts[:, 4] if self.margin_counts is not None and self.margin_counts.shape[1] == 6 else None
+
+    @property
+    def colliding_sweep(self):
+        """(B) int32: the same over the whole swept hand; None without a signed field."""
+        return self.margin_counts[:, 5] if self.margin_counts is not None and self.margin_counts.shape[1] == 6 else None
 
     def passes(self):
         """``Approach.passes()``, and ``margin_hand >= min_margin`` when that is set, compared as float32."""
@@ -139,7 +151,10 @@ def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, sur
 
     ``field``: a ``tsdf.DistanceField`` of the same volume (``volume.distance_field(...)``); the same lattice and ``L`` are then
     also read against it (``regnet_grasp_margin_volume_f32``, one more launch and a conversion to metres) and the result has
-    ``margin_hand`` / ``margin_sweep``.  Nothing else of the result changes."""
+    ``margin_hand`` / ``margin_sweep``.  Nothing else of the result changes.  A SIGNED field (``distance_field(signed=True)``)
+    is read by ``regnet_grasp_margin_volume_signed_f32``: ``margin_hand`` / ``margin_sweep`` are signed metres, a negative value
+    minus the penetration depth of the deepest sample, ``colliding_hand`` / ``colliding_sweep`` count the samples inside an
+    obstacle, and ``min_margin`` judges the signed value."""
     params = approach.ApproachParams.coerce(params) or approach.ApproachParams()
     p = volume.params
     require_cuda("grasp", grasp, torch.float32, 8, at_least=True, error=RuntimeError)
@@ -176,9 +191,10 @@ def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, sur
         if tuple(field.dims) != tuple(p.dims) or field.dist2.device != dev:
             raise ValueError("analyse_volume: the field must be a DistanceField of this volume (same dims, same device)")
         margins = torch.empty((B, 2), dtype=torch.int32, device=dev)
-        margin_counts = torch.empty((B, 4), dtype=torch.int32, device=dev)
-        _lib.call("regnet_grasp_margin_volume_f32", field.dist2, field.dist2.data_ptr(), nx, ny, nz, volume.origin.ctypes.data,
-                  float(p.voxel), int(field.outside), L.data_ptr(), B, *box, float(params.standoff), step, x_extent,
+        signed = field.signed
+        margin_counts = torch.empty((B, 6 if signed else 4), dtype=torch.int32, device=dev)
+        entry = "regnet_grasp_margin_volume_signed_f32" if signed else "regnet_grasp_margin_volume_f32"
+        _lib.call(entry, field.dist2, field.dist2.data_ptr(), nx, ny, nz, volume.origin.ctypes.data, float(p.voxel), int(field.outside), L.data_ptr(), B, *box, float(params.standoff), step, x_extent,
                   margins.data_ptr(), margin_counts.data_ptr())
         margin_metres = field.metres(margins.t().contiguous())      # (2,B): row 0 the hand, row 1 the sweep
     contact_counts = T = None

@@ -42,7 +42,10 @@ command, the contact check and the pre-grasp point; the record additionally carr
 and with ``min_clearance`` / ``min_contact`` the selection sees only the rows that pass.  Without it nothing changes.
 With ``space="volume"`` (``--approach-space``, ``--approach-unseen``, ``--approach-step``, ``--approach-margin``) the hand is held against the TSDF volume instead (``approach.analyse_volume``): ``APPROACH_VOLUME_KEYS`` follow.
 With ``field=True`` (``--approach-field``, ``--min-margin``) the volume's distance field is built once per frame
-(``tsdf.Volume.distance_field``) and ``APPROACH_FIELD_KEYS`` follow those: how much room the hand has.
+(``tsdf.Volume.distance_field``) and ``APPROACH_FIELD_KEYS`` follow those: how much room the hand has.  With
+``field_signed=True`` (``--approach-signed``) the field is signed -- a margin below zero is minus a penetration depth -- and
+``grasp_colliding`` (B,2) int32, the hand's and the swept hand's samples inside an obstacle, follows; ``field_max_distance``
+(``--approach-field-cap``) caps the field's distances, which bounds its cost.
 
 With ``denoise`` (``--denoise``, ``--outlier-mode``, ``--outlier-radius``, ``--outlier-min-neighbours``, ``--outlier-knn``,
 ``--outlier-max-radius``, ``--outlier-std-ratio``) the cloud of a camera frame -- an ``(xyz, rgb)`` pair, a depth frame's or a
@@ -101,6 +104,7 @@ APPROACH_KEYS = ("grasp_clearance", "grasp_width", "grasp_offset", "grasp_openin
 APPROACH_VOLUME_KEYS = ("grasp_clearance_seen", "grasp_clearance_safe", "grasp_unseen",
                         "grasp_solid_hand")                    # ... right after them when its ``space`` is "volume"
 APPROACH_FIELD_KEYS = ("grasp_margin_hand", "grasp_margin_sweep")   # ... and right after those when it has ``field``
+APPROACH_SIGNED_KEYS = ("grasp_colliding",)   # ... and after those when the field is signed: (B,2) int32, hand and sweep
 TSDF_KEYS = ("tsdf_num", "tsdf_counts")                        # added when the frame was a ``MultiView`` and the detector has ``volume``
 TRACK_KEYS = ("track_pose", "track_status", "track_report")    # added beside ``TSDF_KEYS`` when the detector has ``track``
 TSDF_MESH_KEYS = ("tsdf_triangles", "tsdf_vertices", "tsdf_vertex_normals",
@@ -430,7 +434,7 @@ class GraspDetector:
             blocked = self.approach.unseen == "blocked"
             field = self.distance_field = self.tsdf_volume.distance_field(
                 mode="solid_or_unseen" if blocked else "solid", outside=blocked, margin=self.approach.margin,
-                out=self.distance_field)
+                out=self.distance_field, signed=self.approach.field_signed, max_distance=self.approach.field_max_distance)
         result = approach_mod.analyse_volume(self.tsdf_volume, sets[self.approach_source][:, :8], depth, width, self.approach,
                                              to_volume=to_volume, surface=self.fused, field=field)
         extra = dict(zip(APPROACH_KEYS + APPROACH_VOLUME_KEYS,
@@ -438,6 +442,8 @@ class GraspDetector:
                           result.clearance_seen, result.clearance_safe, result.unseen_share, result.solid_hand)))
         if field is not None:
             extra.update(zip(APPROACH_FIELD_KEYS, (result.margin_hand, result.margin_sweep)))
+            if field.signed:
+                extra[APPROACH_SIGNED_KEYS[0]] = result.margin_counts[:, 4:6]
         passing = result.passes().nonzero().view(-1) if self.approach.filters() else None
         return extra, passing
 
@@ -622,6 +628,8 @@ _FLAGS = (
      "in volume space: a voxel nearer than this (%s m) to a surface is solid"),
     ("--min-margin", "approach", "min_margin", float,
      "select only grasps whose hand keeps this distance [m] to the nearest obstacle of the volume (implies --approach-field)"),
+    ("--approach-field-cap", "approach", "field_max_distance", float,
+     "cap the distance field at this distance [m]: margins saturate there and the field costs less (implies --approach-field)"),
     # a TSDF volume in place of the point merge (tsdf.fuse_volume): --tsdf or any of the five turns it on
     ("--tsdf-voxel", "volume", "voxel", float, "edge of the voxels of the volume (%s m)"),
     ("--tsdf-trunc", "volume", "trunc", float, "truncation distance, at least two voxels (%s m)"),
@@ -694,9 +702,11 @@ def register_from_args(args):
 
 
 def approach_from_args(args):
-    """The CLI's twelve approach flags -> an ``approach`` dict, or None when none of them was given."""
+    """The CLI's fourteen approach flags -> an ``approach`` dict, or None when none of them was given."""
     given = _given(args, "approach")
-    if args.approach_field or "min_margin" in given:
+    if args.approach_signed:
+        given["field_signed"] = True
+    if args.approach_field or args.approach_signed or "min_margin" in given or "field_max_distance" in given:
         given["field"] = True
     return given if (given or args.approach) else None
 
@@ -779,6 +789,9 @@ def build_parser():
     parser.add_argument("--approach-field", action="store_true",
                         help="in volume space: build the volume's distance field once per frame and add every grasp's margin, the "
                              "distance from the hand and from the swept hand to the nearest obstacle")
+    parser.add_argument("--approach-signed", action="store_true",
+                        help="build that field signed: a hand in collision reads a negative margin, minus its penetration "
+                             "depth, and the record gains grasp_colliding (implies --approach-field)")
     parser.add_argument("--denoise", action="store_true",
                         help="remove the outliers of a camera frame's cloud before the table plane and the crop")
     regular("outliers")

@@ -637,47 +637,87 @@ class Volume:
         return ModelView(xyz, normals, rgb, status, counts, width, height, k, T)
 
 
-    def distance_field(self, mode="solid", outside=None, margin=0.0, nearest=False, min_weight=None, stream=None, out=None):
+    def distance_field(self, mode="solid", outside=None, margin=0.0, nearest=False, min_weight=None, stream=None, out=None,
+                       signed=False, max_distance=None):
         """The exact Euclidean distance field of the volume as it stands -> ``DistanceField``: per voxel the squared distance, in
         voxels, to the nearest obstacle voxel (csrc/edt.hip).  ``mode``: ``"solid"`` -- the obstacles are the voxels seen solid,
         ``D < margin / trunc`` -- or ``"solid_or_unseen"``: those and the voxels observed fewer than ``min_weight`` (None: the
         volume's) times.  ``outside``: whether everything beyond the volume's six faces is an obstacle too; None: exactly with
         ``"solid_or_unseen"``.  ``nearest``: also keep, per voxel, which obstacle voxel that is.  ``out``: a ``DistanceField`` of
         this volume's dims whose buffers are written instead of new ones (4, with ``nearest`` 8 bytes per voxel).  Three
-        launches, no host read."""
+        launches, no host read.
+
+        ``signed``: a SIGNED field (``regnet_tsdf_sdf``): an obstacle voxel holds minus its squared distance to the nearest
+        non-obstacle voxel (and ``nearest`` the way out), every other voxel the distance above, now >= 1; 0 does not occur.  It
+        takes a second transform over the complement (six launches) and a workspace as large as the field, kept on the result.
+        ``max_distance`` (metres, > 0): a cap -- distances saturate at ``cap`` voxels, the smallest integer
+        ``>= max_distance / voxel`` (1..1023), and no line search goes further than that: what bounds the cost wherever a
+        plane holds no obstacle.  An ``out`` field must have been built ``signed`` to be reused for a signed one."""
         import torch
         p = self.params
         if mode not in FIELD_MODES:
             raise ValueError("distance_field: mode must be one of %s, not %r" % (", ".join(FIELD_MODES), mode))
         outside = (mode == "solid_or_unseen") if outside is None else bool(outside)
         min_weight = int(p.min_weight if min_weight is None else min_weight)
+        signed = bool(signed)
+        cap = field_cap(max_distance, p.voxel)
         nx, ny, nz = p.dims
         n = nx * ny * nz
         dev = self.device
         with torch.cuda.device(dev), stream_scope(stream):
+            work = None
             if out is None:
                 dist2 = torch.empty((n,), dtype=torch.int32, device=dev)
                 near = torch.empty((n,), dtype=torch.int32, device=dev) if nearest else None
+                if signed:
+                    work = torch.empty((n * (2 if nearest else 1),), dtype=torch.int32, device=dev)
             else:
                 if not isinstance(out, DistanceField) or out.dims != p.dims or out.dist2.device != dev:
                     raise ValueError("distance_field: out must be a DistanceField of this volume's dims on its device")
                 if nearest and out.nearest is None:
                     raise ValueError("distance_field: out has no nearest plane")
                 dist2, near = out.dist2, (out.nearest if nearest else None)
-            _lib.call("regnet_tsdf_edt", self.data, self.data.data_ptr(), nx, ny, nz, float(p.trunc), min_weight, float(margin),
-                      FIELD_MODES.index(mode), int(outside), dist2.data_ptr(), None if near is None else near.data_ptr(),
-                      stream=None if stream is None else stream.cuda_stream)
-            record_streams(stream, self.data, dist2, near)
+                if signed:
+                    work = out.work
+                    if work is None or work.numel() < n * (2 if nearest else 1):
+                        raise ValueError("distance_field: out holds no workspace for a signed field%s; build it with signed=True"
+                                         % (" with nearest" if nearest else ""))
+            if signed or cap:
+                _lib.call("regnet_tsdf_sdf", self.data, self.data.data_ptr(), nx, ny, nz, float(p.trunc), min_weight,
+                          float(margin), FIELD_MODES.index(mode), int(outside), int(signed), cap, dist2.data_ptr(),
+                          None if near is None else near.data_ptr(), None if work is None else work.data_ptr(),
+                          stream=None if stream is None else stream.cuda_stream)
+            else:
+                _lib.call("regnet_tsdf_edt", self.data, self.data.data_ptr(), nx, ny, nz, float(p.trunc), min_weight,
+                          float(margin), FIELD_MODES.index(mode), int(outside), dist2.data_ptr(),
+                          None if near is None else near.data_ptr(), stream=None if stream is None else stream.cuda_stream)
+            record_streams(stream, self.data, dist2, near, work)
         if out is not None:
             out.mode, out.outside, out.origin, out.voxel = mode, outside, self.origin, float(p.voxel)
             out.has_nearest = nearest
+            out.signed, out.cap = signed, cap
             return out
-        return DistanceField(dist2, near, p.dims, self.origin, float(p.voxel), mode, outside)
+        return DistanceField(dist2, near, p.dims, self.origin, float(p.voxel), mode, outside, signed=signed, cap=cap, work=work)
 
 
 FIELD_MODES = ("solid", "solid_or_unseen")      # regnet_tsdf_edt's mode 0 and 1
 EDT_NONE = 1 << 30                  # REGNET_EDT_NONE: the squared distance where there is no obstacle at all
 MAX_FIELD_DIM = 1024                # regnet_tsdf_edt's documented limit on every dim
+MAX_FIELD_CAP = 1023                # regnet_tsdf_sdf's largest cap, in voxels
+
+
+def field_cap(max_distance, voxel):
+    """``max_distance`` in metres -> the cap of ``regnet_tsdf_sdf`` in voxels: 0 for None, else the smallest integer
+    ``>= max_distance / voxel`` (float64), which must lie in 1..1023."""
+    if max_distance is None:
+        return 0
+    d = float(max_distance)
+    if not (d > 0.0 and np.isfinite(d)):
+        raise ValueError("distance_field: max_distance must be positive and finite, not %r" % (max_distance,))
+    cap = int(np.ceil(d / float(voxel)))
+    if not 1 <= cap <= MAX_FIELD_CAP:
+        raise ValueError("distance_field: max_distance = %g m is %d voxels; the cap must lie in 1..%d" % (d, cap, MAX_FIELD_CAP))
+    return cap
 
 
 class DistanceField:
@@ -685,24 +725,48 @@ class DistanceField:
     distance in voxels (between voxel centres) to the nearest obstacle voxel, 0 on an obstacle, ``EDT_NONE`` = 2^30 when there is
     none; ``nearest`` (N) int32 or None: that obstacle's linear index -- of several at the same distance the smallest --, -1
     where there is none or the outside of the volume is strictly nearer.  ``dims``, ``origin`` (3 float32, host) and ``voxel`` are
-    the volume's; ``mode`` and ``outside`` say what counted as an obstacle.  Unsigned: 0 everywhere inside an obstacle."""
+    the volume's; ``mode`` and ``outside`` say what counted as an obstacle.  Unsigned by default: 0 everywhere inside an obstacle.
 
-    def __init__(self, dist2, nearest, dims, origin, voxel, mode, outside):
+    ``signed``: ``dist2`` holds signed words instead -- minus the squared distance to the nearest NON-obstacle voxel on an obstacle
+    voxel (``nearest``: that voxel, the way out), never 0, ``-EDT_NONE`` when no voxel is free.  ``cap``: 0, or the voxels at which
+    the distances saturate (``cap * cap`` in ``dist2``, ``nearest`` -1 strictly beyond).  ``work``: the device workspace of the
+    signed transform, kept for ``out=`` reuse (None for an unsigned field)."""
+
+    def __init__(self, dist2, nearest, dims, origin, voxel, mode, outside, signed=False, cap=0, work=None):
         self.dist2, self.nearest, self.dims, self.origin, self.voxel = dist2, nearest, tuple(dims), origin, float(voxel)
         self.mode, self.outside = mode, bool(outside)
+        self.signed, self.cap, self.work = bool(signed), int(cap), work
         self.has_nearest = nearest is not None      # (a reused field may hold a nearest plane its last call did not write)
 
     def bytes(self):
-        """Bytes of the field on the device: 4 per voxel, 8 with ``nearest``."""
-        return int(self.dist2.numel()) * 4 * (1 if self.nearest is None else 2)
+        """Bytes of the field on the device: 4 per voxel, 8 with ``nearest``, and the signed transform's workspace it keeps."""
+        planes = int(self.dist2.numel()) * 4 * (1 if self.nearest is None else 2)
+        return planes + (0 if self.work is None else int(self.work.numel()) * 4)
 
-    def query(self, points, to_volume=None, nearest=False, stream=None):
+    def query(self, points, to_volume=None, nearest=False, stream=None, interpolate=False, gradient=False,
+              gradient_frame="volume"):
         """``points`` (M,3) float32 on the field's device, any strides; ``to_volume``: the 4x4 that takes them into the volume's
         frame (None: identity; its rows 0..2 are rounded to float32 once).  -> ``distance`` (M) float32, metres to the nearest
         obstacle voxel's centre from the centre of the voxel the point lies in: ``+inf`` when there is no obstacle, NaN for a point
         outside the volume or not finite.  With ``nearest`` -> ``(distance, nearest_xyz)``, (M,3) float32: that obstacle voxel's
-        centre in the volume's frame, NaN where there is none.  One launch, no host read."""
+        centre in the volume's frame, NaN where there is none.  One launch, no host read.
+
+        A SIGNED field answers through ``regnet_edt_query_signed_f32``: ``distance`` is the signed distance in metres to the
+        boundary FACE between obstacle and free voxels (``(sqrt|s| - 0.5) voxel`` with the sign of the word), negative inside an
+        obstacle.  ``interpolate``: trilinear between the eight voxel centres around the point instead of the nearest voxel's
+        value (clamped in the outer half-voxel rim); an uncapped field has infinite words wherever a side is empty, and an
+        interpolant that meets one is infinite or NaN, so build the field with ``max_distance`` for interpolated use.
+        ``gradient`` (needs ``interpolate``): also return the (M,3) analytic derivative of the interpolant, dimensionless, of
+        length 1 across a flat wall, pointing out of the obstacle; ``gradient_frame="volume"`` (bit-pinned) or ``"points"``:
+        rotated into the points' frame by the transpose of ``to_volume``'s 3x3 with a torch product, which is NOT bit-pinned.
+        The result is ``distance``, then ``gradient``, then ``nearest_xyz``, as many as were asked for."""
         import torch
+        if gradient_frame not in ("volume", "points"):
+            raise ValueError("query: gradient_frame must be \"volume\" or \"points\", not %r" % (gradient_frame,))
+        if (interpolate or gradient) and not self.signed:
+            raise ValueError("query: interpolate and gradient read a signed field; build it with signed=True")
+        if gradient and not interpolate:
+            raise ValueError("query: the gradient is the interpolant's; give interpolate=True with it")
         points = require_cuda("points", points, torch.float32, 3, error=TypeError)
         dev = self.dist2.device
         if points.device != dev:
@@ -717,24 +781,38 @@ class DistanceField:
         with torch.cuda.device(dev), stream_scope(stream):
             distance = torch.empty((m,), dtype=torch.float32, device=dev)
             xyz = torch.empty((m, 3), dtype=torch.float32, device=dev) if nearest else None
-            _lib.call("regnet_edt_query_f32", self.dist2, self.dist2.data_ptr(),
-                      self.nearest.data_ptr() if self.has_nearest else None, nx, ny, nz, self.origin.ctypes.data, self.voxel,
-                      points.data_ptr(), points.stride(0), points.stride(1), m, rows.ctypes.data, distance.data_ptr(),
-                      None if xyz is None else xyz.data_ptr(), stream=None if stream is None else stream.cuda_stream)
-            record_streams(stream, points, self.dist2, self.nearest, distance, xyz)
-        return (distance, xyz) if nearest else distance
+            grad = torch.empty((m, 3), dtype=torch.float32, device=dev) if gradient else None
+            if self.signed:
+                _lib.call("regnet_edt_query_signed_f32", self.dist2, self.dist2.data_ptr(),
+                          self.nearest.data_ptr() if self.has_nearest else None, nx, ny, nz, self.origin.ctypes.data, self.voxel,
+                          points.data_ptr(), points.stride(0), points.stride(1), m, rows.ctypes.data, int(bool(interpolate)),
+                          distance.data_ptr(), None if grad is None else grad.data_ptr(),
+                          None if xyz is None else xyz.data_ptr(), stream=None if stream is None else stream.cuda_stream)
+                if grad is not None and gradient_frame == "points":
+                    grad = grad @ torch.from_numpy(rows.reshape(3, 4)[:, :3].copy()).to(dev)   # row g R = (R^T g)^T
+            else:
+                _lib.call("regnet_edt_query_f32", self.dist2, self.dist2.data_ptr(),
+                          self.nearest.data_ptr() if self.has_nearest else None, nx, ny, nz, self.origin.ctypes.data, self.voxel,
+                          points.data_ptr(), points.stride(0), points.stride(1), m, rows.ctypes.data, distance.data_ptr(),
+                          None if xyz is None else xyz.data_ptr(), stream=None if stream is None else stream.cuda_stream)
+            record_streams(stream, points, self.dist2, self.nearest, distance, xyz, grad)
+        result = (distance,) + ((grad,) if gradient else ()) + ((xyz,) if nearest else ())
+        return result if len(result) > 1 else distance
 
     def metres(self, dist2=None, stream=None):
         """The whole field as (N) float32 metres, by the query's two operations -- ``sqrtf((float)dist2) * float32(voxel)``,
         ``+inf`` for ``EDT_NONE`` --: a dense grid to hand to a planner; ``view(nz, ny, nx)`` is its lattice.  ``dist2``: any
-        contiguous int32 device tensor of squared distances to convert instead (a grasp's margins)."""
+        contiguous int32 device tensor of squared distances to convert instead (a grasp's margins).  A signed field converts
+        signed words: ``(sqrt|s| - 0.5) voxel`` with the sign of ``s``, the distance to the boundary face, ``-inf`` / ``+inf`` for
+        ``-EDT_NONE`` / ``EDT_NONE``."""
         import torch
         source = self.dist2 if dist2 is None else dist2
         if not (source.is_cuda and source.dtype == torch.int32 and source.is_contiguous()):
             raise TypeError("metres: dist2 must be a contiguous int32 device tensor")
         with torch.cuda.device(source.device), stream_scope(stream):
             out = torch.empty(source.shape, dtype=torch.float32, device=source.device)
-            _lib.call("regnet_edt_metres_f32", source, source.data_ptr(), int(source.numel()), self.voxel, out.data_ptr(),
+            _lib.call("regnet_edt_metres_signed_f32" if self.signed else "regnet_edt_metres_f32", source, source.data_ptr(),
+                      int(source.numel()), self.voxel, out.data_ptr(),
                       stream=None if stream is None else stream.cuda_stream)
             record_streams(stream, source, out)
         return out
