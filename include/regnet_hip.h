@@ -1720,6 +1720,23 @@ int regnet_scatter_plan(const int64_t* index, int64_t B, int64_t num_dest, int64
 int regnet_scatter_segsum_f32(const float* grad_out, int64_t sb, int64_t sc, int64_t s_hi, int64_t s_lo, int64_t inner,
                               const float* weight, int64_t B, int64_t C, int64_t num_dest, int64_t num_src, const void* plan,
                               float* grad_in, void* stream);
+/* regnet_scatter_segsum_route / regnet_scatter_atomic_route: HOST code, no device and no stream -- which kernel the backwards of
+ * group_points / gather_knn / interpolate take for B scenes, C channels, num_dest destinations and num_src sources per scene
+ * (the launchers call the same functions).  route is host memory.
+ *   regnet_scatter_segsum_route: the segment sums of regnet_scatter_segsum_f32 (elem_size 4) and of the float64 backwards
+ *     (elem_size 8); weighted != 0 for interpolate (num_src = N * 3).  route (3 int64):
+ *       [0] 1 segsum_lds_kernel with every source slot staged at once, 2 segsum_lds_kernel over several chunks of slots,
+ *           3 segsum_global_kernel, 0 no segment-sum kernel (an empty size, or unsupported);
+ *       [1] channels per workgroup (1, 2) or per thread (3);  [2] slots per chunk (1, 2), 0 for the global kernel.
+ *   regnet_scatter_atomic_route: the default float32 backwards (regnet_group_points_bwd_f32, regnet_gather_knn_bwd_f32:
+ *     num_src = N2 * K; regnet_interpolate_bwd_f32: num_src = N).  route (2 int64):
+ *       [0] 1 scatter_add_lds_kernel (LDS atomics), 2 zero fill + the global-atomic kernel, 0 no kernel (num_src == 0: zero
+ *           fill alone; or unsupported);   [1] channels per workgroup.
+ * Return REGNET_OK, or REGNET_ERR_UNSUPPORTED exactly where the launcher returns it for these sizes (route zeroed),
+ * REGNET_ERR_SHAPE (negative size, elem_size not 4 or 8, weighted with num_src % 3 != 0), REGNET_ERR_NULL (route == NULL).  */
+int regnet_scatter_segsum_route(int elem_size, int weighted, int64_t B, int64_t C, int64_t num_dest, int64_t num_src,
+                                int64_t* route);
+int regnet_scatter_atomic_route(int64_t B, int64_t C, int64_t num_dest, int64_t num_src, int64_t* route);
 int regnet_scatter_max_grad_det_f32(const float* dy, const int64_t* arg, int64_t R, int64_t F, int64_t scene_rows,
                                     int64_t batch_stride, int64_t row_stride, int64_t ch_stride, float* grad, void* stream);
 int64_t regnet_bn_det_workspace_bytes(int64_t B, int64_t C, int64_t L);

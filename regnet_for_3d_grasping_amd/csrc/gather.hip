@@ -54,15 +54,17 @@ __global__ __launch_bounds__(GT) void interp_fwd_kernel(const float* __restrict_
   const int64_t o = ((int64_t)b * N + n) * 3;
   const int64_t j0 = index[o], j1 = index[o + 1], j2 = index[o + 2];
   const float w0 = weight[o], w1 = weight[o + 1], w2 = weight[o + 2];
+  // the reference asserts; an index outside [0, M) reads as 0 (compared as int64, before any narrowing)
+  const bool ok0 = j0 >= 0 && j0 < M, ok1 = j1 >= 0 && j1 < M, ok2 = j2 >= 0 && j2 < M;
   const int cbeg = blockIdx.y * CH_PER_BLOCK, cend = min(C, cbeg + CH_PER_BLOCK);
   const float* src = in + (int64_t)b * sb;
   float* dst = out + ((int64_t)b * C) * N + n;
   for (int c = cbeg; c < cend; ++c) {
     const float* s = src + (int64_t)c * sc;
     float acc = 0.f;  // accumulate from 0 in k order (interpolate_kernel.cu:165-170)
-    acc += s[j0 * sm] * w0;
-    acc += s[j1 * sm] * w1;
-    acc += s[j2 * sm] * w2;
+    acc += (ok0 ? s[j0 * sm] : 0.f) * w0;
+    acc += (ok1 ? s[j1 * sm] : 0.f) * w1;
+    acc += (ok2 ? s[j2 * sm] : 0.f) * w2;
     dst[(int64_t)c * N] = acc;
   }
 }
@@ -77,15 +79,17 @@ __global__ __launch_bounds__(GT) void interp_bwd_kernel(const float* __restrict_
   const int64_t o = ((int64_t)b * N + n) * 3;
   const int64_t j0 = index[o], j1 = index[o + 1], j2 = index[o + 2];
   const float w0 = weight[o], w1 = weight[o + 1], w2 = weight[o + 2];
+  // a term whose index is outside [0, M) is skipped, as in group_bwd_kernel
+  const bool ok0 = j0 >= 0 && j0 < M, ok1 = j1 >= 0 && j1 < M, ok2 = j2 >= 0 && j2 < M;
   const int cbeg = blockIdx.y * CH_PER_BLOCK, cend = min(C, cbeg + CH_PER_BLOCK);
   const float* src = go + (int64_t)b * sb + (int64_t)n * sn;
   float* dst = gi + ((int64_t)b * C) * M;
   for (int c = cbeg; c < cend; ++c) {
     const float g = src[(int64_t)c * sc];
     float* d = dst + (int64_t)c * M;
-    atomicAdd(d + j0, g * w0);
-    atomicAdd(d + j1, g * w1);
-    atomicAdd(d + j2, g * w2);
+    if (ok0) atomicAdd(d + j0, g * w0);
+    if (ok1) atomicAdd(d + j1, g * w1);
+    if (ok2) atomicAdd(d + j2, g * w2);
   }
 }
 
@@ -135,14 +139,49 @@ __global__ __launch_bounds__(SCAT_T) void scatter_add_lds_kernel(const float* __
   for (int i = threadIdx.x; i < nc * R; i += SCAT_T) dst[i] = acc[i];
 }
 
+static inline bool dims_ok(int64_t B, int64_t C) { return B <= 65535 && (C + CH_PER_BLOCK - 1) / CH_PER_BLOCK <= 65535; }
+
+// Which kernel the default float32 backwards take for B scenes, C channels, R destinations and L source elements per scene
+// (group / gather_knn: N2 * K; interpolate: N), and the channels per workgroup of it: the one place that decides, behind the two
+// launchers below and regnet_scatter_atomic_route.  (The launchers' own limits on N2, K and N are not part of it.)
+#define SCAT_ROUTE_NONE 0     // L == 0: zero fill alone; or no kernel takes the sizes (the status says which)
+#define SCAT_ROUTE_LDS 1      // scatter_add_lds_kernel
+#define SCAT_ROUTE_GLOBAL 2   // zero fill + group_bwd_kernel / interp_bwd_kernel
+static int scatter_atomic_route(int64_t B, int64_t C, int64_t R, int64_t L, int* kind, int* cpb_out) {
+  *kind = SCAT_ROUTE_NONE;
+  *cpb_out = 0;
+  if (L == 0) return REGNET_OK;
+  if (R <= SCAT_LDS_FLOATS && B <= 65535 && C < (int64_t)1 << 31) {
+    int cpb = (int)(SCAT_LDS_FLOATS / R);
+    if (cpb > 32) cpb = 32;
+    // enough workgroups to fill the chip when there are many channels
+    while (cpb > 1 && B * ((C + cpb - 1) / cpb) < 512) cpb = (cpb + 1) / 2;
+    *kind = SCAT_ROUTE_LDS;
+    *cpb_out = cpb;
+    return REGNET_OK;
+  }
+  if (!dims_ok(B, C) || R >= (int64_t)1 << 31) return REGNET_ERR_UNSUPPORTED;
+  *kind = SCAT_ROUTE_GLOBAL;
+  *cpb_out = CH_PER_BLOCK;
+  return REGNET_OK;
+}
+
+extern "C" int regnet_scatter_atomic_route(int64_t B, int64_t C, int64_t num_dest, int64_t num_src, int64_t* route) {
+  if (!route) return REGNET_ERR_NULL;
+  route[0] = route[1] = 0;
+  if (B < 0 || C < 0 || num_dest < 0 || num_src < 0) return REGNET_ERR_SHAPE;
+  if (B == 0 || C == 0 || num_dest == 0) return REGNET_OK;
+  int kind = 0, cpb = 0;
+  const int rc = scatter_atomic_route(B, C, num_dest, num_src, &kind, &cpb);
+  route[0] = kind;
+  route[1] = cpb;
+  return rc;
+}
+
 template <int KK>
 static int launch_scatter_lds(const float* go, int64_t sb, int64_t sc, int64_t s_hi, int64_t s_lo, int64_t inner,
                               const int64_t* index, const float* weight, int64_t B, int64_t C, int64_t R, int64_t L,
-                              float* gi, hipStream_t st) {
-  int cpb = (int)(SCAT_LDS_FLOATS / R);
-  if (cpb > 32) cpb = 32;
-  // enough workgroups to fill the chip when there are many channels
-  while (cpb > 1 && B * ((C + cpb - 1) / cpb) < 512) cpb = (cpb + 1) / 2;
+                              int cpb, float* gi, hipStream_t st) {
   const size_t lds = (size_t)cpb * R * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
@@ -157,8 +196,6 @@ static int launch_scatter_lds(const float* go, int64_t sb, int64_t sc, int64_t s
   REGNET_LAUNCH_CHECK();
   return REGNET_OK;
 }
-
-static inline bool dims_ok(int64_t B, int64_t C) { return B <= 65535 && (C + CH_PER_BLOCK - 1) / CH_PER_BLOCK <= 65535; }
 
 extern "C" int regnet_group_points_fwd_f32(const float* input, int64_t sb, int64_t sc, int64_t sn,
                                            const int64_t* index, int64_t B, int64_t C, int64_t N1, int64_t N2,
@@ -182,15 +219,17 @@ extern "C" int regnet_group_points_bwd_f32(const float* grad_out, int64_t sb, in
   if (B == 0 || C == 0 || N1 == 0) return REGNET_OK;
   if (!grad_in) return REGNET_ERR_NULL;
   const int64_t NK = N2 * K;
-  if (NK > 0 && N1 <= SCAT_LDS_FLOATS && B <= 65535 && C < (int64_t)1 << 31 && K < (int64_t)1 << 31) {
+  int kind = 0, cpb = 0;
+  scatter_atomic_route(B, C, N1, NK, &kind, &cpb);
+  if (kind == SCAT_ROUTE_LDS && K < (int64_t)1 << 31) {
     if (!grad_out || !index) return REGNET_ERR_NULL;
-    return launch_scatter_lds<1>(grad_out, sb, sc, sn2, sk, K, index, nullptr, B, C, N1, NK, grad_in, as_stream(stream));
+    return launch_scatter_lds<1>(grad_out, sb, sc, sn2, sk, K, index, nullptr, B, C, N1, NK, cpb, grad_in,
+                                 as_stream(stream));
   }
   hipError_t e = hipMemsetAsync(grad_in, 0, sizeof(float) * (size_t)(B * C * N1), as_stream(stream));
   if (e != hipSuccess) return (int)e;
   if (NK == 0) return REGNET_OK;
-  if (!dims_ok(B, C) || N1 >= (int64_t)1 << 31 || N2 >= (int64_t)1 << 31 || K >= (int64_t)1 << 31)
-    return REGNET_ERR_UNSUPPORTED;
+  if (kind != SCAT_ROUTE_GLOBAL || N2 >= (int64_t)1 << 31 || K >= (int64_t)1 << 31) return REGNET_ERR_UNSUPPORTED;
   if (!grad_out || !index) return REGNET_ERR_NULL;
   dim3 grid((unsigned)((NK + GT - 1) / GT), (unsigned)((C + CH_PER_BLOCK - 1) / CH_PER_BLOCK), (unsigned)B);
   hipLaunchKernelGGL(group_bwd_kernel, grid, dim3(GT), 0, as_stream(stream), grad_out, sb, sc, sn2, sk, index, (int)C,
@@ -220,14 +259,16 @@ extern "C" int regnet_interpolate_bwd_f32(const float* grad_out, int64_t sb, int
   if (B < 0 || C < 0 || M < 0 || N < 0) return REGNET_ERR_SHAPE;
   if (B == 0 || C == 0 || M == 0) return REGNET_OK;
   if (!grad_in) return REGNET_ERR_NULL;
-  if (N > 0 && M <= SCAT_LDS_FLOATS && B <= 65535 && C < (int64_t)1 << 31) {
+  int kind = 0, cpb = 0;
+  scatter_atomic_route(B, C, M, N, &kind, &cpb);
+  if (kind == SCAT_ROUTE_LDS) {
     if (!grad_out || !index || !weight) return REGNET_ERR_NULL;
-    return launch_scatter_lds<3>(grad_out, sb, sc, sn, 0, 1, index, weight, B, C, M, N, grad_in, as_stream(stream));
+    return launch_scatter_lds<3>(grad_out, sb, sc, sn, 0, 1, index, weight, B, C, M, N, cpb, grad_in, as_stream(stream));
   }
   hipError_t e = hipMemsetAsync(grad_in, 0, sizeof(float) * (size_t)(B * C * M), as_stream(stream));
   if (e != hipSuccess) return (int)e;
   if (N == 0) return REGNET_OK;
-  if (!dims_ok(B, C) || N >= (int64_t)1 << 31 || M >= (int64_t)1 << 31) return REGNET_ERR_UNSUPPORTED;
+  if (kind != SCAT_ROUTE_GLOBAL || N >= (int64_t)1 << 31) return REGNET_ERR_UNSUPPORTED;
   if (!grad_out || !index || !weight) return REGNET_ERR_NULL;
   dim3 grid((unsigned)((N + GT - 1) / GT), (unsigned)((C + CH_PER_BLOCK - 1) / CH_PER_BLOCK), (unsigned)B);
   hipLaunchKernelGGL(interp_bwd_kernel, grid, dim3(GT), 0, as_stream(stream), grad_out, sb, sc, sn, index, weight,

@@ -332,14 +332,59 @@ static bool lds_layout(int64_t B, int64_t C, int64_t R, int64_t NS, int* cpb_out
   return true;
 }
 
+// Which segment-sum kernel takes B scenes, C channels, R destinations and L sources per scene (weighted: L / 3 slots), with
+// its channels per workgroup (LDS kernel) or per thread (global kernel) and its slots per chunk: the one place that decides,
+// behind segsum() and regnet_scatter_segsum_route.
+#define SEG_ROUTE_NONE 0         // no kernel takes the sizes (REGNET_ERR_UNSUPPORTED)
+#define SEG_ROUTE_ONE_CHUNK 1    // segsum_lds_kernel, every slot staged at once, state in registers
+#define SEG_ROUTE_CHUNKS 2       // segsum_lds_kernel, several chunks, one channel, state in LDS
+#define SEG_ROUTE_GLOBAL 3       // segsum_global_kernel
+template <typename T>
+static int segsum_route(bool weighted, int64_t B, int64_t C, int64_t R, int64_t L, int* kind, int* cpb_out,
+                        int* chunk_out) {
+  *kind = SEG_ROUTE_NONE;
+  *cpb_out = *chunk_out = 0;
+  if (!scatter_plan_dims_ok(B, R, L)) return REGNET_ERR_UNSUPPORTED;
+  const int64_t NS = weighted ? L / 3 : L;
+  int cpb = 0, chunk = 0;
+  if (lds_layout<T>(B, C, R, NS, &cpb, &chunk) && (C + cpb - 1) / cpb <= 65535) {
+    *kind = NS > chunk ? SEG_ROUTE_CHUNKS : SEG_ROUTE_ONE_CHUNK;
+    *cpb_out = cpb;
+    *chunk_out = chunk;
+    return REGNET_OK;
+  }
+  if (!seg_g_channels_ok<T>(C) || (R + SEG_G_T - 1) / SEG_G_T >= ((int64_t)1 << 31)) return REGNET_ERR_UNSUPPORTED;
+  *kind = SEG_ROUTE_GLOBAL;
+  *cpb_out = seg_g_ch<T>;
+  return REGNET_OK;
+}
+
+extern "C" int regnet_scatter_segsum_route(int elem_size, int weighted, int64_t B, int64_t C, int64_t num_dest,
+                                           int64_t num_src, int64_t* route) {
+  if (!route) return REGNET_ERR_NULL;
+  route[0] = route[1] = route[2] = 0;
+  if ((elem_size != 4 && elem_size != 8) || B < 0 || C < 0 || num_dest < 0 || num_src < 0 || (weighted && num_src % 3))
+    return REGNET_ERR_SHAPE;
+  if (B == 0 || C == 0 || num_dest == 0 || num_src == 0) return REGNET_OK;
+  int kind = 0, cpb = 0, chunk = 0;
+  const int rc = elem_size == 4 ? segsum_route<float>(weighted != 0, B, C, num_dest, num_src, &kind, &cpb, &chunk)
+                                : segsum_route<double>(weighted != 0, B, C, num_dest, num_src, &kind, &cpb, &chunk);
+  route[0] = kind;
+  route[1] = cpb;
+  route[2] = chunk;
+  return rc;
+}
+
 // gi (B, C, R) = the segment sums of `go` over the plan; REGNET_ERR_UNSUPPORTED when no kernel takes C channels
 template <typename T, bool WEIGHTED>
 static int segsum(const T* go, int64_t sb, int64_t sc, int64_t s_hi, int64_t s_lo, int64_t inner, const T* weight,
                   int64_t B, int64_t C, int64_t R, int64_t L, const void* plan, T* gi, hipStream_t st) {
   const ScatterPlan pl = scatter_plan_parts(const_cast<void*>(plan), B, R);
   const int64_t NS = WEIGHTED ? L / 3 : L;
-  int cpb = 0, chunk = 0;
-  if (lds_layout<T>(B, C, R, NS, &cpb, &chunk) && (C + cpb - 1) / cpb <= 65535) {
+  int kind = 0, cpb = 0, chunk = 0;
+  const int rc = segsum_route<T>(WEIGHTED, B, C, R, L, &kind, &cpb, &chunk);
+  if (rc != REGNET_OK) return rc;
+  if (kind != SEG_ROUTE_GLOBAL) {
     static bool attr_set = false;
     if (!attr_set) {
       hipError_t e = hipFuncSetAttribute((const void*)segsum_lds_kernel<T, WEIGHTED>,
@@ -347,7 +392,7 @@ static int segsum(const T* go, int64_t sb, int64_t sc, int64_t s_hi, int64_t s_l
       if (e != hipSuccess) return (int)e;
       attr_set = true;
     }
-    const bool multi = NS > chunk;
+    const bool multi = kind == SEG_ROUTE_CHUNKS;
     const size_t lds = sizeof(T) * ((size_t)cpb * chunk + (multi ? (size_t)cpb * R : 0)) + (multi ? sizeof(int) * R : 0);
     const int dense = !WEIGHTED && s_lo == 1 && s_hi == inner;
     dim3 grid((unsigned)((C + cpb - 1) / cpb), (unsigned)B);
@@ -356,7 +401,6 @@ static int segsum(const T* go, int64_t sb, int64_t sc, int64_t s_hi, int64_t s_l
     REGNET_LAUNCH_CHECK();
     return REGNET_OK;
   }
-  if (!seg_g_channels_ok<T>(C) || (R + SEG_G_T - 1) / SEG_G_T >= ((int64_t)1 << 31)) return REGNET_ERR_UNSUPPORTED;
   dim3 grid((unsigned)((R + SEG_G_T - 1) / SEG_G_T), (unsigned)((C + seg_g_ch<T> - 1) / seg_g_ch<T>), (unsigned)B);
   hipLaunchKernelGGL((segsum_global_kernel<T, WEIGHTED>), grid, dim3(SEG_G_T), 0, st, go, sb, sc, s_hi, s_lo, (int)inner,
                      weight, (int)C, (int)R, L, pl.off, pl.perm, gi);

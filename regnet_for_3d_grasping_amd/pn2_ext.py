@@ -344,7 +344,10 @@ def point_search(query_xyz, key_xyz, num_neighbours):
 def _check_interp(first, index, weight, B, N):
     _need_i64(index, "index")
     _need_float(weight, "weight", first)
+    _eq(index.dim(), 3, "index.dim() does not equal to 3")
+    _eq(weight.dim(), 3, "weight.dim() does not equal to 3")
     _eq(index.size(0), B, "index.size(0) does not equal to batch_size")
+    _eq(index.size(1), N, "index.size(1) does not equal to num_select")
     _eq(index.size(2), 3, "index.size(2) does not equal to K")
     _eq(weight.size(0), B, "weight.size(0) does not equal to batch_size")
     _eq(weight.size(1), N, "weight.size(1) does not equal to num_select")

@@ -196,7 +196,7 @@ def interpolate_backward(grad_output, index, weight, num_inst):
     w = _cpu64(weight, "weight")
     idx = index.contiguous().numpy()
     B, C, N = g.shape
-    if idx.shape[0] != B or idx.shape[2] != 3 or w.shape != (B, N, 3):
+    if idx.shape != (B, N, 3) or w.shape != (B, N, 3):
         raise RuntimeError("interpolate_backward: shape mismatch")
     out = np.zeros((B, C, int(num_inst)))
     for b in range(B):

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from tests import det_reference as D
+from tests.scatter_cases import mixed_grad
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -25,10 +26,7 @@ def det():
         torch.use_deterministic_algorithms(was, warn_only=warn)
 
 
-def _grad(rng, shape):
-    # values of mixed magnitudes: sums of them depend on the order of the additions
-    g = rng.standard_normal(shape) * np.exp2(rng.integers(-12, 12, shape))
-    return torch.from_numpy(g.astype(np.float32))
+_grad = mixed_grad     # values of mixed magnitudes: sums of them depend on the order of the additions
 
 
 def _bits_equal(a, b):
