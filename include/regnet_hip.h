@@ -1670,8 +1670,56 @@ int regnet_grasp_approach_volume_f32(const void* volume, int64_t nx, int64_t ny,
  * is minus the squared depth in voxels of the deepest sample.  An OUTSIDE sample under outside = 1 contributes -1 (an obstacle
  * of unknown depth; 0 is not a value of a signed field).  counts (B,6) int32: the four above, then the hand samples with a
  * negative value, then the swept samples with one (OUTSIDE samples under outside = 1 included).  Errors, launch and reductions
- * as in the unsigned entry, which is unchanged.                                                                               */
+ * as in the unsigned entry, which is unchanged.
+ *
+ * Retreat fan (csrc/retreat.hip).  regnet_grasp_retreat_fan_f32 / regnet_grasp_retreat_fan_signed_f32 (one kernel, a template
+ * parameter): the rigid hand at its FINAL pose moved along R candidate directions in K steps and read against the field at every
+ * step.  field, dims, origin3 (HOST), voxel, outside, L (B,12), the box arguments, step, x_extent and the limits on the dims are
+ * the margin entries'; the lookup is theirs (csrc/hand_lattice.h).  Canonical fp32 arithmetic as everywhere in this family.
+ *   lattice     the margin entries' with standoff = 0: xs = x_lo.  Only HAND samples are used -- back || finger, a sample that
+ *               is both counted once; the region between the fingers is not part of the hand.  Membership is decided once per
+ *               sample, at the final pose.
+ *   dirs        DEVICE float32, in the grasp's LOCAL frame: row (b, r) at dirs + b dirs_grasp_stride + 3 r; a stride of 0 is one
+ *               table shared by all grasps.  R in 1..16.  Not normalised: the vector is used as given.
+ *   steps       k = 0 .. K, K in 1..64.  ds_f = float32(ds), t_k = (float)k * ds_f; the sample (x, y, z) at step k is
+ *               (x + (t_k * d_x), y + (t_k * d_y), z + (t_k * d_z)) and then goes through L as the margin entries' samples do.
+ *               Step 0 is the final pose for every finite direction.
+ *   value       the field word of the sample's voxel.  An OUTSIDE sample contributes 0 (signed: -1) under outside = 1 and
+ *               nothing under outside = 0.  A non-finite position (a NaN row of L, a NaN direction -- at step 0 too, 0 * NaN
+ *               being a NaN) is OUTSIDE.
+ *   profile     (B, R, K + 1) int32 or NULL: the minimum value over the hand samples at each step, REGNET_EDT_NONE for an empty
+ *               set.
+ *   result      (B, R, 4) int32: { free_steps = the largest n in 0..K with profile[k] >= thresh for all 1 <= k <= n (step 0 is
+ *               not judged: a hand that collides at the final pose is the margin's business); the minimum of profile over steps
+ *               1..free_steps, REGNET_EDT_NONE when free_steps is 0; the minimum over steps 1..K; the number of OUTSIDE lookups
+ *               over steps 1..K, whatever `outside` says }.
+ * One workgroup of 256 threads per (grasp, direction), the tile walk of the approach analysis.  The per-step minima are LDS
+ * words lowered by LDS integer minima (a minimum has no order), the OUTSIDE count an integer sum (a wave butterfly, then the four
+ * waves through LDS): no floating-point sum, no global atomic, no host read, no allocation; capturable; two runs give the same
+ * bytes.  Errors, all before the launch: B < 0, a dim < 1, outside not 0 / 1, R or K < 1, a negative dirs_grasp_stride ->
+ * REGNET_ERR_SHAPE; a dim > 1024, N > 2^28, B >= 2^31, step or voxel not finite or not positive (in float32 too), R > 16, K > 64,
+ * B R (K + 1) > 2^28, ds negative or not finite (in float32 too; ds == 0 is allowed, every step then equals step 0), a lattice
+ * count that is not finite or n_x n_y n_z > 2^22 -> REGNET_ERR_UNSUPPORTED; then B == 0: success without a launch; then a NULL
+ * field, origin3, L, dirs or result -> REGNET_ERR_NULL.
+ *
+ * Pick.  regnet_grasp_retreat_pick(result, B, R, best, stream): one lane per grasp.  best (B,4) int32 = { r*, free_steps of r*,
+ * its free-prefix minimum, 0 }: r* is the direction with the most free steps; among equals the larger free-prefix minimum wins;
+ * among equals of that the smallest r -- the caller lists the directions in order of preference.  Errors: B < 0 or R < 1 ->
+ * REGNET_ERR_SHAPE; R > 16 or B >= 2^31 -> REGNET_ERR_UNSUPPORTED; then B == 0: success; then a NULL result or best ->
+ * REGNET_ERR_NULL.                                                                                                            */
 #define REGNET_EDT_NONE (1 << 30)
+int regnet_grasp_retreat_fan_f32(const int32_t* field, int64_t nx, int64_t ny, int64_t nz, const float* origin3, double voxel,
+                                 int outside, const float* L, int64_t B, float x_lo, float x_hi, const float* x_hi_per_grasp,
+                                 float half_thickness, float half_width, float half_space, float back_x, double step,
+                                 float x_extent, const float* dirs, int64_t dirs_grasp_stride, int64_t R, int64_t K, double ds,
+                                 int thresh, int32_t* profile, int32_t* result, void* stream);
+int regnet_grasp_retreat_fan_signed_f32(const int32_t* field, int64_t nx, int64_t ny, int64_t nz, const float* origin3,
+                                        double voxel, int outside, const float* L, int64_t B, float x_lo, float x_hi,
+                                        const float* x_hi_per_grasp, float half_thickness, float half_width, float half_space,
+                                        float back_x, double step, float x_extent, const float* dirs, int64_t dirs_grasp_stride,
+                                        int64_t R, int64_t K, double ds, int thresh, int32_t* profile, int32_t* result,
+                                        void* stream);
+int regnet_grasp_retreat_pick(const int32_t* result, int64_t B, int64_t R, int32_t* best, void* stream);
 int64_t regnet_tsdf_sdf_workspace_bytes(int64_t nx, int64_t ny, int64_t nz, int sign, int with_nearest);
 int regnet_tsdf_sdf(const void* volume, int64_t nx, int64_t ny, int64_t nz, double trunc, int64_t min_weight, double margin,
                     int mode, int outside, int sign, int64_t cap, int32_t* field, int32_t* nearest, void* work, void* stream);

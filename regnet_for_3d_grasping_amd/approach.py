@@ -19,7 +19,7 @@ and min / max only, so ``tests/approach_reference.py`` restates it in numpy and 
 device or waits for it: ``analyse`` can be captured into a graph.  GPU only: there is no CPU path.
 """
 import math
-from dataclasses import dataclass
+from dataclasses import dataclass, field as dataclass_field
 from typing import Optional
 
 import numpy as np
@@ -59,7 +59,13 @@ class ApproachParams(ParamsBase):
     threshold, not this.)  ``field_signed``: build the field SIGNED (``distance_field(signed=True)``): a hand in collision reads a
     negative ``margin_hand``, minus the depth of its deepest sample, the record gains ``grasp_colliding``, and ``min_margin``
     judges the signed value: it may then be negative, e.g. -0.002 lets a hand through that is at most 2 mm inside an obstacle.  ``field_max_distance``: None, or ``distance_field``'s ``max_distance`` [m], the cap that bounds
-    the field's cost; margins saturate there.  Both need ``field``."""
+    the field's cost; margins saturate there.  Both need ``field``.
+
+    ``retreat``: None, True (the defaults) or a ``retreat.RetreatParams`` / a dict of its fields: also move the hand at its final
+    pose along a fan of retreat directions and read the field at every step (``approach.retreat_fan``); the record gains the
+    picked direction, its free length, margin and pre-grasp point.  ``min_retreat``: None, or the least free length [m] of the
+    picked direction a grasp must have to be selected.  Both need ``space="volume"`` and ``field=True``; both are keyword-only.  Off by default (``retreat=False`` is None); the
+    fan's defaults, too, are a choice nobody has measured on a robot."""
     WORD = "approach"
     source: Optional[str] = None
     standoff: float = 0.10
@@ -76,10 +82,27 @@ class ApproachParams(ParamsBase):
     margin: float = 0.0
     field: bool = False
     min_margin: Optional[float] = None
+    # keyword-only, so the positional order of the fields around them is what it was
+    retreat: Optional[object] = dataclass_field(default=None, kw_only=True)
+    min_retreat: Optional[float] = dataclass_field(default=None, kw_only=True)
     field_signed: bool = False
     field_max_distance: Optional[float] = None
 
     def __post_init__(self):
+        if self.retreat is False:                 # off, as None is
+            self.retreat = None
+        if self.retreat is not None or self.min_retreat is not None:
+            if self.space != "volume" or not self.field:
+                raise ValueError("approach: retreat and min_retreat read the distance field of the TSDF volume; set "
+                                 "space=\"volume\" and field=True")
+            if self.retreat is None:
+                raise ValueError("approach: min_retreat is judged on the retreat fan; set retreat=True (or its parameters)")
+            if self.min_retreat is not None and not (float(self.min_retreat) >= 0.0 and np.isfinite(self.min_retreat)):
+                raise ValueError("approach: min_retreat must be None or non-negative and finite")
+            from . import retreat as retreat_mod
+            self.retreat = retreat_mod.RetreatParams() if self.retreat is True else retreat_mod.RetreatParams.coerce(self.retreat)
+            if float(self.retreat.min_margin) < 0.0 and not self.field_signed:
+                raise ValueError("approach: a negative retreat min_margin is a tolerated penetration; it needs field_signed=True")
         if (self.field_signed or self.field_max_distance is not None) and not self.field:
             raise ValueError("approach: field_signed and field_max_distance shape the distance field; set field=True (and "
                              "space=\"volume\")")
@@ -118,7 +141,8 @@ class ApproachParams(ParamsBase):
 
     def filters(self):
         """Whether ``passes()`` can drop a grasp at all."""
-        return self.min_clearance is not None or self.min_contact is not None or self.min_margin is not None
+        return (self.min_clearance is not None or self.min_contact is not None or self.min_margin is not None
+                or self.min_retreat is not None)
 
 
 def cos_friction(friction_deg):
@@ -227,8 +251,18 @@ def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, sur
     return approach_volume.analyse_volume(volume, grasp, depth, width, params, to_volume, surface, max_depth, field)
 
 
+def retreat_fan(volume, field, grasp, depth, width, params=None, to_volume=None, max_depth=None):
+    """Several retreat directions per grasp against the volume's distance field: ``retreat.retreat_fan``, which is imported only
+    here (``approach.RetreatParams`` / ``approach.RetreatFan`` are its classes)."""
+    from . import retreat
+    return retreat.retreat_fan(volume, field, grasp, depth, width, params, to_volume, max_depth)
+
+
 def __getattr__(name):
     if name == "VolumeApproach":
         from . import approach_volume
         return approach_volume.VolumeApproach
+    if name in ("RetreatParams", "RetreatFan"):
+        from . import retreat
+        return getattr(retreat, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

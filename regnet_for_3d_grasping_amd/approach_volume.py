@@ -55,6 +55,7 @@ class VolumeApproach(approach.Approach):
         super().__init__(counts, values, frame, center, params, half_space)
         self.contact_counts, self.L, self.T, self.samples = contact_counts, L, T, samples
         self.margins, self.margin_counts, self._margin_metres = margins, margin_counts, margin_metres
+        self.retreat = None                       # the ``retreat.RetreatFan`` of ``params.retreat``, set by ``analyse_volume``
 
     @property
     def margin_hand(self):
@@ -80,12 +81,17 @@ class VolumeApproach(approach.Approach):
         return self.margin_counts[:, 5] if self.margin_counts is not None and self.margin_counts.shape[1] == 6 else None
 
     def passes(self):
-        """``Approach.passes()``, and ``margin_hand >= min_margin`` when that is set, compared as float32."""
+        """``Approach.passes()``, and ``margin_hand >= min_margin`` and the retreat fan's ``free_length >= min_retreat`` when
+        those are set, compared as float32."""
         ok = super().passes()
         if self.params.min_margin is not None:
             if self._margin_metres is None:
                 raise ValueError("approach: min_margin needs a distance field; give analyse_volume field=...")
             ok = ok & (self.margin_hand >= float(np.float32(self.params.min_margin)))
+        if self.params.min_retreat is not None:
+            if self.retreat is None:
+                raise ValueError("approach: min_retreat needs the retreat fan; give analyse_volume field=... and params.retreat")
+            ok = ok & self.retreat.passes(self.params.min_retreat)
         return ok
 
     @property
@@ -135,6 +141,21 @@ def _times_rows(matrix, rows):
                          + rows[:, 2, :] * float(matrix[r, 2])) + rows[:, 3, :] * float(matrix[r, 3]) for r in range(4)], dim=1)
 
 
+def local_to_volume(grasp, to_volume):
+    """``grasp`` (B, >=8) float32 on the device, ``to_volume`` a 4x4 or None (identity) -> (the 4x4 as a float64 host array,
+    ``frame`` (B,3,3), ``center`` (B,3), ``L`` (B,12) float32): ``L = to_volume @ [frame | centre]`` per grasp, formed on the
+    device in float64 and rounded once -- the rows ``analyse_volume`` and ``retreat.retreat_fan`` hand to their kernels."""
+    B, dev = int(grasp.shape[0]), grasp.device
+    to_volume = np.eye(4) if to_volume is None else matrix4(to_volume, "to_volume must be a finite 4x4 transform", finite=True)
+    frame, center = eval_collision.grasp_frames(grasp[:, :8].contiguous())
+    local = torch.zeros((B, 4, 4), dtype=torch.float64, device=dev)
+    local[:, :3, :3] = frame
+    local[:, :3, 3] = center
+    local[:, 3, 3] = 1.0
+    L = _times_rows(to_volume, local)[:, :3, :].reshape(B, 12).to(torch.float32).contiguous()
+    return to_volume, frame, center, L
+
+
 def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, surface=None, max_depth=None, field=None):
     """``volume``: a ``tsdf.Volume``; ``grasp`` (B, >=8) float32 on its device; ``depth``: a float or one depth per grasp -- then
     ``max_depth``, a bound on them, is the lattice's far end (nothing is read back to find it; a ValueError without it);
@@ -154,8 +175,12 @@ def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, sur
     ``margin_hand`` / ``margin_sweep``.  Nothing else of the result changes.  A SIGNED field (``distance_field(signed=True)``)
     is read by ``regnet_grasp_margin_volume_signed_f32``: ``margin_hand`` / ``margin_sweep`` are signed metres, a negative value
     minus the penetration depth of the deepest sample, ``colliding_hand`` / ``colliding_sweep`` count the samples inside an
-    obstacle, and ``min_margin`` judges the signed value."""
+    obstacle, and ``min_margin`` judges the signed value.  With ``params.retreat`` and a field the result's ``retreat`` is
+    ``retreat.retreat_fan``'s ``RetreatFan`` of the same grasps (two launches more, on the ``L`` formed here); None without
+    ``params.retreat``, and ``params.retreat`` without a field is a ValueError."""
     params = approach.ApproachParams.coerce(params) or approach.ApproachParams()
+    if params.retreat is not None and field is None:
+        raise ValueError("analyse_volume: params.retreat reads a distance field; give field=volume.distance_field(...)")
     p = volume.params
     require_cuda("grasp", grasp, torch.float32, 8, at_least=True, error=RuntimeError)
     dev = volume.device
@@ -167,13 +192,7 @@ def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, sur
         raise ValueError("analyse_volume: with one depth per grasp give max_depth, the far end of the sample lattice")
     if per_grasp and not isinstance(depth, torch.Tensor):
         depth = to_device(np.asarray(depth, dtype=np.float32), dev)
-    to_volume = np.eye(4) if to_volume is None else matrix4(to_volume, "to_volume must be a finite 4x4 transform", finite=True)
-    frame, center = eval_collision.grasp_frames(grasp[:, :8].contiguous())
-    local = torch.zeros((B, 4, 4), dtype=torch.float64, device=dev)
-    local[:, :3, :3] = frame
-    local[:, :3, 3] = center
-    local[:, 3, 3] = 1.0
-    L = _times_rows(to_volume, local)[:, :3, :].reshape(B, 12).to(torch.float32).contiguous()
+    to_volume, frame, center, L = local_to_volume(grasp, to_volume)
     box, keep = eval_collision._box_args(depth, width, B, dev)
     x_extent = float(max_depth) if per_grasp else float(depth)
     step = float(p.voxel) if params.step is None else float(params.step)
@@ -216,5 +235,10 @@ def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, sur
                   normals.stride(0), normals.stride(1), int(points.shape[0]), T.data_ptr(), B, *box, float(params.standoff),
                   float(params.contact_depth), approach.cos_friction(params.friction_deg), contact_counts.data_ptr(),
                   contact_values.data_ptr())
-    return VolumeApproach(counts, values, frame, center, params, box[5], contact_counts, L, T, samples, margins, margin_counts,
-                          margin_metres)
+    result = VolumeApproach(counts, values, frame, center, params, box[5], contact_counts, L, T, samples, margins, margin_counts,
+                            margin_metres)
+    if params.retreat is not None:
+        from . import retreat
+        result.retreat = retreat.retreat_fan(volume, field, grasp, depth, width, params.retreat, to_volume, max_depth,
+                                             rows=(frame, center, L))
+    return result

@@ -51,6 +51,7 @@ SOURCES = [
     ("mesh_simplify.hip", ["-ffp-contract=off"]),   # vertex clustering: cells on individually rounded fp32, the float64 finalise one rounding per operation
     ("approach_volume.hip", ["-ffp-contract=off"]),   # approach against the volume: every sample's voxel and set are decided on individually rounded fp32
     ("edt.hip", ["-ffp-contract=off"]),   # distance field: integer passes; the query's and the margin's lookups are approach_volume.hip's
+    ("retreat.hip", ["-ffp-contract=off"]),   # retreat fan: every step's sample and voxel are decided on individually rounded fp32
 ]
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc"]
@@ -86,7 +87,8 @@ NO_VGPR_SPILL = {"mlp.o": ["mlp_gemm_kernelILi0E", "gemm2_kernel"], "sa_chain.o"
                  "ingest.o": ["ingest_"], "nms.o": ["nms_"], "plane.o": ["plane_"], "depth.o": ["depth_"],
                  "fuse.o": ["fuse_"], "icp.o": ["icp_"], "outlier.o": ["outlier_"], "tsdf.o": ["tsdf_"], "tsdf_mesh.o": ["tsdf_mesh_"],
                  "mesh_simplify.o": ["ms_"],
-                 "approach.o": ["approach_kernel"], "approach_volume.o": ["approach_volume_"], "edt.o": ["edt_"]}
+                 "approach.o": ["approach_kernel"], "approach_volume.o": ["approach_volume_"], "edt.o": ["edt_"],
+                 "retreat.o": ["retreat_"]}
 
 
 def check_no_vgpr_spill(obj_path, fragments):

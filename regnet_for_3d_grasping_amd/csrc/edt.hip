@@ -29,7 +29,7 @@ namespace {
 constexpr int EDT_NONE = REGNET_EDT_NONE;
 constexpr int EDT_T = 256;
 constexpr int EDT_W = EDT_T / 64;
-constexpr int EDT_MAX_DIM = 1024;
+constexpr int EDT_MAX_DIM = FIELD_MAX_DIM;
 constexpr int EDT_TILE_BYTES = 64 * 1024;
 
 // min_j f[j stride] + (i - j)^2 over the n words of a line, and the smallest j that attains it (-1: none, best == NONE)
@@ -330,13 +330,6 @@ __global__ __launch_bounds__(HL_T) void edt_margin_kernel(const int32_t* __restr
 }
 
 bool finite_f32(float f) { return f == f && f != __builtin_inff() && f != -__builtin_inff(); }
-
-// the dims of a field: REGNET_OK, or the status of the first rule they break
-int field_dims(int64_t nx, int64_t ny, int64_t nz) {
-  if (nx < 1 || ny < 1 || nz < 1) return REGNET_ERR_SHAPE;
-  if (nx > EDT_MAX_DIM || ny > EDT_MAX_DIM || nz > EDT_MAX_DIM || nx * ny * nz > ((int64_t)1 << 28)) return REGNET_ERR_UNSUPPORTED;
-  return REGNET_OK;
-}
 
 // log2 of the lines per tile of a pass along an axis of n voxels: the largest of 64, 32, 16, 8 within 64 KiB
 int tile_log(int64_t n, int words) {

@@ -84,3 +84,12 @@ static inline bool lattice_of(float x_lo, float standoff, float half_thickness, 
   *lat = Lattice{n_x, n_y, n_z, xs, h};
   return true;
 }
+
+// The dims of a distance field (edt.hip builds it; its margin kernel and retreat.hip read it): REGNET_OK, or the status of the
+// first rule they break.
+constexpr int FIELD_MAX_DIM = 1024;
+static inline int field_dims(int64_t nx, int64_t ny, int64_t nz) {
+  if (nx < 1 || ny < 1 || nz < 1) return REGNET_ERR_SHAPE;
+  if (nx > FIELD_MAX_DIM || ny > FIELD_MAX_DIM || nz > FIELD_MAX_DIM || nx * ny * nz > ((int64_t)1 << 28)) return REGNET_ERR_UNSUPPORTED;
+  return REGNET_OK;
+}

@@ -46,6 +46,9 @@ With ``field=True`` (``--approach-field``, ``--min-margin``) the volume's distan
 ``field_signed=True`` (``--approach-signed``) the field is signed -- a margin below zero is minus a penetration depth -- and
 ``grasp_colliding`` (B,2) int32, the hand's and the swept hand's samples inside an obstacle, follows; ``field_max_distance``
 (``--approach-field-cap``) caps the field's distances, which bounds its cost.
+With ``retreat`` (``--approach-retreat``, ``--retreat-length``, ``--retreat-steps``, ``--retreat-tilt``, ``--retreat-up``,
+``--min-retreat``) the hand at its final pose is moved along a fan of retreat directions against that field
+(``approach.retreat_fan``) and ``APPROACH_RETREAT_KEYS`` follow: the picked direction, its free length, margin and pre-grasp point.
 
 With ``denoise`` (``--denoise``, ``--outlier-mode``, ``--outlier-radius``, ``--outlier-min-neighbours``, ``--outlier-knn``,
 ``--outlier-max-radius``, ``--outlier-std-ratio``) the cloud of a camera frame -- an ``(xyz, rgb)`` pair, a depth frame's or a
@@ -105,6 +108,10 @@ APPROACH_VOLUME_KEYS = ("grasp_clearance_seen", "grasp_clearance_safe", "grasp_u
                         "grasp_solid_hand")                    # ... right after them when its ``space`` is "volume"
 APPROACH_FIELD_KEYS = ("grasp_margin_hand", "grasp_margin_sweep")   # ... and right after those when it has ``field``
 APPROACH_SIGNED_KEYS = ("grasp_colliding",)   # ... and after those when the field is signed: (B,2) int32, hand and sweep
+APPROACH_RETREAT_KEYS = ("grasp_retreat_index", "grasp_retreat_length", "grasp_retreat_margin", "grasp_retreat_direction",
+                         "grasp_retreat_pregrasp", "grasp_retreat_steps")   # ... and after the field keys with ``retreat``: the
+                                                  # picked direction's row, free length, margin, vector and pre-grasp point (in the
+                                                  # grasps' frame), and the (B,R) free steps of all directions
 TSDF_KEYS = ("tsdf_num", "tsdf_counts")                        # added when the frame was a ``MultiView`` and the detector has ``volume``
 TRACK_KEYS = ("track_pose", "track_status", "track_report")    # added beside ``TSDF_KEYS`` when the detector has ``track``
 TSDF_MESH_KEYS = ("tsdf_triangles", "tsdf_vertices", "tsdf_vertex_normals",
@@ -444,7 +451,12 @@ class GraspDetector:
             extra.update(zip(APPROACH_FIELD_KEYS, (result.margin_hand, result.margin_sweep)))
             if field.signed:
                 extra[APPROACH_SIGNED_KEYS[0]] = result.margin_counts[:, 4:6]
-        passing = result.passes().nonzero().view(-1) if self.approach.filters() else None
+        if result.retreat is not None:
+            fan = result.retreat
+            extra.update(zip(APPROACH_RETREAT_KEYS, (fan.index, fan.free_length, fan.margin, fan.direction, fan.pregrasp,
+                                                     fan.free_steps)))
+        ok = result.passes() if self.approach.filters() else None
+        passing = ok.nonzero().view(-1) if ok is not None else None
         return extra, passing
 
     def _record(self, fr, kept, output_score, sets, keys, extra, segmented):
@@ -702,8 +714,17 @@ def register_from_args(args):
 
 
 def approach_from_args(args):
-    """The CLI's fourteen approach flags -> an ``approach`` dict, or None when none of them was given."""
+    """The CLI's twenty approach flags -> an ``approach`` dict, or None when none of them was given."""
     given = _given(args, "approach")
+    retreat = {field: value for field, value in (("length", args.retreat_length), ("steps", args.retreat_steps),
+                                                 ("tilt_deg", args.retreat_tilt)) if value is not None}
+    if args.retreat_up is not None:
+        retreat["up"] = tuple(float(v) for v in args.retreat_up)
+    if args.approach_retreat or retreat or args.min_retreat is not None:
+        given["retreat"] = retreat or True
+        given["field"] = True
+    if args.min_retreat is not None:
+        given["min_retreat"] = args.min_retreat
     if args.approach_signed:
         given["field_signed"] = True
     if args.approach_field or args.approach_signed or "min_margin" in given or "field_max_distance" in given:
@@ -792,6 +813,23 @@ def build_parser():
     parser.add_argument("--approach-signed", action="store_true",
                         help="build that field signed: a hand in collision reads a negative margin, minus its penetration "
                              "depth, and the record gains grasp_colliding (implies --approach-field)")
+    fan = approach_mod.RetreatParams()
+    parser.add_argument("--approach-retreat", action="store_true",
+                        help="in volume space: move the hand at its final pose along a fan of retreat directions against the "
+                             "distance field and add the best direction, its free length, margin and pre-grasp point (implies "
+                             "--approach-field; the fan's defaults are a choice nobody has measured on a robot)")
+    parser.add_argument("--retreat-length", type=float, default=None,
+                        help="the length of every retreat path, %g m unless given (implies --approach-retreat)" % fan.length)
+    parser.add_argument("--retreat-steps", type=int, default=None,
+                        help="the steps a retreat path is cut into, 1..64, %d unless given (implies --approach-retreat)" % fan.steps)
+    parser.add_argument("--retreat-tilt", type=float, default=None,
+                        help="the tilt of the fan's side directions off the straight retreat, %g degrees unless given (implies "
+                             "--approach-retreat)" % fan.tilt_deg)
+    parser.add_argument("--retreat-up", type=float, nargs=3, metavar=("X", "Y", "Z"), default=None,
+                        help="a direction in the grasps' frame to also retreat along, and half way towards (off; implies "
+                             "--approach-retreat)")
+    parser.add_argument("--min-retreat", type=float, default=None,
+                        help="select only grasps whose best retreat direction is free this far [m] (implies --approach-retreat)")
     parser.add_argument("--denoise", action="store_true",
                         help="remove the outliers of a camera frame's cloud before the table plane and the crop")
     regular("outliers")
