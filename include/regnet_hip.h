@@ -1747,6 +1747,72 @@ int regnet_grasp_margin_volume_f32(const int32_t* dist2, int64_t nx, int64_t ny,
                                    float half_thickness, float half_width, float half_space, float back_x, float standoff,
                                    double step, float x_extent, int32_t* margins, int32_t* counts, void* stream);
 
+/* ---- next-best view (csrc/view_gain.hip): which candidate camera pose reveals the most of the space no view has observed --------
+ * The approach analysis above reports the unobserved space a grasp's hand sweeps through; these entry points say where a camera
+ * should go so that it becomes observed.  Integer results only; canonical fp32 arithmetic (individually rounded binary32
+ * operations in the written order, -ffp-contract=off, __fdiv_rn, strict comparisons) decides which voxel a ray's sample falls in.
+ * The volume is only read.  tests/view_gain_reference.py restates all three.
+ *
+ * regnet_tsdf_view_mark_f32: per candidate pose, the UNKNOWN voxels its rays reach.
+ *   volume, dims, origin3 (3 float32, HOST), voxel, trunc, min_weight, margin   as for regnet_grasp_approach_volume_f32:
+ *               voxel_f = float32(voxel), d_solid = float32(margin / trunc), the division in float64, rounded once.
+ *   intrinsics4 (4 float32, HOST), near, step, n_steps, width, height, clip   as for regnet_tsdf_raycast_f32.
+ *   poses       (P,12) float32 DEVICE: per candidate rows 0..2 of the row-major 4x4 CAMERA-TO-COMMON transform.  1 <= P <= 32.
+ *   ray point   of pixel (u, v) of pose p at sample i: regnet_tsdf_raycast_f32's.  z_i = near_f + ((float)i * step_f); c_x =
+ *               (((float)u - cx) * z) * rfx, c_y = (((float)v - cy) * z) * rfy, c_z = z; w_k = (((r_k0 c_x) + (r_k1 c_y)) + (r_k2
+ *               c_z)) + t_k with pose p's rows.
+ *   lookup      regnet_grasp_approach_volume_f32's: per axis c = floorf(__fdiv_rn(w - o, voxel_f)), INSIDE iff c >= 0 && c <
+ *               (float)n on all three axes, compared in float; the NEAREST voxel l, nothing interpolated.
+ *   class       regnet_grasp_approach_volume_f32's OUTSIDE / UNKNOWN / SOLID / FREE (one definition, csrc/hand_lattice.h).
+ *   march       over i ascending.  OUTSIDE or FREE: go on.  SOLID: the ray ends BLOCKED.  UNKNOWN at voxel l: when interest is
+ *               NULL or interest[l] != 0, bit p of plane[l] is set (a bit REQUEST); whether or not, the ray's count of unknown
+ *               samples goes up by one, and when it reaches max_unknown (1 .. n_steps) the ray ends SATURATED: a camera does not
+ *               see through that much unobserved matter.  Consecutive samples in one voxel each count.  A ray that ends neither
+ *               way: EXITED.
+ *   interest    (N) uint8 DEVICE or NULL: the voxels whose observation is wanted.
+ * Outputs, DEVICE memory: plane (N) uint32, N = nx ny nz: cleared by a fill on the stream, then bit p of word l set iff a ray of
+ * pose p requested it (an integer atomic OR; a plain load first skips the atomic when the bit is already there, which cannot
+ * change the result: bits are only set); status (P, height width) uint8 or NULL: 0 EXITED, 1 BLOCKED, 2 SATURATED, row v width +
+ * u; rays (P,4) int32: the histogram of status and, in column 3, the rays with at least one bit request (a request counts even
+ * when the bit was already set), cleared by a fill, then collected in LDS with one integer atomic per workgroup and column.
+ * Grid z is the pose; 16 x 16 pixels per 256-thread workgroup, an 8 x 8 tile per wave.  clip as for the raycast (the same
+ * float64 slab test, csrc/ray_clip.h: the samples it leaves out are OUTSIDE): it changes the time and no bit.  Three launches
+ * (the two fills are kernels); no host read, no synchronisation, no allocation, no floating-point atomic: capturable.  Errors, all before any
+ * launch: a dim, P, width, height, n_steps, min_weight or max_unknown < 1 -> REGNET_ERR_SHAPE; P > 32, max_unknown > n_steps, a
+ * dim > 2^24, N > 2^28, min_weight >= 2^31, width height > 2^21, n_steps > 4096, voxel, trunc, near or step not finite or not
+ * positive (in float32 too), margin / trunc not finite in float32 -> REGNET_ERR_UNSUPPORTED; a NULL volume, origin3,
+ * intrinsics4, poses, plane or rays -> REGNET_ERR_NULL.
+ *
+ * regnet_tsdf_view_pick: the greedy JOINT selection of K of the P poses of a plane, so that the second pick adds what the first
+ * does not cover.  gain (P) int32: per pose the number of words with its bit set.  Round r = 0 .. K - 1: per pose the number of
+ * words with its bit set and NO bit of an already chosen pose; the largest count wins, the lowest index among equals;
+ * order[r] = that pose, order_gain[r] = its count, and the pose joins the chosen ones.  When the best count is < max(min_gain, 1)
+ * this and every later round write order = -1, order_gain = 0.  state: REGNET_VIEW_PICK_STATE_WORDS int32 of DEVICE scratch (the
+ * chosen mask, the stop flag, the round's counts), cleared by a fill.  Per round a counting launch over the plane (wave ballots
+ * and population counts; one integer atomic per workgroup and pose) and a one-workgroup decision launch: 2 K + 1
+ * launches with the fill, no host read: capturable.  Integer sums only, so the result has no order.  Errors: N, P or K < 1 or min_gain < 0 ->
+ * REGNET_ERR_SHAPE; N > 2^28, P > 32 or K > P -> REGNET_ERR_UNSUPPORTED; a NULL pointer -> REGNET_ERR_NULL.
+ *
+ * regnet_tsdf_view_interest_hands: the interest plane of the swept hands of B grasps.  The arguments up to x_extent, the lattice,
+ * the sets and the lookup are regnet_grasp_approach_volume_f32's.  For every looked-up sample (region, hand or blocker) whose
+ * voxel is UNKNOWN, interest[l] = 1: a plain byte store of the same value from every writer, no atomic.  OUTSIDE samples have no
+ * voxel and store nothing.  The caller clears interest (N) uint8.  counts (B) int32: the UNKNOWN samples per grasp, an integer
+ * sum (a sample counts once, whatever its hand membership).  One launch, one workgroup of 256 threads per grasp; capturable.
+ * Errors: regnet_grasp_approach_volume_f32's, with interest and counts the required outputs.                                 */
+#define REGNET_VIEW_PICK_STATE_WORDS 64
+int regnet_tsdf_view_mark_f32(const void* volume, int64_t nx, int64_t ny, int64_t nz, const float* origin3, double voxel,
+                              double trunc, int64_t min_weight, double margin, const float* intrinsics4, const float* poses,
+                              int64_t P, double near, double step, int64_t n_steps, int64_t width, int64_t height, int clip,
+                              int64_t max_unknown, const uint8_t* interest, uint32_t* plane, uint8_t* status, int32_t* rays,
+                              void* stream);
+int regnet_tsdf_view_pick(const uint32_t* plane, int64_t N, int64_t P, int64_t K, int64_t min_gain, int32_t* state, int32_t* gain,
+                          int32_t* order, int32_t* order_gain, void* stream);
+int regnet_tsdf_view_interest_hands(const void* volume, int64_t nx, int64_t ny, int64_t nz, const float* origin3, double voxel,
+                                    double trunc, int64_t min_weight, double margin, const float* L, int64_t B, float x_lo,
+                                    float x_hi, const float* x_hi_per_grasp, float half_thickness, float half_width,
+                                    float half_space, float back_x, float standoff, double step, float x_extent,
+                                    uint8_t* interest, int32_t* counts, void* stream);
+
 /* ---- deterministic mode (csrc/scatter.hip, csrc/det.hip, csrc/bn_train.hip) ------------------------------------------
  * The float32 kernels behind torch.use_deterministic_algorithms(True): every sum of the training backward is formed in one
  * fixed order, so runs agree bit for bit.  The default entry points above are unchanged.

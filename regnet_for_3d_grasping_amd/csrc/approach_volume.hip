@@ -20,14 +20,6 @@ constexpr int AV_T = HL_T;
 constexpr int AV_W = HL_W;
 constexpr int AV_NI = 8, AV_NF = 4;                  // reduced integers and floats
 
-struct VolumeView {
-  const float* D;
-  const int32_t* W;
-  VoxelGrid grid;
-  float d_solid;
-  int min_weight;
-};
-
 __global__ __launch_bounds__(AV_T) void approach_volume_kernel(VolumeView vol, const float* __restrict__ L, GraspBox box,
                                                                const float* __restrict__ x_hi_per_grasp, float standoff,
                                                                Lattice lat, int32_t* __restrict__ counts,
@@ -50,12 +42,8 @@ __global__ __launch_bounds__(AV_T) void approach_volume_kernel(VolumeView vol, c
     grasp_apply(g, x, y, z, wx, wy, wz);
     int64_t v;
     const bool inside = grid_voxel(vol.grid, wx, wy, wz, v);
-    bool solid = false, unseen = true;
-    if (inside && vol.W[v] >= vol.min_weight) {
-      const float d = vol.D[v];
-      unseen = d != d;                               // a NaN distance: UNKNOWN
-      solid = d < vol.d_solid;
-    }
+    const VoxelClass cls = voxel_class(vol, inside, v);
+    const bool solid = cls == VC_SOLID, unseen = cls == VC_OUTSIDE || cls == VC_UNKNOWN;
     members += member;
     members_outside += inside ? 0 : member;
     if (solid) {

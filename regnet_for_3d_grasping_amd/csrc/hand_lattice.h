@@ -35,6 +35,26 @@ __device__ __forceinline__ bool grid_voxel(const VoxelGrid& grid, float wx, floa
   return inside;
 }
 
+// The volume as a lookup reads it, and THE class of a looked-up voxel (include/regnet_hip.h "class"), which approach_volume.hip
+// and view_gain.hip share: one W is loaded, and D only when W >= min_weight.
+struct VolumeView {
+  const float* D;
+  const int32_t* W;
+  VoxelGrid grid;
+  float d_solid;
+  int min_weight;
+};
+
+enum VoxelClass { VC_OUTSIDE = 0, VC_UNKNOWN = 1, VC_SOLID = 2, VC_FREE = 3 };
+
+__device__ __forceinline__ VoxelClass voxel_class(const VolumeView& vol, bool inside, int64_t v) {
+  if (!inside) return VC_OUTSIDE;
+  if (vol.W[v] < vol.min_weight) return VC_UNKNOWN;
+  const float d = vol.D[v];
+  if (d != d) return VC_UNKNOWN;                     // a NaN distance
+  return d < vol.d_solid ? VC_SOLID : VC_FREE;
+}
+
 // The walk of one workgroup of HL_T threads over the lattice: a wave takes 8 x 8 tiles of the x-y plane, tile t = wave, wave + 4,
 // ..., lane l at (l & 7, l >> 3) of the tile, and walks the n_z layers.  visit(x, y, z, sets) is called for every sample of
 // this thread, with hand_box.h's sets for the grasp's own x_hi.

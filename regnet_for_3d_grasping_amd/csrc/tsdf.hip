@@ -24,6 +24,7 @@
 //     against the box of voxel centres leaves it (conservatively: the samples skipped are unknown by the sample rule, so the
 //     clip changes no bit).  The histogram collects in LDS as integrate's does.
 // The launches are ordered by the stream: no workgroup waits for another, no flags, no cooperative launch.
+#include "ray_clip.h"
 #include "tsdf_volume.h"
 
 namespace {
@@ -274,7 +275,6 @@ constexpr int RC_TILE = 8;                          // a wave is an 8 x 8 pixel 
 constexpr int RC_WX = 2, RC_WY = 2;                 // ... and a 256-thread workgroup 2 x 2 of them
 constexpr int RC_MAX_STEPS = 4096;
 constexpr int RC_MAX_DIM = 1 << 24;                 // the inside test compares exact floats up to here
-constexpr double RC_SLACK = 1.0 / 262144.0;         // 2^-18: 64 float32 roundings of the clip's magnitudes
 
 enum { RC_NO_SURFACE = 0, RC_BACK_FACE = 1, RC_HIT = 2, RC_HIT_NO_NORMAL = 3, RC_CODES = 4 };
 
@@ -340,36 +340,10 @@ __device__ __forceinline__ bool rc_sample(const Planes& v, const RaycastArgs& a,
   return true;
 }
 
-// the samples [first, last] outside which the ray's point cannot lie inside the box of voxel centres: a slab test in float64 on
-// the exact ray t + z d, the box grown by a voxel and by RC_SLACK of every magnitude that enters the float32 point (64 times the
-// roundings of rc_point and rc_cell), the range grown by a sample either way.  A NaN constrains nothing.
+// the samples [first, last] outside which the ray's point cannot lie inside the box of voxel centres (ray_clip.h, which
+// view_gain.hip's march shares)
 __device__ __forceinline__ void rc_clip(const RaycastArgs& a, float du, float dv, int& first, int& last) {
-  const double near = (double)a.near, step = (double)a.step;
-  const double far = near + (double)(a.n_steps - 1) * step;
-  const double dcx = (double)du * (double)a.rfx, dcy = (double)dv * (double)a.rfy;
-  const double zs = RC_SLACK * (fabs(near) + far);
-  double za = near - zs, zb = far + zs;
-  bool empty = false;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const double r0 = (double)a.r[4 * k], r1 = (double)a.r[4 * k + 1], r2 = (double)a.r[4 * k + 2], t = (double)a.r[4 * k + 3];
-    const double d = (r0 * dcx + r1 * dcy) + r2;
-    const double o = (double)a.o[k], vx = (double)a.voxel, extent = (double)a.n[k] * vx;
-    const double reach = (fabs(r0 * dcx) + fabs(r1 * dcy) + fabs(r2)) * far;
-    const double m = vx + RC_SLACK * (fabs(t) + reach + fabs(o) + extent);
-    const double lo = o + 0.5 * vx - m, hi = o + extent - 0.5 * vx + m;
-    if (d == 0.0) {
-      empty = empty || t < lo || t > hi;
-    } else {
-      const double z1 = (lo - t) / d, z2 = (hi - t) / d;
-      za = fmax(za, fmin(z1, z2));
-      zb = fmin(zb, fmax(z1, z2));
-    }
-  }
-  if (empty || za > zb) { first = 1; last = 0; return; }
-  const double top = (double)(a.n_steps - 1);
-  first = (int)fmin(fmax(floor((za - near) / step) - 1.0, 0.0), top);
-  last = (int)fmin(fmax(ceil((zb - near) / step) + 1.0, 0.0), top);
+  ray_clip(a.r, a.n, a.o, a.voxel, a.near, a.step, a.n_steps, du, dv, a.rfx, a.rfy, first, last);
 }
 
 __global__ __launch_bounds__(TS_BLOCK) void tsdf_raycast_kernel(Planes vol, const RaycastArgs a, float* __restrict__ xyz,

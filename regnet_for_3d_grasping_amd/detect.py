@@ -117,6 +117,8 @@ TRACK_KEYS = ("track_pose", "track_status", "track_report")    # added beside ``
 TSDF_MESH_KEYS = ("tsdf_triangles", "tsdf_vertices", "tsdf_vertex_normals",
                   "tsdf_vertex_colors")                        # added after them when the detector has ``mesh``
 TSDF_MESH_REPORT_KEYS = ("tsdf_mesh_report",)                  # added after them when the detector has ``mesh_cell``
+VIEW_KEYS = ("view_pose", "view_gain", "view_rays", "view_order",
+             "view_order_gain")                                 # added last when the detector has ``view``: the next-best view
 DENOISE_KEYS = ("denoise_num",)                                 # added when the detector has ``denoise`` and the frame was a camera frame
 
 
@@ -192,12 +194,21 @@ class GraspDetector:
     ``mesh_cell`` [m] (implies ``mesh``; may ride in the dicts too): the mesh goes through ``tsdf.Mesh.simplify(cell=mesh_cell)``
     on the device before it is downloaded -- the four mesh keys and the PLY are then the simplified mesh, whose triangles ascend
     by the full mesh's rows, and ``tsdf_mesh_report`` (12,) int32 is ``SimplifiedMesh.report``.  The cloud the networks see is
-    the full surface either way.  Without it every key and file is what it is without the option."""
+    the full surface either way.  Without it every key and file is what it is without the option.
+    ``view``: None, or a ``view_plan.ViewParams`` / a dict of its fields (``width``, ``height``, ``near``, ``far``, ``step``,
+    ``max_unknown``, ``top_k``, ``min_gain``, ``interest``, ``azimuths``, ``elevations``, ``radius``, ...), with ``volume`` or
+    ``track`` (anything else is a ValueError): where the camera should go next.  Candidate poses orbit the centroid of the kept
+    grasps of the analysed (else the selected) set -- the volume's centre when there are none -- and are ranked by the unobserved
+    voxels of the frame's volume each would reveal (``view_plan.view_gain``); ``interest="grasps"`` (it needs ``approach`` with
+    ``space="volume"``) counts only those inside the swept hands of the analysed grasps.  The record also carries, last,
+    ``view_pose`` (P,4,4) float64 camera-to-common in the volume's frame, ``view_gain`` (P,) int32, ``view_rays`` (P,4) int32,
+    ``view_order`` (K,) int32, the joint greedy pick (-1: nothing more to gain), and ``view_order_gain`` (K,) int32.  Without it
+    nothing is launched, allocated or imported for it and every record is what it was."""
 
     def __init__(self, score_net, region_net, params=TEST_PARAMS, gripper_params=GRIPPER_PARAMS, eval_params=EVAL_PARAMS,
                  transform=None, bounds=None, num_points=ALL_POINTS_NUM, use_theta=USE_THETA, select=None, depth=None, segment=None,
                  fuse=None, register=None, approach=None, denoise=None, volume=None, track=None, mesh=False, mesh_ply=False,
-                 mesh_cell=None):
+                 mesh_cell=None, view=None):
         from . import depth_frame, fusion, grasp_select, ingest, registration
         from . import segment as segment_mod
         self.fuse = fusion.FuseParams.coerce(fuse)
@@ -252,6 +263,15 @@ class GraspDetector:
                 self.volume = tsdf.TsdfParams()
         if self.approach is not None and self.approach.space == "volume" and self.volume is None:
             raise ValueError("approach: space=\"volume\" analyses the detector's TSDF volume; give volume=... or track=...")
+        self.view = self.view_camera = self.approach_result = None
+        if view is not None:                      # (the module is not even imported without it)
+            if self.volume is None:
+                raise ValueError("view: the next-best view is planned in the detector's TSDF volume; give volume=... or track=...")
+            from . import view_plan
+            self.view = view_plan.ViewParams.coerce(view)
+            if self.view.interest == "grasps" and (self.approach is None or self.approach.space != "volume"):
+                raise ValueError("view: interest=\"grasps\" counts the unseen space of the analysed hands; give "
+                                 "approach=ApproachParams(space=\"volume\")")
         self.denoise = None
         if denoise is not None:                   # (the module is not even imported without it)
             from . import outliers
@@ -286,6 +306,11 @@ class GraspDetector:
         if isinstance(frame, dict):
             return ingest.ingest_record(frame, self.num_points, self.device)
         fused = table = denoised = tracked = meshed = None
+        if self.view is not None:                 # the camera whose field of view the candidates get: the (first) depth frame's
+            first = frame.frames[0] if isinstance(frame, fusion.MultiView) else frame
+            self.view_camera = None
+            if isinstance(first, depth_frame.DepthFrame):
+                self.view_camera = (first.intrinsics, int(first.depth.shape[1]), int(first.depth.shape[0]))
         if self.track is not None and isinstance(frame, fusion.MultiView):
             raise ValueError("track: a MultiView's views carry their poses; track takes the DepthFrames of one moving camera")
         if self.track is not None and isinstance(frame, depth_frame.DepthFrame):   # one blocking read: the registration's state
@@ -444,6 +469,7 @@ class GraspDetector:
                 out=self.distance_field, signed=self.approach.field_signed, max_distance=self.approach.field_max_distance)
         result = approach_mod.analyse_volume(self.tsdf_volume, sets[self.approach_source][:, :8], depth, width, self.approach,
                                              to_volume=to_volume, surface=self.fused, field=field)
+        self.approach_result = result             # (the next-best view's interest reads its rows)
         extra = dict(zip(APPROACH_KEYS + APPROACH_VOLUME_KEYS,
                          (result.clearance, result.width, result.offset, result.opening, result.contact, result.pregrasp,
                           result.clearance_seen, result.clearance_safe, result.unseen_share, result.solid_hand)))
@@ -458,6 +484,33 @@ class GraspDetector:
         ok = result.passes() if self.approach.filters() else None
         passing = ok.nonzero().view(-1) if ok is not None else None
         return extra, passing
+
+    def _next_view(self, sets):
+        """The next-best view of the frame's volume -> ``VIEW_KEYS`` as numpy arrays (``view_plan.plan``: one blocking read, and
+        one of 12 bytes for the grasps' centroid).  The candidates orbit the centroid of the analysed (else the selected, else
+        the stage-3) set's centres, taken to the volume's frame; the volume's centre when the set is empty."""
+        from . import tsdf, view_plan
+        if self.tsdf_volume is None or not isinstance(self.fused, tsdf.Surface) or self.view_camera is None:
+            raise ValueError("view: the next-best view is planned in the detector's TSDF volume, and this frame has none: hand "
+                             "detect a MultiView (volume) or a DepthFrame (track)")
+        volume = self.tsdf_volume
+        transform = self.transform if self.table is None else self.table[0]
+        to_volume = np.linalg.inv(np.asarray(transform, dtype=np.float64))
+        source = self.approach_source or (self.select.source if self.select is not None else "grasp_stage3")
+        grasp = sets[source]
+        p = volume.params
+        target = np.asarray(volume.origin, dtype=np.float64) + 0.5 * float(p.voxel) * np.asarray(p.dims, dtype=np.float64)
+        if grasp.shape[0] >= 1:
+            from . import eval_collision
+            _, center = eval_collision.grasp_frames(grasp[:, :8].contiguous())
+            centroid = center.mean(dim=0).cpu().numpy().astype(np.float64)
+            target = (to_volume @ np.append(centroid, 1.0))[:3]
+        interest = None
+        if self.view.interest == "grasps" and grasp.shape[0] >= 1:
+            depth, width = self.eval_params[0], self.eval_params[1]
+            interest, _ = view_plan.interest_hands(volume, grasp[:, :8], depth, width, self.approach, to_volume=to_volume,
+                                                   rows=self.approach_result.L)
+        return view_plan.plan(volume, self.view, target, self.view.scaled_intrinsics(*self.view_camera), interest=interest)
 
     def _record(self, fr, kept, output_score, sets, keys, extra, segmented):
         """The downloads, in the order they have always been made -> the record, its keys in the documented order."""
@@ -541,7 +594,10 @@ class GraspDetector:
                 points32 = fr.points32[:kept]
                 self._collision_filter(sets, points32)
                 keys, extra, segmented = self._select_and_segment(sets, points32)
-                return self._record(fr, kept, output_score, sets, keys, extra, segmented)
+                record = self._record(fr, kept, output_score, sets, keys, extra, segmented)
+                if self.view is not None:         # last: the volume is final and the analysed hands are known
+                    record.update(self._next_view(sets))
+                return record
         finally:
             self.score_net.train(was_training[0])
             self.region_net.train(was_training[1])
@@ -732,6 +788,17 @@ def approach_from_args(args):
     return given if (given or args.approach) else None
 
 
+def view_from_args(args):
+    """The CLI's five next-view flags -> a ``view`` dict, or None when none of them was given."""
+    given = {}
+    if args.view_candidates is not None:
+        given["azimuths"], given["elevations"] = (int(v) for v in args.view_candidates)
+    for field, value in (("radius", args.view_radius), ("top_k", args.view_top_k), ("interest", args.view_interest)):
+        if value is not None:
+            given[field] = value
+    return given if (given or args.next_view) else None
+
+
 def outliers_from_args(args):
     """The CLI's seven outlier flags -> a ``denoise`` dict, or None when none of them was given."""
     given = _given(args, "outliers")
@@ -858,6 +925,21 @@ def build_parser():
     parser.add_argument("--track-smooth", type=float, nargs=3, metavar=("RADIUS", "SIGMA_SPACE", "SIGMA_DEPTH"), default=None,
                         help="smooth the frame's depth for the registration by a bilateral filter: window radius 1..4 pixels, "
                              "spatial sigma [pixels], depth sigma [m] (off; 3 2 0.01 are the filter's own defaults)")
+    from . import view_plan
+    view = view_plan.ViewParams()
+    parser.add_argument("--next-view", action="store_true",
+                        help="with --tsdf or --track: rank candidate camera poses by the unobserved voxels of the volume each would "
+                             "reveal and add the joint pick to the record (the defaults are a choice nobody has measured on a robot)")
+    parser.add_argument("--view-candidates", type=int, nargs=2, metavar=("AZ", "EL"), default=None,
+                        help="the candidates: AZ azimuths times EL elevations on an orbit about the kept grasps, at most 32 in all, "
+                             "%d %d unless given (implies --next-view)" % (view.azimuths, view.elevations))
+    parser.add_argument("--view-radius", type=float, default=None,
+                        help="the radius of that orbit, %g m unless given (implies --next-view)" % view.radius)
+    parser.add_argument("--view-top-k", type=int, default=None,
+                        help="pick so many poses jointly, %d unless given (implies --next-view)" % view.top_k)
+    parser.add_argument("--view-interest", choices=list(view_plan.INTERESTS), default=None,
+                        help="count every unobserved voxel (all, the default), or only those inside the swept hands of the analysed "
+                             "grasps (grasps: needs --approach-space volume; implies --next-view)")
     return parser
 
 
@@ -879,7 +961,7 @@ def main(argv=None):
                              segment=segment_from_args(args), fuse=fuse_from_args(args), register=register_from_args(args),
                              approach=approach_from_args(args), denoise=outliers_from_args(args),
                              volume=volume_from_args(args), track=track_from_args(args), mesh=args.tsdf_mesh,
-                             mesh_ply=args.tsdf_mesh_ply, mesh_cell=args.tsdf_mesh_cell)
+                             mesh_ply=args.tsdf_mesh_ply, mesh_cell=args.tsdf_mesh_cell, view=view_from_args(args))
     real_data = "real_data" in args.folder
     if args.file:
         paths = [os.path.join(args.folder, args.file)]

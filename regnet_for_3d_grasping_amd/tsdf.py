@@ -451,6 +451,7 @@ class Volume:
         self.origin = np.ascontiguousarray(np.asarray(self.params.origin, dtype=np.float64).astype(np.float32))
         self.mesh_scratch = None                # extract_mesh's row lookup plane, (N) int32: allocated on its first call
         self.simplify_buffers = {}              # Mesh.simplify's (workspace, result) per sizes: allocated on the first call with them
+        self.view_plane = None                  # view_gain's bit plane, (N) int32: allocated on its first call
         self.reset()
 
     @property
@@ -636,6 +637,14 @@ class Volume:
             record_streams(stream, self.data, *out)
         return ModelView(xyz, normals, rgb, status, counts, width, height, k, T)
 
+    def view_gain(self, poses, intrinsics, width, height, near=None, far=None, step=None, max_unknown=None, margin=0.0,
+                  interest=None, status=True, clip=True, stream=None, out=None):
+        """Per candidate camera pose (at most 32) the unobserved voxels its rays would reach -> ``view_plan.ViewGain``:
+        ``view_plan.view_gain`` on this volume, which see.  The bit plane, 4 bytes per voxel, is allocated on the first call and
+        kept on the volume, like the mesh's row plane."""
+        from . import view_plan
+        return view_plan.view_gain(self, poses, intrinsics, width, height, near, far, step, max_unknown, margin, interest,
+                                   status, clip, stream, out)
 
     def distance_field(self, mode="solid", outside=None, margin=0.0, nearest=False, min_weight=None, stream=None, out=None,
                        signed=False, max_distance=None):
