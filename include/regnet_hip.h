@@ -239,7 +239,16 @@ int regnet_gather_max_scene_f32(const float* feat, int64_t num_rows, int64_t F, 
  * 16, zero padded); scale/shift are the eval-mode BatchNorm folded to a per-channel affine.
  *
  * regnet_mlp_layer_f32: C[P,N] = act(scale * (A[P,Ka] . W^T) + shift); pool_group == 64 additionally
- * takes the max over every 64 consecutive rows (torch.max(x, 3), modules.py:245) -> C[P/64, N].  */
+ * takes the max over every 64 consecutive rows (torch.max(x, 3), modules.py:245) -> C[P/64, N].
+ *
+ * What is read and written (all entry points of this section and regnet_sa_premul_layer_f32, regnet_interp_concat_f32,
+ * regnet_interp_affine_f32, regnet_score_head_f32 below; tests/test_gpu_mlp_modes.py): an operand with a leading
+ * dimension of its own is read in its valid columns only -- A below Ka, feat below Cf, U and V below C1, Yd and the
+ * output's scale / shift below C, x below C -- so the padding up to lda / ldu / ldv / ldd / ldx may hold anything, NaN
+ * included; the zero columns of the operand up to Kpad come from the kernel, not from memory.  Index arrays are read
+ * for the rows of the problem only.  Of the output exactly the rows below P (P / 64 when pooled) and the columns below
+ * N (Cout, C) are written: columns [N, ldc) and whatever follows the last row are left as they were, for any P, N and
+ * ldc, aligned or not.                                                                                              */
 int regnet_mlp_layer_f32(const float* A, int64_t lda, int64_t Ka, const float* W, int64_t Kpad,
                          const float* scale, const float* shift, float* C, int64_t ldc, int64_t P,
                          int64_t N, int relu, int pool_group, void* stream);
