@@ -1756,6 +1756,48 @@ int regnet_grasp_margin_volume_f32(const int32_t* dist2, int64_t nx, int64_t ny,
                                    float half_thickness, float half_width, float half_space, float back_x, float standoff,
                                    double step, float x_extent, int32_t* margins, int32_t* counts, void* stream);
 
+/* ---- hand paths (csrc/hand_path.hip): posed trajectories of the hand against the distance field ---------------------------------
+ * The retreat fan above translates the rigid hand at its final pose.  regnet_grasp_path_check_f32 /
+ * regnet_grasp_path_check_signed_f32 (one kernel, a template parameter) take the POSE of the hand at every waypoint, so a path
+ * may turn the hand as it moves.  field, dims, origin3 (HOST), voxel, outside, the box arguments, x_hi_per_grasp, step, x_extent
+ * and thresh are the fan's and mean the same; canonical fp32 arithmetic as everywhere in this family.
+ *   P           (B, R, K + 1, 12) float32 DEVICE: for grasp b, candidate path r and waypoint k the three rows of the hand's
+ *               row-major LOCAL-TO-VOLUME matrix at that waypoint.  Waypoint 0 is the final grasp pose.  R in 1..16, K in 1..64.
+ *   lattice     the fan's: the margin entries' with standoff = 0, hand samples only (back || finger for the grasp's own x_hi, a
+ *               sample that is both counted once).  Membership is decided once per sample, in the hand's local frame.
+ *   value       for every hand sample (x, y, z) and every k = 0 .. K: w = rows(b, r, k) applied by affine3 (csrc/common.h), the
+ *               nearest voxel of w (csrc/hand_lattice.h: grid_voxel), the field word there.  An OUTSIDE sample contributes 0
+ *               (signed: -1) under outside = 1 and nothing under outside = 0; a non-finite position (a NaN row) is OUTSIDE.
+ *   profile     (B, R, K + 1) int32 or NULL: the minimum value over the hand samples at each waypoint, REGNET_EDT_NONE for an
+ *               empty set.
+ *   result      (B, R, 4) int32, the fan's layout byte for byte, so regnet_grasp_retreat_pick picks from it unchanged:
+ *               { free_steps = the largest n in 0..K with profile[k] >= thresh for all 1 <= k <= n (waypoint 0 is not judged);
+ *               the minimum of profile over waypoints 1..free_steps, REGNET_EDT_NONE when free_steps is 0; the minimum over
+ *               waypoints 1..K; the number of OUTSIDE lookups over waypoints 1..K, whatever `outside` says }.
+ *   disp        (B, R, K) float32 or NULL: disp[b, r, k] is the largest distance a point of the hand's bounding box moves from
+ *               waypoint k to k + 1: the maximum (NaN when either operand is one), over the 8 corners c in {x_lo, x_hi of grasp
+ *               b} x {-half_width, +half_width} x {-half_thickness, +half_thickness}, of sqrt(dot3(d, d)) with d_i = affine3(row
+ *               i of waypoint k + 1, c) - affine3(row i of waypoint k, c): one float32 subtraction per component, dot3's order,
+ *               a correctly rounded float32 root.  The displacement under a difference of two affine maps is convex in the
+ *               point, so the maximum over the corners is the maximum over the box.
+ * One workgroup of 256 threads per (grasp, path), the tile walk of the approach analysis; the path's rows are staged in LDS once.
+ * The per-waypoint minima are LDS words lowered by LDS integer minima, the OUTSIDE count an integer sum: no floating-point sum,
+ * no global atomic, no host read, no allocation; capturable; two runs give the same bytes.  Errors, all before the launch and in
+ * the fan's order: B < 0, a dim < 1, outside not 0 / 1, R or K < 1 -> REGNET_ERR_SHAPE; a dim > 1024, N > 2^28, B >= 2^31, step
+ * or voxel not finite or not positive (in float32 too), R > 16, K > 64, B R (K + 1) > 2^28, a lattice count that is not finite
+ * or n_x n_y n_z > 2^22 -> REGNET_ERR_UNSUPPORTED; then B == 0: success without a launch; then a NULL field, origin3, P or result
+ * -> REGNET_ERR_NULL.                                                                                                          */
+int regnet_grasp_path_check_f32(const int32_t* field, int64_t nx, int64_t ny, int64_t nz, const float* origin3, double voxel,
+                                int outside, const float* P, int64_t B, int64_t R, int64_t K, float x_lo, float x_hi,
+                                const float* x_hi_per_grasp, float half_thickness, float half_width, float half_space,
+                                float back_x, double step, float x_extent, int thresh, int32_t* profile, int32_t* result,
+                                float* disp, void* stream);
+int regnet_grasp_path_check_signed_f32(const int32_t* field, int64_t nx, int64_t ny, int64_t nz, const float* origin3,
+                                       double voxel, int outside, const float* P, int64_t B, int64_t R, int64_t K, float x_lo,
+                                       float x_hi, const float* x_hi_per_grasp, float half_thickness, float half_width,
+                                       float half_space, float back_x, double step, float x_extent, int thresh, int32_t* profile,
+                                       int32_t* result, float* disp, void* stream);
+
 /* ---- next-best view (csrc/view_gain.hip): which candidate camera pose reveals the most of the space no view has observed --------
  * The approach analysis above reports the unobserved space a grasp's hand sweeps through; these entry points say where a camera
  * should go so that it becomes observed.  Integer results only; canonical fp32 arithmetic (individually rounded binary32

@@ -139,10 +139,53 @@ class ApproachParams(ParamsBase):
         if not (float(self.normal_radius) > 0.0 and int(self.normal_max_nn) >= 3):
             raise ValueError("approach: normal_radius must be positive and normal_max_nn at least 3")
 
+    # the hand paths are ``PathApproachParams``' fields; off here (class attributes, so that every reader may ask for them)
+    paths = None
+    min_path = None
+
+    @classmethod
+    def coerce(cls, value):
+        """``ParamsBase.coerce``; a dict that names ``paths`` or ``min_path`` becomes a ``PathApproachParams``."""
+        if cls is ApproachParams and isinstance(value, dict) and ("paths" in value or "min_path" in value):
+            return PathApproachParams(**value)
+        return super().coerce(value)
+
     def filters(self):
         """Whether ``passes()`` can drop a grasp at all."""
         return (self.min_clearance is not None or self.min_contact is not None or self.min_margin is not None
-                or self.min_retreat is not None)
+                or self.min_retreat is not None or self.min_path is not None)
+
+
+@dataclass
+class PathApproachParams(ApproachParams):
+    """``ApproachParams`` with the hand paths (``approach.check_paths``), both keyword-only.  ``paths``: None, True (the
+    defaults) or a ``hand_path.PathParams`` / a dict of its fields: also take the hand through candidate trajectories of POSES --
+    the fan's five directions and four turns of the straight retreat, or ``PathParams.paths`` -- and read the field at every
+    waypoint; the record gains the picked path, every path's free and certified steps, the picked path's margin and the
+    pre-grasp pose.  ``min_path``: None, or the least CERTIFIED length [m] of the picked path (``PathCheck.certified_length``) a
+    grasp must have to be selected.  Both need ``space="volume"`` and ``field=True``.  Off by default (``paths=False`` is None);
+    independent of ``retreat``.  A dict with either key handed to ``ApproachParams.coerce`` (``GraspDetector(approach=...)``,
+    ``analyse_volume``) builds this class; ``ApproachParams``' own constructor is what it was.  The defaults of the paths, too, are
+    a choice nobody has measured on a robot."""
+    paths: Optional[object] = dataclass_field(default=None, kw_only=True)
+    min_path: Optional[float] = dataclass_field(default=None, kw_only=True)
+
+    def __post_init__(self):
+        if self.paths is False:                   # off, as None is
+            self.paths = None
+        if self.paths is not None or self.min_path is not None:
+            if self.space != "volume" or not self.field:
+                raise ValueError("approach: paths and min_path read the distance field of the TSDF volume; set "
+                                 "space=\"volume\" and field=True")
+            if self.paths is None:
+                raise ValueError("approach: min_path is judged on the hand paths; set paths=True (or their parameters)")
+            if self.min_path is not None and not (float(self.min_path) >= 0.0 and np.isfinite(self.min_path)):
+                raise ValueError("approach: min_path must be None or non-negative and finite")
+            from . import hand_path
+            self.paths = hand_path.PathParams() if self.paths is True else hand_path.PathParams.coerce(self.paths)
+            if float(self.paths.min_margin) < 0.0 and not self.field_signed:
+                raise ValueError("approach: a negative paths min_margin is a tolerated penetration; it needs field_signed=True")
+        super().__post_init__()
 
 
 def cos_friction(friction_deg):
@@ -258,10 +301,20 @@ def retreat_fan(volume, field, grasp, depth, width, params=None, to_volume=None,
     return retreat.retreat_fan(volume, field, grasp, depth, width, params, to_volume, max_depth)
 
 
+def check_paths(volume, field, grasp, depth, width, params=None, to_volume=None, max_depth=None, rows=None, poses=None):
+    """Posed hand trajectories per grasp against the volume's distance field: ``hand_path.check_paths``, which is imported only
+    here (``approach.PathParams`` / ``approach.PathCheck`` are its classes)."""
+    from . import hand_path
+    return hand_path.check_paths(volume, field, grasp, depth, width, params, to_volume, max_depth, rows, poses)
+
+
 def __getattr__(name):
     if name == "VolumeApproach":
         from . import approach_volume
         return approach_volume.VolumeApproach
+    if name in ("PathParams", "PathCheck"):
+        from . import hand_path
+        return getattr(hand_path, name)
     if name in ("RetreatParams", "RetreatFan"):
         from . import retreat
         return getattr(retreat, name)

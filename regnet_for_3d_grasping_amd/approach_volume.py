@@ -56,6 +56,7 @@ class VolumeApproach(approach.Approach):
         self.contact_counts, self.L, self.T, self.samples = contact_counts, L, T, samples
         self.margins, self.margin_counts, self._margin_metres = margins, margin_counts, margin_metres
         self.retreat = None                       # the ``retreat.RetreatFan`` of ``params.retreat``, set by ``analyse_volume``
+        self.paths = None                         # the ``hand_path.PathCheck`` of ``params.paths``, set by ``analyse_volume``
 
     @property
     def margin_hand(self):
@@ -92,6 +93,10 @@ class VolumeApproach(approach.Approach):
             if self.retreat is None:
                 raise ValueError("approach: min_retreat needs the retreat fan; give analyse_volume field=... and params.retreat")
             ok = ok & self.retreat.passes(self.params.min_retreat)
+        if self.params.min_path is not None:      # the picked path's CERTIFIED length, compared as float32
+            if self.paths is None:
+                raise ValueError("approach: min_path needs the hand paths; give analyse_volume field=... and params.paths")
+            ok = ok & (self.paths.certified_length >= float(np.float32(self.params.min_path)))
         return ok
 
     @property
@@ -177,10 +182,13 @@ def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, sur
     minus the penetration depth of the deepest sample, ``colliding_hand`` / ``colliding_sweep`` count the samples inside an
     obstacle, and ``min_margin`` judges the signed value.  With ``params.retreat`` and a field the result's ``retreat`` is
     ``retreat.retreat_fan``'s ``RetreatFan`` of the same grasps (two launches more, on the ``L`` formed here); None without
-    ``params.retreat``, and ``params.retreat`` without a field is a ValueError."""
+    ``params.retreat``, and ``params.retreat`` without a field is a ValueError.  ``params.paths`` (``approach.PathApproachParams``)
+    likewise sets the result's ``paths`` to ``hand_path.check_paths``' ``PathCheck``."""
     params = approach.ApproachParams.coerce(params) or approach.ApproachParams()
     if params.retreat is not None and field is None:
         raise ValueError("analyse_volume: params.retreat reads a distance field; give field=volume.distance_field(...)")
+    if params.paths is not None and field is None:
+        raise ValueError("analyse_volume: params.paths reads a distance field; give field=volume.distance_field(...)")
     p = volume.params
     require_cuda("grasp", grasp, torch.float32, 8, at_least=True, error=RuntimeError)
     dev = volume.device
@@ -240,5 +248,9 @@ def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, sur
     if params.retreat is not None:
         from . import retreat
         result.retreat = retreat.retreat_fan(volume, field, grasp, depth, width, params.retreat, to_volume, max_depth,
+                                             rows=(frame, center, L))
+    if params.paths is not None:                  # (``approach.PathApproachParams``) the same grasps through posed paths
+        from . import hand_path
+        result.paths = hand_path.check_paths(volume, field, grasp, depth, width, params.paths, to_volume, max_depth,
                                              rows=(frame, center, L))
     return result

@@ -49,6 +49,10 @@ With ``field=True`` (``--approach-field``, ``--min-margin``) the volume's distan
 With ``retreat`` (``--approach-retreat``, ``--retreat-length``, ``--retreat-steps``, ``--retreat-tilt``, ``--retreat-up``,
 ``--min-retreat``) the hand at its final pose is moved along a fan of retreat directions against that field
 (``approach.retreat_fan``) and ``APPROACH_RETREAT_KEYS`` follow: the picked direction, its free length, margin and pre-grasp point.
+With ``paths`` (``--approach-paths``, ``--path-turn``, ``--path-length``, ``--path-steps``, ``--path-pivot``, ``--min-path``) the hand
+is taken through candidate trajectories of POSES against that field (``approach.check_paths``: the fan's five directions and four
+turns of the straight retreat) and ``APPROACH_PATH_KEYS`` follow; ``min_path`` selects on the picked path's certified length.  The
+fan and the paths are independent.
 
 With ``denoise`` (``--denoise``, ``--outlier-mode``, ``--outlier-radius``, ``--outlier-min-neighbours``, ``--outlier-knn``,
 ``--outlier-max-radius``, ``--outlier-std-ratio``) the cloud of a camera frame -- an ``(xyz, rgb)`` pair, a depth frame's or a
@@ -112,6 +116,11 @@ APPROACH_RETREAT_KEYS = ("grasp_retreat_index", "grasp_retreat_length", "grasp_r
                          "grasp_retreat_pregrasp", "grasp_retreat_steps")   # ... and after the field keys with ``retreat``: the
                                                   # picked direction's row, free length, margin, vector and pre-grasp point (in the
                                                   # grasps' frame), and the (B,R) free steps of all directions
+APPROACH_PATH_KEYS = ("grasp_path_index", "grasp_path_steps", "grasp_path_certified", "grasp_path_margin",
+                      "grasp_path_pose")          # ... and after those with ``paths``: the picked path's row, the (B,R) free and
+                                                  # certified steps of all paths, the picked path's margin and the pre-grasp POSE
+                                                  # (B,12): rows 0..2 of the hand's pose at the picked path's last free step, in
+                                                  # the grasps' frame
 TSDF_KEYS = ("tsdf_num", "tsdf_counts")                        # added when the frame was a ``MultiView`` and the detector has ``volume``
 TRACK_KEYS = ("track_pose", "track_status", "track_report")    # added beside ``TSDF_KEYS`` when the detector has ``track``
 TSDF_MESH_KEYS = ("tsdf_triangles", "tsdf_vertices", "tsdf_vertex_normals",
@@ -481,6 +490,10 @@ class GraspDetector:
             fan = result.retreat
             extra.update(zip(APPROACH_RETREAT_KEYS, (fan.index, fan.free_length, fan.margin, fan.direction, fan.pregrasp,
                                                      fan.free_steps)))
+        if result.paths is not None:
+            check = result.paths
+            extra.update(zip(APPROACH_PATH_KEYS, (check.index, check.free_steps, check.certified_steps(), check.margin,
+                                                  _rows_to_frame(transform, check.waypoint))))
         ok = result.passes() if self.approach.filters() else None
         passing = ok.nonzero().view(-1) if ok is not None else None
         return extra, passing
@@ -769,8 +782,21 @@ def register_from_args(args):
     return given if (given or args.refine_poses) else None
 
 
+def _rows_to_frame(transform, rows):
+    """``rows`` (B,12) float32 on the device, poses in the volume's frame; ``transform`` the host 4x4 from the volume's frame to
+    the grasps' -> (B,12) float32: ``transform @ pose`` per row, on the device in float64 and rounded once."""
+    import torch
+    from . import approach_volume
+    B = int(rows.shape[0])
+    full = torch.zeros((B, 4, 4), dtype=torch.float64, device=rows.device)
+    full[:, :3, :] = rows.reshape(B, 3, 4)
+    full[:, 3, 3] = 1.0
+    moved = approach_volume._times_rows(np.asarray(transform, dtype=np.float64), full)
+    return moved[:, :3, :].reshape(B, 12).to(torch.float32).contiguous()
+
+
 def approach_from_args(args):
-    """The CLI's twenty approach flags -> an ``approach`` dict, or None when none of them was given."""
+    """The CLI's approach flags -> an ``approach`` dict, or None when none of them was given."""
     given = _given(args, "approach")
     retreat = {field: value for field, value in (("length", args.retreat_length), ("steps", args.retreat_steps),
                                                  ("tilt_deg", args.retreat_tilt)) if value is not None}
@@ -781,6 +807,15 @@ def approach_from_args(args):
         given["field"] = True
     if args.min_retreat is not None:
         given["min_retreat"] = args.min_retreat
+    paths = {field: value for field, value in (("turn_deg", args.path_turn), ("length", args.path_length),
+                                               ("steps", args.path_steps)) if value is not None}
+    if args.path_pivot is not None:
+        paths["pivot"] = tuple(float(v) for v in args.path_pivot)
+    if args.approach_paths or paths or args.min_path is not None:
+        given["paths"] = paths or True
+        given["field"] = True
+    if args.min_path is not None:
+        given["min_path"] = args.min_path
     if args.approach_signed:
         given["field_signed"] = True
     if args.approach_field or args.approach_signed or "min_margin" in given or "field_max_distance" in given:
@@ -897,6 +932,22 @@ def build_parser():
                              "--approach-retreat)")
     parser.add_argument("--min-retreat", type=float, default=None,
                         help="select only grasps whose best retreat direction is free this far [m] (implies --approach-retreat)")
+    hand = approach_mod.PathParams()
+    parser.add_argument("--approach-paths", action="store_true",
+                        help="in volume space: take the hand through candidate trajectories of poses (five straight, four turning) "
+                             "against the distance field and add the picked path, the free and certified steps, its margin and the "
+                             "pre-grasp pose (implies --approach-field; the defaults are a choice nobody has measured on a robot)")
+    parser.add_argument("--path-turn", type=float, default=None,
+                        help="the angle the turning paths turn through, %g degrees unless given (implies --approach-paths)" % hand.turn_deg)
+    parser.add_argument("--path-length", type=float, default=None,
+                        help="how far every path translates, %g m unless given (implies --approach-paths)" % hand.length)
+    parser.add_argument("--path-steps", type=int, default=None,
+                        help="the steps a path is cut into, 1..64, %d unless given (implies --approach-paths)" % hand.steps)
+    parser.add_argument("--path-pivot", type=float, nargs=3, metavar=("X", "Y", "Z"), default=None,
+                        help="the point of the hand's local frame the turns are about, the origin unless given (implies "
+                             "--approach-paths)")
+    parser.add_argument("--min-path", type=float, default=None,
+                        help="select only grasps whose picked path is certified free this far [m] (implies --approach-paths)")
     parser.add_argument("--denoise", action="store_true",
                         help="remove the outliers of a camera frame's cloud before the table plane and the crop")
     regular("outliers")
