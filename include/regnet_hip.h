@@ -1798,6 +1798,59 @@ int regnet_grasp_path_check_signed_f32(const int32_t* field, int64_t nx, int64_t
                                        float half_space, float back_x, double step, float x_extent, int thresh, int32_t* profile,
                                        int32_t* result, float* disp, void* stream);
 
+/* ---- push-out (csrc/hand_adjust.hip): a colliding hand moved free along the signed field's gradient ------------------------------
+ * The margin, the fan and the paths judge a pose.  regnet_grasp_push_out_f32 MOVES the rigid hand of every grasp by a translation
+ * until its interpolated signed margin reaches `target`; the rotation is kept.  Deepest-sample projection: at every iterate the
+ * hand sample with the smallest interpolated signed distance is found, and the hand steps along the gradient there by the
+ * distance that is missing.  field is the SIGNED plane (there is no unsigned twin: an unsigned field has no inside); dims,
+ * origin3 (HOST), voxel, outside, L (B,12), the box arguments, x_hi_per_grasp, step and x_extent are the retreat fan's and mean
+ * the same; canonical fp32 arithmetic as everywhere in this family.
+ *   axes3       HOST, 3 float32: a factor per LOCAL axis (approach, closing, thickness) on the step; (1,1,1) moves freely,
+ *               (0,1,0) along the closing axis only.
+ *   target      metres, target_f = float32(target): the margin the hand is to reach.  max_shift: metres, cap2 = max_shift_f *
+ *               max_shift_f, one float32 product.  T: the most steps, 1..64.
+ *   samples     the fan's lattice (standoff = 0), HAND samples only (back || finger for the grasp's own x_hi, a sample that is
+ *               both counted once), membership decided in the local frame.  The sample (i, j, k) has the linear index
+ *               (i n_y + j) n_z + k.
+ *   pose        at iterate n the rows are L's rotation and the translation t_i = (((r_i0 s_0) + (r_i1 s_1)) + (r_i2 s_2)) + t0_i
+ *               = affine3(r_i0, r_i1, r_i2, t0_i, s) of the accumulated LOCAL shift s, recomputed from s at every applied step
+ *               and never accumulated in the volume's frame.  While no step has been applied the rows are L's own, bit for bit.
+ *   evaluate    for every hand sample w = affine3(row, x, y, z); an INSIDE sample (csrc/hand_lattice.h: grid_voxel) has the
+ *               value of regnet_edt_query_signed_f32 with interpolate = 1 at w (csrc/sdf_sample.h).  A sample that is OUTSIDE
+ *               or whose value is a NaN (infinite corners of an uncapped field) has no value and is counted as an OUTSIDE
+ *               lookup.  The minimum is over the 64-bit keys (ordered(value) << 32) | index with ordered(v) = b ^ ((b >> 31) |
+ *               0x80000000) of the value's bits b (an arithmetic shift): -0 sorts below +0, and of equal values the smallest
+ *               index wins.  low = the winning value, +inf when no sample has one.
+ *   decide      in this order, n the iterate:  1. no sample has a value and none was counted (the hand set is empty):
+ *               ALREADY_FREE.  2. no sample has a value, or outside = 1 and any was counted: LEFT_VOLUME.  3. low >= target_f:
+ *               ALREADY_FREE when n = 0, else FREED.  4. n == T: MAX_ITER.  5. g = the gradient of the interpolant at the worst
+ *               sample (the volume's frame), a_k = axes_k * dot3(column k of the rotation, g), e = target_f - low, d_k = e *
+ *               a_k, s'_k = s_k + d_k.  Any a_k a NaN, or d_0 == d_1 == d_2 == 0: STUCK.  !(dot3(s', s') <= cap2): CAPPED,
+ *               and the step is NOT applied.  Otherwise s = s' and iterate n + 1 is evaluated.
+ *   pose        (B,12) float32 DEVICE out: the final rows.  shift (B,3) float32: the local s.
+ *   trace       (B, T + 1) float32 or NULL: low at every evaluated iterate, the NaN 0x7fc00000 at the others.
+ *   info        (B,4) int32: { the status REGNET_PUSH_*, the steps applied, the worst sample's linear index at the last
+ *               evaluation or -1 when none had a value, the OUTSIDE lookups at the last evaluation }.
+ * One workgroup of 256 threads per grasp, the iteration inside the kernel, the tile walk of the approach analysis per iterate;
+ * the keys are reduced by the wave butterfly and the four waves through LDS (a minimum has no order), the count is an integer
+ * sum; every thread takes the same decision, so the exit is workgroup-uniform.  No floating-point sum, no global atomic, no host
+ * read, no allocation; capturable; two runs give the same bytes.  Errors, all before the launch and in the fan's order: B < 0, a
+ * dim < 1, outside not 0 / 1, T < 1 -> REGNET_ERR_SHAPE; a dim > 1024, N > 2^28, B >= 2^31, step or voxel not finite or not
+ * positive (in float32 too), T > 64, target not finite in float32, max_shift negative or not finite in float32, a non-finite
+ * axes3 (where it is given), a lattice count that is not finite or n_x n_y n_z > 2^22 -> REGNET_ERR_UNSUPPORTED; then B == 0:
+ * success without a launch; then a NULL field, origin3, L, axes3, pose, shift or info -> REGNET_ERR_NULL.                        */
+#define REGNET_PUSH_ALREADY_FREE 0
+#define REGNET_PUSH_FREED 1
+#define REGNET_PUSH_MAX_ITER 2
+#define REGNET_PUSH_CAPPED 3
+#define REGNET_PUSH_STUCK 4
+#define REGNET_PUSH_LEFT_VOLUME 5
+int regnet_grasp_push_out_f32(const int32_t* field, int64_t nx, int64_t ny, int64_t nz, const float* origin3, double voxel,
+                              int outside, const float* L, int64_t B, float x_lo, float x_hi, const float* x_hi_per_grasp,
+                              float half_thickness, float half_width, float half_space, float back_x, double step,
+                              float x_extent, const float* axes3, double target, double max_shift, int64_t T, float* pose,
+                              float* shift, float* trace, int32_t* info, void* stream);
+
 /* ---- next-best view (csrc/view_gain.hip): which candidate camera pose reveals the most of the space no view has observed --------
  * The approach analysis above reports the unobserved space a grasp's hand sweeps through; these entry points say where a camera
  * should go so that it becomes observed.  Integer results only; canonical fp32 arithmetic (individually rounded binary32

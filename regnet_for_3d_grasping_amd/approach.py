@@ -142,12 +142,19 @@ class ApproachParams(ParamsBase):
     # the hand paths are ``PathApproachParams``' fields; off here (class attributes, so that every reader may ask for them)
     paths = None
     min_path = None
+    # ... and the push-out is ``PushApproachParams'``
+    push = None
+    push_keep = "all"
 
     @classmethod
     def coerce(cls, value):
-        """``ParamsBase.coerce``; a dict that names ``paths`` or ``min_path`` becomes a ``PathApproachParams``."""
-        if cls is ApproachParams and isinstance(value, dict) and ("paths" in value or "min_path" in value):
-            return PathApproachParams(**value)
+        """``ParamsBase.coerce``; a dict that names ``paths`` or ``min_path`` becomes a ``PathApproachParams``, one that names
+        ``push`` or ``push_keep`` a ``PushApproachParams`` (which has the paths' fields too)."""
+        if cls is ApproachParams and isinstance(value, dict):
+            if "push" in value or "push_keep" in value:
+                return PushApproachParams(**value)
+            if "paths" in value or "min_path" in value:
+                return PathApproachParams(**value)
         return super().coerce(value)
 
     def filters(self):
@@ -186,6 +193,43 @@ class PathApproachParams(ApproachParams):
             if float(self.paths.min_margin) < 0.0 and not self.field_signed:
                 raise ValueError("approach: a negative paths min_margin is a tolerated penetration; it needs field_signed=True")
         super().__post_init__()
+
+
+PUSH_KEEP = ("all", "freed")       # what the selection sees of a pushed set: every grasp, or only those that have the target margin
+
+
+@dataclass
+class PushApproachParams(PathApproachParams):
+    """``PathApproachParams`` with the push-out (``approach.push_out``), both keyword-only.  ``push``: None, True (the defaults)
+    or a ``hand_adjust.PushParams`` / a dict of its fields: before anything else is analysed, move every hand that has less than
+    the target margin along the signed field's gradient; a grasp the move FREED is analysed -- classification, margins, fan and
+    paths -- at its moved centre, every other grasp as it was, and the record gains the status, the shift, the margin and the
+    moved centre.  ``push_keep``: ``"all"``, or ``"freed"``: a grasp that does not have the target margin after the push-out
+    (neither ALREADY_FREE nor FREED) is hidden from the selection.  Needs ``space="volume"``, ``field=True``,
+    ``field_signed=True`` and a ``field_max_distance`` (the interpolation needs finite corners).  Off by default
+    (``push=False`` is None).  A dict with either key handed to ``ApproachParams.coerce`` builds this class;
+    ``ApproachParams'`` own constructor is what it was.  The defaults of the push-out, too, are a choice nobody has measured on
+    a robot."""
+    push: Optional[object] = dataclass_field(default=None, kw_only=True)
+    push_keep: str = dataclass_field(default="all", kw_only=True)
+
+    def __post_init__(self):
+        if self.push is False:                    # off, as None is
+            self.push = None
+        if self.push_keep not in PUSH_KEEP:
+            raise ValueError("approach: push_keep must be one of %s, not %r" % (", ".join(PUSH_KEEP), self.push_keep))
+        if self.push is None and self.push_keep != "all":
+            raise ValueError("approach: push_keep is judged on the push-out; set push=True (or its parameters)")
+        if self.push is not None:
+            if self.space != "volume" or not self.field or not self.field_signed or self.field_max_distance is None:
+                raise ValueError("approach: push follows the gradient of the signed, capped distance field of the TSDF volume; set "
+                                 "space=\"volume\", field=True, field_signed=True and a field_max_distance")
+            from . import hand_adjust
+            self.push = hand_adjust.PushParams() if self.push is True else hand_adjust.PushParams.coerce(self.push)
+        super().__post_init__()
+
+    def filters(self):
+        return super().filters() or (self.push is not None and self.push_keep == "freed")
 
 
 def cos_friction(friction_deg):
@@ -308,7 +352,17 @@ def check_paths(volume, field, grasp, depth, width, params=None, to_volume=None,
     return hand_path.check_paths(volume, field, grasp, depth, width, params, to_volume, max_depth, rows, poses)
 
 
+def push_out(volume, field, grasp, depth, width, params=None, to_volume=None, max_depth=None, rows=None):
+    """Colliding hands moved free along the gradient of the volume's signed distance field: ``hand_adjust.push_out``, which is
+    imported only here (``approach.PushParams`` / ``approach.PushOut`` are its classes)."""
+    from . import hand_adjust
+    return hand_adjust.push_out(volume, field, grasp, depth, width, params, to_volume, max_depth, rows)
+
+
 def __getattr__(name):
+    if name in ("PushParams", "PushOut"):
+        from . import hand_adjust
+        return getattr(hand_adjust, name)
     if name == "VolumeApproach":
         from . import approach_volume
         return approach_volume.VolumeApproach

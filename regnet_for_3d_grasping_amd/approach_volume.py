@@ -57,6 +57,8 @@ class VolumeApproach(approach.Approach):
         self.margins, self.margin_counts, self._margin_metres = margins, margin_counts, margin_metres
         self.retreat = None                       # the ``retreat.RetreatFan`` of ``params.retreat``, set by ``analyse_volume``
         self.paths = None                         # the ``hand_path.PathCheck`` of ``params.paths``, set by ``analyse_volume``
+        self.push = None                          # the ``hand_adjust.PushOut`` of ``params.push``, set by ``analyse_volume``:
+                                                  # ``center`` and ``L`` are then the MOVED ones of the grasps it freed
 
     @property
     def margin_hand(self):
@@ -97,6 +99,10 @@ class VolumeApproach(approach.Approach):
             if self.paths is None:
                 raise ValueError("approach: min_path needs the hand paths; give analyse_volume field=... and params.paths")
             ok = ok & (self.paths.certified_length >= float(np.float32(self.params.min_path)))
+        if self.params.push is not None and self.params.push_keep == "freed":
+            if self.push is None:
+                raise ValueError("approach: push_keep needs the push-out; give analyse_volume field=... and params.push")
+            ok = ok & self.push.freed()
         return ok
 
     @property
@@ -183,12 +189,21 @@ def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, sur
     obstacle, and ``min_margin`` judges the signed value.  With ``params.retreat`` and a field the result's ``retreat`` is
     ``retreat.retreat_fan``'s ``RetreatFan`` of the same grasps (two launches more, on the ``L`` formed here); None without
     ``params.retreat``, and ``params.retreat`` without a field is a ValueError.  ``params.paths`` (``approach.PathApproachParams``)
-    likewise sets the result's ``paths`` to ``hand_path.check_paths``' ``PathCheck``."""
+    likewise sets the result's ``paths`` to ``hand_path.check_paths``' ``PathCheck``.
+
+    ``params.push`` (``approach.PushApproachParams``; it needs a signed, capped field) runs ``hand_adjust.push_out`` on the grasps
+    FIRST, one launch, and sets the result's ``push`` to its ``PushOut``.  A grasp it FREED is then analysed -- everything above:
+    classification, margins, contact, fan and paths -- at its moved centre: its row of ``L`` is the push-out's ``pose`` and its
+    row of the result's ``center`` is ``PushOut.moved_centres``'.  Every other grasp is analysed as it came, whatever the
+    push-out made of it.  The choice is a ``torch.where`` on the device: still no host read."""
     params = approach.ApproachParams.coerce(params) or approach.ApproachParams()
     if params.retreat is not None and field is None:
         raise ValueError("analyse_volume: params.retreat reads a distance field; give field=volume.distance_field(...)")
     if params.paths is not None and field is None:
         raise ValueError("analyse_volume: params.paths reads a distance field; give field=volume.distance_field(...)")
+    if params.push is not None and field is None:
+        raise ValueError("analyse_volume: params.push follows a distance field; give field=volume.distance_field(signed=True, "
+                         "max_distance=...)")
     p = volume.params
     require_cuda("grasp", grasp, torch.float32, 8, at_least=True, error=RuntimeError)
     dev = volume.device
@@ -201,6 +216,13 @@ def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, sur
     if per_grasp and not isinstance(depth, torch.Tensor):
         depth = to_device(np.asarray(depth, dtype=np.float32), dev)
     to_volume, frame, center, L = local_to_volume(grasp, to_volume)
+    pushed = None
+    if params.push is not None:                   # first: the grasps it frees are analysed where it left them
+        from . import hand_adjust
+        pushed = hand_adjust.push_out(volume, field, grasp, depth, width, params.push, to_volume, max_depth, rows=(frame, center, L))
+        moved = pushed.moved().unsqueeze(1)
+        L = torch.where(moved, pushed.pose, L).contiguous()
+        center = torch.where(moved, pushed.moved_centres(center, frame).to(center.dtype), center)
     box, keep = eval_collision._box_args(depth, width, B, dev)
     x_extent = float(max_depth) if per_grasp else float(depth)
     step = float(p.voxel) if params.step is None else float(params.step)
@@ -245,6 +267,7 @@ def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, sur
                   contact_values.data_ptr())
     result = VolumeApproach(counts, values, frame, center, params, box[5], contact_counts, L, T, samples, margins, margin_counts,
                             margin_metres)
+    result.push = pushed
     if params.retreat is not None:
         from . import retreat
         result.retreat = retreat.retreat_fan(volume, field, grasp, depth, width, params.retreat, to_volume, max_depth,

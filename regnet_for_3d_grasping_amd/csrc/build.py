@@ -54,6 +54,7 @@ SOURCES = [
     ("retreat.hip", ["-ffp-contract=off"]),   # retreat fan: every step's sample and voxel are decided on individually rounded fp32
     ("view_gain.hip", ["-ffp-contract=off"]),   # next-best view: every ray sample's voxel is decided on individually rounded fp32
     ("hand_path.hip", ["-ffp-contract=off"]),   # hand paths: every waypoint's sample, voxel and displacement are individually rounded fp32
+    ("hand_adjust.hip", ["-ffp-contract=off"]),   # push-out: every iterate's values, gradient and step are individually rounded fp32
 ]
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
           "-fno-gpu-rdc"]
@@ -90,7 +91,7 @@ NO_VGPR_SPILL = {"mlp.o": ["mlp_gemm_kernelILi0E", "gemm2_kernel"], "sa_chain.o"
                  "fuse.o": ["fuse_"], "icp.o": ["icp_"], "outlier.o": ["outlier_"], "tsdf.o": ["tsdf_"], "tsdf_mesh.o": ["tsdf_mesh_"],
                  "mesh_simplify.o": ["ms_"],
                  "approach.o": ["approach_kernel"], "approach_volume.o": ["approach_volume_"], "edt.o": ["edt_"],
-                 "retreat.o": ["retreat_"], "view_gain.o": ["view_"], "hand_path.o": ["hand_path_"]}
+                 "retreat.o": ["retreat_"], "view_gain.o": ["view_"], "hand_path.o": ["hand_path_"], "hand_adjust.o": ["push_out_"]}
 
 
 def check_no_vgpr_spill(obj_path, fragments):

@@ -21,8 +21,9 @@
 // positive value is 0 is an obstacle and takes minus its distance to free space; the tile, its bank argument and the tie rule are
 // unchanged.  A cap of c voxels ends every search at d > c and turns an intermediate above c^2 into NONE: a voxel whose true
 // squared distance is <= c^2 has every partial sum of its three terms <= c^2, so nothing it needs is lost; only the last pass
-// writes c^2 into the words still above it.  The signed query interpolates the signed metres trilinearly, in a pinned order.
-#include "hand_lattice.h"
+// writes c^2 into the words still above it.  The signed query interpolates the signed metres trilinearly, in a pinned order
+// (sdf_sample.h, which the push-out of hand_adjust.hip shares).
+#include "sdf_sample.h"
 
 namespace {
 
@@ -143,38 +144,11 @@ __device__ __forceinline__ float edt_metres(int d2, float voxel) {
   return d2 >= EDT_NONE ? __builtin_inff() : (sqrtf((float)d2) * voxel) + 0.0f;
 }
 
-// a signed word s: a = sqrtf((float)|s|), then (a - 0.5f) * voxel with the sign of s -- the distance to the boundary FACE between
-// the classes, not to a voxel centre; every operation rounded on its own
-__device__ __forceinline__ float sdf_metres(int s, float voxel) {
-  const int a2 = s < 0 ? -s : s;
-  if (a2 >= EDT_NONE) return s < 0 ? -__builtin_inff() : __builtin_inff();
-  const float a = sqrtf((float)a2);
-  const float h = a - 0.5f;
-  const float m = h * voxel;
-  return copysignf(m, (float)s) + 0.0f;
-}
-
-__device__ __forceinline__ float sdf_lerp(float a, float b, float t) {
-  const float d = b - a;
-  const float s = t * d;
-  return a + s;
-}
-
 __device__ __forceinline__ float canonical_nan(float v) { return v != v ? __builtin_nanf("") : v; }
 
 struct Rows12 {
   float r[3][4];
 };
-
-// one axis of the trilinear query: u = (w - o) / voxel - 0.5, the two corner indices clamped into the lattice, and the weight
-__device__ __forceinline__ void sdf_axis(float w, float o, float voxel, int n, int& i0, int& i1, float& t) {
-  const float u = __fdiv_rn(w - o, voxel) - 0.5f;
-  const float f = floorf(u);
-  t = u - f;
-  const int i = (int)f;                              // (the point is INSIDE: -1 <= f <= n - 1)
-  i0 = min(max(i, 0), n - 1);
-  i1 = min(max(i + 1, 0), n - 1);
-}
 
 __global__ __launch_bounds__(EDT_T) void edt_query_signed_kernel(const int32_t* __restrict__ field,
                                                                  const int32_t* __restrict__ nearest, VoxelGrid grid,
@@ -193,29 +167,7 @@ __global__ __launch_bounds__(EDT_T) void edt_query_signed_kernel(const int32_t* 
   if (grid_voxel(grid, wx, wy, wz, v)) {
     const float vox = grid.voxel;
     if (interpolate) {
-      int x0, x1, y0, y1, z0, z1;
-      float tx, ty, tz;
-      sdf_axis(wx, grid.ox, vox, grid.nx, x0, x1, tx);
-      sdf_axis(wy, grid.oy, vox, grid.ny, y0, y1, ty);
-      sdf_axis(wz, grid.oz, vox, grid.nz, z0, z1, tz);
-      const int64_t r00 = ((int64_t)z0 * grid.ny + y0) * grid.nx, r10 = ((int64_t)z0 * grid.ny + y1) * grid.nx;
-      const int64_t r01 = ((int64_t)z1 * grid.ny + y0) * grid.nx, r11 = ((int64_t)z1 * grid.ny + y1) * grid.nx;
-      // c[z][y][x]
-      const float c000 = sdf_metres(field[r00 + x0], vox), c001 = sdf_metres(field[r00 + x1], vox);
-      const float c010 = sdf_metres(field[r10 + x0], vox), c011 = sdf_metres(field[r10 + x1], vox);
-      const float c100 = sdf_metres(field[r01 + x0], vox), c101 = sdf_metres(field[r01 + x1], vox);
-      const float c110 = sdf_metres(field[r11 + x0], vox), c111 = sdf_metres(field[r11 + x1], vox);
-      dist = sdf_lerp(sdf_lerp(sdf_lerp(c000, c001, tx), sdf_lerp(c010, c011, tx), ty),
-                      sdf_lerp(sdf_lerp(c100, c101, tx), sdf_lerp(c110, c111, tx), ty), tz);
-      if (gradient) {
-        // per axis the four differences of the corner values along it over the voxel, lerped over the other two axes, x before y before z
-        gx = sdf_lerp(sdf_lerp(__fdiv_rn(c001 - c000, vox), __fdiv_rn(c011 - c010, vox), ty),
-                      sdf_lerp(__fdiv_rn(c101 - c100, vox), __fdiv_rn(c111 - c110, vox), ty), tz);
-        gy = sdf_lerp(sdf_lerp(__fdiv_rn(c010 - c000, vox), __fdiv_rn(c011 - c001, vox), tx),
-                      sdf_lerp(__fdiv_rn(c110 - c100, vox), __fdiv_rn(c111 - c101, vox), tx), tz);
-        gz = sdf_lerp(sdf_lerp(__fdiv_rn(c100 - c000, vox), __fdiv_rn(c101 - c001, vox), tx),
-                      sdf_lerp(__fdiv_rn(c110 - c010, vox), __fdiv_rn(c111 - c011, vox), tx), ty);
-      }
+      dist = sdf_sample(field, grid, wx, wy, wz, gradient != nullptr, gx, gy, gz);
     } else {
       dist = sdf_metres(field[v], vox);
     }

@@ -57,7 +57,32 @@ __device__ __forceinline__ VoxelClass voxel_class(const VolumeView& vol, bool in
 
 // The walk of one workgroup of HL_T threads over the lattice: a wave takes 8 x 8 tiles of the x-y plane, tile t = wave, wave + 4,
 // ..., lane l at (l & 7, l >> 3) of the tile, and walks the n_z layers.  visit(x, y, z, sets) is called for every sample of
-// this thread, with hand_box.h's sets for the grasp's own x_hi.
+// this thread, with hand_box.h's sets for the grasp's own x_hi.  lattice_walk_at also hands over the sample's place (i, j, k) in
+// the lattice; lattice_point gives the coordinates of a place again, with the walk's own arithmetic.
+__device__ __forceinline__ void lattice_point(const Lattice& lat, const GraspBox& box, int i, int j, int k, float& x, float& y,
+                                              float& z) {
+  x = lat.xs + (((float)i + 0.5f) * lat.h);
+  y = (((float)j + 0.5f) * lat.h) - box.half_width;
+  z = (((float)k + 0.5f) * lat.h) - box.half_thickness;
+}
+
+template <typename Visit>
+__device__ __forceinline__ void lattice_walk_at(const Lattice& lat, const GraspBox& box, float x_hi, Visit visit) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int tiles_x = (lat.nx + HL_TILE - 1) / HL_TILE, tiles_y = (lat.ny + HL_TILE - 1) / HL_TILE;
+  const int tiles = tiles_x * tiles_y;
+  for (int t = wave; t < tiles; t += HL_W) {
+    const int ty = t / tiles_x, tx = t - ty * tiles_x;
+    const int i = tx * HL_TILE + (lane & (HL_TILE - 1)), j = ty * HL_TILE + (lane >> 3);
+    if (i >= lat.nx || j >= lat.ny) continue;
+    for (int k = 0; k < lat.nz; ++k) {
+      float x, y, z;
+      lattice_point(lat, box, i, j, k, x, y, z);
+      visit(i, j, k, x, y, z, hand_sets(box, x_hi, lat.xs, x, y, z));
+    }
+  }
+}
+
 template <typename Visit>
 __device__ __forceinline__ void lattice_walk(const Lattice& lat, const GraspBox& box, float x_hi, Visit visit) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;

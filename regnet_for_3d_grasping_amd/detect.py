@@ -53,6 +53,9 @@ With ``paths`` (``--approach-paths``, ``--path-turn``, ``--path-length``, ``--pa
 is taken through candidate trajectories of POSES against that field (``approach.check_paths``: the fan's five directions and four
 turns of the straight retreat) and ``APPROACH_PATH_KEYS`` follow; ``min_path`` selects on the picked path's certified length.  The
 fan and the paths are independent.
+With ``push`` (``--approach-push``, ``--push-target``, ``--push-max-shift``, ``--push-iterations``, ``--push-axes``,
+``--push-keep``) every hand that has less than the target margin is first moved along the signed field's gradient
+(``approach.push_out``); a grasp that move freed is analysed at its moved centre and ``APPROACH_PUSH_KEYS`` follow.
 
 With ``denoise`` (``--denoise``, ``--outlier-mode``, ``--outlier-radius``, ``--outlier-min-neighbours``, ``--outlier-knn``,
 ``--outlier-max-radius``, ``--outlier-std-ratio``) the cloud of a camera frame -- an ``(xyz, rgb)`` pair, a depth frame's or a
@@ -121,6 +124,11 @@ APPROACH_PATH_KEYS = ("grasp_path_index", "grasp_path_steps", "grasp_path_certif
                                                   # certified steps of all paths, the picked path's margin and the pre-grasp POSE
                                                   # (B,12): rows 0..2 of the hand's pose at the picked path's last free step, in
                                                   # the grasps' frame
+APPROACH_PUSH_KEYS = ("grasp_push_status", "grasp_push_shift", "grasp_push_margin",
+                      "grasp_push_centre")        # ... and after those with ``push``: the push-out's status (an index into
+                                                  # ``hand_adjust.STATUS``), the (B,3) move in the hand's LOCAL frame, the margin
+                                                  # at its last iterate, and the (B,3) centre the grasp was analysed at, in the
+                                                  # grasps' frame: the moved one where the status is FREED
 TSDF_KEYS = ("tsdf_num", "tsdf_counts")                        # added when the frame was a ``MultiView`` and the detector has ``volume``
 TRACK_KEYS = ("track_pose", "track_status", "track_report")    # added beside ``TSDF_KEYS`` when the detector has ``track``
 TSDF_MESH_KEYS = ("tsdf_triangles", "tsdf_vertices", "tsdf_vertex_normals",
@@ -494,6 +502,8 @@ class GraspDetector:
             check = result.paths
             extra.update(zip(APPROACH_PATH_KEYS, (check.index, check.free_steps, check.certified_steps(), check.margin,
                                                   _rows_to_frame(transform, check.waypoint))))
+        if result.push is not None:
+            extra.update(zip(APPROACH_PUSH_KEYS, (result.push.status, result.push.shift, result.push.margin, result.center)))
         ok = result.passes() if self.approach.filters() else None
         passing = ok.nonzero().view(-1) if ok is not None else None
         return extra, passing
@@ -816,6 +826,15 @@ def approach_from_args(args):
         given["field"] = True
     if args.min_path is not None:
         given["min_path"] = args.min_path
+    push = {field: value for field, value in (("target", args.push_target), ("max_shift", args.push_max_shift),
+                                              ("iterations", args.push_iterations)) if value is not None}
+    if args.push_axes is not None:
+        push["axes"] = tuple(float(v) for v in args.push_axes)
+    if args.approach_push or push or args.push_keep is not None:
+        given["push"] = push or True
+        given["field"] = given["field_signed"] = True
+    if args.push_keep is not None:
+        given["push_keep"] = args.push_keep
     if args.approach_signed:
         given["field_signed"] = True
     if args.approach_field or args.approach_signed or "min_margin" in given or "field_max_distance" in given:
@@ -948,6 +967,23 @@ def build_parser():
                              "--approach-paths)")
     parser.add_argument("--min-path", type=float, default=None,
                         help="select only grasps whose picked path is certified free this far [m] (implies --approach-paths)")
+    shove = approach_mod.PushParams()
+    parser.add_argument("--approach-push", action="store_true",
+                        help="in volume space: first move every hand that has less than the target margin along the gradient of the "
+                             "signed distance field, analyse the grasps that move freed at their moved centre and add the status, "
+                             "the shift, the margin and that centre (implies --approach-signed; it needs --approach-field-cap; the "
+                             "defaults are a choice nobody has measured on a robot)")
+    parser.add_argument("--push-target", type=float, default=None,
+                        help="the signed margin the hand is moved to, %g m unless given (implies --approach-push)" % shove.target)
+    parser.add_argument("--push-max-shift", type=float, default=None,
+                        help="the longest move of a hand, %g m unless given (implies --approach-push)" % shove.max_shift)
+    parser.add_argument("--push-iterations", type=int, default=None,
+                        help="the most steps of a move, 1..64, %d unless given (implies --approach-push)" % shove.iterations)
+    parser.add_argument("--push-axes", type=float, nargs=3, metavar=("X", "Y", "Z"), default=None,
+                        help="a factor per local axis of the hand (approach, closing, thickness) on every step, 1 1 1 unless given; "
+                             "0 1 0 re-centres along the closing axis only (implies --approach-push)")
+    parser.add_argument("--push-keep", choices=("all", "freed"), default=None,
+                        help="freed: select only grasps that have the target margin after the move (implies --approach-push)")
     parser.add_argument("--denoise", action="store_true",
                         help="remove the outliers of a camera frame's cloud before the table plane and the crop")
     regular("outliers")
