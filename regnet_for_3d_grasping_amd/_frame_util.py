@@ -53,6 +53,16 @@ def require_cuda(name, t, dtype=None, cols=None, at_least=False, error=None):
     return t
 
 
+def check_step(word, step):
+    """A parameter class' ``step``, the distance between two samples of the hand: None, or positive and finite as a float32 too;
+    else a ValueError that opens with ``word``."""
+    if step is not None:
+        with np.errstate(over="ignore", under="ignore"):
+            step32 = np.float32(step)
+        if not (float(step) > 0.0 and step32 > 0.0 and np.isfinite(step32)):
+            raise ValueError("%s: step must be None or positive and finite in float32" % word)
+
+
 def stream_scope(stream):
     """The context in which work is launched on ``stream`` (None: the current stream, nothing to enter)."""
     if stream is None:

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib, eval_collision, grasp_select
-from ._frame_util import ParamsBase, require_cuda, to_device
+from ._frame_util import ParamsBase, check_step, require_cuda, to_device
 
 SPACES = ("cloud", "volume")        # what the hand is held against: ``analyse``'s points or ``analyse_volume``'s TSDF volume
 UNSEEN = ("free", "blocked")        # what ``analyse_volume``'s clearance makes of space no camera has seen
@@ -121,11 +121,7 @@ class ApproachParams(ParamsBase):
             raise ValueError("approach: space must be one of %s, not %r" % (", ".join(SPACES), self.space))
         if self.unseen not in UNSEEN:
             raise ValueError("approach: unseen must be one of %s, not %r" % (", ".join(UNSEEN), self.unseen))
-        if self.step is not None:
-            with np.errstate(over="ignore", under="ignore"):
-                step32 = np.float32(self.step)
-            if not (float(self.step) > 0.0 and step32 > 0.0 and np.isfinite(step32)):
-                raise ValueError("approach: step must be None or positive and finite in float32")
+        check_step("approach", self.step)
         if not (float(self.margin) >= 0.0 and np.isfinite(self.margin)):
             raise ValueError("approach: margin must be non-negative and finite")
         if self.source is not None and self.source not in grasp_select.SOURCES:

@@ -167,6 +167,43 @@ def local_to_volume(grasp, to_volume):
     return to_volume, frame, center, L
 
 
+def hand_call(who, volume, grasp, depth, max_depth):
+    """The opening of every function that holds the hand's sample lattice against ``volume`` or its distance field (``who``: its
+    name, for the messages): the grasps are (B, >=8) float32 on the volume's device, and a depth per grasp needs ``max_depth`` and
+    goes to the device.  -> (the device, B, ``depth``, ``x_extent``: the far end of the lattice).  The caller's own rules and
+    its rows come next, then ``hand_lattice``."""
+    require_cuda("grasp", grasp, torch.float32, 8, at_least=True, error=RuntimeError)
+    dev = volume.device
+    if grasp.device != dev:
+        raise RuntimeError("%s: the grasps are on %s, the volume on %s" % (who, grasp.device, dev))
+    per_grasp = (isinstance(depth, torch.Tensor) and depth.dim() > 0) or (not isinstance(depth, torch.Tensor) and np.ndim(depth) > 0)
+    if per_grasp and max_depth is None:
+        raise ValueError("%s: with one depth per grasp give max_depth, the far end of the sample lattice" % who)
+    if per_grasp and not isinstance(depth, torch.Tensor):
+        depth = to_device(np.asarray(depth, dtype=np.float32), dev)
+    return dev, int(grasp.shape[0]), depth, float(max_depth) if per_grasp else float(depth)
+
+
+def hand_lattice(who, volume, depth, width, B, step, standoff, x_extent):
+    """The box and the lattice of a call that ``hand_call`` opened -> (``eval_collision._box_args``' tuple, the tensor it points
+    into -- keep it until the launch --, the step [m], (n_x, n_y, n_z)).  ``step``: None is the volume's voxel; ``standoff``: how
+    far the hand is swept, None for the hand at its final pose.  More than 2^22 samples are a ValueError."""
+    box, keep = eval_collision._box_args(depth, width, B, volume.device)
+    step = float(volume.params.voxel) if step is None else float(step)
+    samples = lattice(box, 0.0 if standoff is None else standoff, step, x_extent)
+    if samples[0] * samples[1] * samples[2] > MAX_SAMPLES:
+        raise ValueError("%s: %d x %d x %d samples of the %s, more than 2^22; raise step"
+                         % ((who,) + samples + ("hand" if standoff is None else "swept hand",)))
+    return box, keep, step, samples
+
+
+def require_field(who, volume, field):
+    """``field`` must be a ``tsdf.DistanceField`` of ``volume`` -- the same dims, on its device -- else a ValueError."""
+    if not (hasattr(field, "dist2") and hasattr(field, "metres")) or tuple(field.dims) != tuple(volume.params.dims) \
+            or field.dist2.device != volume.device:
+        raise ValueError("%s: the field must be a DistanceField of this volume (same dims, same device)" % who)
+
+
 def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, surface=None, max_depth=None, field=None):
     """``volume``: a ``tsdf.Volume``; ``grasp`` (B, >=8) float32 on its device; ``depth``: a float or one depth per grasp -- then
     ``max_depth``, a bound on them, is the lattice's far end (nothing is read back to find it; a ValueError without it);
@@ -205,16 +242,7 @@ def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, sur
         raise ValueError("analyse_volume: params.push follows a distance field; give field=volume.distance_field(signed=True, "
                          "max_distance=...)")
     p = volume.params
-    require_cuda("grasp", grasp, torch.float32, 8, at_least=True, error=RuntimeError)
-    dev = volume.device
-    if grasp.device != dev:
-        raise RuntimeError("analyse_volume: the grasps are on %s, the volume on %s" % (grasp.device, dev))
-    B = int(grasp.shape[0])
-    per_grasp = (isinstance(depth, torch.Tensor) and depth.dim() > 0) or (not isinstance(depth, torch.Tensor) and np.ndim(depth) > 0)
-    if per_grasp and max_depth is None:
-        raise ValueError("analyse_volume: with one depth per grasp give max_depth, the far end of the sample lattice")
-    if per_grasp and not isinstance(depth, torch.Tensor):
-        depth = to_device(np.asarray(depth, dtype=np.float32), dev)
+    dev, B, depth, x_extent = hand_call("analyse_volume", volume, grasp, depth, max_depth)
     to_volume, frame, center, L = local_to_volume(grasp, to_volume)
     pushed = None
     if params.push is not None:                   # first: the grasps it frees are analysed where it left them
@@ -223,12 +251,7 @@ def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, sur
         moved = pushed.moved().unsqueeze(1)
         L = torch.where(moved, pushed.pose, L).contiguous()
         center = torch.where(moved, pushed.moved_centres(center, frame).to(center.dtype), center)
-    box, keep = eval_collision._box_args(depth, width, B, dev)
-    x_extent = float(max_depth) if per_grasp else float(depth)
-    step = float(p.voxel) if params.step is None else float(params.step)
-    samples = lattice(box, params.standoff, step, x_extent)
-    if samples[0] * samples[1] * samples[2] > MAX_SAMPLES:
-        raise ValueError("analyse_volume: %d x %d x %d samples of the swept hand, more than 2^22; raise step" % samples)
+    box, keep, step, samples = hand_lattice("analyse_volume", volume, depth, width, B, params.step, params.standoff, x_extent)
     nx, ny, nz = p.dims
     counts = torch.empty((B, 8), dtype=torch.int32, device=dev)
     values = torch.empty((B, 4), dtype=torch.float32, device=dev)
@@ -237,8 +260,7 @@ def analyse_volume(volume, grasp, depth, width, params=None, to_volume=None, sur
               float(params.standoff), step, x_extent, counts.data_ptr(), values.data_ptr())
     margins = margin_counts = margin_metres = None
     if field is not None:
-        if tuple(field.dims) != tuple(p.dims) or field.dist2.device != dev:
-            raise ValueError("analyse_volume: the field must be a DistanceField of this volume (same dims, same device)")
+        require_field("analyse_volume", volume, field)
         margins = torch.empty((B, 2), dtype=torch.int32, device=dev)
         signed = field.signed
         margin_counts = torch.empty((B, 6 if signed else 4), dtype=torch.int32, device=dev)

@@ -101,20 +101,16 @@ extern "C" int regnet_grasp_approach_volume_f32(const void* volume, int64_t nx, 
   if (B >= (int64_t)1 << 31 || min_weight >= (int64_t)1 << 31) return REGNET_ERR_UNSUPPORTED;
   float voxel_f, trunc_f, h;
   if (!positive_f32(voxel, &voxel_f) || !positive_f32(trunc, &trunc_f) || !positive_f32(step, &h)) return REGNET_ERR_UNSUPPORTED;
-  if (!(standoff >= 0.0f) || standoff == __builtin_inff()) return REGNET_ERR_UNSUPPORTED;   // negative, NaN or infinite
   const float d_solid = (float)(margin / trunc);
-  if (!(d_solid == d_solid) || d_solid == __builtin_inff() || d_solid == -__builtin_inff()) return REGNET_ERR_UNSUPPORTED;
-  Lattice lat;
-  if (!lattice_of(x_lo, standoff, half_thickness, half_width, x_extent, h, &lat)) return REGNET_ERR_UNSUPPORTED;
-  if (B == 0) return REGNET_OK;
-  if (!volume || !origin3 || !L || !counts || !values) return REGNET_ERR_NULL;
-  const int64_t n = nx * ny * nz;
-  const Planes planes = planes_of(const_cast<void*>(volume), n);
-  const VolumeView vol{planes.D, planes.W, VoxelGrid{(int)nx, (int)ny, (int)nz, origin3[0], origin3[1], origin3[2], voxel_f},
-                       d_solid, (int)min_weight};
+  if (!finite_f32(d_solid)) return REGNET_ERR_UNSUPPORTED;
+  LatticeCall call{VoxelGrid{(int)nx, (int)ny, (int)nz, 0.0f, 0.0f, 0.0f, voxel_f}, Lattice{}, h};
   const GraspBox box{x_lo, x_hi, half_thickness, half_width, half_space, back_x};
+  const int status = lattice_call_tail(&call, box, standoff, x_extent, B, origin3, volume && L && counts && values);
+  if (status != REGNET_OK || B == 0) return status;
+  const Planes planes = planes_of(const_cast<void*>(volume), nx * ny * nz);
+  const VolumeView vol{planes.D, planes.W, call.grid, d_solid, (int)min_weight};
   hipLaunchKernelGGL(approach_volume_kernel, dim3((unsigned)B), dim3(AV_T), 0, as_stream(stream), vol, L, box, x_hi_per_grasp,
-                     standoff, lat, counts, values);
+                     standoff, call.lat, counts, values);
   REGNET_LAUNCH_CHECK();
   return REGNET_OK;
 }

@@ -247,16 +247,15 @@ __global__ __launch_bounds__(HL_T) void edt_margin_kernel(const int32_t* __restr
     if (!(hand || in.blocker)) return;               // not in the swept set: no lookup
     float wx, wy, wz;
     grasp_apply(g, x, y, z, wx, wy, wz);
-    int64_t v;
-    const bool inside = grid_voxel(grid, wx, wy, wz, v);
+    int d2;
+    const FieldLookup at = field_lookup<SIGNED>(dist2, grid, outside, wx, wy, wz, d2);
     sweep_n += 1;
     hand_n += (int)hand;
-    if (!inside) {
+    if (!at.inside) {
       sweep_out += 1;
       hand_out += (int)hand;
-      if (!outside) return;                          // skipped; else it lies in an obstacle: 0 (signed: -1)
     }
-    const int d2 = inside ? dist2[v] : (SIGNED ? -1 : 0);
+    if (!at.has_value) return;                       // an OUTSIDE sample under outside = 0: counted and skipped
     sweep_min = min(sweep_min, d2);
     if (hand) hand_min = min(hand_min, d2);
     if (SIGNED && d2 < 0) {
@@ -280,8 +279,6 @@ __global__ __launch_bounds__(HL_T) void edt_margin_kernel(const int32_t* __restr
     margins[(int64_t)blockIdx.x * 2 + 1] = block_min<HL_W>(red_m[1]);
   }
 }
-
-bool finite_f32(float f) { return f == f && f != __builtin_inff() && f != -__builtin_inff(); }
 
 // log2 of the lines per tile of a pass along an axis of n voxels: the largest of 64, 32, 16, 8 within 64 KiB
 int tile_log(int64_t n, int words) {
@@ -464,21 +461,14 @@ int margin_volume(const int32_t* dist2, int64_t nx, int64_t ny, int64_t nz, cons
                   const float* L, int64_t B, float x_lo, float x_hi, const float* x_hi_per_grasp, float half_thickness,
                   float half_width, float half_space, float back_x, float standoff, double step, float x_extent, int32_t* margins,
                   int32_t* counts, void* stream) {
-  if (B < 0 || outside < 0 || outside > 1) return REGNET_ERR_SHAPE;
-  const int dims = field_dims(nx, ny, nz);
-  if (dims != REGNET_OK) return dims;
-  if (B >= (int64_t)1 << 31) return REGNET_ERR_UNSUPPORTED;
-  float voxel_f, h;
-  if (!positive_f32(voxel, &voxel_f) || !positive_f32(step, &h)) return REGNET_ERR_UNSUPPORTED;
-  if (!(standoff >= 0.0f) || standoff == __builtin_inff()) return REGNET_ERR_UNSUPPORTED;   // negative, NaN or infinite
-  Lattice lat;
-  if (!lattice_of(x_lo, standoff, half_thickness, half_width, x_extent, h, &lat)) return REGNET_ERR_UNSUPPORTED;
-  if (B == 0) return REGNET_OK;
-  if (!dist2 || !origin3 || !L || !margins || !counts) return REGNET_ERR_NULL;
-  const VoxelGrid grid{(int)nx, (int)ny, (int)nz, origin3[0], origin3[1], origin3[2], voxel_f};
+  LatticeCall call;
+  int status = field_call_checks(nx, ny, nz, voxel, outside, B, step, &call);
+  if (status != REGNET_OK) return status;
   const GraspBox box{x_lo, x_hi, half_thickness, half_width, half_space, back_x};
-  hipLaunchKernelGGL(edt_margin_kernel<SIGNED>, dim3((unsigned)B), dim3(HL_T), 0, as_stream(stream), dist2, grid, outside, L, box,
-                     x_hi_per_grasp, lat, margins, counts);
+  status = lattice_call_tail(&call, box, standoff, x_extent, B, origin3, dist2 && L && margins && counts);
+  if (status != REGNET_OK || B == 0) return status;
+  hipLaunchKernelGGL(edt_margin_kernel<SIGNED>, dim3((unsigned)B), dim3(HL_T), 0, as_stream(stream), dist2, call.grid, outside, L,
+                     box, x_hi_per_grasp, call.lat, margins, counts);
   REGNET_LAUNCH_CHECK();
   return REGNET_OK;
 }

@@ -122,8 +122,6 @@ __global__ __launch_bounds__(HL_T) void push_out_kernel(const int32_t* __restric
   }
 }
 
-bool finite_f32(float f) { return f == f && f != __builtin_inff() && f != -__builtin_inff(); }
-
 }  // namespace
 
 extern "C" int regnet_grasp_push_out_f32(const int32_t* field, int64_t nx, int64_t ny, int64_t nz, const float* origin3,
@@ -132,25 +130,20 @@ extern "C" int regnet_grasp_push_out_f32(const int32_t* field, int64_t nx, int64
                                          float back_x, double step, float x_extent, const float* axes3, double target,
                                          double max_shift, int64_t T, float* pose, float* shift, float* trace, int32_t* info,
                                          void* stream) {
-  if (B < 0 || outside < 0 || outside > 1 || T < 1) return REGNET_ERR_SHAPE;
-  const int dims = field_dims(nx, ny, nz);
-  if (dims != REGNET_OK) return dims;
-  if (B >= (int64_t)1 << 31) return REGNET_ERR_UNSUPPORTED;
-  float voxel_f, h;
-  if (!positive_f32(voxel, &voxel_f) || !positive_f32(step, &h)) return REGNET_ERR_UNSUPPORTED;
+  if (T < 1) return REGNET_ERR_SHAPE;                // (with the opening checks' own SHAPE rules: one status)
+  LatticeCall call;
+  int status = field_call_checks(nx, ny, nz, voxel, outside, B, step, &call);
+  if (status != REGNET_OK) return status;
   if (T > PO_MAX_T) return REGNET_ERR_UNSUPPORTED;
   const float target_f = (float)target, cap_f = (float)max_shift;
   if (!finite_f32(target_f) || !(max_shift >= 0.0) || !(cap_f >= 0.0f) || !finite_f32(cap_f)) return REGNET_ERR_UNSUPPORTED;
   if (axes3 && !(finite_f32(axes3[0]) && finite_f32(axes3[1]) && finite_f32(axes3[2]))) return REGNET_ERR_UNSUPPORTED;
-  Lattice lat;
-  if (!lattice_of(x_lo, 0.0f, half_thickness, half_width, x_extent, h, &lat)) return REGNET_ERR_UNSUPPORTED;
-  if (B == 0) return REGNET_OK;
-  if (!field || !origin3 || !L || !axes3 || !pose || !shift || !info) return REGNET_ERR_NULL;
-  const VoxelGrid grid{(int)nx, (int)ny, (int)nz, origin3[0], origin3[1], origin3[2], voxel_f};
   const GraspBox box{x_lo, x_hi, half_thickness, half_width, half_space, back_x};
+  status = lattice_call_tail(&call, box, 0.0f, x_extent, B, origin3, field && L && axes3 && pose && shift && info);
+  if (status != REGNET_OK || B == 0) return status;
   const Push push{axes3[0], axes3[1], axes3[2], target_f, cap_f * cap_f, (int)T};
-  hipLaunchKernelGGL(push_out_kernel, dim3((unsigned)B), dim3(HL_T), 0, as_stream(stream), field, grid, outside, L, box,
-                     x_hi_per_grasp, lat, push, pose, shift, trace, info);
+  hipLaunchKernelGGL(push_out_kernel, dim3((unsigned)B), dim3(HL_T), 0, as_stream(stream), field, call.grid, outside, L, box,
+                     x_hi_per_grasp, call.lat, push, pose, shift, trace, info);
   REGNET_LAUNCH_CHECK();
   return REGNET_OK;
 }

@@ -1,8 +1,9 @@
-// hand_lattice.h -- the lattice of samples of the swept hand and its lookup in a voxel grid, shared by approach_volume.hip (which
-// classifies the sample's voxel of the TSDF volume) and edt.hip's margin kernel (which reads the distance field there): the
-// lattice's counts on the host, the tile walk of a workgroup of 256 threads, and the sample's nearest voxel.  include/regnet_hip.h
-// ("approach analysis against the TSDF volume": lattice, sets, lookup) is the contract of all three.  The translation unit must
-// be built with -ffp-contract=off (hand_box.h).
+// hand_lattice.h -- the lattice of samples of the swept hand and its lookup in a voxel grid, shared by every kernel that holds the
+// hand against the TSDF volume (approach_volume.hip, view_gain.hip's interest kernel: voxel_class) or against its distance field
+// (edt.hip's margin kernel, retreat.hip, hand_path.hip: field_lookup; hand_adjust.hip interpolates, sdf_sample.h): the lattice's
+// counts and an entry point's checks on the host, the tile walk of a workgroup of 256 threads, and the sample's nearest voxel.
+// include/regnet_hip.h ("approach analysis against the TSDF volume": lattice, sets, lookup) is the contract of them all.  The
+// translation unit must be built with -ffp-contract=off (hand_box.h).
 #pragma once
 #include "hand_box.h"
 #include "tsdf_volume.h"
@@ -55,6 +56,22 @@ __device__ __forceinline__ VoxelClass voxel_class(const VolumeView& vol, bool in
   return d < vol.d_solid ? VC_SOLID : VC_FREE;
 }
 
+// THE value of a looked-up voxel of a distance field (include/regnet_hip.h "distance field", the OUTSIDE rule): the field's word
+// of the nearest voxel; a point outside the grid has no value when outside = 0 (the sample is skipped) and else lies in an
+// obstacle: 0, or -1 of a SIGNED field (an obstacle of unknown depth; 0 is not a value of a signed field).
+struct FieldLookup {
+  bool inside, has_value;
+};
+
+template <bool SIGNED>
+__device__ __forceinline__ FieldLookup field_lookup(const int32_t* __restrict__ field, const VoxelGrid& grid, int outside, float wx,
+                                                    float wy, float wz, int& value) {
+  int64_t v;
+  const bool inside = grid_voxel(grid, wx, wy, wz, v);
+  value = inside ? field[v] : (SIGNED ? -1 : 0);
+  return FieldLookup{inside, inside || outside != 0};
+}
+
 // The walk of one workgroup of HL_T threads over the lattice: a wave takes 8 x 8 tiles of the x-y plane, tile t = wave, wave + 4,
 // ..., lane l at (l & 7, l >> 3) of the tile, and walks the n_z layers.  visit(x, y, z, sets) is called for every sample of
 // this thread, with hand_box.h's sets for the grasp's own x_hi.  lattice_walk_at also hands over the sample's place (i, j, k) in
@@ -70,7 +87,7 @@ template <typename Visit>
 __device__ __forceinline__ void lattice_walk_at(const Lattice& lat, const GraspBox& box, float x_hi, Visit visit) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int tiles_x = (lat.nx + HL_TILE - 1) / HL_TILE, tiles_y = (lat.ny + HL_TILE - 1) / HL_TILE;
-  const int tiles = tiles_x * tiles_y;
+  const int tiles = tiles_x * tiles_y;               // (at most 2^22 samples in all: no overflow)
   for (int t = wave; t < tiles; t += HL_W) {
     const int ty = t / tiles_x, tx = t - ty * tiles_x;
     const int i = tx * HL_TILE + (lane & (HL_TILE - 1)), j = ty * HL_TILE + (lane >> 3);
@@ -83,6 +100,9 @@ __device__ __forceinline__ void lattice_walk_at(const Lattice& lat, const GraspB
   }
 }
 
+// (Kept beside lattice_walk_at, whose expressions it shares, out of caution: as a wrapper over it no check failed, but
+// approach_volume_kernel and view_interest_kernel came out as other code, and as it stands they are unchanged;
+// profiles/hand_field_refactor.txt.)
 template <typename Visit>
 __device__ __forceinline__ void lattice_walk(const Lattice& lat, const GraspBox& box, float x_hi, Visit visit) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -107,6 +127,7 @@ static inline bool positive_f32(double v, float* out) {   // finite and positive
   *out = f;
   return v > 0.0 && f > 0.0f && f != __builtin_inff() && f == f;
 }
+static inline bool finite_f32(float f) { return f == f && f != __builtin_inff() && f != -__builtin_inff(); }
 
 // max(1, ceil(extent / h)) in float64; false when it cannot be a lattice count (not finite, or beyond the sample limit)
 static inline bool lattice_count(double extent, double h, int* n) {
@@ -136,5 +157,37 @@ constexpr int FIELD_MAX_DIM = 1024;
 static inline int field_dims(int64_t nx, int64_t ny, int64_t nz) {
   if (nx < 1 || ny < 1 || nz < 1) return REGNET_ERR_SHAPE;
   if (nx > FIELD_MAX_DIM || ny > FIELD_MAX_DIM || nz > FIELD_MAX_DIM || nx * ny * nz > ((int64_t)1 << 28)) return REGNET_ERR_UNSUPPORTED;
+  return REGNET_OK;
+}
+
+// The checks of an entry point that holds the lattice against a grid, in the header's order, around the caller's own limit
+// checks: field_call_checks (the entry points that read a distance field) opens, lattice_call_tail (those and the volume's) closes.
+struct LatticeCall {
+  VoxelGrid grid;   // dims and edge by the opening checks (or the caller), the corner by the tail
+  Lattice lat;
+  float h;
+};
+
+// B, outside, the field's dims, B < 2^31, voxel and step -> REGNET_OK, or the status of the first rule they break
+static inline int field_call_checks(int64_t nx, int64_t ny, int64_t nz, double voxel, int outside, int64_t B, double step,
+                                    LatticeCall* call) {
+  if (B < 0 || outside < 0 || outside > 1) return REGNET_ERR_SHAPE;
+  const int dims = field_dims(nx, ny, nz);
+  if (dims != REGNET_OK) return dims;
+  if (B >= (int64_t)1 << 31) return REGNET_ERR_UNSUPPORTED;
+  float voxel_f;
+  if (!positive_f32(voxel, &voxel_f) || !positive_f32(step, &call->h)) return REGNET_ERR_UNSUPPORTED;
+  call->grid = VoxelGrid{(int)nx, (int)ny, (int)nz, 0.0f, 0.0f, 0.0f, voxel_f};
+  return REGNET_OK;
+}
+
+// The standoff, the lattice, B == 0 (REGNET_OK: the caller returns without a launch) and the pointers; then the grid's corner.
+static inline int lattice_call_tail(LatticeCall* call, const GraspBox& box, float standoff, float x_extent, int64_t B,
+                                    const float* origin3, bool pointers) {
+  if (!(standoff >= 0.0f) || standoff == __builtin_inff()) return REGNET_ERR_UNSUPPORTED;   // negative, NaN or infinite
+  if (!lattice_of(box.x_lo, standoff, box.half_thickness, box.half_width, x_extent, call->h, &call->lat)) return REGNET_ERR_UNSUPPORTED;
+  if (B == 0) return REGNET_OK;
+  if (!origin3 || !pointers) return REGNET_ERR_NULL;
+  call->grid.ox = origin3[0]; call->grid.oy = origin3[1]; call->grid.oz = origin3[2];
   return REGNET_OK;
 }

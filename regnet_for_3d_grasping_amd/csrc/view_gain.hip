@@ -284,14 +284,12 @@ extern "C" int regnet_tsdf_view_interest_hands(const void* volume, int64_t nx, i
   float voxel_f, d_solid, h;
   if (!volume_supported(nx, ny, nz, min_weight, voxel, trunc, margin, &voxel_f, &d_solid)) return REGNET_ERR_UNSUPPORTED;
   if (B >= (int64_t)1 << 31 || !positive_f32(step, &h)) return REGNET_ERR_UNSUPPORTED;
-  if (!(standoff >= 0.0f) || standoff == __builtin_inff()) return REGNET_ERR_UNSUPPORTED;   // negative, NaN or infinite
-  Lattice lat;
-  if (!lattice_of(x_lo, standoff, half_thickness, half_width, x_extent, h, &lat)) return REGNET_ERR_UNSUPPORTED;
-  if (B == 0) return REGNET_OK;
-  if (!volume || !origin3 || !L || !interest || !counts) return REGNET_ERR_NULL;
+  LatticeCall call{VoxelGrid{}, Lattice{}, h};       // (the grid is view_of's)
   const GraspBox box{x_lo, x_hi, half_thickness, half_width, half_space, back_x};
+  const int status = lattice_call_tail(&call, box, standoff, x_extent, B, origin3, volume && L && interest && counts);
+  if (status != REGNET_OK || B == 0) return status;
   hipLaunchKernelGGL(view_interest_kernel, dim3((unsigned)B), dim3(HL_T), 0, as_stream(stream),
-                     view_of(volume, nx, ny, nz, origin3, voxel_f, d_solid, min_weight), L, box, x_hi_per_grasp, lat, interest,
+                     view_of(volume, nx, ny, nz, origin3, voxel_f, d_solid, min_weight), L, box, x_hi_per_grasp, call.lat, interest,
                      counts);
   REGNET_LAUNCH_CHECK();
   return REGNET_OK;

@@ -16,8 +16,8 @@ from typing import Any, Optional
 import numpy as np
 import torch
 
-from . import _lib, approach_volume, eval_collision
-from ._frame_util import ParamsBase, require_cuda, to_device
+from . import _lib, approach_volume
+from ._frame_util import ParamsBase, check_step
 
 __all__ = ["PushParams", "PushOut", "push_out", "STATUS", "MAX_ITERATIONS"]
 
@@ -60,11 +60,7 @@ class PushParams(ParamsBase):
         with np.errstate(over="ignore"):
             if axes.shape != (3,) or not np.isfinite(axes.astype(np.float32)).all():
                 raise ValueError("push: axes must be 3 numbers, finite in float32")
-        if self.step is not None:
-            with np.errstate(over="ignore", under="ignore"):
-                step32 = np.float32(self.step)
-            if not (float(self.step) > 0.0 and step32 > 0.0 and np.isfinite(step32)):
-                raise ValueError("push: step must be None or positive and finite in float32")
+        check_step("push", self.step)
 
 
 class PushOut:
@@ -119,26 +115,11 @@ def push_out(volume, field, grasp, depth, width, params=None, to_volume=None, ma
     interpolated.  One launch on the current stream, no host read: capturable."""
     params = PushParams.coerce(params) or PushParams()
     p = volume.params
-    require_cuda("grasp", grasp, torch.float32, 8, at_least=True, error=RuntimeError)
-    dev = volume.device
-    if grasp.device != dev:
-        raise RuntimeError("push_out: the grasps are on %s, the volume on %s" % (grasp.device, dev))
-    if not (hasattr(field, "dist2") and hasattr(field, "metres")) or tuple(field.dims) != tuple(p.dims) or field.dist2.device != dev:
-        raise ValueError("push_out: the field must be a DistanceField of this volume (same dims, same device)")
+    dev, B, depth, x_extent = approach_volume.hand_call("push_out", volume, grasp, depth, max_depth)
+    approach_volume.require_field("push_out", volume, field)
     if not field.signed or not field.cap:
         raise ValueError("push_out: the field must be signed and capped: volume.distance_field(signed=True, max_distance=...)")
-    B = int(grasp.shape[0])
-    per_grasp = (isinstance(depth, torch.Tensor) and depth.dim() > 0) or (not isinstance(depth, torch.Tensor) and np.ndim(depth) > 0)
-    if per_grasp and max_depth is None:
-        raise ValueError("push_out: with one depth per grasp give max_depth, the far end of the sample lattice")
-    if per_grasp and not isinstance(depth, torch.Tensor):
-        depth = to_device(np.asarray(depth, dtype=np.float32), dev)
-    box, keep = eval_collision._box_args(depth, width, B, dev)
-    x_extent = float(max_depth) if per_grasp else float(depth)
-    step = float(p.voxel) if params.step is None else float(params.step)
-    samples = approach_volume.lattice(box, 0.0, step, x_extent)
-    if samples[0] * samples[1] * samples[2] > approach_volume.MAX_SAMPLES:
-        raise ValueError("push_out: %d x %d x %d samples of the hand, more than 2^22; raise step" % samples)
+    box, keep, step, _ = approach_volume.hand_lattice("push_out", volume, depth, width, B, params.step, None, x_extent)
     L = approach_volume.local_to_volume(grasp, to_volume)[3] if rows is None else rows[2]
     T = int(params.iterations)
     axes = np.ascontiguousarray(np.asarray(params.axes, dtype=np.float32))

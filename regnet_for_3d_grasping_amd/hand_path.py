@@ -19,9 +19,9 @@ from typing import Any, Optional
 import numpy as np
 import torch
 
-from . import _lib, approach_volume, eval_collision
-from ._frame_util import ParamsBase, require_cuda, to_device
-from .retreat import EDT_NONE, MAX_DIRECTIONS as MAX_PATHS, MAX_STEPS, threshold_word
+from . import _lib, approach_volume
+from ._frame_util import ParamsBase, check_step, to_device
+from .retreat import EDT_NONE, MAX_DIRECTIONS as MAX_PATHS, MAX_STEPS, StepCheck, threshold_word
 
 __all__ = ["PathParams", "PathCheck", "straight_paths", "turn_paths", "default_paths", "compose", "check_paths"]
 
@@ -67,11 +67,7 @@ class PathParams(ParamsBase):
                 raise ValueError("paths: paths must be (R,K+1,12) or (B,R,K+1,12) with R in 1..%d and K in 1..%d" % (MAX_PATHS, MAX_STEPS))
         if not np.isfinite(self.min_margin):
             raise ValueError("paths: min_margin must be finite")
-        if self.step is not None:
-            with np.errstate(over="ignore", under="ignore"):
-                step32 = np.float32(self.step)
-            if not (float(self.step) > 0.0 and step32 > 0.0 and np.isfinite(step32)):
-                raise ValueError("paths: step must be None or positive and finite in float32")
+        check_step("paths", self.step)
 
 
 def _rotation(axis, angle):
@@ -147,36 +143,16 @@ def compose(L, local):
     return out.reshape(B, R, K1, 12).to(torch.float32).contiguous()
 
 
-class PathCheck:
+class PathCheck(StepCheck):
     """``check_paths``' result, all on the device.  ``result`` (B,R,4) int32 = (free_steps, the minimum word over steps
     1..free_steps, the minimum over steps 1..K, OUTSIDE lookups over steps 1..K), ``profile`` (B,R,K+1) int32 and ``disp``
     (B,R,K) float32 are the check kernel's, ``best`` (B,4) int32 = (r*, its free_steps, its free-prefix minimum, 0) the fan's
     pick kernel's; ``P`` (B,R,K+1,12) float32 the poses that were checked, ``thresh`` the word ``min_margin`` became, ``step``
-    the lattice step [m]."""
+    the lattice step [m].  ``free_steps``, ``profile_metres``, ``index`` and ``margin`` are ``StepCheck``'s."""
 
     def __init__(self, result, profile, best, disp, P, field, thresh, step, voxel, params):
         self.result, self.profile, self.best, self.disp, self.P = result, profile, best, disp, P
         self.field, self.thresh, self.step, self.voxel, self.params = field, int(thresh), float(step), float(voxel), params
-
-    @property
-    def free_steps(self):
-        """(B,R) int32: per path the steps from the final pose on which the hand keeps ``min_margin``."""
-        return self.result[:, :, 0]
-
-    @property
-    def profile_metres(self):
-        """(B,R,K+1) float32 [m]: the hand's margin at every waypoint, ``field.metres`` of ``profile``."""
-        return self.field.metres(self.profile.contiguous())
-
-    @property
-    def index(self):
-        """(B) int64: the picked path's row."""
-        return self.best[:, 0].to(torch.int64)
-
-    @property
-    def margin(self):
-        """(B) float32 [m]: the smallest margin over the picked path's free steps, +inf where it has none."""
-        return self.field.metres(self.best[:, 2].contiguous())
 
     def length_at(self, steps):
         """``steps`` (B) integers in 0..K -> (B) float32 [m]: how far the hand's farthest point moves on the PICKED path up to
@@ -257,26 +233,11 @@ def check_paths(volume, field, grasp, depth, width, params=None, to_volume=None,
     fourth row is not checked), and without ``poses`` ``compose`` adds its torch operations."""
     params = PathParams.coerce(params) or PathParams()
     p = volume.params
-    require_cuda("grasp", grasp, torch.float32, 8, at_least=True, error=RuntimeError)
-    dev = volume.device
-    if grasp.device != dev:
-        raise RuntimeError("check_paths: the grasps are on %s, the volume on %s" % (grasp.device, dev))
-    if not (hasattr(field, "dist2") and hasattr(field, "metres")) or tuple(field.dims) != tuple(p.dims) or field.dist2.device != dev:
-        raise ValueError("check_paths: the field must be a DistanceField of this volume (same dims, same device)")
+    dev, B, depth, x_extent = approach_volume.hand_call("check_paths", volume, grasp, depth, max_depth)
+    approach_volume.require_field("check_paths", volume, field)
     if float(params.min_margin) < 0.0 and not field.signed:
         raise ValueError("check_paths: a negative min_margin is a tolerated penetration; it needs a signed field")
-    B = int(grasp.shape[0])
-    per_grasp = (isinstance(depth, torch.Tensor) and depth.dim() > 0) or (not isinstance(depth, torch.Tensor) and np.ndim(depth) > 0)
-    if per_grasp and max_depth is None:
-        raise ValueError("check_paths: with one depth per grasp give max_depth, the far end of the sample lattice")
-    if per_grasp and not isinstance(depth, torch.Tensor):
-        depth = to_device(np.asarray(depth, dtype=np.float32), dev)
-    box, keep = eval_collision._box_args(depth, width, B, dev)
-    x_extent = float(max_depth) if per_grasp else float(depth)
-    step = float(p.voxel) if params.step is None else float(params.step)
-    samples = approach_volume.lattice(box, 0.0, step, x_extent)
-    if samples[0] * samples[1] * samples[2] > approach_volume.MAX_SAMPLES:
-        raise ValueError("check_paths: %d x %d x %d samples of the hand, more than 2^22; raise step" % samples)
+    box, keep, step, _ = approach_volume.hand_lattice("check_paths", volume, depth, width, B, params.step, None, x_extent)
     if poses is not None:
         if not isinstance(poses, torch.Tensor) or poses.device != dev or poses.dtype != torch.float32:
             raise RuntimeError("check_paths: poses must be a float32 tensor on the volume's device")

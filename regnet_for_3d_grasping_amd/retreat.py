@@ -19,8 +19,8 @@ from typing import Any, Optional
 import numpy as np
 import torch
 
-from . import _lib, approach_volume, eval_collision
-from ._frame_util import ParamsBase, require_cuda, to_device
+from . import _lib, approach_volume
+from ._frame_util import ParamsBase, check_step, to_device
 
 EDT_NONE = 1 << 30
 MAX_DIRECTIONS = 16                 # regnet_grasp_retreat_fan_f32's documented limits
@@ -68,11 +68,7 @@ class RetreatParams(ParamsBase):
                 raise ValueError("retreat: directions must be (R,3) or (B,R,3) with R in 1..%d" % MAX_DIRECTIONS)
         if not np.isfinite(self.min_margin):
             raise ValueError("retreat: min_margin must be finite")
-        if self.step is not None:
-            with np.errstate(over="ignore", under="ignore"):
-                step32 = np.float32(self.step)
-            if not (float(self.step) > 0.0 and step32 > 0.0 and np.isfinite(step32)):
-                raise ValueError("retreat: step must be None or positive and finite in float32")
+        check_step("retreat", self.step)
 
 
 def word_metres(word, voxel, signed):
@@ -135,20 +131,14 @@ def default_fan(tilt_deg, device, frame=None, up=None):
     return torch.cat([table.unsqueeze(0).expand(B, 5, 3), local.unsqueeze(1), mid.unsqueeze(1)], dim=1).contiguous()
 
 
-class RetreatFan:
-    """``retreat_fan``'s result, all on the device.  ``result`` (B,R,4) int32 = (free_steps, the minimum word over steps
-    1..free_steps, the minimum over steps 1..K, OUTSIDE lookups over steps 1..K), ``profile`` (B,R,K+1) int32 and ``best`` (B,4)
-    int32 = (r*, its free_steps, its free-prefix minimum, 0) are the kernels'; ``dirs`` (R,3) or (B,R,3) float32 the local
-    directions they were given, ``L`` (B,12) the local-to-volume rows, ``thresh`` the word ``min_margin`` became, ``ds`` the step
-    length [m]."""
-
-    def __init__(self, result, profile, best, dirs, L, frame, center, field, thresh, ds, params):
-        self.result, self.profile, self.best, self.dirs, self.L = result, profile, best, dirs, L
-        self.frame, self.center, self.field, self.thresh, self.ds, self.params = frame, center, field, int(thresh), float(ds), params
+class StepCheck:
+    """What ``RetreatFan`` and ``hand_path.PathCheck`` share: R candidates per grasp (directions of the fan, paths) of K steps
+    each, read off ``result`` (B,R,4) int32, ``profile`` (B,R,K+1) int32, ``best`` (B,4) int32 and the ``field`` they were
+    checked against."""
 
     @property
     def free_steps(self):
-        """(B,R) int32: per direction the steps from the final pose on which the hand keeps ``min_margin``."""
+        """(B,R) int32: per candidate the steps from the final pose on which the hand keeps ``min_margin``."""
         return self.result[:, :, 0]
 
     @property
@@ -158,18 +148,30 @@ class RetreatFan:
 
     @property
     def index(self):
-        """(B) int64: the picked direction's row in ``dirs``."""
+        """(B) int64: the picked candidate's row."""
         return self.best[:, 0].to(torch.int64)
+
+    @property
+    def margin(self):
+        """(B) float32 [m]: the smallest margin over the picked candidate's free steps, +inf where it has none."""
+        return self.field.metres(self.best[:, 2].contiguous())
+
+
+class RetreatFan(StepCheck):
+    """``retreat_fan``'s result, all on the device.  ``result`` (B,R,4) int32 = (free_steps, the minimum word over steps
+    1..free_steps, the minimum over steps 1..K, OUTSIDE lookups over steps 1..K), ``profile`` (B,R,K+1) int32 and ``best`` (B,4)
+    int32 = (r*, its free_steps, its free-prefix minimum, 0) are the kernels'; ``dirs`` (R,3) or (B,R,3) float32 the local
+    directions they were given, ``L`` (B,12) the local-to-volume rows, ``thresh`` the word ``min_margin`` became, ``ds`` the step
+    length [m].  ``index`` (``StepCheck``'s) is the picked direction's row in ``dirs``."""
+
+    def __init__(self, result, profile, best, dirs, L, frame, center, field, thresh, ds, params):
+        self.result, self.profile, self.best, self.dirs, self.L = result, profile, best, dirs, L
+        self.frame, self.center, self.field, self.thresh, self.ds, self.params = frame, center, field, int(thresh), float(ds), params
 
     @property
     def free_length(self):
         """(B) float32 [m]: ``free_steps * ds`` of the picked direction."""
         return self.best[:, 1].to(torch.float32) * float(np.float32(self.ds))
-
-    @property
-    def margin(self):
-        """(B) float32 [m]: the smallest margin over the picked direction's free steps, +inf where it has none."""
-        return self.field.metres(self.best[:, 2].contiguous())
 
     @property
     def direction(self):
@@ -206,27 +208,12 @@ def retreat_fan(volume, field, grasp, depth, width, params=None, to_volume=None,
     caller has formed them already (``analyse_volume`` has); None: they are formed here."""
     params = RetreatParams.coerce(params) or RetreatParams()
     p = volume.params
-    require_cuda("grasp", grasp, torch.float32, 8, at_least=True, error=RuntimeError)
-    dev = volume.device
-    if grasp.device != dev:
-        raise RuntimeError("retreat_fan: the grasps are on %s, the volume on %s" % (grasp.device, dev))
-    if not (hasattr(field, "dist2") and hasattr(field, "metres")) or tuple(field.dims) != tuple(p.dims) or field.dist2.device != dev:
-        raise ValueError("retreat_fan: the field must be a DistanceField of this volume (same dims, same device)")
+    dev, B, depth, x_extent = approach_volume.hand_call("retreat_fan", volume, grasp, depth, max_depth)
+    approach_volume.require_field("retreat_fan", volume, field)
     if float(params.min_margin) < 0.0 and not field.signed:
         raise ValueError("retreat_fan: a negative min_margin is a tolerated penetration; it needs a signed field")
-    B = int(grasp.shape[0])
-    per_grasp = (isinstance(depth, torch.Tensor) and depth.dim() > 0) or (not isinstance(depth, torch.Tensor) and np.ndim(depth) > 0)
-    if per_grasp and max_depth is None:
-        raise ValueError("retreat_fan: with one depth per grasp give max_depth, the far end of the sample lattice")
-    if per_grasp and not isinstance(depth, torch.Tensor):
-        depth = to_device(np.asarray(depth, dtype=np.float32), dev)
     frame, center, L = approach_volume.local_to_volume(grasp, to_volume)[1:] if rows is None else rows
-    box, keep = eval_collision._box_args(depth, width, B, dev)
-    x_extent = float(max_depth) if per_grasp else float(depth)
-    step = float(p.voxel) if params.step is None else float(params.step)
-    samples = approach_volume.lattice(box, 0.0, step, x_extent)
-    if samples[0] * samples[1] * samples[2] > approach_volume.MAX_SAMPLES:
-        raise ValueError("retreat_fan: %d x %d x %d samples of the hand, more than 2^22; raise step" % samples)
+    box, keep, step, _ = approach_volume.hand_lattice("retreat_fan", volume, depth, width, B, params.step, None, x_extent)
     if params.directions is not None:
         dirs = params.directions
         if not isinstance(dirs, torch.Tensor):

@@ -21,7 +21,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib, approach, approach_volume, depth_frame, eval_collision, tsdf
+from . import _lib, approach, approach_volume, depth_frame, tsdf
 from ._frame_util import ParamsBase, matrix4, record_streams, require_cuda, stream_scope, to_device
 
 MAX_POSES = 32                      # regnet_tsdf_view_mark_f32's documented limits: a pose is a bit of a 32-bit word
@@ -282,23 +282,9 @@ def interest_hands(volume, grasp, depth, width, params=None, to_volume=None, max
     (``VolumeApproach.L``), which is then not formed again.  One fill and one launch, no host read."""
     params = approach.ApproachParams.coerce(params) or approach.ApproachParams()
     p = volume.params
-    require_cuda("grasp", grasp, torch.float32, 8, at_least=True, error=RuntimeError)
-    dev = volume.device
-    if grasp.device != dev:
-        raise RuntimeError("interest_hands: the grasps are on %s, the volume on %s" % (grasp.device, dev))
-    B = int(grasp.shape[0])
-    per_grasp = (isinstance(depth, torch.Tensor) and depth.dim() > 0) or (not isinstance(depth, torch.Tensor) and np.ndim(depth) > 0)
-    if per_grasp and max_depth is None:
-        raise ValueError("interest_hands: with one depth per grasp give max_depth, the far end of the sample lattice")
-    if per_grasp and not isinstance(depth, torch.Tensor):
-        depth = to_device(np.asarray(depth, dtype=np.float32), dev)
+    dev, B, depth, x_extent = approach_volume.hand_call("interest_hands", volume, grasp, depth, max_depth)
     L = approach_volume.local_to_volume(grasp, to_volume)[3] if rows is None else rows
-    box, _ = eval_collision._box_args(depth, width, B, dev)
-    x_extent = float(max_depth) if per_grasp else float(depth)
-    step = float(p.voxel) if params.step is None else float(params.step)
-    samples = approach_volume.lattice(box, params.standoff, step, x_extent)
-    if samples[0] * samples[1] * samples[2] > approach_volume.MAX_SAMPLES:
-        raise ValueError("interest_hands: %d x %d x %d samples of the swept hand, more than 2^22; raise step" % samples)
+    box, keep, step, _ = approach_volume.hand_lattice("interest_hands", volume, depth, width, B, params.step, params.standoff, x_extent)
     nx, ny, nz = p.dims
     n = nx * ny * nz
     if out is None:
